@@ -15,7 +15,9 @@ pool and schedules pools one after the other (scheduling_algo.go:165); here pool
 collective (DESIGN.md "Multi-GPU").  Each rank schedules its own pool of the full per-GPU size (weak scaling),
 value = pools-rounds of all ranks / max-over-ranks time.
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps rounds and prints the headline; --full adds the roofline, the
+CPU-oracle leg (cpu_baseline + parity) and the other_configs sub-records, with the full record before the line and in bench_full.json.
+--dump-outputs DIR writes the last timed round's result arrays (dump_outputs).
 """
 import argparse
 import json
@@ -64,6 +66,36 @@ def round_diff(a, b):
         if x.shape != y.shape or not bool(np.array_equal(x, y)):
             bad.append(f)
     return bad
+
+
+DUMP_LIMIT = 64_000_000   # bytes, all files of --dump-outputs together
+
+
+def dump_outputs(res, outdir):
+    """--dump-outputs: what round_diff compares, as DIR/<name>.npy in float64 (every value of a default-size round is exact in it).  The scheduled / preempted
+    lists become per-job arrays over all m jobs of the round input, so that every shape follows from the input alone: job_scheduled_node and job_preempted_node
+    hold -1 for a job not scheduled / not preempted, job_scheduled_priority and job_scheduled_method 0 (ASCHED_METHOD_NONE) for a job not scheduled.  Over
+    DUMP_LIMIT the per-job arrays keep a fixed seeded sample of the jobs, the same for all of them, named by DIR/job_sample_index.npy."""
+    import numpy as np
+    m = len(res.job_unschedulable_reason)
+    per_job = {k: np.full(m, fill, np.float64) for k, fill in (("job_scheduled_node", -1), ("job_scheduled_priority", 0), ("job_scheduled_method", 0), ("job_preempted_node", -1))}
+    per_job["job_scheduled_node"][res.scheduled_job] = res.scheduled_node
+    per_job["job_scheduled_priority"][res.scheduled_job] = res.scheduled_priority_arr
+    per_job["job_scheduled_method"][res.scheduled_job] = res.scheduled_method_arr
+    per_job["job_preempted_node"][res.preempted_job] = res.preempted_node
+    per_job["job_unschedulable_reason"] = np.asarray(res.job_unschedulable_reason, np.float64)
+    other = {"queue_allocated_by_pc": res.queue_allocated_by_pc, "fair_share": res.fair_share, "demand_capped_adjusted_fair_share": res.demand_capped_adjusted_fair_share,
+             "uncapped_adjusted_fair_share": res.uncapped_adjusted_fair_share, "queue_tokens_after": res.queue_tokens_after, "termination_reason": [res.termination_reason],
+             "num_evicted_phase1": [res.num_evicted_phase1], "num_evicted_phase3": [res.num_evicted_phase3], "global_tokens_after": [res.global_tokens_after]}
+    other = {k: np.asarray(v, np.float64) for k, v in other.items()}
+    small = sum(a.nbytes for a in other.values())
+    if small + 8 * m * len(per_job) > DUMP_LIMIT:
+        keep = np.sort(np.random.default_rng(0).choice(m, (DUMP_LIMIT - small) // (8 * (len(per_job) + 1)), replace=False))
+        per_job = {k: a[keep] for k, a in per_job.items()}
+        per_job["job_sample_index"] = keep.astype(np.float64)
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in {**per_job, **other}.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
 
 
 def parity_record(gpu_res, oracle_res, num_jobs, what):
@@ -1061,11 +1093,11 @@ def main():
     ap.add_argument("--queues", type=int, default=64)
     ap.add_argument("--gangs", type=int, default=0, help="queued gangs of size 2-64 (BASELINE configs[3] shape)")
     ap.add_argument("--occupied", type=float, default=0.5, help="fraction of every node filled with running jobs (0.95: the preemption-heavy configs[4] shape)")
-    ap.add_argument("--cpu-budget", type=float, default=75.0, help="seconds of CPU-oracle work allowed for cpu_baseline (0 = skip)")
+    ap.add_argument("--cpu-budget", type=float, default=75.0, help="seconds of CPU-oracle work allowed for cpu_baseline (0 = skip; the round bench runs it with --full only)")
     ap.add_argument("--submit-check", action="store_true", help="measure the submit check (SURVEY 8f-2) instead of the round; 1 GPU")
     ap.add_argument("--submit-jobs", type=int, default=50_000)
     ap.add_argument("--submit-keys", type=int, default=2_000)
-    ap.add_argument("--no-other", action="store_true", help="skip the other_configs sub-records (configs[1], [3], [4], submit check)")
+    ap.add_argument("--no-other", action="store_true", help="with --full: skip the other_configs sub-records (configs[1], [3], [4], submit check)")
     ap.add_argument("--other-budget", type=float, default=480.0, help="seconds after which no further other_configs sub-record is started")
     ap.add_argument("--no-full-other", action="store_true", help="skip the full-size (100k x 1M) run of configs[4] (~40 s); the reduced size with its oracle leg still runs")
     ap.add_argument("--other-scale", type=float, default=1.0, help="scale the other_configs workloads (tests)")
@@ -1076,7 +1108,12 @@ def main():
                          "node-sharded-round = ONE pool's whole round on every GPU with the wide node passes split N ways and all-reduced (asched_shard_round), exact; "
                          "queue-hash = the north_star's split of ONE pool's queues over the GPUs with one all-reduce SUM and an ordered replay, approximate: the line "
                          "reports the mismatch against the exact round")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: roofline (kernel ISA hash, committed PMC traffic), cpu_baseline + parity "
+                                                         "against the oracle round, the other_configs sub-records, and bench_full.json.  Off: set up, warm up, time the steps, print the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the result arrays of the last timed round (the round bench) to DIR/<name>.npy as float64")
     args = ap.parse_args()
+    if args.dump_outputs and (args.submit_check or args.mode != "pools"):
+        ap.error("--dump-outputs writes the round bench's results: not with --submit-check or --mode " + args.mode)
     if args.submit_check:
         emit(submit_check_record(args))
         return 0
@@ -1169,67 +1206,73 @@ def main():
                   "host_ms": float(np.mean(lat_ms)), "stats": s.round_stats()},
         "input_build_s": build_s, "round_prepare_s": prep_s / (args.warmup + args.steps),
         "prepare_inclusive_rounds_per_s": 1.0 / (total / args.steps + prep_s / (args.warmup + args.steps)),
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                     "frac_kind": "unbatched-equivalent: SURVEY 8d's per-query bytes x the queries the ALGORITHM issues; no node plane is scanned (passes_executed), the kernel is a serial "
-                                  "chain of placements, not an HBM stream — ticks_per_placement is its real figure of merit",
-                     "traffic": None, "kernel": "k_control", "algorithmic_bytes_per_launch": alg,
-                     "note": "algorithmic bytes = node_queries_issued x N x (R*8+8) + binds x 256 (SURVEY 8d); duration = the persistent k_control launch(es) of one round "
-                             "(HIP events on the launch stream; the grid-wide bulk kernels around them are in round.device_ms)"},
     }
-    # HBM bytes actually moved by one round launch: rocprofv3 PMC passes (FETCH_SIZE x2 per the gfx950 correction + WRITE_SIZE),
-    # collected once per round of work on this exact workload and committed under profiles/ (rocprofv3 cannot run inside bench.py)
-    import glob
-    pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_hbm_traffic.json")))
-    if pmcs and args.nodes == 100_000 and args.jobs == 1_000_000 and args.queues == 64 and not args.gangs and args.occupied == 0.5:
-        try:
-            c = json.load(open(pmcs[-1]))["counters"]
-            fetch = max(x["max_kb"] for x in c["FETCH_SIZE"] if x["kernel"].startswith("k_control"))
-            write = max(x["max_kb"] for x in c["WRITE_SIZE"] if x["kernel"].startswith("k_control"))
-            out["roofline"]["traffic"] = (2 * fetch + write) * 1024
-            out["roofline"]["traffic_kernel_isa_hash"] = json.load(open(pmcs[-1])).get("kernel_isa_hash")   # equal to kernel_isa_hash below <=> the counters were taken from this round kernel
-            out["roofline"]["traffic_source"] = (f"profiles/{os.path.basename(pmcs[-1])} (2*FETCH_SIZE + WRITE_SIZE of the round launch) — NOT measured in this run: rocprofv3 PMC passes cannot run "
-                                                 f"inside bench.py; the file is the newest committed PMC collection on this exact workload (tools/gpu_call.sh) and may predate the library under test")
-        except Exception:
-            pass
-    out["roofline"]["kernel_isa_hash"] = kernel_isa_hash()
-    out["roofline"]["kernel_avg_ms"] = kern_ms
-    out["roofline"]["kernel_ms_per_round"] = [round(x, 3) for x in ctl]
-    if out["roofline"].get("traffic") is not None and out["roofline"].get("traffic_kernel_isa_hash") != out["roofline"]["kernel_isa_hash"]:
-        out["roofline"]["traffic_of_another_build"] = out["roofline"]["traffic"]   # kept in the full record for reference only
-        out["roofline"]["traffic"] = None
-        out["roofline"]["traffic_stale"] = True   # the committed PMC passes were taken from a different round kernel: no byte count is claimed for this one
-    st_ = s.round_stats()
-    placed = max(1, len(res.scheduled))
-    out["roofline"]["ticks_per_placement"] = (st_["kclk_pass1"] + st_["kclk_pass2"]) * 1000.0 / placed   # shader clocks of the two sequential passes per job placed (last round)
-    out["roofline"]["passes_executed"] = {"base_window_reads": st_["base_scan_steps"], "plane_scan_kclk": st_["kclk_plane_scans"], "stream_runs": st_["stream_runs"]}
+    if args.dump_outputs:
+        dump_outputs(res, args.dump_outputs)
     rc = 0
-    if args.cpu_budget > 0 and world == 1:  # rank 0 at N=1 only
-        try:
-            out["cpu_baseline"], ores = cpu_baseline(wl, args.cpu_budget, iters, min_rounds=3 if not cut_possible(wl, args.cpu_budget, iters) else 1)
-            if ores is not None:  # the headline number is self-verifying: the timed GPU round against the oracle round on the same input
-                out["parity"] = parity_record(res, ores, wl.num_jobs, "oracle round of the cpu_baseline leg, same input")
-                out["parity"]["excluded_nodes"] = excluded_parity(s, ores)
-                if not out["parity"]["identical"] or out["parity"]["excluded_nodes"].get("identical") is False:
-                    rc = 3
-            else:
-                out["parity"] = {"checked": False, "reason": "cpu_baseline ran with a cut burst (--cpu-budget)"}
-        except Exception as e:  # the checker must never take the bench line down
-            out["cpu_baseline"] = {"error": str(e)}
-    else:
-        out["parity"] = {"checked": False, "reason": "no oracle leg at --cpu-budget 0 / N>1"}
-    if world == 1 and not args.no_other:
-        s.close()
-        out["other_configs"] = []
-        watchdog_arm(out, args.watchdog)   # from here on the headline exists: a sub-record that never returns (a hung kernel: profiles/r05y_bulk_skip_hang.txt) must not take it down
-        other_configs(hip, args, time.perf_counter(), sink=out["other_configs"])
-        watchdog_disarm()
-        for r in out["other_configs"]:
-            for p in (r.get("parity"), (r.get("reduced") or {}).get("parity")):
-                if p and p.get("checked") and not p.get("identical"):
-                    rc = 3
+    if args.full:   # beyond the headline: roofline, the oracle leg (cpu_baseline + parity), the other_configs sub-records
+        out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                          "frac_kind": "unbatched-equivalent: SURVEY 8d's per-query bytes x the queries the ALGORITHM issues; no node plane is scanned (passes_executed), the kernel is a serial "
+                                       "chain of placements, not an HBM stream — ticks_per_placement is its real figure of merit",
+                          "traffic": None, "kernel": "k_control", "algorithmic_bytes_per_launch": alg,
+                          "note": "algorithmic bytes = node_queries_issued x N x (R*8+8) + binds x 256 (SURVEY 8d); duration = the persistent k_control launch(es) of one round "
+                                  "(HIP events on the launch stream; the grid-wide bulk kernels around them are in round.device_ms)"}
+        # HBM bytes actually moved by one round launch: rocprofv3 PMC passes (FETCH_SIZE x2 per the gfx950 correction + WRITE_SIZE),
+        # collected once per round of work on this exact workload and committed under profiles/ (rocprofv3 cannot run inside bench.py)
+        import glob
+        pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_hbm_traffic.json")))
+        if pmcs and args.nodes == 100_000 and args.jobs == 1_000_000 and args.queues == 64 and not args.gangs and args.occupied == 0.5:
+            try:
+                c = json.load(open(pmcs[-1]))["counters"]
+                fetch = max(x["max_kb"] for x in c["FETCH_SIZE"] if x["kernel"].startswith("k_control"))
+                write = max(x["max_kb"] for x in c["WRITE_SIZE"] if x["kernel"].startswith("k_control"))
+                out["roofline"]["traffic"] = (2 * fetch + write) * 1024
+                out["roofline"]["traffic_kernel_isa_hash"] = json.load(open(pmcs[-1])).get("kernel_isa_hash")   # equal to kernel_isa_hash below <=> the counters were taken from this round kernel
+                out["roofline"]["traffic_source"] = (f"profiles/{os.path.basename(pmcs[-1])} (2*FETCH_SIZE + WRITE_SIZE of the round launch) — NOT measured in this run: rocprofv3 PMC passes cannot run "
+                                                     f"inside bench.py; the file is the newest committed PMC collection on this exact workload (tools/gpu_call.sh) and may predate the library under test")
+            except Exception:
+                pass
+        out["roofline"]["kernel_isa_hash"] = kernel_isa_hash()
+        out["roofline"]["kernel_avg_ms"] = kern_ms
+        out["roofline"]["kernel_ms_per_round"] = [round(x, 3) for x in ctl]
+        if out["roofline"].get("traffic") is not None and out["roofline"].get("traffic_kernel_isa_hash") != out["roofline"]["kernel_isa_hash"]:
+            out["roofline"]["traffic_of_another_build"] = out["roofline"]["traffic"]   # kept in the full record for reference only
+            out["roofline"]["traffic"] = None
+            out["roofline"]["traffic_stale"] = True   # the committed PMC passes were taken from a different round kernel: no byte count is claimed for this one
+        st_ = s.round_stats()
+        placed = max(1, len(res.scheduled))
+        out["roofline"]["ticks_per_placement"] = (st_["kclk_pass1"] + st_["kclk_pass2"]) * 1000.0 / placed   # shader clocks of the two sequential passes per job placed (last round)
+        out["roofline"]["passes_executed"] = {"base_window_reads": st_["base_scan_steps"], "plane_scan_kclk": st_["kclk_plane_scans"], "stream_runs": st_["stream_runs"]}
+        if args.cpu_budget > 0 and world == 1:  # rank 0 at N=1 only
+            try:
+                out["cpu_baseline"], ores = cpu_baseline(wl, args.cpu_budget, iters, min_rounds=3 if not cut_possible(wl, args.cpu_budget, iters) else 1)
+                if ores is not None:  # the headline number is self-verifying: the timed GPU round against the oracle round on the same input
+                    out["parity"] = parity_record(res, ores, wl.num_jobs, "oracle round of the cpu_baseline leg, same input")
+                    out["parity"]["excluded_nodes"] = excluded_parity(s, ores)
+                    if not out["parity"]["identical"] or out["parity"]["excluded_nodes"].get("identical") is False:
+                        rc = 3
+                else:
+                    out["parity"] = {"checked": False, "reason": "cpu_baseline ran with a cut burst (--cpu-budget)"}
+            except Exception as e:  # the checker must never take the bench line down
+                out["cpu_baseline"] = {"error": str(e)}
+        else:
+            out["parity"] = {"checked": False, "reason": "no oracle leg at --cpu-budget 0 / N>1"}
+        if world == 1 and not args.no_other:
+            s.close()
+            out["other_configs"] = []
+            watchdog_arm(out, args.watchdog)   # from here on the headline exists: a sub-record that never returns (a hung kernel: profiles/r05y_bulk_skip_hang.txt) must not take it down
+            other_configs(hip, args, time.perf_counter(), sink=out["other_configs"])
+            watchdog_disarm()
+            for r in out["other_configs"]:
+                for p in (r.get("parity"), (r.get("reduced") or {}).get("parity")):
+                    if p and p.get("checked") and not p.get("identical"):
+                        rc = 3
     if world > 1:
         out["scaling_note"] = "pool-per-GPU replicas (weak scaling, no data-path collective); no single-pool multi-GPU scaling curve is claimed by this line"
-    emit(out)
+    if args.full:
+        emit(out)
+    else:
+        print(compact_line(out))   # the one result line
     if dist is not None:
         dist.destroy_process_group()
     return rc

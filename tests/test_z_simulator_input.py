@@ -12,16 +12,15 @@ import pytest
 from armada_amd import simulator_input as S
 
 FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "simulator_basic_input.json")
+# verbatim copies of the reference's internal/scheduler/simulator/testdata files the fixture was made from
+TESTDATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "simulator_testdata")
 
 
 def test_fixture_matches_the_reference_files():
-    """when the reference checkout is present (build container) the fixture is exactly what its three files say"""
-    ref = "/root/reference/internal/scheduler/simulator/testdata"
-    if not os.path.isdir(ref):
-        pytest.skip("no reference checkout here (GPU box)")
+    """the fixture is exactly what the reference's three files say"""
     a = S.from_fixture(FIXTURE)
     import copy, yaml
-    docs = [yaml.safe_load(open(os.path.join(ref, p))) for p in ("clusters/cpu_1_1_100.yaml", "workloads/basicWorkload.yaml", "configs/basicSchedulingConfig.yaml")]
+    docs = [yaml.safe_load(open(os.path.join(TESTDATA, p))) for p in ("clusters/cpu_1_1_100.yaml", "workloads/basicWorkload.yaml", "configs/basicSchedulingConfig.yaml")]
     docs[1]["queues"][0]["jobTemplates"][0]["number"] = 1000
     b = S.from_documents(*docs)
     assert np.array_equal(a.workload.node_total, b.workload.node_total) and np.array_equal(a.workload.job_req, b.workload.job_req)

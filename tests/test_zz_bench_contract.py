@@ -65,7 +65,7 @@ def check_line(out, metric_word):
 
 
 def test_round_bench_line(fake_gpu, monkeypatch, capsys):
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--nodes", "500", "--jobs", "5000", "--queues", "8", "--steps", "2", "--warmup", "1", "--cpu-budget", "5", "--other-scale", "0.01"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--nodes", "500", "--jobs", "5000", "--queues", "8", "--steps", "2", "--warmup", "1", "--cpu-budget", "5", "--other-scale", "0.01", "--full"])
     fake_gpu.main()
     line = check_line(capsys.readouterr().out, "rounds/sec")
     assert line["steps"] == 2 and line["warmup"] == 1 and line["unit"] == "rounds/s" and line["round"]["scheduled"] > 0
@@ -111,12 +111,104 @@ def test_round_bench_detects_a_mismatch(fake_gpu, monkeypatch, capsys):
     """a GPU round that differs from the oracle's makes bench.py say so in the line and exit non-zero"""
     real = fake_gpu.round_diff
     monkeypatch.setattr(fake_gpu, "round_diff", lambda a, b: real(a, b) + ["scheduled (injected)"])
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--nodes", "300", "--jobs", "3000", "--queues", "4", "--steps", "1", "--warmup", "0", "--cpu-budget", "5", "--no-other"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--nodes", "300", "--jobs", "3000", "--queues", "4", "--steps", "1", "--warmup", "0", "--cpu-budget", "5", "--no-other", "--full"])
     rc = fake_gpu.main()
     lines = capsys.readouterr().out.strip().splitlines()
     line, compact = json.loads(lines[-2]), json.loads(lines[-1])
     assert rc == 3 and line["parity"]["checked"] and not line["parity"]["identical"] and "other_configs" not in line
     assert compact["parity"]["checked"] and compact["parity"]["identical"] is False
+
+
+PLAIN = ["bench.py", "--gpus", "1", "--nodes", "500", "--jobs", "5000", "--queues", "8", "--steps", "3", "--warmup", "2"]
+
+
+def _forbid_extras(bench, monkeypatch):
+    """a plain run does only what the headline needs: none of the --full legs may start"""
+    def refuse(*a, **k):
+        raise AssertionError("a plain bench run started a --full leg")
+    for name in ("cpu_baseline", "other_configs", "kernel_isa_hash", "emit"):
+        monkeypatch.setattr(bench, name, refuse)
+
+
+def test_plain_round_bench_line(fake_gpu, monkeypatch, capsys):
+    """without --full: exactly --warmup + --steps rounds, one stdout line with the headline keys, no oracle leg, roofline or sub-records"""
+    from armada_amd import workloads as W
+    _forbid_extras(fake_gpu, monkeypatch)
+    prepared = []
+    real_prepare = W.prepare
+    monkeypatch.setattr(W, "prepare", lambda *a, **k: (prepared.append(1), real_prepare(*a, **k))[1])
+    monkeypatch.setattr(sys, "argv", PLAIN)
+    assert (fake_gpu.main() or 0) == 0
+    lines = capsys.readouterr().out.strip().splitlines()
+    assert len(lines) == 1 and len(prepared) == 2 + 3
+    line = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config", "round"} <= set(line), line
+    assert not {"roofline", "cpu_baseline", "parity", "other_configs"} & set(line), line
+    assert "rounds/sec" in line["metric"] and line["unit"] == "rounds/s" and line["higher_is_better"] is True and line["dtype"] == "int64"
+    assert line["steps"] == 3 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["round"]["scheduled"] > 0
+    assert abs(line["value"] - 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"]   # one pool: rounds/s and ms per timed round say the same
+
+
+def test_dump_outputs(fake_gpu, monkeypatch, capsys, oracle_lib, tmp_path):
+    """--dump-outputs: the last timed round's results as float64 .npy, one entry per job where the round returns lists (no file empty, every shape set by the
+    input), the same on every run with the same arguments, and the oracle's round on that input"""
+    import numpy as np
+    from armada_amd import workloads as W
+    from armada_amd.multipool import pool_seed
+    _forbid_extras(fake_gpu, monkeypatch)
+    dumps = []
+    for run in ("a", "b"):
+        monkeypatch.setattr(sys, "argv", PLAIN + ["--dump-outputs", str(tmp_path / run)])
+        fake_gpu.main()
+        line = json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in sorted(os.listdir(tmp_path / run))})
+    a, b = dumps
+    wl = W.config3(n_nodes=500, n_jobs=5000, n_queues=8, seed=pool_seed(W.SEED, 0), gangs=0, occupied=0.5)   # bench.py main()'s input
+    wl.global_burst, wl.queue_burst = max(1, int(200_000 * 0.005)), max(1, int(20_000 * 0.005))
+    m, q = wl.num_jobs, wl.num_queues
+    shapes = {"job_scheduled_node": (m,), "job_scheduled_priority": (m,), "job_scheduled_method": (m,), "job_preempted_node": (m,), "job_unschedulable_reason": (m,),
+              "queue_allocated_by_pc": (q, len(wl.config.pc_priority), W.R), "fair_share": (q,), "demand_capped_adjusted_fair_share": (q,), "uncapped_adjusted_fair_share": (q,),
+              "queue_tokens_after": (q,), "termination_reason": (1,), "num_evicted_phase1": (1,), "num_evicted_phase3": (1,), "global_tokens_after": (1,)}
+    assert {k: x.shape for k, x in a.items()} == shapes and all(x.dtype == np.float64 and x.size > 0 for x in a.values())
+    assert sum(x.nbytes for x in a.values()) <= 64_000_000
+    assert a.keys() == b.keys() and all(np.array_equal(a[f], b[f]) for f in a)
+    assert int((a["job_scheduled_node"] >= 0).sum()) == line["round"]["scheduled"] > 0
+    s = W.load(oracle_lib, wl)
+    W.prepare(s, wl)
+    want = s.schedule_round()
+    node, prio, meth, pre = np.full(m, -1), np.zeros(m), np.zeros(m), np.full(m, -1)
+    node[want.scheduled_job], prio[want.scheduled_job], meth[want.scheduled_job] = want.scheduled_node, want.scheduled_priority_arr, want.scheduled_method_arr
+    pre[want.preempted_job] = want.preempted_node
+    assert np.array_equal(a["job_scheduled_node"], node) and np.array_equal(a["job_scheduled_priority"], prio) and np.array_equal(a["job_scheduled_method"], meth)
+    assert np.array_equal(a["job_preempted_node"], pre) and np.array_equal(a["job_unschedulable_reason"], want.job_unschedulable_reason)
+    assert np.array_equal(a["queue_allocated_by_pc"], want.queue_allocated_by_pc) and np.array_equal(a["fair_share"], want.fair_share)
+    assert a["termination_reason"].tolist() == [want.termination_reason] and a["global_tokens_after"].tolist() == [want.global_tokens_after]
+
+
+def test_dump_outputs_samples_over_the_limit(fake_gpu, monkeypatch, tmp_path):
+    """over the size limit the per-job arrays keep a fixed sample of the jobs, the same jobs in every array, with the jobs named"""
+    import numpy as np
+    monkeypatch.setattr(fake_gpu, "DUMP_LIMIT", 64 * 1024)
+    m = 100_000
+    rng = np.random.default_rng(1)
+    jobs = np.sort(rng.choice(m, 4000, replace=False)).astype(np.int32)
+    res = type("R", (), dict(scheduled_job=jobs, scheduled_node=jobs % 97, scheduled_priority_arr=jobs % 3, scheduled_method_arr=np.ones(4000, np.int32),
+                             preempted_job=np.zeros(0, np.int32), preempted_node=np.zeros(0, np.int32), queue_allocated_by_pc=np.arange(96, dtype=np.int64).reshape(2, 3, 16),
+                             job_unschedulable_reason=np.arange(m, dtype=np.int32) % 5, fair_share=np.ones(2), demand_capped_adjusted_fair_share=np.ones(2),
+                             uncapped_adjusted_fair_share=np.ones(2), queue_tokens_after=np.zeros(2), termination_reason=3, num_evicted_phase1=0, num_evicted_phase3=0,
+                             global_tokens_after=1.5))
+    for run in ("a", "b"):
+        fake_gpu.dump_outputs(res, str(tmp_path / run))
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sum(x.nbytes for x in got.values()) <= 64 * 1024 and all(x.dtype == np.float64 and x.size > 0 for x in got.values())
+    idx = got["job_sample_index"].astype(np.int64)
+    assert len(idx) > 100 and np.all(np.diff(idx) > 0) and all(len(got[k]) == len(idx) for k in got if k.startswith("job_"))
+    node = np.full(m, -1); node[jobs] = jobs % 97
+    prio = np.zeros(m); prio[jobs] = jobs % 3
+    assert np.array_equal(got["job_scheduled_node"], node[idx]) and np.array_equal(got["job_scheduled_priority"], prio[idx])
+    assert np.array_equal(got["job_unschedulable_reason"], idx % 5) and np.all(got["job_preempted_node"] == -1)
+    assert got["queue_allocated_by_pc"].shape == (2, 3, 16) and got["global_tokens_after"].tolist() == [1.5]
+    assert all(np.array_equal(got[f], np.load(tmp_path / "b" / (f + ".npy"))) for f in got)   # the same sample every time
 
 
 def test_submit_check_bench_line(fake_gpu, monkeypatch, capsys):

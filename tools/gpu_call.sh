@@ -14,9 +14,9 @@ if [ "$KEXPR" != "none" ]; then
   else timeout 1800 python -m pytest tests -q -m gpu -p no:cacheprovider --durations=15 > "$OUT/pytest_gpu.log" 2>&1; fi
   echo "pytest rc=$?" | tee -a "$OUT/summary.txt"; tail -25 "$OUT/pytest_gpu.log" | tee -a "$OUT/summary.txt"
 fi
-timeout 1200 python bench.py --steps "$STEPS" --warmup 2 $EXTRA > "$OUT/bench_full.json" 2> "$OUT/bench_full.err"; echo "bench rc=$?" | tee -a "$OUT/summary.txt"
+timeout 1200 python bench.py --full --steps "$STEPS" --warmup 2 $EXTRA > "$OUT/bench_full.json" 2> "$OUT/bench_full.err"; echo "bench rc=$?" | tee -a "$OUT/summary.txt"
 # kernel stats of the same command (fewer steps, no oracle legs): k_control, k_fit_batch and k_control_aux rows in one table
-( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d "$OLDPWD/$OUT/prof_stats" -- python "$OLDPWD/bench.py" --steps 3 --warmup 1 --cpu-budget 0 $EXTRA > "$OLDPWD/$OUT/prof_stats.log" 2>&1 )
+( cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats -d "$OLDPWD/$OUT/prof_stats" -- python "$OLDPWD/bench.py" --full --steps 3 --warmup 1 --cpu-budget 0 $EXTRA > "$OLDPWD/$OUT/prof_stats.log" 2>&1 )
 DB=$(find "$OUT/prof_stats" -name "*.db" | head -1); [ -n "$DB" ] && python tools/rocprof_summary.py "$DB" "$OUT/kernel_stats.csv" > /dev/null
 for C in FETCH_SIZE WRITE_SIZE; do
   ( cd /tmp && timeout 900 rocprofv3 --pmc $C --kernel-trace -d "$OLDPWD/$OUT/pmc_$C" -- python "$OLDPWD/bench.py" --steps 1 --warmup 0 --cpu-budget 0 --no-other $EXTRA > "$OLDPWD/$OUT/pmc_$C.log" 2>&1 )
