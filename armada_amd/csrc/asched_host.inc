@@ -1,7 +1,7 @@
 // asched_host.inc — host side of the C ABI (include/armada_sched.h): input marshalling (string-free static
 // matching per (requirement class x node), scheduling-key shapes, pre-sorted job order, key packing), upload
 // to HBM, kernel launches and result download.  All scheduling arithmetic runs in the kernels
-// (round_ctl.h / round_run.h / armada_sched.hip); nothing here computes a placement.
+// (round_ctl.h / round_run.h / round_kernel.h); nothing here computes a placement.
 //
 // Included by armada_sched.hip (the product, HIP/gfx950) and by tests/hostsim/hostsim.cpp (debug build of the
 // same control code for a GPU-less container).  The platform layer (plat_*) is provided by the includer.
@@ -203,8 +203,6 @@ struct asched {
   uint64_t stateEpoch = 1, optIndexEpoch = 0;   // stateEpoch: bumped by everything that can change which job sits on which node (control launches, round phases, uploads); the optimiser's
                                                 // node -> jobs index is rebuilt when it is older
   bool argsOverflow = false;     // the last setArgs did not fit the command mailbox: runControl refuses the command
-  long lastPreemptFast = 0;   // jobs that needed preemption and stayed in the fast loop in this handle's previous round (round_stats preempt_fast_iterations)
-  bool ftEligible = false;   // the job / node set admits a fair-share threshold table (buildFast); allocated by ensureFt when the pool needs it
   long long* commStatus = nullptr;   // one device word: the status all-reduce in front of every collective (collectiveAgree)
   struct { bool valid = false; EvKey* key = nullptr; QsIn* in = nullptr; int64_t* part = nullptr; int32_t* len = nullptr; QsSave* save = nullptr; } qsOrig;   // the QCAPF-sized stream buffers of jobs_set while a wide round uses Q-sized ones
   bool haveRoundResult = false;  // d.resJob / resNode / resPreJob hold the last round's lists (round_delta reads them on the device)
@@ -536,38 +534,6 @@ int rebuildMasks(asched* h) {
   return buildFast(h, classMask);
 }
 
-// the fair-share threshold table (round_ft.h): one int32 per (scheduling-key shape, node) + its two levels of maxima (freed with the fast-path tables)
-static void allocFt(asched* h) {
-  Dev& d = h->dev;
-  int S = h->S, N = h->N;
-  d.ftS = S; d.ftNB1 = (N + 63) / 64;
-  d.ftT = h->fastBufs.alloc<int32_t>((size_t)S * d.cfg.Npad);
-  d.ftB1 = h->fastBufs.alloc<int32_t>((size_t)S * d.ftNB1);
-  d.ftB2 = h->fastBufs.alloc<int32_t>((size_t)S * 64);
-  std::vector<int32_t> prio(S);
-  for (int s = 0; s < S; s++) prio[s] = h->pcPriority[h->shapePc[s]];
-  d.ftPrio = h->fastBufs.upload(prio);
-}
-// round_prepare: does this pool's round run on the round kernel with the table (k_control_ft)?  Worth it where a wide pass per preempting job is expensive and preempting jobs
-// are many (measured: BASELINE configs[4] at 100 000 nodes; slower at 20 000): from ASCHED_FT_MIN_NODES nodes on (default 50 000) once the handle's PREVIOUS round kept at
-// least ASCHED_FT_MIN_PREEMPT (default 2 000) preempting jobs in the fast loop.  Results do not depend on it (both kernels compute the reference's round).  ASCHED_FT=0: never.
-static void ensureFt(asched* h) {
-#ifndef ASCHED_HOSTSIM
-  Dev& d = h->dev;
-  if (d.ftT || !h->ftEligible) return;
-  if (const char* e = getenv("ASCHED_FT")) if (e[0] == '0' || e[0] == '1') return;   // (1: allocated by buildFast already)
-  // Off unless asked for (ASCHED_FT=1, or ASCHED_FT_MIN_NODES / _MIN_PREEMPT for the automatic variant): measured in round 5 with the table in a code object of its own
-  // (k_control_ft), configs[4] took 10.58 s with it against 10.27 s without (reduced shape 1942 against 1738 ms, profiles/r05y_ab_first_park_resume.txt): the fair-share
-  // selects fall from 8.8 M to 1.4 M kilo-ticks, but every preempting job for which the table finds no node still pays a wide pass for the gate and the urgency sweep
-  // (6 M kilo-ticks) and the node updates cost 2 M more.  It starts to pay when the gate / urgency questions are index lookups too (DESIGN.md 9).
-  long minNodes = LONG_MAX, minPre = 2000;
-  if (const char* e = getenv("ASCHED_FT_MIN_NODES")) minNodes = atol(e);
-  if (const char* e = getenv("ASCHED_FT_MIN_PREEMPT")) minPre = atol(e);
-  if (h->N >= minNodes && h->lastPreemptFast >= minPre) allocFt(h);
-#else
-  (void)h;
-#endif
-}
 // Fast path tables (round_fast.h): exactness conditions, per-shape packed key deltas, JobRec array, node class bits, base buffers.
 // Called from rebuildMasks once nodes and jobs are both known.
 int buildFast(asched* h, const std::vector<uint64_t>& classMask) {
@@ -590,30 +556,10 @@ int buildFast(asched* h, const std::vector<uint64_t>& classMask) {
   f.E = std::min<int>((int)extra.size(), MAXE);
   for (int e = 0; e < f.E; e++) f.extraCol[e] = extra[e];
   // one multi-level plane pass for the gate + urgency sweep: planes monotone in the level, and room for a level tag above the packed key
-  const bool twoWords = d.cfg.keyWords == 2;   // two-word order keys (layoutKeys): the generic path of k_control_wk serves the handle — no fast structure, no fused pass, no threshold table
+  const bool twoWords = d.cfg.keyWords == 2;   // two-word order keys (layoutKeys): the generic path of k_control_wk serves the handle — no fast structure, no fused pass
   if (twoWords) ok = false;
   f.cascadeFuse = !twoWords && !h->hasAllocByPrio && reqNonNeg && K > 0 && d.cfg.keyShift[0] + d.cfg.keyWidth[0] + d.cfg.keyGuard <= SCAN_LEVEL_SHIFT && h->P <= 15;
   if (const char* e = getenv("ASCHED_NO_CASCADE_FUSE")) if (e[0] == '1') f.cascadeFuse = 0;
-  // fair-share threshold table (round_ft.h): one int32 per (scheduling-key shape, node) + its two levels of maxima.  Worth its memory where a wide pass per
-  // preempting job is expensive: from ASCHED_FT_MIN_NODES nodes on (default 4096; ASCHED_FT=0 never, ASCHED_FT=1 always; the CPU build of the tests: always)
-  d.ftT = nullptr; d.ftB1 = nullptr; d.ftB2 = nullptr; d.ftPrio = nullptr; d.ftS = 0; d.ftNB1 = 0;
-  {
-    long minNodes = 4096;
-#ifdef ASCHED_HOSTSIM
-    minNodes = 0;
-#endif
-    if (const char* e = getenv("ASCHED_FT_MIN_NODES")) minNodes = atol(e);
-    bool want = N >= minNodes;
-    if (const char* e = getenv("ASCHED_FT")) want = e[0] == '1' ? true : e[0] == '0' ? false : want;
-#if !defined(ASCHED_HOSTSIM)
-    // The product: the default round kernel is built WITHOUT the table (round_ctl.h ASCHED_NO_FT: its call sites cost the headline 2-3 % by placement); a second build of the
-    // round kernel that has it lives in its own code object (armada_sched_ft.hip) and is launched for rounds of a handle that carries a table.  ASCHED_FT=1: always;
-    // otherwise the table is allocated by round_prepare (ensureFt) once the pool has shown that it needs it.
-    { const char* e = getenv("ASCHED_FT"); want = e && e[0] == '1'; }
-#endif
-    h->ftEligible = f.cascadeFuse && !d.cfg.disableFair && S > 0 && S <= FT_MAXS && N > 0 && N <= 64 * 64 * 64 && M > 0;
-    if (want && h->ftEligible) allocFt(h);
-  }
   for (int c = 0; c < K && !twoWords; c++) {
     int w = d.cfg.keyWidth[c];
     f.fieldMask[c] = (w >= 64 ? ~0ull : ((1ull << w) - 1)) << d.cfg.keyShift[c];
@@ -1916,7 +1862,6 @@ static int64_t multiplyResource(int64_t res, double m) {  // resource_list.go:31
 int32_t asched_round_prepare(asched_t* h, const asched_queues* in) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
   if (h) { h->haveRoundResult = false; h->stateEpoch++; }
   if (!h->nodesSet || !h->jobsSet) return fail(h, ASCHED_ERR_INVALID, "round_prepare: nodes_upsert and jobs_set first");
-  ensureFt(h);
   h->queueBufs.recycle();
   h->allocPristine = false;   // populateNodeDb binds the running jobs
   HostProf prof("round_prepare");
@@ -2374,7 +2319,6 @@ static int runRoundSplit(asched* h, int32_t* io) {
   }
   double t[3]; plat_round_times(t);
   h->roundTotalMs = t[0]; h->roundControlMs = t[1]; h->roundLaunches = (int)t[2];
-  h->lastPreemptFast = h->rsHost.statHybrid;
   io[0] = n1; io[1] = n3; io[2] = ns; io[3] = np;
   return 0;
 }
@@ -2556,7 +2500,7 @@ int32_t asched_round_stats(asched_t* h, int32_t* out) { if (!h) return ASCHED_ER
   const RoundScalars& r = h->rsHost;
   for (int i = 0; i < 24; i++) out[i] = 0;
   out[20] = r.statHybrid;
-  out[21] = r.statFt[0]; out[22] = r.statFt[1]; out[23] = r.statFt[2];   // fair-share threshold table (round_ft.h): queries, validation retries, node updates
+  // out[21..23]: reserved, always 0
   out[0] = r.statFastIters; out[1] = r.statGenericIters; out[2] = r.statScanSteps; out[3] = r.statRefills; out[4] = r.statL0Max;
   out[5] = r.statFastReplay; out[6] = r.fastOverflow; out[7] = r.fastActive;
   out[16] = r.statStreamRuns; out[17] = r.statStreamJobs; out[18] = r.statStreamPrepared; out[19] = r.statStreamEmitted;

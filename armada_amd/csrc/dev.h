@@ -70,9 +70,18 @@ struct DevCfg {
   int32_t keyWords;      // 2: the order key is TWO words (asched_host.inc layoutKeys: more than 64 bits of fields).  `keys` then holds [2][P][Npad]: the high words of every level,
                          // then the low words (node-index rank in the low idxBits of the LOW word); keyShift[c] >= 64 names a field of the high word.  (In the slot of a pad word.)
 };
-// Node-sharded wide passes (shardWorld above): compiled into the CPU build and k_control_wk only.
-#if defined(ASCHED_HOSTSIM) || defined(ASCHED_WK_TU)
+// Features of the round kernel that not every code object carries: each .hip file that includes round_kernel.h sets the ones its code object has
+// (armada_sched_aux.hip, armada_sched_wk.hip); the CPU build of the tests (tests/hostsim) has all of them.
+//   ASCHED_MARKET_ROUND     market-driven rounds (round_mkt.h)
+//   ASCHED_TWO_WORD_KEYS    order keys of two words (WIDE_KEYS below)
+//   ASCHED_SHARDED_PASSES   wide passes sharded across GPUs (SHARD_ON below)
+#ifdef ASCHED_HOSTSIM
+#define ASCHED_MARKET_ROUND 1
+#define ASCHED_TWO_WORD_KEYS 1
 #define ASCHED_SHARDED_PASSES 1
+#endif
+// Node-sharded wide passes (shardWorld above).
+#ifdef ASCHED_SHARDED_PASSES
 #define SHARD_ON(cfg) ((cfg).shardWorld > 1)
 #define SHARD_LO(cfg) (SHARD_ON(cfg) ? (int)((long long)(((cfg).N + 63) >> 6) * (cfg).shardRank / (cfg).shardWorld) * 64 : 0)
 #define SHARD_HI(cfg) (SHARD_ON(cfg) ? ((cfg).shardRank + 1 == (cfg).shardWorld ? (cfg).N : (int)((long long)(((cfg).N + 63) >> 6) * ((cfg).shardRank + 1) / (cfg).shardWorld) * 64) : (cfg).N)
@@ -87,12 +96,8 @@ struct DevCfg {
 #define XCHG_WORD0 8
 // Two-word order keys are served by the generic path of a round kernel of their own (armada_sched_wk.hip: k_control_wk, k_bulk_wk): in every other device code object the
 // test below is a compile-time `false`, so the one-word kernels carry none of it (their ISA is what it was); the CPU build of the tests decides per handle.
-#if defined(ASCHED_HOSTSIM)
-#define WIDE_KEYS(cfg) ((cfg).keyWords == 2)
-#define ASCHED_TWO_WORD_KEYS 1
-#elif defined(ASCHED_WK_TU)
+#ifdef ASCHED_TWO_WORD_KEYS
 #define WIDE_KEYS(cfg) ((cfg).keyWords == 2)   // (k_control_wk also serves one-word handles whose wide passes are sharded across GPUs: SHARD_ON)
-#define ASCHED_TWO_WORD_KEYS 1
 #else
 #define WIDE_KEYS(cfg) false
 #endif
@@ -134,7 +139,7 @@ struct ShapeReq { uint64_t fieldMin; int64_t ex0, ex1; int32_t cls, never; };
 // Level-0 ("fit without preemption", priority -2) fast structure, DESIGN.md "Sorted base + LDS delta".
 struct FastCfg {
   int structOk, iterOk;       // host-verified exactness conditions (asched_host.inc: fastConditions); iterOk: 1 = fast iterations (Q <= QCAPF, round_fast.h), 2 = wide runs (Q > QCAPF, round_wide.h)
-  int relocAll;               // ASCHED_RELOC_ALL=1: stage the per-queue arrays in LDS for any Q (default: only Q <= 64, see armada_sched.hip relocateIn)
+  int relocAll;               // ASCHED_RELOC_ALL=1: stage the per-queue arrays in LDS for any Q (default: only Q <= 64, see round_kernel.h relocateIn)
   int cascadeFuse;            // the gate + urgency sweep of one job may run as ONE multi-level plane pass (round_ctl.h selectAtPriority): planes are monotone in the level (no explicit alloc_by_prio, non-negative requests) and a level tag fits above the packed key
   int F;                      // fit shapes: distinct (key fields, extras, requirement class) among the scheduling-key shapes — what node selection at priority -2 depends on;
                               // JobRec.shape, the candidate cache, the shape table and the fit masks are indexed by fit shape (scheduling keys that differ only in the
@@ -182,9 +187,11 @@ struct RoundScalars {
   int64_t totalNewJobNs;     // sctx.TotalNewJobSchedulingTime (context/scheduling.go:212-240)
   int32_t optMode;           // the fairness optimiser's candidate iteration is running: a job popped from a queue keeps the failure reason of an earlier attempt until its new
                              // jctx is added to the scheduling context (qctx.addJobSchedulingContext drops the old one there, context/queue.go:235-237)
-  int32_t ftWanted;          // this launch may build / use the threshold table (a scheduling pass of a round: set by the pass, cleared at kernel start)
-  int32_t ftValid;           // the fair-share threshold table (round_ft.h) describes the current planes + evicted table (an upper bound per entry); cleared with fairIndexValid and at every launch
-  int32_t statFt[3];         // threshold table: queries, validation retries, node updates
+  // The fair-share threshold table's words; the table is gone.  This struct is copied into the round kernel's LDS, so it keeps its layout, and the
+  // kernels keep their stores to the two flags (nothing reads them any more): their code is instruction for instruction what it was.  Compacting the struct and
+  // dropping the stores is a change of its own, measured on its own.
+  int32_t ftWanted, ftValid;   // written, never read
+  int32_t reserved[3];         // always 0
   int64_t statSeg[40];       // [24..39]: (profiling builds) segments of the generic iteration
   int64_t gsT;                     // (profiling builds) shader-clock ticks per segment of a fast iteration
   int64_t statClk[8];        // shader-clock ticks per phase of the round (device builds): evict, replay, pass 1, oversub evict, pass 2, unbind+results
@@ -362,12 +369,11 @@ struct Dev {
   int32_t* fairEnt;      // [M] evicted-table Index
   int32_t* fairEntJob;   // [M] its job
   int32_t* fairPart;     // [FAIR_CHUNKS+1] chunk sums of the offset scan
-  // fair-share threshold table (round_ft.h): T[s][n] = fairNodeBest of scheduling-key shape s on node n, its maxima per 64 / 4096 nodes; NULL = not in use
-  int32_t* ftT;          // [ftS][Npad]
-  int32_t* ftB1;         // [ftS][ftNB1]
-  int32_t* ftB2;         // [ftS][64]
-  int32_t* ftPrio;       // [ftS] priority a job of the shape asks with (its priority class's)
-  int32_t ftS, ftNB1;
+  // The fair-share threshold table's arrays; the table is gone.  Dev is copied into the round kernel's LDS and passed as a kernel argument, so it keeps
+  // its layout (and controlMain its test of ftT, which the host never sets) until a change that compacts it is measured on its own.
+  int32_t* ftT;                // always NULL
+  int32_t* reservedP[3];       // always NULL
+  int32_t reservedI[2];        // always 0
   uint8_t *optSched, *optPre;   // [M] how often the fairness optimiser scheduled / preempted a job in this round: its result lists are merged into the round's at the END
                          // of its phase (pqs.go:232-249), where a job it scheduled, preempted, scheduled again and preempted again comes out preempted
   int32_t* optGhost;     // [M] -1, or the node on which a job the optimiser has bound elsewhere STILL holds its evicted resources: scheduled earlier in the round, evicted by the

@@ -1,4 +1,4 @@
-// engine_hc.h — the node engine of a bulk-merged stream run (device only; included by armada_sched.hip).
+// engine_hc.h — the node engine of a bulk-merged stream run (device only; included by round_kernel.h).
 //
 // Why.  With the merge off the control wave (round_merge.h) the node engine is the round's only serial chain: first fit at priority -2 for one job after the other
 // (nodedb.go:737 -> 840-879), ~4.4 k shader clocks per job on BASELINE configs[2] (profiles/r05b_headline_engine_segments.txt: 1.9 k searching the LDS list of dirty
@@ -26,7 +26,7 @@
 //   HC_I  an entry H evicts (payload ring)                             it stays in H ("evicting") until wave 3's counter (HCB.insDone) covers it: no query can miss it
 //   HC_D  slot picked by the engine: the entry leaves C                HC_C  an evicting entry was picked while in flight: its insert is taken back
 //   HC_E  the session ends: compact the LDS list, publish its length
-// Every wait of this protocol reads the launch's `abandon` word (armada_sched.hip "bounded waits") and leaves through an exit its loop has anyway.
+// Every wait of this protocol reads the launch's `abandon` word (round_kernel.h "bounded waits") and leaves through an exit its loop has anyway.
 #pragma once
 
 #define HC_CMDS 32
@@ -132,7 +132,7 @@ template <int E> __device__ static void coldSession(Dev& d, KREF k) {
     LDS_ORDER();
     const int typeV = c.type, aV = c.a, seqV = c.seq;
     HcNeed q; q.fmin = c.fieldMin; q.ex0 = c.ex0; q.ex1 = c.ex1; q.cls = c.cls;   // (every lane reads the same words)
-    if (__builtin_amdgcn_readfirstlane(pubV) == done) { __builtin_amdgcn_s_sleep(1); if (waitGaveUp(spins)) return; continue; }   // (a wait given up: armada_sched.hip "bounded waits")
+    if (__builtin_amdgcn_readfirstlane(pubV) == done) { __builtin_amdgcn_s_sleep(1); if (waitGaveUp(spins)) return; continue; }   // (a wait given up: round_kernel.h "bounded waits")
     spins = 0;
     if (debugHang > 0 && done == debugHang) { for (;;) { __builtin_amdgcn_s_sleep(1); if (waitGaveUp(spins)) return; } }   // (tests: a cold-set wave that stops answering; only the bounded waits end this)
 #ifdef ASCHED_FASTPROF
@@ -423,7 +423,7 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
   HcShapes sc; hcShapesLoad(k, sc);
   int total = __builtin_amdgcn_readfirstlane(g_fl.l0Count);   // dirty nodes alive (H + C): the list's high-water mark for round_stats
   int i = 0, fail = 0;
-  // (bounded waits, armada_sched.hip: a turn of a wait here reads the launch's `abandon` word — 0 or 1 — and leaves through an exit the loop has anyway; NO flag is carried
+  // (bounded waits, round_kernel.h: a turn of a wait here reads the launch's `abandon` word — 0 or 1 — and leaves through an exit the loop has anyway; NO flag is carried
   //  around the per-job loop: a bool live across this loop is a lane mask merged with three scalar instructions at every join, +5 % on the headline round)
   HcJobV cur; bool haveCur = false;
 #ifdef ASCHED_FASTPROF

@@ -206,21 +206,6 @@ DEV void updateKeys(Dev& d, int n) { for (int l = 0; l < d.cfg.P; l++) KEY(d, l,
 #define CTL_WAVE() false
 #define CTL_LANE() 0
 #endif
-DEV_COLD void ftUpdateNode(Dev& d, int n);   // round_ft.h: the fair-share threshold table follows every change the generic code makes to a node
-DEV_COLD int ftQuery(Dev& d, int s);
-DEV_COLD void ftAfterAbort(Dev& d, int undoCount);
-// The fair-share threshold table (round_ft.h) is NOT part of the default device build.  Measured on the MI355X (profiles/r03g_*): BASELINE configs[4] at full
-// size 17.2 -> 15.1 s per round, the same shape at 20k nodes 2.55 -> 2.70 s (half of the preempting jobs need urgency preemption, which still takes a wide
-// pass), and its mere presence in k_control costs the headline 2-3 % (code placement: profiles/r03f_*).  -DASCHED_WITH_FT builds it in; the CPU build of the
-// tests always has it (its logic is soaked against the oracle like everything else).
-#if !defined(ASCHED_WITH_FT) && !defined(ASCHED_HOSTSIM)
-#define ASCHED_NO_FT 1
-#endif
-#ifdef ASCHED_NO_FT
-DEV void ftTouch(Dev&, int) {}
-#else
-DEV void ftTouch(Dev& d, int n) { if (d.ftT && d.rs->ftValid) ftUpdateNode(d, n); }
-#endif
 DEV void updateKeysCtl(Dev& d, int n) {  // control-flow call sites (not the bulk rebuild)
 #ifdef ASCHED_TWO_WORD_KEYS
   if (CTL_WAVE()) { int l = CTL_LANE(); if (l < d.cfg.P) storeKey(d, l, n); }   // one level per lane
@@ -229,7 +214,6 @@ DEV void updateKeysCtl(Dev& d, int n) {  // control-flow call sites (not the bul
 #endif
   else updateKeys(d, n);
   fastTouch(d, n);
-  ftTouch(d, n);
 }
 
 DEV bool fitsAlloc(Dev& d, const int64_t* req, int level, int n) {  // DynamicJobRequirementsMet (is/nodedb/nodematching.go:194-197)
@@ -345,9 +329,6 @@ DEV void txnAbort(Dev& d, Txn& t) {
       d.rs->fairIndexValid = 0; d.rs->ftValid = 0;   // an entry comes back: the per-node index may have been built without it (ensureFairIndex)
     }
   }
-#ifndef ASCHED_NO_FT
-  if (d.ftT && d.rs->ftValid && d.rs->undoCount > 0) ftAfterAbort(d, d.rs->undoCount);   // (round_ft.h; out of line: txnAbort is inlined into the fast loop's preempting iteration)
-#endif
   d.rs->undoCount = 0;
 }
 
@@ -379,10 +360,7 @@ DEV double drf(Dev& d, const int64_t* a) {  // fairness.go:103-105 (float64, thi
 DEV void vadd(Dev& d, int64_t* a, const int64_t* b, int sign) { for (int r = 0; r < d.cfg.R; r++) a[r] += sign * b[r]; }
 
 // qctx.addJobSchedulingContext + sctx.AddJobSchedulingContext (context/queue.go:231-265, scheduling.go:410-434)
-// The market-driven round exists in the auxiliary kernel and the CPU build only (round_mkt.h): the round kernel's own translation unit compiles none of it.
-#if (defined(ASCHED_AUX_TU) || defined(ASCHED_WK_TU) || defined(ASCHED_HOSTSIM)) && !defined(ASCHED_MARKET_ROUND)
-#define ASCHED_MARKET_ROUND 1
-#endif
+// The market-driven round exists where ASCHED_MARKET_ROUND is set (round_mkt.h, dev.h): k_control compiles none of it.
 #include "round_mkt.h"
 DEV bool sctxAddJob(Dev& d, int job) {
   int q = d.jQueue[job], pc = d.jPc[job];
@@ -842,41 +820,6 @@ DEV_COLD int selectAtPriority(Dev& d, Ctl& c, int job) {
       // the replay of the evicted jobs is still deferred the two questions are asked one after the other as before — the replay runs loops of its
       // own and belongs where the reference runs it: after a gate that passed.
       ensureFairIndex(d);
-      // The threshold table (round_ft.h) answers the fair-share question for a home attempt of a queued job without a pass over the nodes.  A node found
-      // that way also passes the gate — its considered entries are evicted jobs, which no level above -2 counts: alloc[level] >= alloc[-2] + their requests
-      // >= the request — so the gate (counted as issued) needs no scan.  No node: the gate and the urgency sweep take the multi-level pass as before.
-#ifndef ASCHED_NO_FT
-      if (d.ftT && d.rs->ftValid && !d.rs->awayRowPlus1 && !a.maskB && d.jShape[job] < d.ftS && d.ftPrio[d.jShape[job]] == sap) {
-        long long t1 = CLK();
-        int idx = ftQuery(d, d.jShape[job]);
-        d.rs->statClk[7] += CLK() - t1;
-        XSEG(33);
-        if (idx >= 0) {
-          d.rs->statClk[6] += CLK() - t0;
-          d.rs->numNodeQueries++;                      // the gate
-          d.pcNode[job] = -1; d.pcPap[job] = ASCHED_MIN_PRIORITY;
-          n = fairApply(d, c, job, idx, sap);
-          XSEG(34);
-          if (n >= 0) { d.pcMethod[job] = ASCHED_METHOD_FAIRSHARE; return n; }
-          return -1;                                   // (fairApply raised an error)
-        }
-        if (idx == -1) {   // no node can be freed by fair-share preemption: gate + urgency sweep in one multi-level scan
-          best = wgFirstFitKey(d, a);
-          d.rs->statClk[6] += CLK() - t0;
-          XSEG(23);
-          d.rs->numNodeQueries++;                      // the gate
-          if (best == ~0ull) return -1;
-          d.pcNode[job] = -1; d.pcPap[job] = ASCHED_MIN_PRIORITY;
-          if (d.cfg.disableUrgency) return -2 - d.nodeByRank[best & ((1ull << d.cfg.idxBits) - 1)];
-          int l = lp == 1 ? 1 : (int)(best >> SCAN_LEVEL_SHIFT);
-          d.rs->numNodeQueries += l;                     // levels 1 .. l of the sweep
-          n = d.nodeByRank[best & ((1ull << d.cfg.idxBits) - 1)];
-          d.pcNode[job] = n; d.pcPap[job] = d.cfg.prios[l]; d.pcMethod[job] = ASCHED_METHOD_URGENCY;
-          return n;
-        }
-        // idx == -2: the table was dropped (inconsistent maxima): the wide pass below answers
-      }
-#endif
       FairArgs fa;
       for (int r = 0; r < MAXR; r++) fa.req[r] = a.req[r];
       fa.maskA = a.maskA; fa.maskB = a.maskB; fa.prio = sap; fa.pad = 0;
@@ -1558,4 +1501,3 @@ DEV_COLD void replayEvicted(Dev& d, Ctl& c) {
   c.useReplayAlloc = 0; c.compareSchedPrio = savedCmp;
 }
 
-#include "round_ft.h"

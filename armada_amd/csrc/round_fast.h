@@ -24,7 +24,7 @@
 //  6. The loop (fastRun) is a separate, non-inlined function whose constants (FastK) and scheduling-context scalars
 //     (FastS) live in registers: an iteration is ~4 dependent LDS round trips instead of ~150.
 //
-// Lane-parallel primitives have a device (armada_sched.hip) and a host (tests/hostsim) implementation, same contract.
+// Lane-parallel primitives have a device (round_kernel.h) and a host (tests/hostsim) implementation, same contract.
 #pragma once
 #include "round_ctl.h"
 
@@ -122,7 +122,7 @@ static FastLds g_fl;
 #define DEV_NOINLINE static __attribute__((noinline))
 #else
 __shared__ FastLds g_fl;
-__shared__ RoundScalars g_rs;  // d.rs points here for the whole launch (relocateIn, armada_sched.hip)
+__shared__ RoundScalars g_rs;  // d.rs points here for the whole launch (relocateIn, round_kernel.h)
 #define FLANE ((int)(threadIdx.x & 63))
 #define HD __host__ __device__ static inline
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -194,7 +194,7 @@ int hsBindLag();
 #elif !defined(__HIP_DEVICE_COMPILE__)
 #define STREAM_IDLE() do {} while (0)
 #else
-DEV void streamIdle();   // armada_sched.hip: a short sleep + the bounded-wait bookkeeping
+DEV void streamIdle();   // round_kernel.h: a short sleep + the bounded-wait bookkeeping
 #define STREAM_IDLE() streamIdle()
 #endif
 DEV void uniQHot(QHot& f) {
@@ -408,7 +408,7 @@ DEV void fastEnsureLive(Dev& d, Ctl& c) { if (!c.fqLive) { fastQLoad(d); c.fqLiv
 struct EvDyn { int preempted; int fits; };
 #ifdef ASCHED_HOSTSIM
 #include "fast_serial.h"          // tests/hostsim/: serial stand-ins of the primitives below for the CPU build of the control code (test infrastructure)
-#else  // device versions: armada_sched.hip
+#else  // device versions: round_kernel.h
 struct PQState { uint32_t A, N; unsigned long long X, Y; int q; int count; };  // lane i: the i-th queue in heap order
 DEV void pqBuild(PQState& s, int Q);
 DEV int pqHead(PQState& s, int Q);

@@ -12,7 +12,7 @@
 #pragma once
 #ifdef ASCHED_MARKET_ROUND
 
-// the market state of the launch in progress: a kernel argument of the auxiliary kernel kept in its LDS (armada_sched.hip g_mk), a global of the CPU build
+// the market state of the launch in progress: a kernel argument of the auxiliary kernel kept in its LDS (round_kernel.h g_mk), a global of the CPU build
 DEV MktDev* mktDev();
 #define MKD (*mktDev())
 #define MKS (*mktDev()->s)

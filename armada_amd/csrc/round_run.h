@@ -16,8 +16,10 @@ enum BulkKind {
 };
 
 DEV void wgBulk(Dev& d, int kind, int n);  // every element i in [0,n) through bulkElem(), then a workgroup barrier
-DEV void wgFtBuild(Dev& d, int phase, int n);  // one pass of the fair-share threshold table's build (round_ft.h ftBuildAny), helper workgroups included
 DEV void wgBulkWide(Dev& d, int kind, int n);  // the same with the helper workgroups taking their share (bodies that touch HBM only)
+#ifdef ASCHED_HOSTSIM
+void ftBuildAny(Dev& d, int phase, int i);  // never defined, never called: the CPU harness of earlier trees (tests/hostsim) still defines an unused wrapper over it
+#endif
 #include "round_wide.h"
 #include "round_merge.h"
 DEV int wgCompactFlagged(Dev& d, const int32_t* order, const int32_t* segOff, int nseg, int n, const uint8_t* flag, int32_t* dst, int32_t* outSegOff);
@@ -500,27 +502,8 @@ DEV void schedulePass(Dev& d, Ctl& c, bool withQueued, bool skipKey, bool cmpPri
                                   //  rebuilds give the same time inside the passes, and a rebuild costs 4.5 ms at 900 000 table entries: 17.3 / 14.7 / 14.1 / 13.7 s per round)
 #endif
 #endif
-// The threshold table from the planes and the evicted table as they are now: three grid-wide passes shared with the helper workgroups.  They have an op of their
-// own (wgFtBuild) instead of three more kinds in bulkElem: a call inside that switch cost the stream preparation 3-5 % of the headline round (measured, profiles/r03f).
-#ifndef ASCHED_NO_FT
-DEV void ftBuild(Dev& d) {
-#ifdef ASCHED_HOSTSIM
-  { static long builds = 0; static const bool st = getenv("HS_FT_STATS") != nullptr; if (st && (++builds % 100) == 1) fprintf(stderr, "ftBuild %ld (queries %d retries %d node updates %d)\n", builds, d.rs->statFt[0], d.rs->statFt[1], d.rs->statFt[2]); }
-#endif
-  wgFtBuild(d, 0, d.cfg.N * ((d.ftS + FT_CHUNK - 1) / FT_CHUNK));
-  wgFtBuild(d, 1, d.ftS * d.ftNB1);
-  wgFtBuild(d, 2, d.ftS * 64);
-  d.rs->ftValid = 1;
-#ifdef ASCHED_FT_COUNT_BUILDS
-  d.rs->statFt[1] += 1000;   // (experiment builds: table builds show in ft_retries as thousands)
-#endif
-}
-#endif
 DEV_COLD void ensureFairIndex(Dev& d) {
   const bool periodic = d.rs->fairIndexValid && ++d.accEpoch_unused >= FAIR_REBUILD_EVERY;   // (queries since the last build: a counter of this launch, in the descriptor's LDS copy)
-#ifndef ASCHED_NO_FT
-  if (d.rs->fairIndexValid && !periodic) { if (d.ftT && !d.rs->ftValid && d.rs->ftWanted) ftBuild(d); return; }
-#endif
   if (d.rs->fairIndexValid && !periodic) return;
   d.accEpoch_unused = 0;
   int E = d.rs->evictedTableSize, N = d.cfg.N;
@@ -534,9 +517,6 @@ DEV_COLD void ensureFairIndex(Dev& d) {
   wgBulk(d, B_FAIR_SCATTER, E);
   wgBulk(d, B_FAIR_SORT, N);
   d.rs->fairIndexValid = 1;
-#ifndef ASCHED_NO_FT
-  if (d.ftT && d.rs->ftWanted) ftBuild(d);
-#endif
 }
 
 DEV void swapLoopArrays(Dev& d) {
@@ -1294,7 +1274,7 @@ DEV void controlMainAux(Dev& d, int cmd) {
   c.txn.active = d.rs->txnActive; c.fairStamp = d.rs->fairStamp; c.preList = d.preList; c.preCount = 0;
   c.skipKeyCheck = 0; c.compareSchedPrio = 0; c.preferLarge = d.cfg.preferLarge; c.useReplayAlloc = 0; c.onlyEvicted = 0;
   c.fastEnabled = 0; c.fastEvStatic = 0; c.l1Dirty = 0; c.fqLive = 0; c.skipEnter = 0; c.skipActive = 0; c.cancelSeen = 0; c.fpLimitHit = 0; c.streamNextAt = 0; c.streamBackoff = 0; c.streamCap = QS_CMAX;
-  d.rs->ftValid = 0; d.rs->ftWanted = 0;
+  d.rs->ftValid = 0; d.rs->ftWanted = 0;   // (dev.h RoundScalars: written, never read)
   fastLoad(d);
   runAuxCommand(d, c, cmd);
   fastEnterGeneric(d, c);
@@ -1308,8 +1288,7 @@ DEV void controlMain(Dev& d, int cmd) {
   c.fastEnabled = d.f.iterOk && !d.rs->apiDirty && (cmd == CMD_ROUND || cmd == CMD_QUEUES_ONLY || cmd == CMD_PASS1 || cmd == CMD_PASS2);
   if (d.jAway && (cmd == CMD_PASS2 || cmd == CMD_QUEUES_ONLY)) c.fastEnabled = 0;   // cross-pool away jobs can sit in the queues of these passes (the oversubscribed evictor takes them; a caller's queue-only pass): generic
   c.fastEvStatic = 0; c.l1Dirty = 0; c.fqLive = 0; c.skipEnter = 0; c.skipActive = 0; c.cancelSeen = 0; c.fpLimitHit = 0; c.streamNextAt = 0; c.streamBackoff = 0; c.streamCap = QS_CMAX;
-  // the fair-share threshold table (round_ft.h) lives for one launch of a scheduling pass: the grid-wide phases between launches rewrite planes wholesale
-  d.rs->ftValid = 0;
+  d.rs->ftValid = 0;   // (dev.h RoundScalars, Dev: the threshold table's words, written, never read)
   d.rs->ftWanted = d.ftT != nullptr && !d.rs->apiDirty && (cmd == CMD_ROUND || cmd == CMD_QUEUES_ONLY || cmd == CMD_PASS1 || cmd == CMD_PASS2);
   fastLoad(d);
   runCommand(d, c, cmd);

@@ -462,7 +462,7 @@ DEV_COLD void wideBulkAny(Dev& d, int kind, int i) {
 void hsEngineMustBeStopped(const char* what);   // tests/hostsim/hostsim.cpp: a wide op posted with the node engine live would hang the device
 DEV void wgWide(Dev& d, int kind, int n) { hsEngineMustBeStopped("wgWide"); for (int i = 0; i < n; i++) wideBulkAny(d, kind, i); }
 #else
-DEV void wgWide(Dev& d, int kind, int n);   // armada_sched.hip: the pass on the control workgroup and the helper workgroups (OP_WIDE)
+DEV void wgWide(Dev& d, int kind, int n);   // round_kernel.h: the pass on the control workgroup and the helper workgroups (OP_WIDE)
 #endif
 
 DEV_COLD int skipUnfeasibleBulk(Dev& d, int pos, int max) {

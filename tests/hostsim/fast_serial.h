@@ -1,6 +1,6 @@
 // Serial stand-ins of the lane-parallel primitives of armada_amd/csrc/round_fast.h for the CPU build of the device control code (tests/hostsim).
 // TEST INFRASTRUCTURE: included by round_fast.h only under ASCHED_HOSTSIM (this directory is on the include path of tests/hostsim/Makefile only);
-// the product (armada_sched.hip) has the wave-level versions.  One "lane" = one loop iteration (FOR_LANES), the node engine and the bind wave run inline.
+// the product (round_kernel.h) has the wave-level versions.  One "lane" = one loop iteration (FOR_LANES), the node engine and the bind wave run inline.
 struct PQState { int unused; };
 DEV int pqTopFast(int Q);
 DEV void pqBuild(PQState&, int) {}
@@ -145,7 +145,7 @@ DEV void applyEvictedRange(Dev& d, int q, int p0, int p1, int sign = 1) {
     if (sign < 0) {  // state of a job the evictor has just evicted (eviction.go:245-260, evictApply)
       k.jcHasPctx[job] = 0; k.pcNode[job] = -1; k.pcSap[job] = 0; k.pcPap[job] = ASCHED_MIN_PRIORITY; k.pcMethod[job] = ASCHED_METHOD_NONE;
       k.jobEvictedOnNode[job] = 1; k.jobFlags[job] = F_EVICTED; k.inPreempted[job] = 1;
-      if (!RS.replayPending) { int idx = k.evIdxByPos[p]; k.evTabAlive[idx] = 1; k.evIndexOfJob[job] = idx; RS.ftValid = 0; RS.fairIndexValid = 0; }   // (an entry comes back: round_ft.h "Staleness", ensureFairIndex)
+      if (!RS.replayPending) { int idx = k.evIdxByPos[p]; k.evTabAlive[idx] = 1; k.evIndexOfJob[job] = idx; RS.fairIndexValid = 0; }   // (an entry comes back: ensureFairIndex)
       continue;
     }
     k.jcReason[job] = 0; k.jcHasPctx[job] = 1; k.pcNode[job] = n; k.pcSap[job] = prio;

@@ -33,7 +33,7 @@ DEV void atomicMinU32(uint32_t* p, uint32_t v) { if (v < *p) *p = v; }
 DEV int atomicFetchAddI32(int32_t* p, int32_t v) { int o = *p; *p += v; return o; }
 void hsEngineMustBeStopped(const char* what);
 // sharded wide passes (dev.h shardWorld; asched_shard_round): this rank's share of the node words, then the all-reduce on the handle's communicator — here synchronously
-// through the caller's transport (the device posts the words to the host thread that drives the launch: armada_sched.hip shardReduce / plat_run_control)
+// through the caller's transport (the device posts the words to the host thread that drives the launch: round_kernel.h shardReduce, armada_sched.hip plat_run_control)
 static int plat_allreduce(long long* buf, size_t count, int op);
 static long g_shardExchanges = 0;
 static uint64_t hsShardMin(uint64_t v) {
@@ -81,7 +81,7 @@ DEV uint64_t wgFirstFitKey(Dev& d, const ScanArgs& a) {
       continue;
     }
     uint64_t k = KEY(d, a.level, n);
-    if (WIDE_KEYS(c)) {   // two-word keys: (high word, low word); the LOW word of the minimum is returned (armada_sched.hip wgFirstFitKey does it in two passes)
+    if (WIDE_KEYS(c)) {   // two-word keys: (high word, low word); the LOW word of the minimum is returned (round_kernel.h wgFirstFitKey does it in two passes)
       uint64_t lo = KEYLO(d, a.level, n);
       if (k < a.lowBound || (k == a.lowBound && lo < a.lowBoundLo)) continue;
       if (getenv("HOSTSIM_IGNORE_HIGH_WORD")) k = 0;   // negative control for the tests: a selection that compares low words only
@@ -111,7 +111,6 @@ DEV int wgFirstFit(Dev& d, const ScanArgs& a) {
 DEV int wgScanFair(Dev& d, const ScanArgs& a, const FairArgs& f, uint64_t* bestKey) { *bestKey = wgFirstFitKey(d, a); return wgFairSelect(d, f); }
 DEV void wgBulk(Dev& d, int kind, int n) { hsEngineMustBeStopped("wgBulk"); HsScope prof(kind); for (int i = 0; i < n; i++) bulkElem(d, kind, i); }
 DEV void wgBulkWide(Dev& d, int kind, int n) { wgBulk(d, kind, n); }
-DEV void wgFtBuild(Dev& d, int phase, int n) { hsEngineMustBeStopped("wgFtBuild"); for (int i = 0; i < n; i++) ftBuildAny(d, phase, i); }
 DEV int wgCompactFlagged(Dev& d, const int32_t* order, const int32_t* segOff, int nseg, int n, const uint8_t* flag, int32_t* dst, int32_t* outSegOff) {
   int cnt = 0, q = 0;
   for (int p = 0; p <= n; p++) {
@@ -125,7 +124,7 @@ DEV int wgCompactIota(Dev&, int n, const uint8_t* flag, int32_t* dst) { int c = 
 DEV int pqTop(Dev& d, const Ctl& c) {
   int best = -1;
   for (int q = 0; q < d.cfg.Q; q++) if (d.pqInHeap[q] && (best < 0 || pqLess(d, c, q, best))) best = q;
-  if (getenv("HOSTSIM_TOURNAMENT")) {  // the device's lane tournament (armada_sched.hip pqTop), emulated: must pick the same queue
+  if (getenv("HOSTSIM_TOURNAMENT")) {  // the device's lane tournament (round_kernel.h pqTop), emulated: must pick the same queue
     int lb[64];
     for (int lane = 0; lane < 64; lane++) { lb[lane] = -1; for (int q = lane; q < d.cfg.Q; q += 64) if (d.pqInHeap[q] && (lb[lane] < 0 || pqLess(d, c, q, lb[lane]))) lb[lane] = q; }
     for (int off = 32; off; off >>= 1) {

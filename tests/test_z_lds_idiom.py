@@ -57,7 +57,7 @@ def test_product_sources_fence_every_partial_lane_lds_store():
     read the word again: a source-level audit that fails when a new site forgets it"""
     csrc = os.path.join(HERE, "..", "armada_amd", "csrc")
     offenders = []
-    for fn in ("round_fast.h", "round_run.h", "armada_sched.hip"):
+    for fn in sorted(f for f in os.listdir(csrc) if f.endswith((".h", ".hip"))):
         lines = open(os.path.join(csrc, fn)).read().split("\n")
         for i, line in enumerate(lines):
             if not re.search(r"if \((FLANE|lane) == 0( && [^)]*)?\)", line) or "define " in line:

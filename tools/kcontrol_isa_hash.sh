@@ -1,7 +1,9 @@
 #!/usr/bin/env bash
 # sha256 of the disassembly of k_control (the round kernel) in a built library / object: two builds whose hashes agree run the same round-kernel code
 #   tools/kcontrol_isa_hash.sh [path/to/libarmada_sched.so | armada_sched.o]
+#   tools/kcontrol_isa_hash.sh --all [lib]   one hash per gfx950 code object, labelled by its kernels
 set -e
+ALL=0; if [ "$1" = --all ]; then ALL=1; shift; fi
 LIB=$(readlink -f "${1:-$(dirname "$0")/../armada_amd/csrc/libarmada_sched.so}")
 T=$(mktemp -d); trap 'rm -rf $T' EXIT
 BIN=/opt/rocm/lib/llvm/bin
@@ -22,9 +24,14 @@ for m in re.finditer(re.escape(magic), data):
             open(f'co{n}.o', 'wb').write(data[p + o:p + o + s]); n += 1
 PY
 for f in co*.o; do
-  if $BIN/llvm-readelf -s "$f" 2>/dev/null | grep -q " _Z9k_control3DeviP7HelpBoxi$"; then
-    # the whole text of the round kernel's code object — k_control and the out-of-line functions it calls — as instruction text (addresses and encodings stripped)
+  if [ $ALL = 1 ] || $BIN/llvm-readelf -s "$f" 2>/dev/null | grep -q " _Z9k_control3DeviP7HelpBoxi$"; then
+    # the whole text of the code object — its kernels and the out-of-line functions they call — as instruction text (addresses and encodings stripped)
     $BIN/llvm-objdump -d --no-show-raw-insn "$f" | grep -E "^\s+[a-z_0-9]+ " | sed -E 's/\/\/.*$//' > kc.txt
-    echo "round-kernel code object: $(wc -l < kc.txt) instructions, sha256 $(sha256sum kc.txt | cut -c1-16)"
+    if [ $ALL = 1 ]; then
+      K=$($BIN/llvm-readelf -sW --demangle "$f" | grep -F '(.kd)' | awk '{print $8}' | sed -E 's/\(.*//' | sort -u | paste -sd' ')
+      echo "${K}: $(wc -l < kc.txt) instructions, sha256 $(sha256sum kc.txt | cut -c1-16)"
+    else
+      echo "round-kernel code object: $(wc -l < kc.txt) instructions, sha256 $(sha256sum kc.txt | cut -c1-16)"
+    fi
   fi
 done
