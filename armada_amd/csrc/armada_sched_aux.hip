@@ -1,13 +1,15 @@
 // armada_sched_aux.hip — code object of k_control_aux: the submit-check commands (asched_submit_check; SURVEY 8f-2, internal/scheduler/submitcheck.go:342-371)
 // and market-driven rounds (round_mkt.h), one launch of ONE workgroup with no helpers.  Features: ASCHED_MARKET_ROUND.  A separate code object: whatever is
 // added to the auxiliary commands can never move a register, an LDS offset or an inlining decision in the round kernel, whose code is the measured one
-// (DESIGN.md 3.1, 10).  Device code only: the C ABI lives in armada_sched.hip.
+// (DESIGN.md 3.1, 10).  Device code only: the platform layer that launches it (plat_hip.inc) and the C ABI live in armada_sched.hip.
 #define ASCHED_MARKET_ROUND 1
 #undef HELP_TRACE   // (the trace variant instruments the round kernel only)
+#include <cstring>   // the launch wrappers (host code) at the end of this file
 #include "round_kernel.h"
 
 __global__ __launch_bounds__(CTL_THREADS) void k_control_aux(Dev dev, int cmd, HelpBox* box, MktDev mk) {
-  // workgroup 0 of k_control without helper workgroups: wave 0 runs the command, the other waves serve its mailbox
+  // workgroup 0 of k_control without helper workgroups: wave 0 runs the command, the other waves serve its mailbox.  Its own copy of round_body.h with two differences: the stride of a
+  // shared pass is blockDim.x, spelled in the OP_BULKW loop, and OP_WIDE is not served.  (Through round_body.h the code is equivalent but the object's register allocation moves.)
   if (threadIdx.x == 0) { g_box = box; g_H = 0; g_gen = 0; g_mk = mk; g_fl.eng.abandon = 0; g_fl.eng.idleSince = 0; g_fl.eng.idleLast = 0; g_fl.eng.idleProg = 0; }
   {
     const int* src = (const int*)&dev; int* dst = (int*)&g_dev;

@@ -1,6 +1,6 @@
 // armada_sched_mgpu.hip — third translation unit of libarmada_sched.so: grid kernels outside the round kernel's code object — the ones that produce and consume the words of the
 // multi-GPU exchanges, and since round 4 the submit check's gang units, one workgroup per unit (submit_gang.h): one element per thread over queries / result rows / nodes / jobs, all plain coalesced streaming
-// (the per-element logic is mgpu.h, shared with the CPU build of the tests).  A separate code object so that nothing here moves the
+// (the per-element logic is mgpu.h, shared with the CPU build of the tests; launched by plat_hip.inc through the extern "C" wrappers).  A separate code object so that nothing here moves the
 // round kernel's code (k_control is placement-sensitive: DESIGN.md 9).
 #include <hip/hip_runtime.h>
 #include <stdint.h>

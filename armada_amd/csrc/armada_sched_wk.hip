@@ -8,10 +8,11 @@
 //    fair-share evaluation look at this replica's share of the node words and exchange their two result words — through the host proxy or GPU-to-GPU.  One-word handles keep
 //    their fast path here (the whole round kernel is compiled in).
 //  * every control command of such a handle, the auxiliary ones and market-driven rounds included.
-// Device code only: the C ABI lives in armada_sched.hip.
+// Device code only: workgroup 0's body is round_body.h, shared with k_control; the platform layer that launches these kernels (plat_hip.inc) and the C ABI live in armada_sched.hip.
 #define ASCHED_TWO_WORD_KEYS 1
 #define ASCHED_SHARDED_PASSES 1
 #define ASCHED_MARKET_ROUND 1
+#include <cstring>   // the launch wrappers (host code) at the end of this file
 #include "round_kernel.h"
 
 __global__ __launch_bounds__(CTL_THREADS) void k_control_wk(Dev dev, int cmd, HelpBox* box, int H, MktDev mk) {
@@ -30,51 +31,9 @@ __global__ __launch_bounds__(CTL_THREADS) void k_control_wk(Dev dev, int cmd, He
   }
   if (blockIdx.x != 0) { helperMain(dev, box, H); return; }
   if (threadIdx.x == 0) { g_box = box; g_H = H; g_gen = 0; g_fl.eng.abandon = 0; g_fl.eng.idleSince = 0; g_fl.eng.idleLast = 0; g_fl.eng.idleProg = 0; }
-  // the Dev descriptor (pointers + config) is staged in LDS once; every wave reads it from there
-  {
-    const int* src = (const int*)&dev; int* dst = (int*)&g_dev;
-    for (int i = threadIdx.x; i < (int)(sizeof(Dev) / sizeof(int)); i += blockDim.x) dst[i] = src[i];
-  }
-  __syncthreads();
-  Dev& d = g_dev;
-  relocateIn(d, cmd);
-  if (threadIdx.x >= 64) {  // worker waves: serve mailbox requests until OP_EXIT
-    for (;;) {
-      __syncthreads();
-      int op = g_mb.op;
-      if (op == OP_EXIT) break;
-      if (op == OP_SCAN) {
-        unsigned long long v = scanPart(d, g_mb.scan, threadIdx.x, (g_H + 1) * (int)blockDim.x);
-        if ((threadIdx.x & 63) == 0) g_mb.partial[threadIdx.x >> 6] = v;
-      } else if (op == OP_FAIR) {
-        int v = fairPart(d, g_mb.fair, threadIdx.x, (g_H + 1) * (int)blockDim.x);
-        if ((threadIdx.x & 63) == 0) g_mb.waveCount[threadIdx.x >> 6] = v;
-      } else if (op == OP_SCANFAIR) {
-        unsigned long long v = scanPart(d, g_mb.scan, threadIdx.x, (g_H + 1) * (int)blockDim.x);
-        int w = fairPart(d, g_mb.fair, threadIdx.x, (g_H + 1) * (int)blockDim.x);
-        if ((threadIdx.x & 63) == 0) { g_mb.partial[threadIdx.x >> 6] = v; g_mb.waveCount[threadIdx.x >> 6] = w; }
-      } else if (op == OP_BULK) {
-        bulkPart(d, g_mb.kind, g_mb.n);
-      } else if (op == OP_BULKW) {
-        int nthreads = (g_H + 1) * (int)blockDim.x; int kd = g_mb.kind, nn = g_mb.n;
-        for (int i = threadIdx.x; i < nn; i += nthreads) bulkElem(d, kd, i);
-        __threadfence();
-      }
-      else if (op == OP_WIDE) {
-        int nthreads = (g_H + 1) * (int)blockDim.x; int kd = g_mb.kind, nn = g_mb.n;
-        for (int i = threadIdx.x; i < nn; i += nthreads) wideBulkAny(d, kd, i);
-        __threadfence();
-      }
-      else if (op == OP_COMPACT) {
-        compactPart(d);
-      } else if (op == OP_ENGINE) {
-        if ((threadIdx.x >> 6) == 1) engineLoop(d); else if ((threadIdx.x >> 6) == 2) bindLoop(d); else if ((threadIdx.x >> 6) == 3 && d.f.engineHc) coldLoop(d);
-      }
-      __syncthreads();
-    }
-    relocateOut();
-    return;
-  }
+#define ROUND_STRIDE ((g_H + 1) * (int)blockDim.x)
+#define ROUND_SERVES_WIDE 1
+#include "round_body.h"
   if (cmd >= CMD_AUX_FIRST) controlMainAux(d, cmd); else
   controlMain(d, cmd);
   // GPU-to-GPU exchanges of this launch, for asched_shard_exchanges (the host counts the proxy's itself): the counter went on from the area's word
@@ -96,7 +55,7 @@ __global__ __launch_bounds__(256) void k_bulk_wk(Dev d, int kind, int n) {
   __syncthreads();
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) bulkElem(d, kind, i);
 }
-// k_fit_batch (armada_sched.hip) for a two-word key, one launch per word: pass 0 leaves the minimum HIGH word among a shape's fitting nodes in out[i][0],
+// k_fit_batch (kernels_fit.h) for a two-word key, one launch per word: pass 0 leaves the minimum HIGH word among a shape's fitting nodes in out[i][0],
 // pass 1 the minimum LOW word among the fitting nodes that carry it in out[i][1] (the node-index rank is in its low bits).
 #define FIT_TILE_WK 256
 __global__ __launch_bounds__(FIT_TILE_WK) void k_fit_batch_wk(Dev d, const int32_t* shapes, int nshapes, int level, unsigned long long* out, int pass) {

@@ -4,7 +4,8 @@
 // (round_ctl.h / round_run.h / round_kernel.h); nothing here computes a placement.
 //
 // Included by armada_sched.hip (the product, HIP/gfx950) and by tests/hostsim/hostsim.cpp (debug build of the
-// same control code for a GPU-less container).  The platform layer (plat_*) is provided by the includer.
+// same control code for a GPU-less container).  The platform layer (plat_*) is declared in plat.h and defined by
+// the includer before this file: plat_hip.inc in the product, hostsim.cpp itself in the CPU build.
 
 #include <algorithm>
 #include <cmath>
@@ -123,7 +124,7 @@ struct DevBufs {
 }  // namespace
 
 struct asched {
-  PlatCtx* plat = nullptr;   // device ordinal, launch stream, events, mailbox, cancel word of THIS handle (armada_sched.hip "platform layer")
+  PlatCtx* plat = nullptr;   // device ordinal, launch stream, events, mailbox, cancel word of THIS handle (plat_hip.inc)
   // ---- config
   int R = 0, K = 0, P = 0, npc = 0;
   std::vector<int32_t> indexedCol; std::vector<int64_t> indexedRes;

@@ -90,7 +90,7 @@ struct DevCfg {
 #define SHARD_LO(cfg) 0
 #define SHARD_HI(cfg) ((cfg).N)
 #endif
-// the exchange words of a sharded pass live behind the cancel word in the handle's host-mapped block (armada_sched.hip PlatCtx.cancelHost, 256 bytes): 64-bit words
+// the exchange words of a sharded pass live behind the cancel word in the handle's host-mapped block (plat_hip.inc PlatCtx.cancelHost, 256 bytes): 64-bit words
 // [8] request generation, [9..10] this rank's two words, [11] answer generation, [12..13] the reduced words.  The kernel posts, the host thread that waits for the launch
 // runs the all-reduce on the handle's communicator (RCCL over xGMI on a side stream, or the caller's transport) and answers.
 #define XCHG_WORD0 8

@@ -1,0 +1,99 @@
+// plat.h — the platform interface asched_host.inc is written against: declarations only.  Two implementations, each linked by name inside the one
+// translation unit that includes asched_host.inc: plat_hip.inc (the product: HIP streams, kernel launches, RCCL) and tests/hostsim/hostsim.cpp (the CPU
+// build of the tests: serial loops over the same per-element device functions).  PlatCtx is defined per build.  Default arguments live here only.
+// Included after the control code (round_run.h, round_opt.h, round_price.h: Dev, MktDev, OptArgs, PriceArgs, asched_allreduce_fn) and before the definitions.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+#include "round_opt.h"
+#include "round_price.h"
+
+struct PlatCtx;
+struct GlobalKeyLayout;   // mgpu.h
+
+// ---- context / errors.  One PlatCtx per handle; every ABI entry starts with plat_enter(handle context) and every other call works on the entered context.
+// plat_open leaves the new context entered; on failure it returns nullptr and fills err.  plat_last_error: the text of the last failure.
+static PlatCtx* plat_open(std::string& err, int device);
+static void plat_close(PlatCtx* c);
+static void plat_enter(PlatCtx* c);
+static const char* plat_last_error();
+static bool plat_take_failure();
+static int plat_wall_clock_khz();
+
+// ---- memory and copies.  Device (plat_malloc) and pinned host (plat_pinned) memory; plat_malloc returns nullptr on failure.  Copies and memsets return
+// nothing: a failure latches in the context and is read (and cleared) with plat_take_failure.  plat_d2h_async completes at plat_sync.
+static void* plat_malloc(size_t n);
+static void plat_free(void* p);
+static void plat_memset(void* p, int v, size_t n);
+static void plat_h2d(void* d, const void* s, size_t n);
+static void plat_d2h(void* d, const void* s, size_t n);
+static void plat_d2h_async(void* d, const void* s, size_t n);
+static void plat_sync();
+static void* plat_pinned(size_t n);
+static void plat_pinned_free(void* p);
+
+// ---- deadline and cancel.  plat_set_deadline(s): maxSchedulingDuration of every following round launch (0 = none).  plat_cancel / plat_cancel_clear take
+// the context explicitly: asched_cancel may come from another thread, without plat_enter.
+static void plat_set_deadline(double s);
+static void plat_cancel(PlatCtx* c);
+static void plat_cancel_clear(PlatCtx* c);
+
+// ---- control launches and the split round.  Everything below that returns int: 0, or -1 with the reason in plat_last_error.  plat_run_control runs one
+// command of the control code (controlMain / controlMainAux) to completion; plat_set_market_dev sets the market state of the next launch (nullptr: none).
+// Between plat_round_begin / plat_round_end the deadline runs from the begin and the launches are counted and timed (plat_round_times: total ms,
+// control ms, launches).  The grid-wide steps of the split round work on the HBM state between control launches.
+static void plat_set_market_dev(const MktDev* m);
+static int plat_run_control(Dev& dev, int cmd);
+static double plat_last_control_ms();
+static int plat_last_control_launches();
+static void plat_round_begin();
+static void plat_round_end();
+static void plat_round_times(double* out);
+static int plat_bulk(Dev& d, int kind, int n);
+static int plat_small(Dev& d, int what, int arg);
+static int plat_agg(Dev& d, int queued, int total);
+static int plat_evict_apply(Dev& d, int phase3, int total);
+static int plat_compact(Dev& d, const int32_t* order, int n, const uint8_t* flag, int32_t* dst, uint32_t* prefix, const int32_t* segOff, int nseg, int32_t* outSegOff, int* total);
+static int plat_build_base(Dev& d);
+
+// ---- optimiser and pricer.  plat_opt_score scores every node for one job (detailNode >= 0: that node's preemption list too).  detailOnly: the index and
+// scores of the previous call are still valid; reuseIndex: so is the node -> jobs index (nothing was bound since) — asched_host.inc decides, an
+// implementation may ignore both.  plat_opt_select: 0 = selected on the platform, 1 = not available, take the host loop over plat_opt_score.
+static int plat_opt_score(Dev& d, const OptArgs& a, std::vector<OptNodeOut>& scores, double* jobCost, int detailNode, OptNodeOut* detail, std::vector<int32_t>* pre,
+                          bool detailOnly = false, bool reuseIndex = false);
+static int plat_opt_select(Dev& d, const OptArgs& a, double minPct, bool reuseIndex, int32_t* node, int32_t* npre, double* cost, double* impact, std::vector<int32_t>* pre);
+static int plat_opt_qcosts(Dev& d, double* out, int Q);
+static double plat_last_opt_ms();
+static int plat_price_score(Dev& d, const PriceArgs& a, std::vector<PriceNodeOut>& scores, int detailNode, std::vector<int32_t>* pre);
+
+// ---- fit, submit check and goldens: queries against a fixed node state, synchronous (results are in the host vectors on return).
+static int plat_run_shape_mask(Dev& d, const uint64_t* classMask, const int32_t* shapeClass);
+static int plat_run_fit_batch(Dev& d, const std::vector<int32_t>& shapes, int level, std::vector<int32_t>& out, const int32_t* nodeByRankHost = nullptr);
+static int plat_run_fit_capacity(Dev& d, const std::vector<int32_t>& shapes, std::vector<int32_t>& firstNode, std::vector<long long>& capacity, const int32_t* nodeByRankHost);
+static int plat_run_submit_gangs(Dev& d, const std::vector<int32_t>& off, const std::vector<int32_t>& jobs, std::vector<int32_t>& out);
+static double plat_last_fit_ms();
+static int plat_run_drf(Dev& dev, const std::vector<int64_t>& a, const std::vector<int64_t>& t, double* out);
+static int plat_run_fair_shares(Dev& dev, int q, const int32_t* nameRank, const double* weight, const double* cds, double* fair, double* dc, double* uc);
+
+// ---- communicator and sharding.  One communicator per context (RCCL, or the caller's transport); without one plat_allreduce is a no-op that returns 0.
+// plat_allreduce reduces `count` int64 words in platform memory in place, ordered with the context's other work; op: 0 SUM, 1 MIN, 2 MAX.
+// An implementation without RCCL / exchange areas returns -1 from the calls it cannot serve.
+static int plat_comm_unique_id(char* out128);
+static int plat_comm_init(const char* id128, int rank, int world);
+static int plat_comm_init_external(asched_allreduce_fn fn, void* ctx, int rank, int world);
+static void plat_comm_destroy();
+static void plat_comm_info(int* rank, int* world);
+static bool plat_comm_live();
+static int plat_allreduce(long long* dbuf, size_t count, int op);
+static long plat_last_shard_exchanges();
+static int plat_shard_area(void** ptr, char* ipc64);
+static int plat_shard_open(const char* ipc64, void** out);
+static int plat_shard_peers(void* const* areas, int world, int rank);
+
+// ---- multi-GPU (mgpu.h, replay_rank.h): the words the collectives reduce are produced and consumed per element; buffers are platform memory.
+static int plat_run_fit_batch_global(Dev& d, const std::vector<int32_t>& shapes, const std::vector<int32_t>& slot, int level, GlobalKeyLayout L, const int32_t* globalRank, long long* out, int* badOut);
+static int plat_round_delta(Dev& d, int ns, int np, long long* buf);
+static int plat_delta_resolve(Dev& d, const long long* red, int ns, int np, int32_t* counts, int32_t* node, int32_t* prio, uint8_t* replay);
+static int plat_replay_rank(Dev& d, int n, int keepPending);

@@ -1,18 +1,11 @@
 // round_kernel.h — the device side that every round-kernel code object shares (armada_sched.hip k_control, armada_sched_aux.hip k_control_aux,
-// armada_sched_wk.hip k_control_wk): the control code (round_run.h and what it includes), the LDS mailbox of the worker waves, the helper workgroups'
+// armada_sched_wk.hip k_control_wk; workgroup 0's body of the first and the last is round_body.h): the control code (round_run.h and what it includes), the LDS mailbox of the worker waves, the helper workgroups'
 // HBM mailbox, the device primitives the control code calls (scans, bulk passes, compaction, fair-share evaluation), the fast path's primitives and
 // node engine, the LDS residency of the per-queue arrays and the helper workgroups' loop.  What a code object carries is decided by the feature
 // switches its .hip file sets before it includes this header (ASCHED_MARKET_ROUND, ASCHED_TWO_WORD_KEYS, ASCHED_SHARDED_PASSES: dev.h).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <chrono>
-#include <cstring>
 #include <type_traits>
-#include <string>
-#include <unistd.h>
-#include <vector>
-#include <dlfcn.h>
-#include <rccl/rccl.h>   // types and prototypes only: the functions are bound with dlsym at asched_comm_init (no link-time dependency on librccl)
 
 #define ASCHED_PREFIX asched_
 #include "round_run.h"

@@ -831,7 +831,7 @@ DEV void runCommand(Dev& d, Ctl& c, int cmd) {
       break;
     case CMD_ROUND: runRound(d, c); break;
     // The round as the host drives it by default: evictor filters, eviction, key rebuild, compaction, evicted-stream costs, unbind and the result
-    // lists run as ordinary grid-wide kernels over all CUs (armada_sched.hip k_bulk / k_evict_apply / k_cmp_*); only the two inherently
+    // lists run as ordinary grid-wide kernels over all CUs (kernels_split.h k_bulk / k_evict_apply / k_cmp_*); only the two inherently
     // sequential passes stay in this persistent kernel.  ARG(0) = number of jobs the evictor before this pass evicted.
     case CMD_PASS1: {  // pqs.go:149-166: schedule(evicted ++ queued); before it the tail of evict(): addEvictedJobsToNodeDb unless deferred
       long long t0 = CLK();

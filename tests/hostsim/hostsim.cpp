@@ -16,6 +16,7 @@
 #include "../../armada_amd/csrc/round_run.h"
 #include "../../armada_amd/csrc/round_opt.h"
 #include "../../armada_amd/csrc/round_price.h"
+#include "../../armada_amd/csrc/plat.h"   // the platform interface this file implements serially (plat_hip.inc: the product's)
 static thread_local MktDev g_mk;   // market-driven rounds (round_mkt.h): the market state of the launch in progress (a kernel argument on the device)
 DEV MktDev* mktDev() { return &g_mk; }
 // optional per-primitive wall-clock profile of the serial build (HOSTSIM_PROF=1): where would a wide device primitive matter?
@@ -33,8 +34,7 @@ DEV void atomicMinU32(uint32_t* p, uint32_t v) { if (v < *p) *p = v; }
 DEV int atomicFetchAddI32(int32_t* p, int32_t v) { int o = *p; *p += v; return o; }
 void hsEngineMustBeStopped(const char* what);
 // sharded wide passes (dev.h shardWorld; asched_shard_round): this rank's share of the node words, then the all-reduce on the handle's communicator — here synchronously
-// through the caller's transport (the device posts the words to the host thread that drives the launch: round_kernel.h shardReduce, armada_sched.hip plat_run_control)
-static int plat_allreduce(long long* buf, size_t count, int op);
+// through the caller's transport (the device posts the words to the host thread that drives the launch: round_kernel.h shardReduce, plat_hip.inc plat_run_control)
 static long g_shardExchanges = 0;
 static uint64_t hsShardMin(uint64_t v) {
   long long w = (long long)(v ^ 0x8000000000000000ull);
@@ -137,7 +137,7 @@ DEV int pqTop(Dev& d, const Ctl& c) {
   return best;
 }
 
-// ---- platform layer
+// ---- platform layer (plat.h), serially
 static std::string g_err;
 struct PlatCtx { int32_t cancelWord = 0; double deadlineS = 0; bool inRound = false; int launches = 0; asched_allreduce_fn extFn = nullptr; void* extCtx = nullptr; int commRank = 0, commWorld = 1; };   // per handle, like the device build's (stream / events / mailbox there)
 static thread_local PlatCtx* t_ctx = nullptr;
@@ -231,7 +231,7 @@ static int plat_run_shape_mask(Dev& d, const uint64_t* classMask, const int32_t*
   }
   return 0;
 }
-static int plat_run_fit_batch(Dev& d, const std::vector<int32_t>& shapes, int level, std::vector<int32_t>& out, const int32_t* = nullptr) {
+static int plat_run_fit_batch(Dev& d, const std::vector<int32_t>& shapes, int level, std::vector<int32_t>& out, const int32_t*) {
   for (size_t i = 0; i < shapes.size(); i++) {
     ScanArgs a; memset(&a, 0, sizeof a);
     for (int r = 0; r < d.cfg.R; r++) a.req[r] = d.shapeReq[(size_t)shapes[i] * d.cfg.R + r];
@@ -333,7 +333,7 @@ static int plat_delta_resolve(Dev& d, const long long* red, int ns, int np, int3
 // fairness optimiser: the per-node routine of round_opt.h over all nodes, serially
 static const double* g_lastQCost = nullptr;
 static int plat_opt_qcosts(Dev&, double* out, int Q) { for (int q = 0; q < Q; q++) out[q] = g_lastQCost[q]; return 0; }
-static int plat_opt_score(Dev& dev, const OptArgs& a, std::vector<OptNodeOut>& scores, double* jobCost, int detailNode, OptNodeOut* detail, std::vector<int32_t>* pre, bool detailOnly = false, bool reuseIndex = false) { (void)detailOnly; (void)reuseIndex;
+static int plat_opt_score(Dev& dev, const OptArgs& a, std::vector<OptNodeOut>& scores, double* jobCost, int detailNode, OptNodeOut* detail, std::vector<int32_t>* pre, bool detailOnly, bool reuseIndex) { (void)detailOnly; (void)reuseIndex;
   Dev d = dev;
   int N = d.cfg.N, M = d.cfg.M, Q = d.cfg.Q;
   std::vector<int32_t> off(N + 2, 0), jobs(2 * (size_t)std::max(M, 1));
@@ -347,7 +347,7 @@ static int plat_opt_score(Dev& dev, const OptArgs& a, std::vector<OptNodeOut>& s
   g_lastQCost = qCost.data();
   *jobCost = drf(d, JREQ(d, a.job));
   scores.resize(N);
-  // the device keeps OPT_MAXJ entries per thread and re-scores fuller nodes with a list in HBM (armada_sched.hip plat_opt_score); here: the private list first, the big list on overflow — the same two steps
+  // the device keeps OPT_MAXJ entries per thread and re-scores fuller nodes with a list in HBM (plat_hip.inc plat_opt_score); here: the private list first, the big list on overflow — the same two steps
   std::vector<OptEntry> big;
   auto score = [&](int n, OptNodeOut* o, int32_t* p) {
     optScoreNode(d, a, qCost.data(), off.data(), jobs.data(), d.jLeaseMs, n, o, p && off[n + 1] - off[n] <= OPT_MAXJ ? p : nullptr);

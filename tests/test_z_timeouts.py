@@ -195,7 +195,7 @@ def test_deadline_cancels_a_fast_path_round_in_flight(hip_lib, oracle_lib):
 
 @pytest.mark.gpu
 def test_deadline_ends_a_round_whose_node_engine_is_stuck(hip_lib, monkeypatch):
-    """Round 6 ("bounded waits", armada_sched.hip): ASCHED_DEBUG_HANG=<n> makes the cold-set wave of a bulk-merged stream run stop answering at its n-th command (the node engine then waits for it) — what a protocol
+    """Round 6 ("bounded waits", round_kernel.h): ASCHED_DEBUG_HANG=<n> makes the cold-set wave of a bulk-merged stream run stop answering at its n-th command (the node engine then waits for it) — what a protocol
     defect between the waves of the control workgroup looks like from outside (profiles/r05y_bulk_skip_hang.txt was one).  Every spin on the other side (the control wave's
     ring waits, the bind wave, the cold-set wave, the engine's own waits) counts its turns and looks at the caller's cancel word: with a deadline set the call returns
     ASCHED_ERR_TIMEOUT instead of hanging, and after a fresh round_prepare the handle computes the round a healthy launch computes."""
