@@ -5,7 +5,7 @@
 //   armada_sched.hip       k_control, the grid-wide kernels, the platform layer and the C ABI; no optional feature of the round kernel
 //   armada_sched_aux.hip   k_control_aux: the submit-check commands and market-driven rounds
 //   armada_sched_wk.hip    k_control_wk, k_bulk_wk, k_fit_batch_wk: two-word order keys, sharded wide passes, market-driven rounds
-//   armada_sched_mgpu.hip  the multi-GPU exchange, submit-gang and evicted-table-rank kernels
+//   armada_sched_mgpu.hip  the multi-GPU exchange, submit-gang, evicted-table-rank and literal first-fit (kernels_fit_lit.h) kernels
 // What this file is made of, in the order it includes them (kernel definition order is the code object's text order: keep it):
 //   round_kernel.h    device code every round kernel shares: the control code (round_run.h ...), the worker waves' LDS mailbox and its ops (OP_SCAN,
 //                     OP_BULK, OP_COMPACT, OP_FAIR, OP_ENGINE, ...), the helper workgroups' HBM mailbox, the fast path and node engine

@@ -1,5 +1,6 @@
 // armada_sched_mgpu.hip — third translation unit of libarmada_sched.so: grid kernels outside the round kernel's code object — the ones that produce and consume the words of the
-// multi-GPU exchanges, and since round 4 the submit check's gang units, one workgroup per unit (submit_gang.h): one element per thread over queries / result rows / nodes / jobs, all plain coalesced streaming
+// multi-GPU exchanges, since round 4 the submit check's gang units, one workgroup per unit (submit_gang.h), and the literal batched first fit, one wave per
+// query over a per-call index (kernels_fit_lit.h): one element per thread over queries / result rows / nodes / jobs, all plain coalesced streaming
 // (the per-element logic is mgpu.h, shared with the CPU build of the tests; launched by plat_hip.inc through the extern "C" wrappers).  A separate code object so that nothing here moves the
 // round kernel's code (k_control is placement-sensitive: DESIGN.md 9).
 #include <hip/hip_runtime.h>
@@ -156,5 +157,79 @@ extern "C" int asched_internal_fit_capacity(const Dev* d, const int32_t* shapes,
   int tiles = (d->cfg.N + 255) / 256;
   int ysplit = ns < 1 ? 1 : (ns < (2048 + tiles - 1) / tiles ? ns : (2048 + tiles - 1) / tiles);
   hipLaunchKernelGGL(k_fit_capacity, dim3(tiles, ysplit < 1 ? 1 : ysplit), dim3(256), 0, st, *d, shapes, ns, out);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ------------------------------------------------------------------------------------------------ literal batched first fit (kernels_fit_lit.h)
+#define FL_FN __device__ static inline
+#define FL_LANE ((int)(threadIdx.x & 63))
+#define FL_NL 64
+#define FL_BALLOT(p) ((unsigned long long)__ballot(p))
+#define FL_SHFL(v, l) __shfl(v, l, 64)
+#define FL_UNROLL _Pragma("unroll")
+#include "kernels_fit_lit.h"
+__global__ __launch_bounds__(MG_THREADS) void k_fit_lit_fill(Dev d, const int32_t* nodeType, int level, FlPair* a, int nb2) {
+  long long i = MG_IDX();
+  if (i < nb2) flFill(d, nodeType, level, a, (int)i);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_fit_lit_step(FlPair* a, int j, int k) {
+  unsigned i = blockIdx.x * MG_THREADS + threadIdx.x;
+  unsigned l = i ^ (unsigned)j;
+  if (l > i) {
+    FlPair x = a[i], y = a[l];
+    bool up = (i & (unsigned)k) == 0;
+    if (up ? flPairLess(y, x) : flPairLess(x, y)) { a[i] = y; a[l] = x; }
+  }
+}
+// the in-LDS part of the network (k_bitonic_tile's scheme on 16-byte records): every (k, j) step with j < FL_TILE for one tile of FL_TILE records
+__global__ __launch_bounds__(1024) void k_fit_lit_tile(FlPair* a, int kStart, int kEnd, int jStart) {
+  __shared__ FlPair t[FL_TILE];
+  unsigned base = blockIdx.x * (unsigned)FL_TILE;
+  for (int i = threadIdx.x; i < FL_TILE; i += 1024) t[i] = a[base + i];
+  __syncthreads();
+  for (int k = kStart; k <= kEnd; k <<= 1) {
+    for (int j = (k == kStart ? jStart : k >> 1); j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < FL_TILE; i += 1024) {
+        unsigned l = (unsigned)i ^ (unsigned)j;
+        if (l > (unsigned)i) {
+          FlPair x = t[i], y = t[l];
+          bool up = ((base + i) & (unsigned)k) == 0;
+          if (up ? flPairLess(y, x) : flPairLess(x, y)) { t[i] = y; t[l] = x; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = threadIdx.x; i < FL_TILE; i += 1024) a[base + i] = t[i];
+}
+__global__ __launch_bounds__(MG_THREADS) void k_fit_lit_finish(Dev d, FitLitIdx x, const FlPair* a) {
+  long long i = MG_IDX();
+  if (i < d.cfg.N) flFinish(d, x, a, (int)i);
+}
+// one wave per query (a workgroup IS one wave: the queries spread over every CU and no barrier is needed); the iterator states of its node types in LDS
+__global__ __launch_bounds__(64) void k_fit_lit(Dev d, FitLitIdx x, const int32_t* rows, int nq, int32_t* out) {
+  __shared__ FlIt its[LIT_TMAX];
+  for (int q = blockIdx.x; q < nq; q += gridDim.x) {
+    int r = flQuery(d, x, rows[q], its);
+    if (threadIdx.x == 0) out[q] = r;
+  }
+}
+// a [nb2] sort scratch, nb2 a power of two >= max(N, FL_TILE); typeBeg / typeEnd zeroed by the caller
+extern "C" int asched_internal_fit_lit_build(const Dev* d, const FitLitIdx* x, const int32_t* nodeType, FlPair* a, int nb2, hipStream_t st) {
+  int N = d->cfg.N;
+  if (N <= 0) return 0;
+  hipLaunchKernelGGL(k_fit_lit_fill, dim3(mgBlocks(nb2)), dim3(MG_THREADS), 0, st, *d, nodeType, x->level, a, nb2);
+  int tiles = nb2 / FL_TILE;
+  hipLaunchKernelGGL(k_fit_lit_tile, dim3(tiles), dim3(1024), 0, st, a, 2, FL_TILE, 1);   // all steps with k <= FL_TILE
+  for (int k = 2 * FL_TILE; k <= nb2; k <<= 1) {
+    for (int j = k >> 1; j >= FL_TILE; j >>= 1) hipLaunchKernelGGL(k_fit_lit_step, dim3(mgBlocks(nb2)), dim3(MG_THREADS), 0, st, a, j, k);
+    hipLaunchKernelGGL(k_fit_lit_tile, dim3(tiles), dim3(1024), 0, st, a, k, k, FL_TILE / 2);   // the remaining steps j = FL_TILE / 2 .. 1 inside tiles
+  }
+  hipLaunchKernelGGL(k_fit_lit_finish, dim3(mgBlocks(N)), dim3(MG_THREADS), 0, st, *d, *x, a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_fit_lit_query(const Dev* d, const FitLitIdx* x, const int32_t* rows, int nq, int32_t* out, hipStream_t st) {
+  if (nq <= 0 || d->cfg.N <= 0) return 0;
+  hipLaunchKernelGGL(k_fit_lit, dim3(nq < 65536 ? nq : 65536), dim3(64), 0, st, *d, *x, rows, nq, out);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

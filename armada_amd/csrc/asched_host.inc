@@ -24,6 +24,7 @@
 #include <atomic>
 #include <chrono>
 #include <thread>
+#include "kernels_fit_lit.h"   // FitLitIdx and, in the CPU build of the tests, plat_run_fit_batch_lit
 
 namespace {
 
@@ -179,6 +180,7 @@ struct asched {
   std::vector<int32_t> shapePc, awayRowOff, awayRowClass, awayRowShape;
   int Cext = 0;
   std::vector<uint8_t> rowLiteral;      // per mask row: the literal iterator restatement is needed (round_ctl.h selectAtLevelLiteral)
+  int32_t* dNodeType = nullptr;         // [N] node type per node on the device: the literal batched first fit sorts its index by it (kernels_fit_lit.h)
   std::vector<uint8_t> shapeUnaligned;  // per shape: some indexed request is not a multiple of its resolution
   std::vector<int32_t> nodeIdRank;
   bool jobsSet = false, nodesSet = false, prepared = false;
@@ -214,7 +216,7 @@ struct asched {
   int ordQueues = 0;   // number of queue segments in the pre-sorted job order (max queue index of the job table + 1)
   std::vector<int32_t> ordOffHost;   // host copy of dev.ordAllOff (segment offsets of the pre-sorted order)
   double roundTotalMs = 0, roundControlMs = 0, roundPhaseMs[4] = {0, 0, 0, 0};   // split round: whole sequence / persistent passes / evict-1, evict-3, final bulk phases (host clock)
-  int submitWideUnits = 0, submitWidePasses = 0, submitSeqUnits = 0, submitGangUnits = 0, submitNodePasses = 0;   // how the last submit_check ran (submit_stats)
+  int submitWideUnits = 0, submitWidePasses = 0, submitSeqUnits = 0, submitGangUnits = 0, submitNodePasses = 0, submitLitUnits = 0;   // how the last submit_check ran (submit_stats)
 };
 
 namespace {
@@ -513,6 +515,7 @@ int rebuildMasks(asched* h) {
     d.rowTypeOff = h->maskBufs.upload(rowTypeOff);
     d.rowTypes = h->maskBufs.upload(rowTypes);
     d.typeMask = h->maskBufs.upload(typeMask);
+    h->dNodeType = h->maskBufs.upload(std::vector<int32_t>(h->nodeType.begin(), h->nodeType.end()));
   }
   // uniformity label masks
   std::vector<uint64_t> labelMask;
@@ -1373,7 +1376,7 @@ int32_t asched_submit_check(asched_t* h, int32_t nu, const int32_t* off, const i
   h->submitMs = 0;
   if (h->N == 0) {   // a pool without nodes (no executor reports for it yet): no node for anybody, nothing to launch
     for (int u = 0; u < nu; u++) { out[u].ok = 0; out[u].scheduled_away = 0; out[u].num_schedulable = 0; out[u].first_node = -1; }
-    h->submitWideUnits = h->submitWidePasses = 0; h->submitSeqUnits = 0; h->submitGangUnits = 0; h->submitNodePasses = 0;
+    h->submitWideUnits = h->submitWidePasses = 0; h->submitSeqUnits = 0; h->submitGangUnits = 0; h->submitNodePasses = 0; h->submitLitUnits = 0;
     return 0;
   }
   // ---- wide path: individual checks against a pristine NodeDb.  Every priority plane equals allocatable and nothing is evicted, so
@@ -1381,8 +1384,11 @@ int32_t asched_submit_check(asched_t* h, int32_t nu, const int32_t* off, const i
   // order" (fit at priority -2 succeeds or every later step of the cascade sees the same numbers, nodedb.go:724-789; no evicted
   // jobs to preempt).  That is the fit kernel's question (k_fit_batch: all shapes x all nodes in one pass over the planes, every CU
   // busy) — the per-unit transaction of the sequential path is pointless here because nothing would be left to abort.
+  // A row on the literal iteration path asks the same question of the literal iterators: the rows of a pass are split, the packed-key ones to k_fit_batch, the literal
+  // ones to the literal batched first fit (kernels_fit_lit.h; its index of level 0 is built in the first pass that has one and reused by the later passes: nothing
+  // changes the NodeDb in between).  Not on a two-word order key, which that kernel does not serve: those units keep the sequential path.
   std::vector<uint8_t> done(nu, 0);
-  int widePasses = 0, wideUnits = 0, nodePasses = 0;   // nodePasses: how often a launch of this check walks the node set (SURVEY 8d: ONE query per batched pass)
+  int widePasses = 0, wideUnits = 0, litUnits = 0, nodePasses = 0;   // nodePasses: how often a launch of this check walks the node set (SURVEY 8d: ONE query per batched pass)
   // "pristine" for a job of priority p: the planes of every level up to p's equal level 0's — what the arguments below rest on (a failed fit at priority -2 is a failed selection)
   auto pristineUpTo = [&](int32_t prio) { int l = 0; while (l < h->P && h->prios[l] != prio) l++; return l < h->equalLevels; };
   const char* wideEnv = getenv("ASCHED_SUBMIT_WIDE");   // ASCHED_SUBMIT_WIDE=0: every unit through the sequential path (debugging / A-B)
@@ -1394,16 +1400,17 @@ int32_t asched_submit_check(asched_t* h, int32_t nu, const int32_t* off, const i
       int j = jobs[off[u]], sidx = h->jShape[j], pc = h->jPc[j];
       int kBeg = d.cfg.pcAwayOff[pc], kEnd = (d.cfg.hasAway && !d.cfg.disableAway) ? d.cfg.pcAwayOff[pc + 1] : kBeg;
       if (!pristineUpTo(h->pcPriority[pc]) || (h->equalLevels < h->P && kEnd > kBeg)) continue;   // planes that differ at or below the job's level (or an away attempt at another one): the sequential path
-      bool literal = h->rowLiteral[sidx] != 0;   // rows whose iteration order is not the packed-key order keep the sequential path
+      bool literal = h->rowLiteral[sidx] != 0;   // a row whose iteration order is not the packed-key order: the literal kernel answers it
       for (int k = kBeg; k < kEnd; k++) literal = literal || h->rowLiteral[h->S + h->awayRowOff[sidx] + (k - kBeg)];
-      if (literal) continue;
-      done[u] = 1; wideUnits++;
+      if (literal && d.cfg.keyWords == 2) continue;
+      done[u] = 1; wideUnits++; litUnits += literal;
       out[u].ok = 0; out[u].scheduled_away = 0; out[u].num_schedulable = 0; out[u].first_node = -1;
       bool disallowedReq = false;
       for (int r = 0; r < h->R; r++) if (h->disallowed[r] && h->jReq[(size_t)j * h->R + r] > 0) disallowedReq = true;   // nodedb.go:596-601
       if (disallowedReq) continue;
       pend.push_back({u, j, sidx, d.cfg.disableHome ? kBeg : kBeg - 1, kEnd});   // k == kBeg - 1 stands for the home attempt
     }
+    bool litIndexBuilt = false;
     while (!pend.empty()) {   // pass 0: home rows; pass i: the i-th away entry of the units still without a node
       std::vector<int32_t> rows, slotOfRow((size_t)h->S + h->awayRowClass.size(), -1), rowOf(pend.size(), -1);
       for (size_t i = 0; i < pend.size(); i++) {
@@ -1418,10 +1425,24 @@ int32_t asched_submit_check(asched_t* h, int32_t nu, const int32_t* off, const i
       if (rows.empty()) break;
       std::vector<int32_t> res(rows.size(), -1);
       if (h->N > 0) {   // a pool without nodes (no executor reports for it yet) answers "no node" without a launch
-        if (plat_run_fit_batch(d, rows, 0 /* priority -2 */, res, h->nodeByRank.data())) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
-        h->submitMs += plat_last_fit_ms();
+        std::vector<int32_t> packed, lit, packedAt, litAt;
+        for (size_t i = 0; i < rows.size(); i++) { bool l = h->rowLiteral[rows[i]] != 0; (l ? lit : packed).push_back(rows[i]); (l ? litAt : packedAt).push_back((int32_t)i); }
+        std::vector<int32_t> pr(packed.size(), -1), lr(lit.size(), -1);
+        if (!packed.empty()) {
+          if (plat_run_fit_batch(d, packed, 0 /* priority -2 */, pr, h->nodeByRank.data())) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+          h->submitMs += plat_last_fit_ms();
+        }
+        if (!lit.empty()) {
+          if (plat_run_fit_batch_lit(d, h->dNodeType, (int)h->types.size(), lit, 0, lr, litIndexBuilt, 0.0)) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+          h->submitMs += plat_last_fit_ms();
+          if (!litIndexBuilt) nodePasses++;   // (the index build walks the node set; the queries walk the index)
+          litIndexBuilt = true;
+        }
+        if (!packed.empty()) nodePasses++;
+        for (size_t i = 0; i < packed.size(); i++) res[packedAt[i]] = pr[i];
+        for (size_t i = 0; i < lit.size(); i++) res[litAt[i]] = lr[i];
       }
-      widePasses++; nodePasses++;
+      widePasses++;
       std::vector<Pending> next;
       for (size_t i = 0; i < pend.size(); i++) {
         Pending& p = pend[i];
@@ -1495,7 +1516,7 @@ int32_t asched_submit_check(asched_t* h, int32_t nu, const int32_t* off, const i
     }
   }
   h->submitGangUnits = gangUnits;
-  // ---- sequential path (one control launch): whatever is left — units when the NodeDb is not pristine, away types, literal rows
+  // ---- sequential path (one control launch): whatever is left — units when the NodeDb is not pristine, gang units with away types or literal rows
   std::vector<int32_t> vo(1, 0), vj, vf, unitOf;
   for (int u = 0; u < nu; u++) {
     if (done[u]) continue;
@@ -1505,7 +1526,7 @@ int32_t asched_submit_check(asched_t* h, int32_t nu, const int32_t* off, const i
     vf.push_back(flags ? flags[u] : 0);
   }
   int nd = (int)unitOf.size();
-  h->submitWideUnits = wideUnits; h->submitWidePasses = widePasses; h->submitSeqUnits = nd; h->submitNodePasses = nodePasses;
+  h->submitWideUnits = wideUnits; h->submitWidePasses = widePasses; h->submitSeqUnits = nd; h->submitNodePasses = nodePasses; h->submitLitUnits = litUnits;
   if (nd == 0) return 0;
   DevBufs tmp;
   SubmitArgs a; memset(&a, 0, sizeof a);
@@ -1630,20 +1651,27 @@ int32_t asched_fit_select_batch(asched_t* h, int32_t n, const int32_t* jobs, int
   int level = -1;
   for (int i = 0; i < h->P; i++) if (h->prios[i] == prio) level = i;
   if (level < 0) return fail(h, ASCHED_ERR_INVALID, "fit_select_batch: unknown priority");
-  // identical (shape, level) queries share one scan (SURVEY 8d: batched passes are counted once)
-  std::vector<int32_t> shapeOf(n), uniq; std::vector<int32_t> slot(h->S, -1);
+  // identical (shape, level) queries share one scan (SURVEY 8d: batched passes are counted once).  Shapes whose iteration order is the packed-key order go to k_fit_batch
+  // (one pass over the planes for all of them), shapes on the literal iteration path (unaligned request, several unaligned node types) to the literal batched first fit
+  // (kernels_fit_lit.h: an index of the level built for this call, one wave per shape): a mixed batch is answered whole.
+  std::vector<int32_t> shapeOf(n), uniq, uniqLit; std::vector<int32_t> slot(h->S, -1);   // slot: >= 0 position in uniq, <= -2 position -(slot + 2) in uniqLit
   for (int i = 0; i < n; i++) {
     if (jobs[i] < 0 || jobs[i] >= h->M) return fail(h, ASCHED_ERR_INVALID, "fit_select_batch: job out of range");
     int s = h->jShape[jobs[i]];
-    if (!h->rowLiteral.empty() && h->rowLiteral[s]) return fail(h, ASCHED_ERR_UNSUPPORTED, "fit_select_batch: this job's iteration order is not the packed-key order (unaligned request or several unaligned node types); use select_node");
-    if (slot[s] < 0) { slot[s] = (int32_t)uniq.size(); uniq.push_back(s); }
+    if (slot[s] == -1) {
+      if (!h->rowLiteral.empty() && h->rowLiteral[s]) {
+        if (h->dev.cfg.keyWords == 2) return fail(h, ASCHED_ERR_UNSUPPORTED, "fit_select_batch: this job's iteration order is not the packed-key order and this handle's order key takes two words, which the literal batched first fit does not serve; use select_node");
+        slot[s] = -2 - (int32_t)uniqLit.size(); uniqLit.push_back(s);
+      } else { slot[s] = (int32_t)uniq.size(); uniq.push_back(s); }
+    }
     shapeOf[i] = slot[s];
   }
-  std::vector<int32_t> res(uniq.size(), -1);
+  std::vector<int32_t> res(uniq.size(), -1), resLit(uniqLit.size(), -1);
   h->lastWideWasOpt = false;
-  int rc = h->N > 0 ? plat_run_fit_batch(h->dev, uniq, level, res, h->nodeByRank.data()) : 0;
-  if (rc) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
-  for (int i = 0; i < n; i++) out[i] = res[shapeOf[i]];
+  if (h->N > 0 && !uniq.empty() && plat_run_fit_batch(h->dev, uniq, level, res, h->nodeByRank.data())) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  if (h->N > 0 && !uniqLit.empty() && plat_run_fit_batch_lit(h->dev, h->dNodeType, (int)h->types.size(), uniqLit, level, resLit, false, uniq.empty() ? 0.0 : plat_last_fit_ms()))
+    return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  for (int i = 0; i < n; i++) out[i] = shapeOf[i] >= 0 ? res[shapeOf[i]] : resLit[-(shapeOf[i] + 2)];
   return 0;
 }
 
@@ -2623,7 +2651,7 @@ int32_t asched_excluded_nodes(asched_t* h, int32_t job, asched_excluded_reason* 
   return n;
 }
 int32_t asched_submit_stats(asched_t* h, int32_t* out) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
-  out[0] = h->submitWideUnits; out[1] = h->submitWidePasses; out[2] = h->submitSeqUnits; out[3] = h->submitGangUnits; out[4] = h->submitNodePasses; out[5] = 0;
+  out[0] = h->submitWideUnits; out[1] = h->submitWidePasses; out[2] = h->submitSeqUnits; out[3] = h->submitGangUnits; out[4] = h->submitNodePasses; out[5] = h->submitLitUnits;
   return 0;
 }
 int32_t asched_kernel_times(asched_t* h, double* out) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);

@@ -71,6 +71,10 @@ static int plat_price_score(Dev& d, const PriceArgs& a, std::vector<PriceNodeOut
 // ---- fit, submit check and goldens: queries against a fixed node state, synchronous (results are in the host vectors on return).
 static int plat_run_shape_mask(Dev& d, const uint64_t* classMask, const int32_t* shapeClass);
 static int plat_run_fit_batch(Dev& d, const std::vector<int32_t>& shapes, int level, std::vector<int32_t>& out, const int32_t* nodeByRankHost = nullptr);
+// the literal batched first fit (kernels_fit_lit.h): mask rows on the literal iteration path at one level.  nodeType: [N] node type per node in platform memory.  The index
+// of the level is built first; reuseIndex: the one the previous call built still describes the node state and level (the passes of ONE submit check).  addMs: kernel time
+// of the same batch's packed-key part, added to what plat_last_fit_ms reports afterwards.  The CPU build's definition sits in kernels_fit_lit.h.
+static int plat_run_fit_batch_lit(Dev& d, const int32_t* nodeType, int nTypes, const std::vector<int32_t>& rows, int level, std::vector<int32_t>& out, bool reuseIndex, double addMs);
 static int plat_run_fit_capacity(Dev& d, const std::vector<int32_t>& shapes, std::vector<int32_t>& firstNode, std::vector<long long>& capacity, const int32_t* nodeByRankHost);
 static int plat_run_submit_gangs(Dev& d, const std::vector<int32_t>& off, const std::vector<int32_t>& jobs, std::vector<int32_t>& out);
 static double plat_last_fit_ms();

@@ -19,7 +19,7 @@ struct HelpBox;
 struct PlatCtx {
   int device = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr, fitEv0 = nullptr, fitEv1 = nullptr;
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, fitEv0 = nullptr, fitEv1 = nullptr, litEvMid = nullptr;
   HelpBox* helpBox = nullptr;
   int helpers = -1, cus = 0, wallClockKHz = 100000;
   float lastControlMs = 0.f, lastFitMs = 0.f;
@@ -35,6 +35,7 @@ struct PlatCtx {
   int32_t* cmpScratch = nullptr; size_t cmpScratchInts = 0;   // block counts + total of the grid-wide compaction
   int optIndexN = -1, optIndexM = -1;   // sizes the optimiser's node -> jobs index in the scratch was built for (asched_host.inc decides when it may be reused)
   void* fitScratch = nullptr; size_t fitScratchBytes = 0;   // keys + shape list of a fit batch
+  void* litScratch = nullptr; size_t litScratchBytes = 0;   // index, sort scratch, row list and results of a literal fit batch (kernels_fit_lit.h): its own buffer, the index outlives packed-key passes in between
   void* optSel = nullptr; size_t optSelBytes = 0;   // block partials + result of the device-side candidate selection
   void* optScratch = nullptr; size_t optScratchBytes = 0;     // node -> jobs index, queue costs and per-node scores of the fairness optimiser, kept across calls
   std::string err;
@@ -74,7 +75,7 @@ static PlatCtx* plat_open(std::string& err, int device) {
   int khz = 0;
   if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device) == hipSuccess && khz > 0) c->wallClockKHz = khz;
   bool ok = hipStreamCreate(&c->stream) == hipSuccess && hipEventCreate(&c->ev0) == hipSuccess && hipEventCreate(&c->ev1) == hipSuccess &&
-            hipEventCreate(&c->fitEv0) == hipSuccess && hipEventCreate(&c->fitEv1) == hipSuccess && hipEventCreate(&c->rEv0) == hipSuccess && hipEventCreate(&c->rEv1) == hipSuccess;
+            hipEventCreate(&c->fitEv0) == hipSuccess && hipEventCreate(&c->fitEv1) == hipSuccess && hipEventCreate(&c->litEvMid) == hipSuccess && hipEventCreate(&c->rEv0) == hipSuccess && hipEventCreate(&c->rEv1) == hipSuccess;
   // the mailbox is written from both sides across XCDs: it must not live in an XCD-private L2 -> fine-grained (uncached, device-coherent) memory
   ok = ok && hipExtMallocWithFlags((void**)&c->helpBox, sizeof(HelpBox), hipDeviceMallocFinegrained) == hipSuccess;
   ok = ok && hipHostMalloc((void**)&c->cancelHost, 256, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess;   // [0] the cancel word; from byte 64: the exchange words of sharded passes (dev.h XCHG_WORD0)
@@ -244,12 +245,13 @@ static void plat_close(PlatCtx* c) {
   if (c->xPeerTable) (void)hipFree(c->xPeerTable);
   plat_comm_destroy_ctx(c);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  for (hipEvent_t e : {c->ev0, c->ev1, c->fitEv0, c->fitEv1, c->rEv0, c->rEv1}) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : {c->ev0, c->ev1, c->fitEv0, c->fitEv1, c->litEvMid, c->rEv0, c->rEv1}) if (e) (void)hipEventDestroy(e);
   if (c->helpBox) (void)hipFree(c->helpBox);
   if (c->cmpScratch) (void)hipFree(c->cmpScratch);
   if (c->optScratch) (void)hipFree(c->optScratch);
   if (c->optSel) (void)hipFree(c->optSel);
   if (c->fitScratch) (void)hipFree(c->fitScratch);
+  if (c->litScratch) (void)hipFree(c->litScratch);
   if (c->cancelHost) (void)hipHostFree(c->cancelHost);
   if (c->progress) (void)hipHostFree(c->progress);
   if (t_ctx == c) t_ctx = nullptr;
@@ -765,6 +767,52 @@ static int plat_run_fit_capacity(Dev& d, const std::vector<int32_t>& shapes, std
     firstNode[i] = k == ~0ull ? -1 : nodeByRankHost[k & mask];
     capacity[i] = (long long)got[(size_t)i * FIT_OSTR + 1];
   }
+  return 0;
+}
+// the literal batched first fit (kernels_fit_lit.h; kernels in armada_sched_mgpu.hip): index build (fill, bitonic sort by (type, key), finish) then one wave per query.
+// ASCHED_FIT_LIT_TIMES=1 prints the two device times of every call (tools/probe_fit_literal.py).
+#include "kernels_fit_lit.h"
+extern "C" int asched_internal_fit_lit_build(const Dev* d, const FitLitIdx* x, const int32_t* nodeType, FlPair* a, int nb2, hipStream_t s);
+extern "C" int asched_internal_fit_lit_query(const Dev* d, const FitLitIdx* x, const int32_t* rows, int nq, int32_t* out, hipStream_t s);
+static int plat_run_fit_batch_lit(Dev& d, const int32_t* nodeType, int nTypes, const std::vector<int32_t>& rows, int level, std::vector<int32_t>& out, bool reuseIndex, double addMs) {
+  int nq = (int)rows.size(), N = d.cfg.N;
+  if (nq == 0) return 0;
+  if (N <= 0) { for (int i = 0; i < nq; i++) out[i] = -1; return 0; }
+  PlatCtx* c = t_ctx;
+  hipStream_t st = c->stream;
+  size_t nb2 = FL_TILE; while (nb2 < (size_t)N) nb2 <<= 1;
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  // layout: [index: key | node | planes | typeBeg | typeEnd] [sort scratch] [rows | results]: the index part depends on N, R and the type count only, so a reused index stays where it is
+  size_t oKey = 0, oNode = oKey + up((size_t)N * 8), oAl = oNode + up((size_t)N * 4), oBeg = oAl + up((size_t)d.cfg.R * N * 8), oEnd = oBeg + up((size_t)std::max(nTypes, 1) * 4),
+         oPair = oEnd + up((size_t)std::max(nTypes, 1) * 4), oRows = oPair + up(nb2 * sizeof(FlPair)), oOut = oRows + up((size_t)nq * 4), need = oOut + up((size_t)nq * 4);
+  if (c->litScratchBytes < need) {
+    reuseIndex = false;   // (the index moves with the buffer: build it again)
+    if (c->litScratch) (void)hipFree(c->litScratch);
+    c->litScratch = nullptr; c->litScratchBytes = 0;
+    if (!hipOk(hipMalloc(&c->litScratch, need * 2), "hipMalloc")) return -1;
+    c->litScratchBytes = need * 2;
+  }
+  char* base = (char*)c->litScratch;
+  FitLitIdx x;
+  x.key = (unsigned long long*)(base + oKey); x.node = (int32_t*)(base + oNode); x.al = (int64_t*)(base + oAl); x.typeBeg = (int32_t*)(base + oBeg); x.typeEnd = (int32_t*)(base + oEnd);
+  x.n = N; x.stride = N; x.level = level; x.pad = 0;
+  int32_t *dRows = (int32_t*)(base + oRows), *dOut = (int32_t*)(base + oOut);
+  (void)hipMemcpyAsync(dRows, rows.data(), (size_t)nq * 4, hipMemcpyHostToDevice, st);
+  bool ok = true;
+  (void)hipEventRecord(c->fitEv0, st);
+  if (!reuseIndex) {
+    (void)hipMemsetAsync(base + oBeg, 0, oPair - oBeg, st);
+    ok = asched_internal_fit_lit_build(&d, &x, nodeType, (FlPair*)(base + oPair), (int)nb2, st) == 0;
+  }
+  (void)hipEventRecord(c->litEvMid, st);
+  ok = ok && asched_internal_fit_lit_query(&d, &x, dRows, nq, dOut, st) == 0;
+  (void)hipEventRecord(c->fitEv1, st);
+  ok = ok && hipOk(hipGetLastError(), "k_fit_lit launch") && hipOk(hipMemcpyAsync(out.data(), dOut, (size_t)nq * 4, hipMemcpyDeviceToHost, st), "hipMemcpy") && hipOk(hipStreamSynchronize(st), "k_fit_lit");
+  if (!ok) { if (c->err.empty()) c->err = "k_fit_lit launch failed"; return -1; }
+  float buildMs = 0.f, queryMs = 0.f;
+  (void)hipEventElapsedTime(&buildMs, c->fitEv0, c->litEvMid); (void)hipEventElapsedTime(&queryMs, c->litEvMid, c->fitEv1);
+  c->lastFitMs = buildMs + queryMs + (float)addMs;
+  if (const char* e = getenv("ASCHED_FIT_LIT_TIMES")) if (e[0] == '1') fprintf(stderr, "[asched fit_lit] nodes %d queries %d level %d: index build %.4f ms, query %.4f ms\n", N, nq, level, (double)buildMs, (double)queryMs);
   return 0;
 }
 // a caller-side buffer may be memory of this handle's GPU (a tensor the collective reduces in place: used directly) or host memory (staged)

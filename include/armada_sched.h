@@ -51,7 +51,8 @@ extern "C" {
 /* error codes */
 #define ASCHED_OK 0
 #define ASCHED_ERR_INVALID (-1)      /* bad argument / inconsistent input */
-#define ASCHED_ERR_UNSUPPORTED (-2)  /* feature of the reference not implemented by this backend */
+#define ASCHED_ERR_UNSUPPORTED (-2)  /* feature of the reference not implemented by this backend (the text of last_error names it: a key beyond 128 bits, more than 64 node
+                                        types for one requirement class off the index grid, a batched first fit off the index grid on a two-word order key, ...) */
 #define ASCHED_ERR_DEVICE (-3)       /* HIP runtime failure or no gfx950 device */
 #define ASCHED_ERR_INTERNAL (-4)     /* reference would return an error here (e.g. iteration loop) */
 #define ASCHED_ERR_PEER (-6)         /* a collective entry point: another rank of the communicator failed in front of the exchange (its own call returns the cause); nothing was exchanged */
@@ -425,10 +426,13 @@ int32_t ASCHED_FN(clear_allocated)(asched_t*);
    One device launch serves the whole batch. */
 int32_t ASCHED_FN(submit_check)(asched_t*, int32_t n_units, const int32_t* unit_off /*[n_units+1]*/, const int32_t* unit_jobs,
                                 const int32_t* unit_flags /*[n_units] or NULL*/, asched_submit_result* out /*[n_units]*/);
-/* Measurement hook (no reference counterpart): how the last submit_check ran.  out = {units answered by the wide fit kernel (individual
-   checks on a pristine NodeDb), fit-kernel passes, units through the sequential control launch (a NodeDb holding jobs, away types, literal rows), gang units answered
+/* Measurement hook (no reference counterpart): how the last submit_check ran.  out = {units answered by the wide fit kernels (individual
+   checks on a pristine NodeDb), fit-kernel passes (home rows, then one per away entry), units through the sequential control launch (a NodeDb holding jobs, gang units
+   with away types or with rows off the index grid, every unit off the grid on a two-word order key), gang units answered
    one workgroup per unit on a pristine NodeDb (csrc/submit_gang.h), walks over the node set the wide / capacity / gang-unit launches made (one per launch of the fit or
-   capacity kernel, one per member of a gang unit: what a roofline prices), 0 (reserved)}. */
+   capacity kernel, one per member of a gang unit, one for the index of the literal first fit: what a roofline prices), literal units: the wide units with a
+   home or away mask row on the literal iteration path (a request off the index grid, several node types off it), whose rows the literal batched first fit answered
+   (csrc/kernels_fit_lit.h) — counted in out[0] too}. */
 int32_t ASCHED_FN(submit_stats)(asched_t*, int32_t* out /*[6]*/);
 /* NodeTypesIterator order (nodeiteration.go:74-149) for req at a priority over node types `types` (node_type_override ids; ntypes<0: all types).
    Test hook for the golden orderings of nodeiteration_test.go; the HIP backend materialises its literal iterator restatement (the one rounds use
@@ -436,7 +440,10 @@ int32_t ASCHED_FN(submit_stats)(asched_t*, int32_t* out /*[6]*/);
 int32_t ASCHED_FN(iterate_nodes)(asched_t*, const int64_t* type_ids, int32_t ntypes, int32_t priority,
                                  const int64_t* indexed_req /*[K]*/, int32_t* out_nodes, int32_t cap, int32_t* n_out);
 /* First feasible node per job at `priority` against the CURRENT state, no binding: n independent
-   selectNodeForPodAtPriority calls (nodedb.go:840-879) — BASELINE config 2 ("nodedb fit kernel"). */
+   selectNodeForPodAtPriority calls (nodedb.go:840-879) — BASELINE config 2 ("nodedb fit kernel").  Jobs whose iteration order is the packed-key order share
+   one pass over the node planes; jobs off the index grid (an unaligned request, several node types with unaligned allocatable) are answered by the literal
+   iterators over an index of the level built for the call, one wavefront per distinct shape (csrc/kernels_fit_lit.h); a batch that mixes both is answered whole.
+   ASCHED_ERR_UNSUPPORTED only for a job off the grid on a handle whose order key takes two words (select_node answers those). */
 int32_t ASCHED_FN(fit_select_batch)(asched_t*, int32_t n, const int32_t* jobs, int32_t priority, int32_t* out_node);
 
 /* ------------------------------------------------------------------ one pool on several GPUs (no reference counterpart: SURVEY 8e)
