@@ -214,6 +214,10 @@ class CRoundResult(C.Structure):
     ]
 
 
+class CPreemptionCause(C.Structure):  # asched_preemption_cause
+    _fields_ = [("type", C.c_int32), ("preempting_job", C.c_int32), ("preempted_sibling", C.c_int32), ("cand_off", C.c_int32), ("cand_count", C.c_int32), ("pad_", C.c_int32)]
+
+
 class CExcludedReason(C.Structure):  # asched_excluded_reason
     _fields_ = [("kind", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("c", C.c_int32), ("required", C.c_int64), ("available", C.c_int64),
                 ("count", C.c_int32), ("pad_", C.c_int32)]
@@ -234,9 +238,13 @@ ALL_SYMBOLS = [
     "comm_unique_id", "comm_init", "comm_init_external", "comm_destroy", "comm_rank", "fit_select_batch_sharded", "round_exchange",
     "shard_round", "shard_exchanges", "shard_area", "shard_open", "shard_peers",
     "excluded_nodes", "set_excluded_nodes",
+    "round_preemption_causes", "preemption_join",
 ]
-# entry points the CPU oracle does not implement (it is the single-process checker): the communicator and the collectives that run on it
-OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_destroy", "comm_rank", "fit_select_batch_sharded", "round_exchange", "shard_round", "shard_exchanges", "shard_area", "shard_open", "shard_peers"}
+# entry points the CPU oracle does not implement (it is the single-process checker): the communicator and the collectives that run on it, and the join of a
+# round's result lists into preemption causes (a function of lists the oracle already delivers; tests/test_z_preemption_causes.py restates it)
+OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_destroy", "comm_rank", "fit_select_batch_sharded", "round_exchange", "shard_round", "shard_exchanges", "shard_area", "shard_open", "shard_peers",
+                    "round_preemption_causes", "preemption_join"}
+PREEMPTION_UNKNOWN, PREEMPTION_UNKNOWN_GANG, PREEMPTION_FAIRSHARE, PREEMPTION_URGENCY, PREEMPTION_OPTIMISER = 1, 2, 3, 4, 5   # ASCHED_PREEMPTION_* (context.PreemptionType)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
 
 
@@ -417,6 +425,8 @@ class Library:
         f("round_stats", C.c_int32, [C.c_void_p, _i32p])
         f("excluded_nodes", C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(CExcludedReason), C.c_int32])
         f("set_excluded_nodes", C.c_int32, [C.c_void_p, C.c_int32])
+        f("round_preemption_causes", C.c_int32, [C.c_void_p, C.POINTER(CPreemptionCause), C.c_int32, _i32p, C.c_int32, _i32p])
+        f("preemption_join", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, C.c_int32, _i32p, _i32p, _i32p, _u8p, C.POINTER(CPreemptionCause), _i32p, C.c_int32, _i32p])
 
     def _fn(self, name, restype, argtypes):
         if name in OPTIONAL_SYMBOLS and not hasattr(self.lib, self.prefix + name):
@@ -1182,6 +1192,43 @@ class Scheduler:
         self._check(self.lib.job_key_unfeasible(self.h, job, C.byref(o)))
         return bool(o.value)
 
+    def _preemption_fn(self, name):
+        fn = getattr(self.lib, name, None)
+        if fn is None:
+            raise SchedError(-2, f"this library does not export {self.lib.prefix}{name}")
+        return fn
+
+    @staticmethod
+    def _causes(rec, n, cand):
+        return [(int(rec[i].type), int(rec[i].preempting_job), int(rec[i].preempted_sibling),
+                 tuple(int(x) for x in cand[rec[i].cand_off:rec[i].cand_off + rec[i].cand_count])) for i in range(n)]
+
+    def preemption_causes(self) -> dict:
+        """who preempted each job of the last round and by which kind of preemption (PopulatePreemptionDescriptions):
+        {preempted job: (PREEMPTION_* type, preempting_job or -1, preempted_sibling or -1, candidates)}; candidates: for type URGENCY the jobs scheduled with
+        urgency preemption on the job's node, ascending"""
+        fn = self._preemption_fn("round_preemption_causes")
+        if getattr(self, "_last_preempted", None) is None:   # (the keys of the result: every helper of this package runs its rounds through schedule_round / schedule_queues)
+            self._check(fn(self.h, None, 0, None, 0, C.byref(C.c_int32(0))))   # (the library's own refusal when the handle has no round result)
+            raise SchedError(-1, "preemption_causes: the last round was not run through this Scheduler's schedule_round / schedule_queues")
+        pj, nc = self._last_preempted, self._last_num_scheduled   # (at most every scheduled job is a candidate)
+        n, need = len(pj), C.c_int32(0)
+        rec, cand = (CPreemptionCause * max(n, 1))(), np.zeros(max(nc, 1), dtype=np.int32)
+        self._check(fn(self.h, rec, n, _ptr(cand, C.c_int32), nc, C.byref(need)))
+        return dict(zip((int(j) for j in pj), self._causes(rec, n, cand)))
+
+    def preemption_join(self, sched_job, sched_node, sched_method, pre_node, pre_by, pre_sibling, pre_in_gang, cand_cap: Optional[int] = None):
+        """PopulatePreemptionDescriptions on the caller's lists -> ([(type, preempting_job, preempted_sibling, candidates)] per preempted entry, all candidates grouped by node)"""
+        fn = self._preemption_fn("preemption_join")
+        sj, sn, sm = _arr(sched_job, np.int32), _arr(sched_node, np.int32), _arr(sched_method, np.int32)
+        pn, pb, ps, pg = _arr(pre_node, np.int32), _arr(pre_by, np.int32), _arr(pre_sibling, np.int32), _arr(pre_in_gang, np.uint8)
+        ns, n = len(sj), len(pn)
+        cap = ns if cand_cap is None else int(cand_cap)
+        rec, cand, got = (CPreemptionCause * max(n, 1))(), np.zeros(max(cap, 1), dtype=np.int32), C.c_int32(0)
+        self._check(fn(self.h, ns, _ptr(sj, C.c_int32), _ptr(sn, C.c_int32), _ptr(sm, C.c_int32), n, _ptr(pn, C.c_int32), _ptr(pb, C.c_int32), _ptr(ps, C.c_int32),
+                       _ptr(pg, C.c_uint8), rec, _ptr(cand, C.c_int32), cap, C.byref(got)))
+        return self._causes(rec, n, cand), cand[:got.value].copy()
+
     def schedule_queues(self) -> RoundResult:
         return self.schedule_round(queues_only=True)
 
@@ -1199,6 +1246,7 @@ class Scheduler:
         sj, sn = arr(r.scheduled_job, ns, np.int32), arr(r.scheduled_node, ns, np.int32)
         sp, sm = arr(r.scheduled_priority, ns, np.int32), arr(r.scheduled_method, ns, np.int32)
         pj, pn = arr(r.preempted_job, npre, np.int32), arr(r.preempted_node, npre, np.int32)
+        self._last_preempted, self._last_num_scheduled = pj, ns
         q = self.num_queues
         return RoundResult(
             scheduled_job=sj, scheduled_node=sn, scheduled_priority_arr=sp, scheduled_method_arr=sm, preempted_job=pj, preempted_node=pn,

@@ -233,3 +233,86 @@ extern "C" int asched_internal_fit_lit_query(const Dev* d, const FitLitIdx* x, c
   hipLaunchKernelGGL(k_fit_lit, dim3(nq < 65536 ? nq : 65536), dim3(64), 0, st, *d, *x, rows, nq, out);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// ------------------------------------------------------------------------------------------------ preemption causes: the join over a round's result lists (kernels_preempt_join.h)
+#define PJ_FN __device__ static inline
+#define PJ_ADD32(p, v) atomicAdd((int*)(p), (int)(v))
+#include "kernels_preempt_join.h"
+// exclusive prefix sum of one value per thread over the workgroup of MG_THREADS (4 waves); *total: the workgroup's sum, the same in every thread
+__device__ static inline int pjBlockExclusive(int v, int* wsum /*[4] LDS*/, int* total) {
+  int lane = threadIdx.x & 63, w = threadIdx.x >> 6, inc = v;
+  for (int o = 1; o < 64; o <<= 1) { int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
+  __syncthreads();                                   // (the previous scan's readers are done with wsum)
+  if (lane == 63) wsum[w] = inc;
+  __syncthreads();
+  int before = 0, all = 0;
+  for (int k = 0; k < MG_THREADS / 64; k++) { int s = wsum[k]; if (k < w) before += s; all += s; }
+  *total = all;
+  return before + inc - v;
+}
+__global__ __launch_bounds__(MG_THREADS) void k_pj_count(PjArgs a) {
+  long long i = MG_IDX();
+  if (i < a.ns) pjCount(a, (int)i);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_pj_tile_sum(PjArgs a) {
+  __shared__ int wsum[MG_THREADS / 64];
+  long long base = (long long)blockIdx.x * PJ_TILE + (long long)threadIdx.x * 4;
+  int v = 0, total;
+  for (int k = 0; k < 4; k++) if (base + k < a.N) v += a.cnt[base + k];
+  (void)pjBlockExclusive(v, wsum, &total);
+  if (threadIdx.x == 0) a.tileSum[blockIdx.x] = total;
+}
+// one workgroup: the tile sums become tile offsets, MG_THREADS at a time behind a carry; off[N] = the number of candidates
+__global__ __launch_bounds__(MG_THREADS) void k_pj_tile_scan(PjArgs a, int tiles) {
+  __shared__ int wsum[MG_THREADS / 64];
+  int carry = 0;
+  for (int base = 0; base < tiles; base += MG_THREADS) {
+    int t = base + (int)threadIdx.x, v = t < tiles ? a.tileSum[t] : 0, total;
+    int ex = pjBlockExclusive(v, wsum, &total);
+    if (t < tiles) a.tileSum[t] = carry + ex;
+    carry += total;
+  }
+  if (threadIdx.x == 0) a.off[a.N] = carry;
+}
+__global__ __launch_bounds__(MG_THREADS) void k_pj_tile_apply(PjArgs a) {
+  __shared__ int wsum[MG_THREADS / 64];
+  long long base = (long long)blockIdx.x * PJ_TILE + (long long)threadIdx.x * 4;
+  int c[4], v = 0, total;
+  for (int k = 0; k < 4; k++) { c[k] = base + k < a.N ? a.cnt[base + k] : 0; v += c[k]; }
+  int run = a.tileSum[blockIdx.x] + pjBlockExclusive(v, wsum, &total);
+  for (int k = 0; k < 4; k++) if (base + k < a.N) { a.off[base + k] = run; a.cursor[base + k] = run; run += c[k]; }
+}
+__global__ __launch_bounds__(MG_THREADS) void k_pj_scatter(PjArgs a) {
+  long long i = MG_IDX();
+  if (i < a.ns) pjScatter(a, (int)i);
+}
+// (the number of candidates is on the device only: a grid for all ns entries, the slots behind off[N] return)
+__global__ __launch_bounds__(MG_THREADS) void k_pj_rank(PjArgs a) {
+  long long k = MG_IDX();
+  if (k < a.ns && k < a.off[a.N]) pjRank(a, (int)k);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_pj_gather(Dev d, PjArgs a) {
+  long long i = MG_IDX();
+  if (i < a.np) pjGather(d, a, (int)i);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_pj_cause(PjArgs a) {
+  long long i = MG_IDX();
+  if (i < a.np) pjCause(a, (int)i);
+}
+// cnt [N + 1] and info [2] zeroed by the caller
+extern "C" int asched_internal_preempt_join(const Dev* d, const PjArgs* a, hipStream_t st) {
+  int tiles = pjTiles(a->N);
+  if (a->ns > 0 && a->N > 0) hipLaunchKernelGGL(k_pj_count, dim3(mgBlocks(a->ns)), dim3(MG_THREADS), 0, st, *a);
+  if (tiles > 0) hipLaunchKernelGGL(k_pj_tile_sum, dim3(tiles), dim3(MG_THREADS), 0, st, *a);
+  hipLaunchKernelGGL(k_pj_tile_scan, dim3(1), dim3(MG_THREADS), 0, st, *a, tiles);
+  if (tiles > 0) hipLaunchKernelGGL(k_pj_tile_apply, dim3(tiles), dim3(MG_THREADS), 0, st, *a);
+  if (a->ns > 0 && a->N > 0) {
+    hipLaunchKernelGGL(k_pj_scatter, dim3(mgBlocks(a->ns)), dim3(MG_THREADS), 0, st, *a);
+    hipLaunchKernelGGL(k_pj_rank, dim3(mgBlocks(a->ns)), dim3(MG_THREADS), 0, st, *a);
+  }
+  if (a->np > 0) {
+    if (a->fromRound) hipLaunchKernelGGL(k_pj_gather, dim3(mgBlocks(a->np)), dim3(MG_THREADS), 0, st, *d, *a);
+    hipLaunchKernelGGL(k_pj_cause, dim3(mgBlocks(a->np)), dim3(MG_THREADS), 0, st, *a);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}

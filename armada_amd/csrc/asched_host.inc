@@ -25,6 +25,7 @@
 #include <chrono>
 #include <thread>
 #include "kernels_fit_lit.h"   // FitLitIdx and, in the CPU build of the tests, plat_run_fit_batch_lit
+#include "kernels_preempt_join.h"   // PjArgs and, in the CPU build of the tests, plat_preempt_join
 
 namespace {
 
@@ -160,6 +161,7 @@ struct asched {
   struct OptCfg { bool enabled = false; double minPct = 0; int maxJobs = 0; bool hasMaxSize = false, hasMinSize = false; int64_t maxSize[MAXR] = {0}, minSize[MAXR] = {0}; std::vector<double> maxFraction; int64_t nowMs = 0; } opt;
   bool keyWide = false;                                // the wide (oversubscription-proof) field layout is in use: some request on an indexed column is negative
   DevBufs fastBufs;
+  DevBufs pjBufs;                                  // lists and scratch of the preemption-cause join (kernels_preempt_join.h), kept between calls
   std::vector<int32_t> labelSlots;                 // sorted indexed label keys
   std::vector<std::vector<int32_t>> slotValues;    // per slot: sorted values present on nodes
   std::vector<int32_t> uniOffHost;
@@ -208,6 +210,7 @@ struct asched {
   bool argsOverflow = false;     // the last setArgs did not fit the command mailbox: runControl refuses the command
   long long* commStatus = nullptr;   // one device word: the status all-reduce in front of every collective (collectiveAgree)
   struct { bool valid = false; EvKey* key = nullptr; QsIn* in = nullptr; int64_t* part = nullptr; int32_t* len = nullptr; QsSave* save = nullptr; } qsOrig;   // the QCAPF-sized stream buffers of jobs_set while a wide round uses Q-sized ones
+  bool roundExchanged = false;   // round_exchange resolved the last round against the other replicas: the per-job preemption record is not the resolved round's
   bool haveRoundResult = false;  // d.resJob / resNode / resPreJob hold the last round's lists (round_delta reads them on the device)
   bool lastWideWasOpt = false;   // kernel_times out[1] reports the optimiser's k_opt_score instead of k_fit_batch
   // host staging reused across jobs_set calls (a fresh 200 MB / 60 MB allocation costs more in first-touch page faults than the fill)
@@ -790,7 +793,7 @@ asched_t* asched_create(const asched_config* c) {
 void asched_destroy(asched_t* h) {
   if (!h) return;
   plat_enter(h->plat);
-  h->nodeBufs.freeAll(); h->jobBufs.freeAll(); h->queueBufs.freeAll(); h->maskBufs.freeAll(); h->fastBufs.freeAll();
+  h->nodeBufs.freeAll(); h->jobBufs.freeAll(); h->queueBufs.freeAll(); h->maskBufs.freeAll(); h->fastBufs.freeAll(); h->pjBufs.freeAll();
   plat_pinned_free(h->resPin); plat_free(h->commStatus); plat_free(h->dev.rs); plat_free(h->dev.cmdIO); plat_free(h->dev.scanResult); plat_free(h->dev.undo);
   plat_close(h->plat);
   delete h;
@@ -1238,7 +1241,7 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
   d.optSched = A8(M); d.optPre = A8(M); d.optGhost = A32(M);
   d.jcEvicted = A8(M); d.jcAssigned = A32(M); d.jcReason = A32(M); d.jcHasPctx = A8(M);
   d.pcNode = A32(M); d.pcSap = A32(M); d.pcPap = A32(M); d.pcMethod = A32(M); d.jcGangCard = A32(M); d.jcPreempted = A8(M);
-  d.jcUniValue = A32(M); d.jcStagedBy = A32(M);
+  d.jcUniValue = A32(M); d.jcStagedBy = A32(M); d.jcPreSib = A32(M);
   d.inPreempted = A8(M); d.inScheduled = A8(M); d.inSchedAndEvicted = A8(M); d.preemptedNode = A32(M);
   d.evList = A32(M); d.evSortKey = h->jobBufs.alloc<uint32_t>(M + 1); d.evTabJob = A32(M); d.evTabAlive = A8(M); d.evIndexOfJob = A32(M);
   d.fairEnt = A32(M); d.fairEntJob = A32(M);
@@ -1835,6 +1838,7 @@ int32_t asched_round_exchange(asched_t* h, asched_delta_summary* sum, int32_t* j
   rc = collectiveAgree(h, rc);   // (no round result on one rank, an allocation: every rank returns instead of one of them missing in the all-reduce)
   if (rc == 0 && plat_allreduce(buf, words, 0)) rc = fail(h, ASCHED_ERR_DEVICE, plat_last_error());
   if (rc == 0) rc = asched_round_delta_resolve(h, (const int64_t*)buf, sum, jobNode, jobPrio, jobReplay);
+  if (rc == 0) h->roundExchanged = true;
   plat_free(buf);
   return rc;
 }
@@ -2070,7 +2074,7 @@ int32_t asched_round_prepare(asched_t* h, const asched_queues* in) { if (!h) ret
 static int downloadResult(asched* h, asched_round_result* out, const int32_t* io) {
   Dev& d = h->dev;
   int ns = io[2], np = io[3];
-  h->haveRoundResult = true;
+  h->haveRoundResult = true; h->roundExchanged = false;
   h->resNs = ns; h->resNp = np;
   const int Q = h->Q; const size_t M = (size_t)h->M, qa = (size_t)Q * h->npc * h->R;
   // carve the arena: [sched job|node|prio|method : 4 x ns i32][pre job|node : 2 x np i32][queue alloc : qa i64][fair|dc|uc|tokens : 4 x Q f64][reason : M i32]
@@ -2505,6 +2509,60 @@ int32_t asched_schedule_queues(asched_t* h, asched_round_result* out) { if (!h) 
   int32_t io[4]; getIO(h, io, 4);
   io[0] = io[1] = 0;
   return downloadResult(h, out, io);
+}
+// ---- preemption causes (include/armada_sched.h; kernels_preempt_join.h): the scratch of one join, the passes, the download and the size check
+static int preemptJoinRun(asched* h, PjArgs& a, const char* who, asched_preemption_cause* out, int32_t cap, int32_t* candidates, int32_t candCap, int32_t* numCandidates) {
+  DevBufs& b = h->pjBufs;
+  const size_t N = (size_t)a.N, ns = (size_t)a.ns, np = (size_t)a.np;
+  a.cnt = b.alloc<int32_t>(N + 1); a.off = b.allocRaw<int32_t>(N + 1); a.cursor = b.allocRaw<int32_t>(N); a.tileSum = b.allocRaw<int32_t>((size_t)pjTiles(a.N));
+  a.slot = b.allocRaw<int32_t>(ns); a.cand = b.allocRaw<int32_t>(ns); a.cause = b.allocRaw<asched_preemption_cause>(np); a.info = b.alloc<int32_t>(2);
+  if (a.fromRound) { a.pBy = b.allocRaw<int32_t>(np); a.pSib = b.allocRaw<int32_t>(np); a.pGang = b.allocRaw<uint8_t>(np); }
+  int rc = 0;
+  for (auto& p : b.ptrs) if (!p.first) rc = ASCHED_ERR_DEVICE;
+  if (rc || plat_take_failure() || plat_preempt_join(h->dev, a)) { b.recycle(); return fail(h, ASCHED_ERR_DEVICE, plat_last_error()); }
+  int32_t total = 0, info[2] = {0, 0};
+  plat_d2h(&total, a.off + N, sizeof total); plat_d2h(info, a.info, sizeof info);
+  char buf[192];
+  if (info[0]) { snprintf(buf, sizeof buf, "%s: %d marked job(s) without a preemptor on record", who, info[0]); rc = ASCHED_ERR_INTERNAL; }
+  else if (info[1]) { snprintf(buf, sizeof buf, "%s: %d scheduled entr(ies) name a node outside the handle's nodes", who, info[1]); rc = ASCHED_ERR_INVALID; }
+  else if (cap < a.np || candCap < total) {
+    snprintf(buf, sizeof buf, "%s: buffers too small: %d cause records and %d candidate words are needed (cap %d, cand_cap %d)", who, a.np, total, cap, candCap);
+    rc = ASCHED_ERR_INVALID;
+  }
+  if (numCandidates) *numCandidates = total;
+  if (!rc) {
+    if (np) plat_d2h(out, a.cause, np * sizeof(asched_preemption_cause));
+    if (total) plat_d2h(candidates, a.cand, (size_t)total * 4);
+  }
+  b.recycle();
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  return rc ? fail(h, rc, buf) : 0;
+}
+int32_t asched_round_preemption_causes(asched_t* h, asched_preemption_cause* out, int32_t cap, int32_t* candidates, int32_t candCap, int32_t* numCandidates) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
+  if (numCandidates) *numCandidates = 0;
+  if (!h->haveRoundResult) return fail(h, ASCHED_ERR_INVALID, "round_preemption_causes: no round result on this handle (schedule_round / schedule_queues first)");
+  if (h->roundExchanged) return fail(h, ASCHED_ERR_INVALID, "round_preemption_causes: not after round_exchange (the queue-hash mode resolves preemptions between replicas; the per-job record describes this replica's own round)");
+  if (cap < 0 || candCap < 0 || (cap > 0 && !out) || (candCap > 0 && !candidates)) return fail(h, ASCHED_ERR_INVALID, "round_preemption_causes: bad buffer");
+  Dev& d = h->dev;
+  PjArgs a; memset(&a, 0, sizeof a);
+  a.N = h->N; a.ns = h->resNs; a.np = h->resNp; a.fromRound = 1;
+  a.sJob = d.resJob; a.sNode = d.resNode; a.sMethod = d.resMethod; a.pNode = d.resPreNode;
+  return preemptJoinRun(h, a, "round_preemption_causes", out, cap, candidates, candCap, numCandidates);
+}
+int32_t asched_preemption_join(asched_t* h, int32_t ns, const int32_t* sJob, const int32_t* sNode, const int32_t* sMethod, int32_t np, const int32_t* pNode, const int32_t* pBy,
+                               const int32_t* pSib, const uint8_t* pGang, asched_preemption_cause* out, int32_t* candidates, int32_t candCap, int32_t* numCandidates) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
+  if (numCandidates) *numCandidates = 0;
+  if (ns < 0 || np < 0 || candCap < 0 || (ns > 0 && (!sJob || !sNode || !sMethod)) || (np > 0 && (!pNode || !pBy || !pSib || !pGang || !out)) || (candCap > 0 && !candidates))
+    return fail(h, ASCHED_ERR_INVALID, "preemption_join: bad argument");
+  if (!h->nodesSet) return fail(h, ASCHED_ERR_INVALID, "preemption_join: nodes_upsert first");
+  DevBufs& b = h->pjBufs;
+  auto up32 = [&](const int32_t* p, int n) { int32_t* q = b.allocRaw<int32_t>((size_t)n); if (q && n) plat_h2d(q, p, (size_t)n * 4); return q; };
+  PjArgs a; memset(&a, 0, sizeof a);
+  a.N = h->N; a.ns = ns; a.np = np; a.fromRound = 0;
+  a.sJob = up32(sJob, ns); a.sNode = up32(sNode, ns); a.sMethod = up32(sMethod, ns); a.pNode = up32(pNode, np); a.pBy = up32(pBy, np); a.pSib = up32(pSib, np);
+  a.pGang = b.allocRaw<uint8_t>((size_t)np);
+  if (a.pGang && np) plat_h2d(a.pGang, pGang, (size_t)np);
+  return preemptJoinRun(h, a, "preemption_join", out, np, candidates, candCap, numCandidates);
 }
 int32_t asched_gang_schedule(asched_t* h, int32_t n, const int32_t* jobs, int32_t* ok, int32_t* reason, asched_pod_result* out) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
   if (!h->prepared) return fail(h, ASCHED_ERR_INVALID, "gang_schedule: round_prepare first");

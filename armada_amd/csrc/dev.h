@@ -335,7 +335,11 @@ struct Dev {
   int32_t *pcNode, *pcSap, *pcPap, *pcMethod;
   int32_t* jcGangCard; uint8_t* jcPreempted;  // sctx.PreemptedJobIds
   int32_t* jcUniValue;   // additional node selector (uniformity label value mask id), -1
-  int32_t* jcStagedBy;   // staged preemption (applied on txn commit)
+  int32_t* jcStagedBy;   // the job that preempts this one: staged by ScheduleManyWithTxn, -1 again on abort, KEPT on commit (PreemptionDetails.PreemptingJob, nodedb.go:1034) —
+                         // with jcPreSib what asched_round_preemption_causes reads after the round (kernels_preempt_join.h).  The places that set up a fresh jctx
+                         // (eviction, setupPinned, the queued-job streams) write -1 here; none of them meets a marked job: a mark takes the job off its node and out of
+                         // the evicted table (removeJob, evTabDelete), so no evictor finds it again, selectNodeForJob refuses it, and the streams hold queued jobs only.
+                         // Were that ever broken, pjGather counts the marked job without a preemptor and the call returns ASCHED_ERR_INTERNAL instead of a wrong record.
   // result bookkeeping of PreemptingQueueScheduler.Schedule
   uint8_t* inPreempted; uint8_t* inScheduled; uint8_t* inSchedAndEvicted; int32_t* preemptedNode;
   // ---- queues
@@ -372,7 +376,10 @@ struct Dev {
   // The fair-share threshold table's arrays; the table is gone.  Dev is copied into the round kernel's LDS and passed as a kernel argument, so it keeps
   // its layout (and controlMain its test of ftT, which the host never sets) until a change that compacts it is measured on its own.
   int32_t* ftT;                // always NULL
-  int32_t* reservedP[3];       // always NULL
+  int32_t* jcPreSib;           // [M] PreemptionDetails.PreemptedSiblingJob (nodedb.go:514-520): the directly preempted gang member that pulled this job in, -1 for a direct victim,
+                               // -2 for a victim of the fairness optimiser (jcStagedBy: the job it placed).  Read only for jobs the round preempted.  (In one of the
+                               // three reserved slots: sizeof(Dev) is unchanged.)
+  int32_t* reservedP[2];       // always NULL
   int32_t reservedI[2];        // always 0
   uint8_t *optSched, *optPre;   // [M] how often the fairness optimiser scheduled / preempted a job in this round: its result lists are merged into the round's at the END
                          // of its phase (pqs.go:232-249), where a job it scheduled, preempted, scheduled again and preempted again comes out preempted

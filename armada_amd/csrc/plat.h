@@ -75,6 +75,10 @@ static int plat_run_fit_batch(Dev& d, const std::vector<int32_t>& shapes, int le
 // of the level is built first; reuseIndex: the one the previous call built still describes the node state and level (the passes of ONE submit check).  addMs: kernel time
 // of the same batch's packed-key part, added to what plat_last_fit_ms reports afterwards.  The CPU build's definition sits in kernels_fit_lit.h.
 static int plat_run_fit_batch_lit(Dev& d, const int32_t* nodeType, int nTypes, const std::vector<int32_t>& rows, int level, std::vector<int32_t>& out, bool reuseIndex, double addMs);
+// the preemption-cause join (kernels_preempt_join.h): count, scan, scatter, rank, (gather,) cause over the lists and scratch of `a`, all platform memory; a.cnt and a.info
+// zeroed by the caller.  Synchronous: the outputs are complete on return.  The CPU build's definition sits in kernels_preempt_join.h.
+struct PjArgs;
+static int plat_preempt_join(Dev& d, const PjArgs& a);
 static int plat_run_fit_capacity(Dev& d, const std::vector<int32_t>& shapes, std::vector<int32_t>& firstNode, std::vector<long long>& capacity, const int32_t* nodeByRankHost);
 static int plat_run_submit_gangs(Dev& d, const std::vector<int32_t>& off, const std::vector<int32_t>& jobs, std::vector<int32_t>& out);
 static double plat_last_fit_ms();

@@ -815,6 +815,21 @@ static int plat_run_fit_batch_lit(Dev& d, const int32_t* nodeType, int nTypes, c
   if (const char* e = getenv("ASCHED_FIT_LIT_TIMES")) if (e[0] == '1') fprintf(stderr, "[asched fit_lit] nodes %d queries %d level %d: index build %.4f ms, query %.4f ms\n", N, nq, level, (double)buildMs, (double)queryMs);
   return 0;
 }
+// the preemption-cause join (kernels_preempt_join.h; kernels in armada_sched_mgpu.hip).  ASCHED_PJOIN_TIMES=1 prints the device time of every call (tools/probe_preemption_causes.py).
+#include "kernels_preempt_join.h"
+extern "C" int asched_internal_preempt_join(const Dev* d, const PjArgs* a, hipStream_t s);
+static int plat_preempt_join(Dev& d, const PjArgs& a) {
+  PlatCtx* c = t_ctx;
+  hipStream_t st = c->stream;
+  (void)hipEventRecord(c->fitEv0, st);
+  bool ok = asched_internal_preempt_join(&d, &a, st) == 0;
+  (void)hipEventRecord(c->fitEv1, st);
+  ok = ok && hipOk(hipGetLastError(), "k_pj launch") && hipOk(hipStreamSynchronize(st), "k_pj");
+  if (!ok) { if (c->err.empty()) c->err = "k_pj launch failed"; return -1; }
+  (void)hipEventElapsedTime(&c->lastFitMs, c->fitEv0, c->fitEv1);
+  if (const char* e = getenv("ASCHED_PJOIN_TIMES")) if (e[0] == '1') fprintf(stderr, "[asched preempt_join] nodes %d scheduled %d preempted %d: %.4f ms\n", a.N, a.ns, a.np, (double)c->lastFitMs);
+  return 0;
+}
 // a caller-side buffer may be memory of this handle's GPU (a tensor the collective reduces in place: used directly) or host memory (staged)
 static bool plat_is_device_ptr(const void* p) {
   hipPointerAttribute_t a;

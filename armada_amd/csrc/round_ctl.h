@@ -936,6 +936,7 @@ DEV void preemptSiblings(Dev& d, Ctl& c, int firstPre, int lastPre) {
       updateKeysCtl(d, n);
       evTabDelete(d, idx, true);
       c.preList[c.preCount++] = s;
+      d.jcPreSib[s] = job;   // PreemptedSiblingJob (:514-520)
     }
   }
 }
@@ -968,8 +969,9 @@ DEV_COLD bool scheduleMany(Dev& d, Ctl& c, int ref) {
     updateKeysCtl(d, n);
     int eidx = d.evIndexOfJob[job];
     if (eidx >= 0) evTabDelete(d, eidx, true);
+    for (int i = pre0; i < pre1; i++) d.jcPreSib[c.preList[i]] = -1;
     preemptSiblings(d, c, pre0, pre1);
-    for (int i = pre0; i < c.preCount; i++) d.jcStagedBy[c.preList[i]] = job;
+    for (int i = pre0; i < c.preCount; i++) d.jcStagedBy[c.preList[i]] = job;   // (a sibling's preemptor is its member's)
     XSEG(28);
   }
   fastFence(c);  // the fast members' binds are no-return atomics: visible to whatever reads the planes next (commit bookkeeping, abort's undo)
@@ -979,8 +981,7 @@ DEV_COLD bool scheduleMany(Dev& d, Ctl& c, int ref) {
 // applyPreemptions (gang_scheduler.go:268-273) + MarkJobPreempted (scheduling.go:508-516)
 DEV void applyPreemptions(Dev& d, Ctl& c) {
   for (int i = 0; i < c.preCount; i++) {
-    int p = c.preList[i];
-    d.jcStagedBy[p] = -1;
+    int p = c.preList[i];   // (jcStagedBy / jcPreSib stay: the PreemptionDetails of the committed preemption)
     if (!d.jcPreempted[p]) { d.jcPreempted[p] = 1; d.rs->numPreemptedMarks++; if (d.rs->hasFpLimiter) d.rs->fpTokens -= 1.0; }
   }
   c.preCount = 0;

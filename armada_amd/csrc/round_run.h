@@ -292,7 +292,7 @@ DEV void bulkElem(Dev& d, int kind, int i) {
     case B_RESET_JOBS: {
       d.schedAtPrio[i] = NO_PRIORITY; d.jobNode[i] = -1; d.jobCutoff[i] = 0; d.jobEvictedOnNode[i] = 0; d.jobFlags[i] = 0;
       d.jcEvicted[i] = 0; d.jcAssigned[i] = -1; d.jcReason[i] = 0; d.jcHasPctx[i] = 0; d.pcNode[i] = -1; d.pcSap[i] = 0; d.pcPap[i] = ASCHED_MIN_PRIORITY;
-      d.pcMethod[i] = 0; d.jcGangCard[i] = d.jGang[i] >= 0 ? d.jGangCard[i] : 1; d.jcPreempted[i] = 0; d.jcUniValue[i] = -1; d.jcStagedBy[i] = -1;
+      d.pcMethod[i] = 0; d.jcGangCard[i] = d.jGang[i] >= 0 ? d.jGangCard[i] : 1; d.jcPreempted[i] = 0; d.jcUniValue[i] = -1; d.jcStagedBy[i] = -1; d.jcPreSib[i] = -1;
       d.inPreempted[i] = d.inScheduled[i] = d.inSchedAndEvicted[i] = 0; d.preemptedNode[i] = -1; d.evFlag[i] = 0;
       d.evTabAlive[i] = 0; d.evIndexOfJob[i] = -1;
       if (d.excl) { d.excl[i] = -1; if (i == 0) { EXCL(d)->count = 0; EXCL(d)->dynCount = 0; } }   // (asched_excluded_nodes: a round starts with nothing on record)
@@ -1071,6 +1071,7 @@ DEV void optApply(Dev& d, Ctl& c) {
       sctxPreemptJob(d, v);
       if (d.optPre[v] < 255) d.optPre[v]++;                                            // (merged into the round's sets by optEnd)
       d.preemptedNode[v] = n;
+      d.jcStagedBy[v] = job; d.jcPreSib[v] = -2;                                       // PreemptedWithOptimiserPreemption by this job (optimiser/gang_scheduler.go:226-227)
     }
     d.jcHasPctx[job] = 1; d.pcNode[job] = n; d.pcSap[job] = cf.pcPriority[d.jPc[job]]; d.pcPap[job] = ASCHED_MIN_PRIORITY; d.pcMethod[job] = ASCHED_METHOD_OPTIMISER;
     d.jcReason[job] = 0;

@@ -597,13 +597,49 @@ int32_t ASCHED_FN(schedule_round)(asched_t*, asched_round_result* out);
    On a market-driven pool (set_market) the queue is picked by the market iterator and the spot price is set, as NewQueueScheduler
    does when marketDriven is true (queue_scheduler.go:73-74, 176-203). */
 int32_t ASCHED_FN(schedule_queues)(asched_t*, asched_round_result* out);
+
+/* ---- who preempted each job, and by which kind of preemption (PopulatePreemptionDescriptions, preemption_description.go:21-81, called at the end of
+   PreemptingQueueScheduler.Schedule, preempting_queue_scheduler.go:268).  type is jctx.PreemptionType (context/pod.go:22-31; cycle_metrics.go:710-711
+   counts preemptions by it), preempting_job / preempted_sibling are jctx.PreemptionDetails (PreemptingJob: nodedb.go:1034, applied at gang_scheduler.go:268-273;
+   PreemptedSiblingJob: nodedb.go:514-520) — what the JobRunPreempted event carries as PreemptingJobId (scheduler.go:814,912).  No description strings cross
+   the boundary: the caller formats them with the templates of preemption_description.go:11-19. */
+#define ASCHED_PREEMPTION_UNKNOWN 1       /* context.Unknown (pod.go:25): not rescheduled, nothing on record, no urgency-scheduled job on its node (:50-51) */
+#define ASCHED_PREEMPTION_UNKNOWN_GANG 2  /* context.UnknownGangJob (pod.go:26): the same for a gang member (:46-48) */
+#define ASCHED_PREEMPTION_FAIRSHARE 3     /* context.PreemptedWithFairsharePreemption (pod.go:27): PreemptionDetails.PreemptingJob is set (:28-42); also on a market-driven pool */
+#define ASCHED_PREEMPTION_URGENCY 4       /* context.PreemptedWithUrgencyPreemption (pod.go:28): caused by one of the jobs of its candidate slice (:53-62) */
+#define ASCHED_PREEMPTION_OPTIMISER 5     /* context.PreemptedWithOptimiserPreemption (pod.go:29; optimiser/gang_scheduler.go:226-227) */
+typedef struct asched_preemption_cause {
+  int32_t type;               /* ASCHED_PREEMPTION_* */
+  int32_t preempting_job;     /* FAIRSHARE, OPTIMISER: PreemptionDetails.PreemptingJob / the job the optimiser placed; otherwise -1 */
+  int32_t preempted_sibling;  /* FAIRSHARE: PreemptionDetails.PreemptedSiblingJob — the directly preempted member of its gang that pulled it in; -1 = preempted directly */
+  int32_t cand_off;           /* URGENCY: candidates[cand_off .. cand_off + cand_count) are the jobs scheduled with urgency preemption on its node */
+  int32_t cand_count;
+  int32_t pad_;
+} asched_preemption_cause;
+/* Causes of the last round's preempted jobs: entry i belongs to asched_round_result.preempted_job[i].  `candidates` receives the round's jobs with method
+   ASCHED_METHOD_URGENCY grouped by node (calculateJobsScheduledWithUrgencyBasedPreemptionByNode :67-81), each once, ascending job index within a node (the
+   reference's order is that of a slice built while ranging over a map of scheduled jobs: undefined; ascending is this ABI's rule); every preempted job of a node
+   shares the node's slice.  *num_candidates: how many were written.  Valid after schedule_round and schedule_queues (there every preempted job is a fair-share
+   victim), optimiser and market-driven rounds and each replica of a sharded round included; computed only when asked for (a grid-wide join over the result lists in
+   HBM, csrc/kernels_preempt_join.h).  ASCHED_ERR_INVALID with no round result on the handle or after round_exchange (the approximate queue-hash mode moves
+   preemptions between replicas: the per-job record no longer describes the resolved round), and when cap < num_preempted or cand_cap < the number of candidates:
+   *num_candidates then holds the needed cand_cap and last_error both sizes. */
+int32_t ASCHED_FN(round_preemption_causes)(asched_t*, asched_preemption_cause* out /*[cap]*/, int32_t cap, int32_t* candidates /*[cand_cap]*/, int32_t cand_cap,
+                                           int32_t* num_candidates);
+/* The same join on the caller's lists (PopulatePreemptionDescriptions as a function of its two arguments; test hook like asched_pq_order, for
+   preemption_description_test.go:18-165).  sched_*: [ns] the scheduled jobs, their nodes (in [0, N) of the handle's nodes) and ASCHED_METHOD_*; pre_*: [np] per
+   preempted job its node, PreemptingJob or -1, PreemptedSiblingJob or -1 (-2: its description is already set by the fairness optimiser, :25-27 — type OPTIMISER)
+   and whether it is in a gang.  Candidates of a node come in the order of the scheduled list (a stable sort by node).  out: [np]; candidates: [cand_cap], at most ns are needed. */
+int32_t ASCHED_FN(preemption_join)(asched_t*, int32_t ns, const int32_t* sched_job, const int32_t* sched_node, const int32_t* sched_method, int32_t np,
+                                   const int32_t* pre_node, const int32_t* pre_by, const int32_t* pre_sibling, const uint8_t* pre_in_gang,
+                                   asched_preemption_cause* out, int32_t* candidates, int32_t cand_cap, int32_t* num_candidates);
 /* GangScheduler.Schedule (gang_scheduler.go:100-148) for one gang of queued jobs against the current round state. */
 int32_t ASCHED_FN(gang_schedule)(asched_t*, int32_t n, const int32_t* jobs, int32_t* ok, int32_t* reason, asched_pod_result* out /*[n]*/);
 /* sctx counters: out = {NumScheduledJobs, NumScheduledGangs, NumEvictedJobs, len(UnfeasibleSchedulingKeys)} (context/scheduling.go:55-69) */
 int32_t ASCHED_FN(round_counters)(asched_t*, int32_t* out /*[4]*/);
 /* Measurement hook (no reference counterpart): device time of the kernels behind the last call, taken with HIP events
    on the stream the kernels were launched on.  out[0] = ms of the last schedule_round/schedule_queues device work,
-   out[1] = ms of the last fit_select_batch (or optimiser k_opt_score) kernel, out[2] = kernel launches behind out[0], out[3] = ms of the last submit_check launch.
+   out[1] = ms of the last fit_select_batch (or optimiser k_opt_score) kernel, or of the kernels of the last round_preemption_causes / preemption_join if that came later, out[2] = kernel launches behind out[0], out[3] = ms of the last submit_check launch.
    The CPU oracle reports zeros. */
 int32_t ASCHED_FN(kernel_times)(asched_t*, double* out /*[4]*/);
 /* Measurement hook (no reference counterpart): where the device time of the last schedule_round went.  out = {whole launch sequence ms (HIP

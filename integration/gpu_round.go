@@ -23,10 +23,12 @@ import "C"
 
 import (
 	"context"
+	"fmt"
 	"math"
 	"runtime"
 	"sort"
 	"strconv"
+	"strings"
 	"sync"
 	"time"
 	"unsafe"
@@ -850,7 +852,79 @@ func (g *GpuRound) Schedule(ctx *armadacontext.Context, sctx *schedulercontext.S
 			}
 		}
 	}
-	return g.buildResult(sctx, &out), nil
+	res := g.buildResult(sctx, &out)
+	if err := g.populatePreemptionCauses(res, int(out.num_scheduled)); err != nil {
+		return nil, err
+	}
+	return res, nil
+}
+
+// the templates of preemption_description.go:11-19 (unexported there; the shim lives in the same package and uses the reference's own constants when it is added to it)
+const (
+	gpuUnknownPreemptionCause            = "Preempted by scheduler due to the job failing to reschedule - possibly node resource changed causing this job to be unschedulable\nNode Summary:\n%s"
+	gpuUnknownGangPreemptionCause        = "Preempted by scheduler due to the job failing to reschedule - possibly another job in the gang was preempted or the node resource changed causing this job to be unschedulable"
+	gpuGangSiblingFairSharePreemption    = "Preempted by scheduler using fair share preemption because the fellow gang member %s was preempted by %s"
+	gpuFairSharePreemption               = "Preempted by scheduler using fair share preemption - preempting job %s"
+	gpuMarketBasedPreemption             = "Preempted by scheduler using market based preemption - current job has a bid of %f - preempting job %s has a bid of %f"
+	gpuUrgencyPreemption                 = "Preempted by scheduler using urgency preemption - preempting job %s"
+	gpuUrgencyPreemptionMultiJob         = "Preempted by scheduler using urgency preemption - preemption caused by one of the following jobs %s"
+	gpuOptimiserPreemption               = "Preempted by scheduler using fairness optimiser - preempting job %s" // optimiser/gang_scheduler.go:226
+)
+
+// populatePreemptionCauses == PopulatePreemptionDescriptions (preemption_description.go:21-81) + the PreemptionDetails that applyPreemptions / preemptSiblingGangJobs
+// attach (gang_scheduler.go:268-273, nodedb.go:1034, 514-520): asched_round_preemption_causes returns one record per preempted job (entry i belongs to
+// preempted_job[i], the order of res.PreemptedJobs) and the urgency candidates grouped by node; the strings are formatted here, none crosses the boundary.
+func (g *GpuRound) populatePreemptionCauses(res *SchedulingResult, numScheduled int) error {
+	np := len(res.PreemptedJobs)
+	if np == 0 {
+		return nil
+	}
+	causes := make([]C.asched_preemption_cause, np)
+	cand := make([]int32, numScheduled+1) // at most every scheduled job is a candidate
+	var numCand C.int32_t
+	if err := g.check(C.asched_round_preemption_causes(g.h, &causes[0], C.int32_t(np), (*C.int32_t)(unsafe.Pointer(&cand[0])), C.int32_t(numScheduled), &numCand)); err != nil {
+		return err
+	}
+	marketDriven := g.market != nil && g.market.Enabled
+	for i, jctx := range res.PreemptedJobs {
+		c := causes[i]
+		switch c._type {
+		case C.ASCHED_PREEMPTION_OPTIMISER:
+			jctx.PreemptionType = schedulercontext.PreemptedWithOptimiserPreemption
+			jctx.PreemptionDescription = fmt.Sprintf(gpuOptimiserPreemption, g.jobs[c.preempting_job].Id())
+		case C.ASCHED_PREEMPTION_FAIRSHARE:
+			by := g.jobs[c.preempting_job]
+			jctx.PreemptionDetails = &schedulercontext.PreemptionDetails{PreemptingJob: by}
+			jctx.PreemptionType = schedulercontext.PreemptedWithFairsharePreemption
+			if c.preempted_sibling >= 0 {
+				sib := g.jobs[c.preempted_sibling]
+				jctx.PreemptionDetails.PreemptedSiblingJob = sib
+				jctx.PreemptionDescription = fmt.Sprintf(gpuGangSiblingFairSharePreemption, sib.Id(), by.Id())
+			} else if marketDriven {
+				jctx.PreemptionDescription = fmt.Sprintf(gpuMarketBasedPreemption, jctx.Job.GetBidPrice(g.pool), by.Id(), by.GetBidPrice(g.pool))
+			} else {
+				jctx.PreemptionDescription = fmt.Sprintf(gpuFairSharePreemption, by.Id())
+			}
+		case C.ASCHED_PREEMPTION_URGENCY:
+			ids := make([]string, 0, int(c.cand_count))
+			for _, j := range cand[c.cand_off : c.cand_off+c.cand_count] {
+				ids = append(ids, g.jobs[j].Id())
+			}
+			jctx.PreemptionType = schedulercontext.PreemptedWithUrgencyPreemption
+			if len(ids) == 1 {
+				jctx.PreemptionDescription = fmt.Sprintf(gpuUrgencyPreemption, ids[0])
+			} else {
+				jctx.PreemptionDescription = fmt.Sprintf(gpuUrgencyPreemptionMultiJob, strings.Join(ids, ","))
+			}
+		case C.ASCHED_PREEMPTION_UNKNOWN_GANG:
+			jctx.PreemptionType = schedulercontext.UnknownGangJob
+			jctx.PreemptionDescription = gpuUnknownGangPreemptionCause
+		default:
+			jctx.PreemptionType = schedulercontext.Unknown
+			jctx.PreemptionDescription = fmt.Sprintf(gpuUnknownPreemptionCause, jctx.GetAssignedNode().SummaryString())
+		}
+	}
+	return nil
 }
 
 // PriceGang == pricer.GangPricer.Price (pricer/gang_pricer.go:48-117) on the NodeDb as the round left it; jobs are rows of the uploaded job set (the synthetic
