@@ -218,6 +218,13 @@ class CPreemptionCause(C.Structure):  # asched_preemption_cause
     _fields_ = [("type", C.c_int32), ("preempting_job", C.c_int32), ("preempted_sibling", C.c_int32), ("cand_off", C.c_int32), ("cand_count", C.c_int32), ("pad_", C.c_int32)]
 
 
+class CEvictorReport(C.Structure):  # asched_evictor_report
+    _fields_ = [("num_nodes", C.c_int32), ("num_queues", C.c_int32), ("num_resources", C.c_int32), ("num_evicted", C.c_int32), ("num_affected_nodes", C.c_int32), ("pad_", C.c_int32),
+                ("node_preemptible", C.POINTER(C.c_uint8)), ("node_reasons", C.POINTER(C.c_uint8)), ("node_evicted_jobs", C.POINTER(C.c_int32)),
+                ("queue_evicted_jobs", C.POINTER(C.c_int32)), ("queue_evicted_resources", C.POINTER(C.c_int64)), ("queue_evicted_off", C.POINTER(C.c_int32)),
+                ("evicted_job", C.POINTER(C.c_int32)), ("evicted_node", C.POINTER(C.c_int32))]
+
+
 class CExcludedReason(C.Structure):  # asched_excluded_reason
     _fields_ = [("kind", C.c_int32), ("a", C.c_int32), ("b", C.c_int32), ("c", C.c_int32), ("required", C.c_int64), ("available", C.c_int64),
                 ("count", C.c_int32), ("pad_", C.c_int32)]
@@ -239,12 +246,24 @@ ALL_SYMBOLS = [
     "shard_round", "shard_exchanges", "shard_area", "shard_open", "shard_peers",
     "excluded_nodes", "set_excluded_nodes",
     "round_preemption_causes", "preemption_join",
+    "set_evictor_report", "round_evictor_report",
 ]
 # entry points the CPU oracle does not implement (it is the single-process checker): the communicator and the collectives that run on it, and the join of a
 # round's result lists into preemption causes (a function of lists the oracle already delivers; tests/test_z_preemption_causes.py restates it)
 OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_destroy", "comm_rank", "fit_select_batch_sharded", "round_exchange", "shard_round", "shard_exchanges", "shard_area", "shard_open", "shard_peers",
-                    "round_preemption_causes", "preemption_join"}
+                    "round_preemption_causes", "preemption_join",
+                    "set_evictor_report", "round_evictor_report"}   # (recorded by passes between the launches of the split round: tests/test_z_evictor_report.py restates it)
 PREEMPTION_UNKNOWN, PREEMPTION_UNKNOWN_GANG, PREEMPTION_FAIRSHARE, PREEMPTION_URGENCY, PREEMPTION_OPTIMISER = 1, 2, 3, 4, 5   # ASCHED_PREEMPTION_* (context.PreemptionType)
+# ASCHED_EVR_* bits of asched_evictor_report.node_reasons, in bit order: the reference's reason strings in alphabetical order (makeNodePreemptiblityStats sorts them)
+EVICTOR_REASONS = ("all_jobs_preemptible", "below_protected_fair_share", "invalid_queue", "job_not_preemptible", "node_empty", "node_unschedulable")
+EVR_ALL_JOBS_PREEMPTIBLE, EVR_BELOW_PROTECTED_FAIR_SHARE, EVR_INVALID_QUEUE, EVR_JOB_NOT_PREEMPTIBLE, EVR_NODE_EMPTY, EVR_NODE_UNSCHEDULABLE = 1, 2, 4, 8, 16, 32
+
+
+def evictor_reason_string(mask: int) -> str:
+    """NodePreemptiblityStats.Reason of a node_reasons mask: the set reasons, sorted and comma-joined (eviction.go:275-285)"""
+    return ",".join(name for bit, name in enumerate(EVICTOR_REASONS) if (int(mask) >> bit) & 1)
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32)
 
 
@@ -425,6 +444,8 @@ class Library:
         f("round_stats", C.c_int32, [C.c_void_p, _i32p])
         f("excluded_nodes", C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(CExcludedReason), C.c_int32])
         f("set_excluded_nodes", C.c_int32, [C.c_void_p, C.c_int32])
+        f("set_evictor_report", C.c_int32, [C.c_void_p, C.c_int32])
+        f("round_evictor_report", C.c_int32, [C.c_void_p, C.POINTER(CEvictorReport)])
         f("round_preemption_causes", C.c_int32, [C.c_void_p, C.POINTER(CPreemptionCause), C.c_int32, _i32p, C.c_int32, _i32p])
         f("preemption_join", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, C.c_int32, _i32p, _i32p, _i32p, _u8p, C.POINTER(CPreemptionCause), _i32p, C.c_int32, _i32p])
 
@@ -1161,7 +1182,8 @@ class Scheduler:
     def round_timing(self):
         out = (C.c_double * 8)()
         self._check(self.lib.round_timing(self.h, out))
-        return dict(total_ms=out[0], control_ms=out[1], launches=int(out[2]), evict1_host_ms=out[3], evict3_host_ms=out[4], final_host_ms=out[5])
+        return dict(total_ms=out[0], control_ms=out[1], launches=int(out[2]), evict1_host_ms=out[3], evict3_host_ms=out[4], final_host_ms=out[5],
+                    evr_job_node_ms=out[6], evr_queue_ms=out[7])
 
     def round_stats(self):
         out = (C.c_int32 * 24)()
@@ -1228,6 +1250,26 @@ class Scheduler:
         self._check(fn(self.h, ns, _ptr(sj, C.c_int32), _ptr(sn, C.c_int32), _ptr(sm, C.c_int32), n, _ptr(pn, C.c_int32), _ptr(pb, C.c_int32), _ptr(ps, C.c_int32),
                        _ptr(pg, C.c_uint8), rec, _ptr(cand, C.c_int32), cap, C.byref(got)))
         return self._causes(rec, n, cand), cand[:got.value].copy()
+
+    def set_evictor_report(self, on: bool = True) -> None:
+        """record the EvictorResult of every following schedule_round (off by default: the round then runs exactly the launches it runs without the feature)"""
+        self._check(self._preemption_fn("set_evictor_report")(self.h, 1 if on else 0))
+
+    def round_evictor_report(self) -> dict:
+        """SchedulingInformation.EvictorResult of the last schedule_round as numpy arrays (copies): num_evicted, num_affected_nodes, node_preemptible [N] bool,
+        node_reasons [N] uint8 (EVR_* bits; evictor_reason_string), node_evicted_jobs [N], queue_evicted_jobs [Q], queue_evicted_resources [Q, R], queue_evicted_off [Q+1],
+        evicted_job / evicted_node [num_evicted] (grouped by queue, scheduling order inside a queue)"""
+        fn = self._preemption_fn("round_evictor_report")
+        r = CEvictorReport()
+        self._check(fn(self.h, C.byref(r)))
+        n, q, nr, ne = r.num_nodes, r.num_queues, r.num_resources, r.num_evicted
+
+        def arr(p, count, dtype):
+            return np.ctypeslib.as_array(p, shape=(count,)).astype(dtype, copy=True) if count else np.zeros(0, dtype=dtype)
+        return dict(num_evicted=ne, num_affected_nodes=r.num_affected_nodes,
+                    node_preemptible=arr(r.node_preemptible, n, np.uint8).astype(bool), node_reasons=arr(r.node_reasons, n, np.uint8), node_evicted_jobs=arr(r.node_evicted_jobs, n, np.int32),
+                    queue_evicted_jobs=arr(r.queue_evicted_jobs, q, np.int32), queue_evicted_resources=arr(r.queue_evicted_resources, q * nr, np.int64).reshape(q, nr),
+                    queue_evicted_off=arr(r.queue_evicted_off, q + 1, np.int32), evicted_job=arr(r.evicted_job, ne, np.int32), evicted_node=arr(r.evicted_node, ne, np.int32))
 
     def schedule_queues(self) -> RoundResult:
         return self.schedule_round(queues_only=True)

@@ -316,3 +316,82 @@ extern "C" int asched_internal_preempt_join(const Dev* d, const PjArgs* a, hipSt
   }
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// ------------------------------------------------------------------------------------------------ the evictor report of a round's phase 1 (kernels_evict_report.h)
+#define EVR_FN __device__ static inline
+#include "kernels_evict_report.h"
+static_assert(EVR_TILE == MG_THREADS, "the queue pass holds one entry of its tile per thread");
+// runs of neighbouring lanes with the same key inside a wave.  head: this lane starts a run.  *start: the first lane of this lane's run; returns whether it is the last
+__device__ static inline bool evrRun(bool head, int* start) {
+  int lane = threadIdx.x & 63;
+  unsigned long long heads = __ballot(head) | 1ull;
+  *start = 63 - __builtin_clzll(heads & (lane == 63 ? ~0ull : (2ull << lane) - 1));
+  return lane == 63 || ((heads >> (lane + 1)) & 1);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_evr_jobs(Dev d, EvrArgs a) {
+  long long i = MG_IDX();
+  int lane = threadIdx.x & 63, n = -1, reason = 0, ev = 0;
+  if (i < a.M) evrJobTerms(d, a, (int)i, &n, &reason, &ev);
+  int cnt = n >= 0 ? 1 : 0, prev = __shfl_up(n, 1, 64), start;
+  bool last = evrRun(lane == 0 || prev != n, &start);
+  for (int o = 1; o < 64; o <<= 1) {   // segmented inclusive scan: the last lane of a run ends up with the run's sums
+    int c2 = __shfl_up(cnt, o, 64), r2 = __shfl_up(reason, o, 64), e2 = __shfl_up(ev, o, 64);
+    if (lane - o >= start) { cnt += c2; reason |= r2; ev += e2; }
+  }
+  if (last && n >= 0) {
+    atomicAdd(a.nodeJobs + n, cnt);
+    if (reason) atomicOr(a.nodeOr + n, reason);
+    if (ev) atomicAdd(a.nodeEvicted + n, ev);
+  }
+}
+__global__ __launch_bounds__(MG_THREADS) void k_evr_nodes(EvrArgs a) {
+  __shared__ int wsum[MG_THREADS / 64];
+  long long n = MG_IDX();
+  int aff = n < a.N ? evrNode(a, (int)n) : 0;
+  unsigned long long m = __ballot(aff);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = (int)__builtin_popcountll(m);
+  __syncthreads();
+  if (threadIdx.x == 0) { int s = 0; for (int k = 0; k < MG_THREADS / 64; k++) s += wsum[k]; if (s) atomicAdd(a.affected, s); }
+}
+__global__ __launch_bounds__(MG_THREADS) void k_evr_queues(Dev d, EvrArgs a) {
+  constexpr int NW = MG_THREADS / 64;
+  __shared__ int qEnds[2], headQ[NW], tailQ[NW];
+  __shared__ long long tailSum[NW];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (long long g = MG_IDX(); g <= a.Q; g += (long long)gridDim.x * MG_THREADS) evrCopyOff(d, a, (int)g);
+  const long long base = (long long)blockIdx.x * EVR_TILE;
+  if (base >= a.n1) return;   // (the workgroup of an empty list: only the copy above)
+  const long long p = base + threadIdx.x;
+  const bool valid = p < a.n1;
+  if (threadIdx.x < 2) { long long e = threadIdx.x == 0 ? base : (base + EVR_TILE <= a.n1 ? base + EVR_TILE : a.n1) - 1; qEnds[threadIdx.x] = evrQueueOf(d.evOff, (int)e, 0, a.Q - 1); }
+  __syncthreads();
+  int q = -1, j = 0;
+  if (valid) { q = qEnds[0] == qEnds[1] ? qEnds[0] : evrQueueOf(d.evOff, (int)p, qEnds[0], qEnds[1]); j = d.evList[p]; evrGather(d, a, (int)p); }
+  int prev = __shfl_up(q, 1, 64), start;
+  (void)evrRun(lane == 0 || prev != q, &start);
+  if (lane == 0) headQ[w] = q;
+  if (lane == 63) tailQ[w] = q;
+  __syncthreads();
+  // the lane that ends its queue's run inside the tile: the next entry is another queue's, or there is none in this tile
+  int next = __shfl_down(q, 1, 64);
+  if (lane == 63) next = w + 1 < NW ? headQ[w + 1] : -1;
+  const bool ends = valid && next != q, fromLane0 = start == 0;
+  for (int r = 0; r < a.R; r++) {
+    long long v = valid ? evrReqCol(d, j, r) : 0;
+    for (int o = 1; o < 64; o <<= 1) { long long t = __shfl_up(v, o, 64); if (lane - o >= start) v += t; }
+    if (lane == 63) tailSum[w] = v;   // the sum of the wave's trailing run
+    __syncthreads();
+    if (ends) {
+      // (evList is sorted by queue: equal queues at the ends of two neighbouring waves are ONE run, and a wave whose head and tail are both q holds nothing else)
+      if (fromLane0) for (int k = w - 1; k >= 0 && tailQ[k] == q; k--) { v += tailSum[k]; if (headQ[k] != q) break; }   // the run began in an earlier wave of the tile
+      if (v) atomicAdd((unsigned long long*)(a.qRes + (size_t)q * a.R + r), (unsigned long long)v);
+    }
+    __syncthreads();   // (tailSum is written again for the next column)
+  }
+}
+extern "C" int asched_internal_evict_report(const Dev* d, const EvrArgs* a, int pass, hipStream_t st) {
+  if (pass == EVR_PASS_JOBS) hipLaunchKernelGGL(k_evr_jobs, dim3(mgBlocks(a->M)), dim3(MG_THREADS), 0, st, *d, *a);
+  else if (pass == EVR_PASS_NODES) hipLaunchKernelGGL(k_evr_nodes, dim3(mgBlocks(a->N)), dim3(MG_THREADS), 0, st, *a);
+  else hipLaunchKernelGGL(k_evr_queues, dim3(a->n1 > 0 ? (a->n1 + EVR_TILE - 1) / EVR_TILE : 1), dim3(MG_THREADS), 0, st, *d, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}

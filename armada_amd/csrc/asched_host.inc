@@ -26,6 +26,7 @@
 #include <thread>
 #include "kernels_fit_lit.h"   // FitLitIdx and, in the CPU build of the tests, plat_run_fit_batch_lit
 #include "kernels_preempt_join.h"   // PjArgs and, in the CPU build of the tests, plat_preempt_join
+#include "kernels_evict_report.h"   // EvrArgs and, in the CPU build of the tests, plat_evict_report
 
 namespace {
 
@@ -162,6 +163,15 @@ struct asched {
   bool keyWide = false;                                // the wide (oversubscription-proof) field layout is in use: some request on an indexed column is negative
   DevBufs fastBufs;
   DevBufs pjBufs;                                  // lists and scratch of the preemption-cause join (kernels_preempt_join.h), kept between calls
+  // ---- the evictor report of a round's phase 1 (asched_set_evictor_report; kernels_evict_report.h)
+  enum EvrState { EVR_NONE = 0, EVR_VALID, EVR_MARKET, EVR_SINGLE };
+  bool evrOn = false;                              // the switch
+  bool evrSized = false;                           // evr's buffers fit the handle's N, M, Q, R (round_prepare, or the first round after the switch was turned on)
+  int evrState = EVR_NONE;                         // what the last schedule_round left: a report, nothing (no round, a failed one), or a round that cannot have one
+  DevBufs evrBufs; EvrArgs evr; void* evrZero = nullptr; size_t evrZeroBytes = 0;   // the words the passes add into are ONE block: one memset per round
+  std::vector<uint8_t> nodeUnsched;                // [N] asched_nodes.unschedulable (nodeFlags bit 0 is unschedulable && overAllocated)
+  std::vector<uint8_t> evrNodePre, evrNodeReasons; std::vector<int32_t> evrNodeEvicted, evrQJobs, evrQOff, evrJob, evrNode; std::vector<int64_t> evrQRes;   // the downloaded report
+  double evrMs[3] = {0, 0, 0};                     // device ms of the three passes of the last round (ASCHED_EVR_TIMES=1; asched_round_timing)
   std::vector<int32_t> labelSlots;                 // sorted indexed label keys
   std::vector<std::vector<int32_t>> slotValues;    // per slot: sorted values present on nodes
   std::vector<int32_t> uniOffHost;
@@ -793,7 +803,7 @@ asched_t* asched_create(const asched_config* c) {
 void asched_destroy(asched_t* h) {
   if (!h) return;
   plat_enter(h->plat);
-  h->nodeBufs.freeAll(); h->jobBufs.freeAll(); h->queueBufs.freeAll(); h->maskBufs.freeAll(); h->fastBufs.freeAll(); h->pjBufs.freeAll();
+  h->nodeBufs.freeAll(); h->jobBufs.freeAll(); h->queueBufs.freeAll(); h->maskBufs.freeAll(); h->fastBufs.freeAll(); h->pjBufs.freeAll(); h->evrBufs.freeAll(); h->exclBufs.freeAll();
   plat_pinned_free(h->resPin); plat_free(h->commStatus); plat_free(h->dev.rs); plat_free(h->dev.cmdIO); plat_free(h->dev.scanResult); plat_free(h->dev.undo);
   plat_close(h->plat);
   delete h;
@@ -822,6 +832,7 @@ int32_t asched_nodes_upsert(asched_t* h, const asched_nodes* in) { if (!h) retur
   std::vector<int64_t> totalRes((size_t)R * Npad, 0), allocatable((size_t)R * Npad, 0), alloc0;
   if (in->alloc_by_prio) alloc0.assign((size_t)P * R * Npad, 0);
   std::vector<uint8_t> flags(N, 0);
+  h->nodeUnsched.assign(N, 0); h->evrSized = false;
   int64_t total[MAXR] = {0};
   for (int i = 0; i < N; i++) {
     bool unsched = in->unschedulable && in->unschedulable[i];
@@ -829,6 +840,7 @@ int32_t asched_nodes_upsert(asched_t* h, const asched_nodes* in) { if (!h) retur
     if (unsched) h->nodeTaints[i].push_back({kUnschedulableTaintKey, 0, ASCHED_EFFECT_NO_SCHEDULE});  // node.go:127-129
     if (in->label_off) for (int k = in->label_off[i]; k < in->label_off[i + 1]; k++) h->nodeLabels[i].push_back({in->label_key[k], in->label_value[k]});
     flags[i] = (unsched && in->over_allocated && in->over_allocated[i]) ? 1 : 0;
+    h->nodeUnsched[i] = unsched ? 1 : 0;
     // NewNodeType (internaltypes/node_type.go:68-131)
     HType t; std::string canon;
     int64_t ov = in->node_type_override ? in->node_type_override[i] : -1;
@@ -1892,6 +1904,7 @@ static int64_t multiplyResource(int64_t res, double m) {  // resource_list.go:31
   return (int64_t)((double)res * m);
 }
 
+static void evrSize(asched* h);   // (the evictor report's buffers, below)
 int32_t asched_round_prepare(asched_t* h, const asched_queues* in) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
   if (h) { h->haveRoundResult = false; h->stateEpoch++; }
   if (!h->nodesSet || !h->jobsSet) return fail(h, ASCHED_ERR_INVALID, "round_prepare: nodes_upsert and jobs_set first");
@@ -1902,6 +1915,8 @@ int32_t asched_round_prepare(asched_t* h, const asched_queues* in) { if (!h) ret
   int Q = h->Q = in->q, R = h->R, npc = h->npc, M = h->M;
   if (Q > 4096) return fail(h, ASCHED_ERR_UNSUPPORTED, "more than 4096 queues");
   d.cfg.Q = Q;
+  h->evrState = asched::EVR_NONE; h->evrSized = false;
+  if (h->evrOn) evrSize(h);
   std::vector<int32_t> nameRank(Q); std::vector<double> weight(in->weight, in->weight + Q);
   for (int q = 0; q < Q; q++) nameRank[q] = in->name_rank ? in->name_rank[q] : q;
   std::vector<int64_t> allocByPc((size_t)Q * npc * R, 0), alloc((size_t)Q * R, 0), demand((size_t)Q * R, 0), penalty((size_t)Q * R, 0), pcLimit((size_t)Q * npc * R, 0);
@@ -2115,6 +2130,26 @@ static int downloadResult(asched* h, asched_round_result* out, const int32_t* io
   return 0;
 }
 
+// ---- the evictor report (kernels_evict_report.h): its buffers, sized for the handle's nodes, jobs, queues and resources
+static void evrSize(asched* h) {
+  DevBufs& b = h->evrBufs;
+  b.recycle();
+  EvrArgs& a = h->evr; memset(&a, 0, sizeof a);
+  const size_t N = (size_t)h->N, M = (size_t)h->M, Q = (size_t)h->Q, R = (size_t)h->R;
+  a.N = h->N; a.M = h->M; a.Q = h->Q; a.R = h->R;
+  // [qRes Q x R i64][nodeJobs N][nodeOr N][nodeEvicted N][affected 1]: the words the passes add into
+  h->evrZeroBytes = Q * R * 8 + (3 * N + 1) * 4;
+  char* z = (char*)b.alloc<char>(h->evrZeroBytes); h->evrZero = z;
+  a.qRes = (int64_t*)z; a.nodeJobs = (int32_t*)(z + Q * R * 8); a.nodeOr = a.nodeJobs + N; a.nodeEvicted = a.nodeOr + N; a.affected = a.nodeEvicted + N;
+  a.nodePreemptible = b.allocRaw<uint8_t>(N); a.nodeReasons = b.allocRaw<uint8_t>(N);
+  a.qJobs = b.allocRaw<int32_t>(Q); a.qOff = b.allocRaw<int32_t>(Q + 1); a.evJob = b.allocRaw<int32_t>(M); a.evNode = b.allocRaw<int32_t>(M);
+  uint8_t* u = b.allocRaw<uint8_t>(N);
+  if (u && N) plat_h2d(u, h->nodeUnsched.data(), N);
+  a.nodeUnsched = u;
+  bool ok = true;
+  for (auto& p : b.ptrs) if (!p.first) ok = false;
+  h->evrSized = ok;
+}
 // PreemptingQueueScheduler.evict (pqs.go:291-353) for an evictor whose job filter has been evaluated into evFlag — the grid-wide form of
 // round_run.h pqsEvict: every step is a kernel over all CUs; the number of evicted jobs comes back to the host (it sizes what follows).
 static int evictPhaseSplit(asched* h, bool phase3, int* nOut) {
@@ -2122,11 +2157,17 @@ static int evictPhaseSplit(asched* h, bool phase3, int* nOut) {
   int M = h->M, N = h->N, Q = h->Q, R = h->R;
   int ordTotal = h->ordOffHost.empty() ? 0 : h->ordOffHost[std::min<size_t>((size_t)Q, h->ordOffHost.size() - 1)];
   if (plat_bulk(d, B_GANG_CLOSURE, h->G)) return -1;
+  const bool report = !phase3 && h->evrOn && h->evrSized;
+  if (report) {   // the evictor report's job and node passes: evFlag is EvictedJctxsByJobId, jobEvictedOnNode still the start-of-round state
+    plat_memset(h->evrZero, 0, h->evrZeroBytes);
+    if (plat_evict_report(d, h->evr, EVR_PASS_JOBS) || plat_evict_report(d, h->evr, EVR_PASS_NODES)) return -1;
+  }
   if (plat_evict_apply(d, phase3 ? 1 : 0, ordTotal)) return -1;
   if (plat_bulk(d, B_KEYS_ALL, N)) return -1;
   // InMemoryJobRepository.EnqueueMany (jobiteration.go:85-108): per-queue lists in SchedulingOrderCompare order == order-preserving compaction of the pre-sorted job order
   int n = 0;
   if (plat_compact(d, d.ordAll, ordTotal, d.evFlag, d.evList, d.evSortKey, d.ordAllOff, Q, d.evOff, &n)) return -1;
+  if (report) { h->evr.n1 = n; if (plat_evict_report(d, h->evr, EVR_PASS_QUEUES)) return -1; }   // (before phase 3 reuses evList / evOff)
   if (plat_bulk(d, B_RESET_EVTAB, M)) return -1;   // nodeDb.Reset() (nodedb.go:299-313)
   if (plat_small(d, SM_EVICT_POST, n)) return -1;
   if (plat_bulk(d, B_RESET_GANGSEEN, h->G)) return -1;
@@ -2362,6 +2403,8 @@ int32_t asched_schedule_round(asched_t* h, asched_round_result* out) { if (!h) r
   static const bool singleEnv = [] { const char* e = getenv("ASCHED_SINGLE_LAUNCH"); return e && e[0] == '1'; }();
   const bool single = singleEnv && !h->opt.enabled;   // (the optimiser's phase sits between the launches of the split round)
   int32_t io[4];
+  h->evrState = asched::EVR_NONE;
+  if (h->evrOn && !h->evrSized && !h->market.enabled && !single) evrSize(h);   // (the switch was turned on after round_prepare)
   if (h->market.enabled) {
     // a market-driven round (round_mkt.h): the whole of PreemptingQueueScheduler.Schedule in ONE launch of the auxiliary kernel — its code lives in that kernel's
     // code object only, and it is the generic path throughout (a literal container/heap picks the queue: there is no packed key to sort by)
@@ -2376,16 +2419,20 @@ int32_t asched_schedule_round(asched_t* h, asched_round_result* out) { if (!h) r
     h->roundMs = plat_last_control_ms(); h->roundLaunches = plat_last_control_launches();
     h->roundTotalMs = h->roundControlMs = h->roundMs;
     getIO(h, io, 4);
+    if (h->evrOn) h->evrState = asched::EVR_MARKET;
   } else if (single) {
     int rc = runControl(h, CMD_ROUND);
     if (rc) return rc;
     h->roundMs = plat_last_control_ms(); h->roundLaunches = plat_last_control_launches();
     h->roundTotalMs = h->roundControlMs = h->roundMs;
     getIO(h, io, 4);
+    if (h->evrOn) h->evrState = asched::EVR_SINGLE;
   } else {
+    const bool report = h->evrOn && h->evrSized;
     int rc = runRoundSplit(h, io);
     if (rc) return rc;
     h->roundMs = h->roundTotalMs;
+    if (report) { h->evrState = asched::EVR_VALID; plat_evict_report_ms(h->evrMs); }
   }
   return downloadResult(h, out, io);
 }
@@ -2487,9 +2534,12 @@ int32_t asched_market_result(asched_t* h, asched_market_outcome* out) { if (!h) 
   return 0;
 }
 // Measurement hook: device time of the last schedule_round.  out = {whole sequence ms (events on the stream), persistent k_control launches ms,
-// kernel launches, host ms of the evict-1 / evict-3 / final bulk phases incl. their count read-backs, 0, 0}
+// kernel launches, host ms of the evict-1 / evict-3 / final bulk phases incl. their count read-backs, ms of the evictor report's job + node passes, of its queue
+// pass (ASCHED_EVR_TIMES=1 and the report on: events around them; else 0)}
 int32_t asched_round_timing(asched_t* h, double* out) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
-  out[0] = h->roundTotalMs; out[1] = h->roundControlMs; out[2] = h->roundLaunches; out[3] = h->roundPhaseMs[0]; out[4] = h->roundPhaseMs[1]; out[5] = h->roundPhaseMs[2]; out[6] = out[7] = 0;
+  out[0] = h->roundTotalMs; out[1] = h->roundControlMs; out[2] = h->roundLaunches; out[3] = h->roundPhaseMs[0]; out[4] = h->roundPhaseMs[1]; out[5] = h->roundPhaseMs[2];
+  const bool evr = h->evrState == asched::EVR_VALID;
+  out[6] = evr ? h->evrMs[0] + h->evrMs[1] : 0; out[7] = evr ? h->evrMs[2] : 0;
   return 0;
 }
 int32_t asched_schedule_queues(asched_t* h, asched_round_result* out) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
@@ -2563,6 +2613,46 @@ int32_t asched_preemption_join(asched_t* h, int32_t ns, const int32_t* sJob, con
   a.pGang = b.allocRaw<uint8_t>((size_t)np);
   if (a.pGang && np) plat_h2d(a.pGang, pGang, (size_t)np);
   return preemptJoinRun(h, a, "preemption_join", out, np, candidates, candCap, numCandidates);
+}
+// ---- the evictor report of the last round (include/armada_sched.h; kernels_evict_report.h)
+int32_t asched_set_evictor_report(asched_t* h, int32_t on) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
+  if ((on != 0) != h->evrOn) { h->evrOn = on != 0; h->evrState = asched::EVR_NONE; h->evrSized = false; }   // (the buffers are sized at the next round_prepare or round)
+  if (!h->evrOn) h->evrBufs.recycle();
+  return 0;
+}
+int32_t asched_round_evictor_report(asched_t* h, asched_evictor_report* out) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
+  if (!out) return fail(h, ASCHED_ERR_INVALID, "round_evictor_report: no output struct");
+  memset(out, 0, sizeof *out);
+  if (!h->evrOn) return fail(h, ASCHED_ERR_INVALID, "round_evictor_report: the report is switched off (asched_set_evictor_report before the round)");
+  if (h->market.enabled || h->evrState == asched::EVR_MARKET)
+    return fail(h, ASCHED_ERR_UNSUPPORTED, "round_evictor_report: a market-driven round is one launch of the auxiliary kernel: the passes that record the report run between the launches of the split round");
+  if (h->evrState == asched::EVR_SINGLE)
+    return fail(h, ASCHED_ERR_UNSUPPORTED, "round_evictor_report: ASCHED_SINGLE_LAUNCH=1 runs the round in one launch: the passes that record the report run between the launches of the split round");
+  if (h->evrState != asched::EVR_VALID || !h->haveRoundResult)
+    return fail(h, ASCHED_ERR_INVALID, "round_evictor_report: no completed schedule_round with the report switched on (none since the switch or round_prepare, or the last one failed or timed out)");
+  if (h->roundExchanged)
+    return fail(h, ASCHED_ERR_UNSUPPORTED, "round_evictor_report: not after round_exchange (the queue-hash mode resolves preemptions between replicas; the report describes this replica's own round)");
+  const EvrArgs& a = h->evr;
+  const size_t N = (size_t)a.N, Q = (size_t)a.Q, R = (size_t)a.R, n1 = (size_t)a.n1;
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  int32_t affected = 0;
+  h->evrNodePre.assign(N + 1, 0); h->evrNodeReasons.assign(N + 1, 0); h->evrNodeEvicted.assign(N + 1, 0);
+  h->evrQJobs.assign(Q + 1, 0); h->evrQRes.assign(Q * R + 1, 0); h->evrQOff.assign(Q + 1, 0); h->evrJob.assign(n1 + 1, 0); h->evrNode.assign(n1 + 1, 0);
+  if (N) { plat_d2h(h->evrNodePre.data(), a.nodePreemptible, N); plat_d2h(h->evrNodeReasons.data(), a.nodeReasons, N); }
+  plat_d2h(h->evrNodeEvicted.data(), a.nodeEvicted, (N + 1) * 4);   // (the affected-node count sits directly behind the N counters: evrSize)
+  if (Q) { plat_d2h(h->evrQJobs.data(), a.qJobs, Q * 4); plat_d2h(h->evrQRes.data(), a.qRes, Q * R * 8); }
+  plat_d2h(h->evrQOff.data(), a.qOff, (Q + 1) * 4);
+  if (n1) { plat_d2h(h->evrJob.data(), a.evJob, n1 * 4); plat_d2h(h->evrNode.data(), a.evNode, n1 * 4); }
+  affected = h->evrNodeEvicted[N];
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  if (h->evrQOff[Q] != a.n1) return fail(h, ASCHED_ERR_INTERNAL, "round_evictor_report: the per-queue offsets do not end at the number of evicted jobs");
+  out->num_nodes = a.N; out->num_queues = a.Q; out->num_resources = a.R; out->num_evicted = a.n1; out->num_affected_nodes = affected;
+  out->node_preemptible = h->evrNodePre.data(); out->node_reasons = h->evrNodeReasons.data(); out->node_evicted_jobs = h->evrNodeEvicted.data();
+  out->queue_evicted_jobs = h->evrQJobs.data(); out->queue_evicted_resources = h->evrQRes.data(); out->queue_evicted_off = h->evrQOff.data();
+  out->evicted_job = h->evrJob.data(); out->evicted_node = h->evrNode.data();
+  if (const char* e = getenv("ASCHED_EVR_TIMES")) if (e[0] == '1')
+    fprintf(stderr, "[asched evict_report] nodes %d jobs %d evicted %d: job pass %.4f ms, node pass %.4f ms, queue pass %.4f ms\n", a.N, a.M, a.n1, h->evrMs[0], h->evrMs[1], h->evrMs[2]);
+  return 0;
 }
 int32_t asched_gang_schedule(asched_t* h, int32_t n, const int32_t* jobs, int32_t* ok, int32_t* reason, asched_pod_result* out) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
   if (!h->prepared) return fail(h, ASCHED_ERR_INVALID, "gang_schedule: round_prepare first");

@@ -79,6 +79,11 @@ static int plat_run_fit_batch_lit(Dev& d, const int32_t* nodeType, int nTypes, c
 // zeroed by the caller.  Synchronous: the outputs are complete on return.  The CPU build's definition sits in kernels_preempt_join.h.
 struct PjArgs;
 static int plat_preempt_join(Dev& d, const PjArgs& a);
+// one pass of the evictor report of a round's phase 1 (kernels_evict_report.h: EVR_PASS_JOBS / _NODES / _QUEUES) over the buffers of `a`, all platform memory, queued behind
+// the round's other launches: nothing is waited for.  A pass over no elements (no jobs, no nodes) is not launched.  The CPU build's definition sits in kernels_evict_report.h.
+struct EvrArgs;
+static int plat_evict_report(Dev& d, const EvrArgs& a, int pass);
+static void plat_evict_report_ms(double* out /*[3]*/);   // measurement hook: device ms of the passes of the last round (events around them when ASCHED_EVR_TIMES=1, else zeros)
 static int plat_run_fit_capacity(Dev& d, const std::vector<int32_t>& shapes, std::vector<int32_t>& firstNode, std::vector<long long>& capacity, const int32_t* nodeByRankHost);
 static int plat_run_submit_gangs(Dev& d, const std::vector<int32_t>& off, const std::vector<int32_t>& jobs, std::vector<int32_t>& out);
 static double plat_last_fit_ms();

@@ -31,6 +31,7 @@ struct PlatCtx {
   bool inRound = false;             // between plat_round_begin / plat_round_end: the deadline runs from the begin, the cancel word is consumed at the end
   std::chrono::steady_clock::time_point roundT0;
   hipEvent_t rEv0 = nullptr, rEv1 = nullptr;
+  hipEvent_t evrEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool evrTimed[3] = {false, false, false};   // ASCHED_EVR_TIMES=1: around the passes of the evictor report
   float roundTotalMs = 0.f, roundControlMs = 0.f; int roundLaunches = 0;
   int32_t* cmpScratch = nullptr; size_t cmpScratchInts = 0;   // block counts + total of the grid-wide compaction
   int optIndexN = -1, optIndexM = -1;   // sizes the optimiser's node -> jobs index in the scratch was built for (asched_host.inc decides when it may be reused)
@@ -246,6 +247,7 @@ static void plat_close(PlatCtx* c) {
   plat_comm_destroy_ctx(c);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   for (hipEvent_t e : {c->ev0, c->ev1, c->fitEv0, c->fitEv1, c->litEvMid, c->rEv0, c->rEv1}) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->evrEv) if (e) (void)hipEventDestroy(e);
   if (c->helpBox) (void)hipFree(c->helpBox);
   if (c->cmpScratch) (void)hipFree(c->cmpScratch);
   if (c->optScratch) (void)hipFree(c->optScratch);
@@ -829,6 +831,33 @@ static int plat_preempt_join(Dev& d, const PjArgs& a) {
   (void)hipEventElapsedTime(&c->lastFitMs, c->fitEv0, c->fitEv1);
   if (const char* e = getenv("ASCHED_PJOIN_TIMES")) if (e[0] == '1') fprintf(stderr, "[asched preempt_join] nodes %d scheduled %d preempted %d: %.4f ms\n", a.N, a.ns, a.np, (double)c->lastFitMs);
   return 0;
+}
+// the evictor report of a round's phase 1 (kernels_evict_report.h; kernels in armada_sched_mgpu.hip): one launch per pass on the round's stream.  ASCHED_EVR_TIMES=1 puts
+// a pair of events around every pass; plat_evict_report_ms reads them once the round is over (tools/probe_evictor_report.py).
+#include "kernels_evict_report.h"
+extern "C" int asched_internal_evict_report(const Dev* d, const EvrArgs* a, int pass, hipStream_t s);
+static hipEvent_t* evrEvents() {
+  static const bool on = [] { const char* e = getenv("ASCHED_EVR_TIMES"); return e && e[0] == '1'; }();
+  PlatCtx* c = t_ctx;
+  if (!on) return nullptr;
+  if (!c->evrEv[5]) for (int i = 0; i < 6; i++) if (!c->evrEv[i] && hipEventCreate(&c->evrEv[i]) != hipSuccess) { c->evrEv[i] = nullptr; return nullptr; }
+  return c->evrEv;
+}
+static int plat_evict_report(Dev& d, const EvrArgs& a, int pass) {
+  if ((pass == EVR_PASS_JOBS && a.M <= 0) || (pass == EVR_PASS_NODES && a.N <= 0)) return 0;
+  PlatCtx* c = t_ctx;
+  hipEvent_t* ev = evrEvents();
+  if (ev) (void)hipEventRecord(ev[2 * pass], c->stream);
+  bool ok = asched_internal_evict_report(&d, &a, pass, c->stream) == 0;
+  if (ev) { (void)hipEventRecord(ev[2 * pass + 1], c->stream); c->evrTimed[pass] = true; }
+  c->roundLaunches++;
+  if (!ok) { c->err = "k_evr launch failed"; return -1; }
+  return 0;
+}
+// device ms of the three passes of the last round (after the round's end: the events have completed); zeros without ASCHED_EVR_TIMES=1
+static void plat_evict_report_ms(double* out) {
+  hipEvent_t* ev = evrEvents();
+  for (int k = 0; k < 3; k++) { float ms = 0.f; if (ev && t_ctx->evrTimed[k] && hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
 }
 // a caller-side buffer may be memory of this handle's GPU (a tensor the collective reduces in place: used directly) or host memory (staged)
 static bool plat_is_device_ptr(const void* p) {

@@ -633,6 +633,42 @@ int32_t ASCHED_FN(round_preemption_causes)(asched_t*, asched_preemption_cause* o
 int32_t ASCHED_FN(preemption_join)(asched_t*, int32_t ns, const int32_t* sched_job, const int32_t* sched_node, const int32_t* sched_method, int32_t np,
                                    const int32_t* pre_node, const int32_t* pre_by, const int32_t* pre_sibling, const uint8_t* pre_in_gang,
                                    asched_preemption_cause* out, int32_t* candidates, int32_t cand_cap, int32_t* num_candidates);
+/* ---- the evictor result of a round (SchedulingInformation.EvictorResult, scheduling/result.go:81-94, filled at preempting_queue_scheduler.go:274-281): what the
+   balancing evictor of phase 1 did (EvictorResult, eviction.go:27-79).  Consumers in the reference: the cycle metrics (metrics/cycle_metrics.go:629-647: evicted
+   jobs and resources per queue, preemptibility per node), the async runner (runner/async.go:435) and evict's log line (preempting_queue_scheduler.go:308).
+   Recorded on the device while phase 1 runs (csrc/kernels_evict_report.h) and only when switched on: nothing of it can be recovered after the round.  All values are
+   as of the moment the node evictor of phase 1 runs (preempting_queue_scheduler.go:96-138).
+   Reason bits of a node, numbered in the alphabetical order of the reference's reason strings, so that ascending bit order is the sorted, comma-joined string of
+   makeNodePreemptiblityStats (eviction.go:275-285); no strings cross the boundary.  missing_annotations / missing_node_selector (preempting_queue_scheduler.go:109-116)
+   have no counterpart behind this boundary. */
+#define ASCHED_EVR_ALL_JOBS_PREEMPTIBLE 1        /* "all_jobs_preemptible" (eviction.go:234): the node has jobs and no reason is set; alone */
+#define ASCHED_EVR_BELOW_PROTECTED_FAIR_SHARE 2  /* "below_protected_fair_share" (preempting_queue_scheduler.go:131-133) */
+#define ASCHED_EVR_INVALID_QUEUE 4               /* "invalid_queue" (:105-108): a job whose queue is outside [0, Q) */
+#define ASCHED_EVR_JOB_NOT_PREEMPTIBLE 8         /* "job_not_preemptible" (:120-122) */
+#define ASCHED_EVR_NODE_EMPTY 16                 /* "node_empty" (eviction.go:89-96): no job holds resources on the node */
+#define ASCHED_EVR_NODE_UNSCHEDULABLE 32         /* "node_unschedulable" (eviction.go:203-206, 228-230) */
+typedef struct asched_evictor_report {
+  int32_t num_nodes, num_queues, num_resources, num_evicted;
+  int32_t num_affected_nodes, pad_;            /* len(AffectedNodesById) */
+  const uint8_t* node_preemptible;             /* [N] NodePreemptiblityStats.Preemptible */
+  const uint8_t* node_reasons;                 /* [N] ASCHED_EVR_* bits */
+  const int32_t* node_evicted_jobs;            /* [N] jobs evicted from the node (>0 = affected) */
+  const int32_t* queue_evicted_jobs;           /* [Q] EvictorPerQueueStats.EvictedJobCount (eviction.go:60-71) */
+  const int64_t* queue_evicted_resources;      /* [Q][R] EvictedResources: the sum of KubernetesResourceRequirements — the request rows with the floating columns as 0 */
+  const int32_t* queue_evicted_off;            /* [Q+1] into the two lists below */
+  const int32_t* evicted_job;                  /* [num_evicted] grouped by queue, SchedulingOrderCompare order inside a queue (the phase-1 evList) */
+  const int32_t* evicted_node;                 /* [num_evicted] NodeIdByJobId */
+} asched_evictor_report;
+/* The switch, off by default.  Off, schedule_round issues exactly the launches it issues without the feature and allocates nothing for it.  On, a round that goes
+   through the split launch sequence (one- and two-word-key handles, optimiser rounds, asched_shard_round) queues three more launches in phase 1 — a pass over the
+   jobs, one over the nodes, one over the compacted evicted list — and waits for none of them.  The evicted set is EvictedJctxsByJobId after evictGangs has been
+   merged in (preempting_queue_scheduler.go:316-326); the gang evictor's own node stats are discarded, as in the reference. */
+int32_t ASCHED_FN(set_evictor_report)(asched_t*, int32_t on);
+/* The report of the last schedule_round.  The buffers belong to the handle until the next round_prepare, like the round result.  ASCHED_ERR_INVALID: the switch is
+   off, no round has completed since it was turned on, or the last round failed or timed out.  ASCHED_ERR_UNSUPPORTED (last_error names the cause): a market-driven
+   handle (set_market: the whole round is one launch of the auxiliary kernel), ASCHED_SINGLE_LAUNCH=1, and after round_exchange (the queue-hash mode moves
+   preemptions between replicas: the record describes this replica's own round). */
+int32_t ASCHED_FN(round_evictor_report)(asched_t*, asched_evictor_report* out);
 /* GangScheduler.Schedule (gang_scheduler.go:100-148) for one gang of queued jobs against the current round state. */
 int32_t ASCHED_FN(gang_schedule)(asched_t*, int32_t n, const int32_t* jobs, int32_t* ok, int32_t* reason, asched_pod_result* out /*[n]*/);
 /* sctx counters: out = {NumScheduledJobs, NumScheduledGangs, NumEvictedJobs, len(UnfeasibleSchedulingKeys)} (context/scheduling.go:55-69) */

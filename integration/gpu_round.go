@@ -104,6 +104,10 @@ type GpuRound struct {
 	rlf                *internaltypes.ResourceListFactory
 	// config.GetMarketConfig(pool) (preempting_queue_scheduler.go:61-62): nil or !Enabled = fair-share scheduling
 	market *configuration.MarketSchedulingConfig
+	// cfg.GetProtectedFractionOfFairShare(pool): SchedulingInformation.ProtectedFractionOfFairShare (result.go:88-89)
+	protectedFraction float64
+	// asched_set_evictor_report: on by default in the shim; a market-driven pool has no report (SetEvictorReport)
+	evictorReport bool
 }
 
 func effectOf(e v1.TaintEffect) int32 {
@@ -347,6 +351,11 @@ func NewGpuRound(cfg configuration.SchedulingConfig, rlf *internaltypes.Resource
 	g.h = C.asched_create(&c)
 	if g.h == nil {
 		return nil, errors.New("asched_create failed: no gfx950 device, or a configuration the library does not represent")
+	}
+	g.protectedFraction = cfg.GetProtectedFractionOfFairShare(pool)
+	if err := g.SetEvictorReport(true); err != nil {
+		g.Close()
+		return nil, err
 	}
 	return g, nil
 }
@@ -856,7 +865,87 @@ func (g *GpuRound) Schedule(ctx *armadacontext.Context, sctx *schedulercontext.S
 	if err := g.populatePreemptionCauses(res, int(out.num_scheduled)); err != nil {
 		return nil, err
 	}
+	if err := g.populateEvictorResult(res); err != nil {
+		return nil, err
+	}
 	return res, nil
+}
+
+// SetEvictorReport switches the recording of the balancing evictor's result on or off (asched_set_evictor_report; on by default here).  Off, a round issues the
+// launches it issues without the feature and SchedulingInformation.EvictorResult stays empty.
+func (g *GpuRound) SetEvictorReport(on bool) error {
+	v := C.int32_t(0)
+	if on {
+		v = 1
+	}
+	if err := g.check(C.asched_set_evictor_report(g.h, v)); err != nil {
+		return err
+	}
+	g.evictorReport = on
+	return nil
+}
+
+// the reference's reason strings in the order of the ASCHED_EVR_* bits: alphabetical, so that joining the set bits in ascending order is the sorted,
+// comma-joined string of makeNodePreemptiblityStats (eviction.go:275-285)
+var gpuEvictorReasons = [...]string{"all_jobs_preemptible", "below_protected_fair_share", "invalid_queue", "job_not_preemptible", "node_empty", "node_unschedulable"}
+
+func evictorReasonString(mask uint8) string {
+	var parts []string
+	for bit, name := range gpuEvictorReasons {
+		if mask&(1<<uint(bit)) != 0 {
+			parts = append(parts, name)
+		}
+	}
+	return strings.Join(parts, ",")
+}
+
+// populateEvictorResult fills SchedulingInformation.EvictorResult (result.go:81-94; preempting_queue_scheduler.go:274-281) from asched_round_evictor_report: the
+// evicted jctxs with IsEvicted and the node they were evicted from (eviction.go:245-260), NodeIdByJobId, AffectedNodesById and one NodePreemptiblityStats per node
+// (name, executor and reporting type from the Go node, the string from the bits).  The additional tolerations of :257 are not rebuilt: nothing after the round reads
+// them.  A market-driven pool has no report on this library (the whole round is one launch): EvictorResult stays an empty result there.
+func (g *GpuRound) populateEvictorResult(res *SchedulingResult) error {
+	er := &EvictorResult{
+		EvictedJctxsByJobId: map[string]*schedulercontext.JobSchedulingContext{},
+		AffectedNodesById:   map[string]*internaltypes.Node{},
+		NodeIdByJobId:       map[string]string{},
+	}
+	res.AdditionalSchedulingInfo = &SchedulingInformation{EvictorResult: er, ProtectedFractionOfFairShare: g.protectedFraction}
+	if !g.evictorReport || (g.market != nil && g.market.Enabled) {
+		return nil
+	}
+	var rep C.asched_evictor_report
+	if err := g.check(C.asched_round_evictor_report(g.h, &rep)); err != nil {
+		return err
+	}
+	n, ne := int(rep.num_nodes), int(rep.num_evicted)
+	pre := unsafe.Slice((*uint8)(unsafe.Pointer(rep.node_preemptible)), n)
+	reasons := unsafe.Slice((*uint8)(unsafe.Pointer(rep.node_reasons)), n)
+	evicted := unsafe.Slice((*int32)(unsafe.Pointer(rep.node_evicted_jobs)), n)
+	ej := unsafe.Slice((*int32)(unsafe.Pointer(rep.evicted_job)), ne)
+	en := unsafe.Slice((*int32)(unsafe.Pointer(rep.evicted_node)), ne)
+	er.NodePreemptiblityStats = make([]NodePreemptiblityStats, 0, n)
+	for i := 0; i < n; i++ {
+		node := g.nodes[i]
+		er.NodePreemptiblityStats = append(er.NodePreemptiblityStats, NodePreemptiblityStats{
+			NodeName:    node.GetName(),
+			Cluster:     node.GetExecutor(),
+			NodeType:    node.GetReportingNodeType(),
+			Preemptible: pre[i] != 0,
+			Reason:      evictorReasonString(reasons[i]),
+		})
+		if evicted[i] > 0 {
+			er.AffectedNodesById[node.GetId()] = node
+		}
+	}
+	for i := 0; i < ne; i++ {
+		job, node := g.jobs[ej[i]], g.nodes[en[i]]
+		jctx := schedulercontext.JobSchedulingContextFromJob(job)
+		jctx.IsEvicted = true
+		jctx.SetAssignedNode(node)
+		er.EvictedJctxsByJobId[job.Id()] = jctx
+		er.NodeIdByJobId[job.Id()] = node.GetId()
+	}
+	return nil
 }
 
 // the templates of preemption_description.go:11-19 (unexported there; the shim lives in the same package and uses the reference's own constants when it is added to it)
