@@ -247,12 +247,14 @@ ALL_SYMBOLS = [
     "excluded_nodes", "set_excluded_nodes",
     "round_preemption_causes", "preemption_join",
     "set_evictor_report", "round_evictor_report",
+    "jobs_patch",
 ]
 # entry points the CPU oracle does not implement (it is the single-process checker): the communicator and the collectives that run on it, and the join of a
 # round's result lists into preemption causes (a function of lists the oracle already delivers; tests/test_z_preemption_causes.py restates it)
 OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_destroy", "comm_rank", "fit_select_batch_sharded", "round_exchange", "shard_round", "shard_exchanges", "shard_area", "shard_open", "shard_peers",
                     "round_preemption_causes", "preemption_join",
-                    "set_evictor_report", "round_evictor_report"}   # (recorded by passes between the launches of the split round: tests/test_z_evictor_report.py restates it)
+                    "set_evictor_report", "round_evictor_report",   # (recorded by passes between the launches of the split round: tests/test_z_evictor_report.py restates it)
+                    "jobs_patch"}   # (an incremental jobs_set: the oracle is given the whole table; tests/test_z_jobs_patch.py)
 PREEMPTION_UNKNOWN, PREEMPTION_UNKNOWN_GANG, PREEMPTION_FAIRSHARE, PREEMPTION_URGENCY, PREEMPTION_OPTIMISER = 1, 2, 3, 4, 5   # ASCHED_PREEMPTION_* (context.PreemptionType)
 # ASCHED_EVR_* bits of asched_evictor_report.node_reasons, in bit order: the reference's reason strings in alphabetical order (makeNodePreemptiblityStats sorts them)
 EVICTOR_REASONS = ("all_jobs_preemptible", "below_protected_fair_share", "invalid_queue", "job_not_preemptible", "node_empty", "node_unschedulable")
@@ -446,6 +448,7 @@ class Library:
         f("set_excluded_nodes", C.c_int32, [C.c_void_p, C.c_int32])
         f("set_evictor_report", C.c_int32, [C.c_void_p, C.c_int32])
         f("round_evictor_report", C.c_int32, [C.c_void_p, C.POINTER(CEvictorReport)])
+        f("jobs_patch", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _i64p])
         f("round_preemption_causes", C.c_int32, [C.c_void_p, C.POINTER(CPreemptionCause), C.c_int32, _i32p, C.c_int32, _i32p])
         f("preemption_join", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, C.c_int32, _i32p, _i32p, _i32p, _u8p, C.POINTER(CPreemptionCause), _i32p, C.c_int32, _i32p])
 
@@ -707,6 +710,17 @@ class Scheduler:
             (cls.aff_term_off, cls.aff_expr_off, cls.aff_expr_key, cls.aff_expr_op, cls.aff_value_off, cls.aff_values) = (_ptr(x, C.c_int32) for x in arrs[1:])
         self._check(self.lib.jobs_set(self.h, C.byref(s), C.byref(cls)))
         self.num_jobs = m
+
+    def jobs_patch(self, jobs, node, scheduled_at_priority=None, run_timestamp=None):
+        """jobdb.Txn.Upsert for run-state changes: rows `jobs` of the resident job table now run on `node` (-1: no active run any more) at `scheduled_at_priority`,
+        leased at `run_timestamp` (ns; a scalar is given to every row).  Leaves the handle as jobs_set of the patched table would; go on with round_prepare."""
+        fn = self._preemption_fn("jobs_patch")
+        jb, nd = _arr(jobs, np.int32).reshape(-1), _arr(node, np.int32).reshape(-1)
+        n = len(jb)
+        assert len(nd) == n, "node"
+        sp = None if scheduled_at_priority is None else _arr(np.broadcast_to(np.asarray(scheduled_at_priority, dtype=np.int32), (n,)), np.int32)
+        ts = None if run_timestamp is None else _arr(np.broadcast_to(np.asarray(run_timestamp, dtype=np.int64), (n,)), np.int64)
+        self._check(fn(self.h, n, _ptr(jb, C.c_int32), _ptr(nd, C.c_int32), _ptr(sp, C.c_int32), _ptr(ts, C.c_int64)))
 
     def txn_begin(self): self._check(self.lib.txn_begin(self.h))
     def txn_commit(self): self._check(self.lib.txn_commit(self.h))

@@ -395,3 +395,65 @@ extern "C" int asched_internal_evict_report(const Dev* d, const EvrArgs* a, int 
   else hipLaunchKernelGGL(k_evr_queues, dim3(a->n1 > 0 ? (a->n1 + EVR_TILE - 1) / EVR_TILE : 1), dim3(MG_THREADS), 0, st, *d, *a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// ------------------------------------------------------------------------------------------------ the run-state patch of the resident job table (kernels_jobs_patch.h)
+#define JP_FN __device__ static inline
+#include "kernels_jobs_patch.h"
+__global__ __launch_bounds__(MG_THREADS) void k_jp_scatter(Dev d, JpArgs a) {
+  long long i = MG_IDX();
+  if (i < a.nb2) jpScatter(d, a, (int)i);
+}
+// one compare-exchange step of the bitonic network in HBM: distance j, direction by bit k of the position
+__global__ __launch_bounds__(MG_THREADS) void k_jp_step(JpKey* a, int nb2, int j, int k) {
+  unsigned i = blockIdx.x * MG_THREADS + threadIdx.x;
+  unsigned l = i ^ (unsigned)j;
+  if (i < (unsigned)nb2 && l > i) {
+    JpKey x = a[i], y = a[l];
+    bool up = (i & (unsigned)k) == 0;
+    if (up ? jpLess(y, x) : jpLess(x, y)) { a[i] = y; a[l] = x; }
+  }
+}
+// the in-LDS part of the network (k_fit_lit_tile's scheme on 40-byte records): every (k, j) step with j < JP_TILE for one tile of JP_TILE records.  A thread owns
+// the pairs (i, i ^ j) with bit j of i clear: every record is touched by exactly one thread per step
+__global__ __launch_bounds__(MG_THREADS) void k_jp_tile(JpKey* a, int kStart, int kEnd, int jStart) {
+  __shared__ JpKey t[JP_TILE];
+  const unsigned base = blockIdx.x * (unsigned)JP_TILE;
+  for (int i = threadIdx.x; i < JP_TILE; i += MG_THREADS) t[i] = a[base + i];
+  __syncthreads();
+  for (int k = kStart; k <= kEnd; k <<= 1) {
+    for (int j = (k == kStart ? jStart : k >> 1); j > 0; j >>= 1) {
+      for (int p = threadIdx.x; p < JP_TILE / 2; p += MG_THREADS) {
+        unsigned i = (((unsigned)p & ~((unsigned)j - 1)) << 1) | ((unsigned)p & ((unsigned)j - 1)), l = i | (unsigned)j;   // the p-th position with bit j clear
+        JpKey x = t[i], y = t[l];
+        bool up = ((base + i) & (unsigned)k) == 0;
+        if (up ? jpLess(y, x) : jpLess(x, y)) { t[i] = y; t[l] = x; }
+      }
+      __syncthreads();
+    }
+  }
+  for (int i = threadIdx.x; i < JP_TILE; i += MG_THREADS) a[base + i] = t[i];
+}
+__global__ __launch_bounds__(MG_THREADS) void k_jp_merge(Dev d, JpArgs a) {
+  long long i = MG_IDX();
+  if (i < (long long)a.nT + a.nKept + a.n) jpMerge(d, a, i);
+}
+extern "C" int asched_internal_jp_scatter(const Dev* d, const JpArgs* a, hipStream_t st) {
+  if (a->nb2 > 0) hipLaunchKernelGGL(k_jp_scatter, dim3(mgBlocks(a->nb2)), dim3(MG_THREADS), 0, st, *d, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+// a->keys [a->nb2], nb2 a power of two >= JP_TILE
+extern "C" int asched_internal_jp_sort(const JpArgs* a, hipStream_t st) {
+  const int nb2 = a->nb2, tiles = nb2 / JP_TILE;
+  if (tiles <= 0 || (nb2 & (nb2 - 1)) || nb2 % JP_TILE) return -1;
+  hipLaunchKernelGGL(k_jp_tile, dim3(tiles), dim3(MG_THREADS), 0, st, a->keys, 2, JP_TILE, 1);   // all steps with k <= JP_TILE
+  for (long long k = 2ll * JP_TILE; k <= nb2; k <<= 1) {
+    for (long long j = k >> 1; j >= JP_TILE; j >>= 1) hipLaunchKernelGGL(k_jp_step, dim3(mgBlocks(nb2)), dim3(MG_THREADS), 0, st, a->keys, nb2, (int)j, (int)k);
+    hipLaunchKernelGGL(k_jp_tile, dim3(tiles), dim3(MG_THREADS), 0, st, a->keys, (int)k, (int)k, JP_TILE / 2);   // the remaining steps j = JP_TILE / 2 .. 1 inside tiles
+  }
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_jp_merge(const Dev* d, const JpArgs* a, hipStream_t st) {
+  const long long work = (long long)a->nT + a->nKept + a->n;
+  if (work > 0) hipLaunchKernelGGL(k_jp_merge, dim3(mgBlocks(work)), dim3(MG_THREADS), 0, st, *d, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}

@@ -27,6 +27,7 @@
 #include "kernels_fit_lit.h"   // FitLitIdx and, in the CPU build of the tests, plat_run_fit_batch_lit
 #include "kernels_preempt_join.h"   // PjArgs and, in the CPU build of the tests, plat_preempt_join
 #include "kernels_evict_report.h"   // EvrArgs and, in the CPU build of the tests, plat_evict_report
+#include "kernels_jobs_patch.h"     // JpArgs and, in the CPU build of the tests, plat_jobs_patch
 
 namespace {
 
@@ -228,6 +229,13 @@ struct asched {
   std::vector<OrdKey> stageKeys;
   int ordQueues = 0;   // number of queue segments in the pre-sorted job order (max queue index of the job table + 1)
   std::vector<int32_t> ordOffHost;   // host copy of dev.ordAllOff (segment offsets of the pre-sorted order)
+  // ---- asched_jobs_patch (kernels_jobs_patch.h).  jobs_set keeps the order-key inputs only the host sees (queue priority, submit time, run timestamp) as host copies;
+  // the first patch of a job table uploads them and allocates the keep flags and the second order buffer (all in jobBufs: gone with the job table)
+  std::vector<uint32_t> jQPrioHost; std::vector<int64_t> jSubmitHost, jRunTsHost;
+  struct { bool built = false; uint8_t* keep = nullptr; uint32_t* qprio = nullptr; int64_t* submit = nullptr; int64_t* runTs = nullptr; int32_t* ordSpare = nullptr; } jp;
+  std::vector<uint8_t> jpSeen;       // [M] all zero between calls: a row named twice in one patch
+  DevBufs jpBufs; char* jpScratch = nullptr; size_t jpScratchBytes = 0;   // the entries, the sort array and the kept list of a patch: one block, kept between calls and only ever grown
+  double jpMs[4] = {0, 0, 0, 0};     // device ms of the four passes of the last patch (ASCHED_JP_TIMES=1)
   double roundTotalMs = 0, roundControlMs = 0, roundPhaseMs[4] = {0, 0, 0, 0};   // split round: whole sequence / persistent passes / evict-1, evict-3, final bulk phases (host clock)
   int submitWideUnits = 0, submitWidePasses = 0, submitSeqUnits = 0, submitGangUnits = 0, submitNodePasses = 0, submitLitUnits = 0;   // how the last submit_check ran (submit_stats)
 };
@@ -803,7 +811,7 @@ asched_t* asched_create(const asched_config* c) {
 void asched_destroy(asched_t* h) {
   if (!h) return;
   plat_enter(h->plat);
-  h->nodeBufs.freeAll(); h->jobBufs.freeAll(); h->queueBufs.freeAll(); h->maskBufs.freeAll(); h->fastBufs.freeAll(); h->pjBufs.freeAll(); h->evrBufs.freeAll(); h->exclBufs.freeAll();
+  h->nodeBufs.freeAll(); h->jobBufs.freeAll(); h->queueBufs.freeAll(); h->maskBufs.freeAll(); h->fastBufs.freeAll(); h->pjBufs.freeAll(); h->evrBufs.freeAll(); h->exclBufs.freeAll(); h->jpBufs.freeAll();
   plat_pinned_free(h->resPin); plat_free(h->commStatus); plat_free(h->dev.rs); plat_free(h->dev.cmdIO); plat_free(h->dev.scanResult); plat_free(h->dev.undo);
   plat_close(h->plat);
   delete h;
@@ -966,6 +974,7 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
   if (h) { h->haveRoundResult = false; h->stateEpoch++; }
   fastInvalidate(h);
   h->jobBufs.freeAll();
+  h->jp = {};   // (its buffers lived in jobBufs)
   HostProf prof("jobs_set");
   Dev& d = h->dev;
   int M = h->M = j->m, R = h->R;
@@ -1263,6 +1272,7 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
   d.unfeasible = A8(std::max(h->S, 1)); d.unfeasibleReason = A32(std::max(h->S, 1));
   d.resJob = A32(M); d.resNode = A32(M); d.resPrio = A32(M); d.resMethod = A32(M); d.resPreJob = A32(M); d.resPreNode = A32(M);
   h->jobsSet = true; h->prepared = false;
+  h->jQPrioHost.swap(qprio); h->jSubmitHost.swap(submit); h->jRunTsHost.swap(runTs);   // (asched_jobs_patch uploads them when it is first called; nothing is copied here)
   prof.lap("uploads + per-job state allocation");
   if (h->nodesSet) if (int lrc = layoutKeys(h)) return lrc;   // (a negative request on an indexed column needs the wide field layout; the keys themselves are rebuilt by CMD_UPSERT_RESET below)
   int rc = rebuildMasks(h);
@@ -1278,6 +1288,110 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
   h->evictedDirty = false;
   prof.lap("state reset launches");
   return rc;
+}
+
+// jobdb.Txn.Upsert for run-state changes (scheduling/scheduling_algo.go:280-283 with the jobs of :956-981; jobdb/jobdb.go:572-700): the named rows get a new active run
+// or lose theirs, on the device (kernels_jobs_patch.h).  Leaves the handle as asched_jobs_set would have, given the table with those rows replaced — without the static
+// masks, the JobRec upload, the sort of all jobs or a new fast structure: none of them depends on run state.
+int32_t asched_jobs_patch(asched_t* h, int32_t n, const int32_t* job, const int32_t* node, const int32_t* scheduled_at_priority, const int64_t* run_timestamp) {
+  if (!h) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  const int M = h->M;
+  // ---- every refusal before anything changes
+  if (!h->jobsSet || h->jQPrioHost.size() != (size_t)M || h->jSubmitHost.size() != (size_t)M || h->jRunTsHost.size() != (size_t)M || h->jNode.size() != (size_t)M)
+    return fail(h, ASCHED_ERR_INVALID, "jobs_patch: no job table on this handle (jobs_set first)");
+  if (n < 0 || (n > 0 && (!job || !node))) return fail(h, ASCHED_ERR_INVALID, "jobs_patch: bad arguments");
+  if (h->mkJobsBuilt) return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_patch: the job set carries the market order, which depends on run state too (jobs_set instead)");
+  if (n > (1 << 29)) return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_patch: more than 2^29 entries");
+  if (h->jpSeen.size() != (size_t)M) h->jpSeen.assign(M, 0);
+  int bad = 0, nT = 0;
+  const char* why = nullptr;
+  int code = ASCHED_ERR_INVALID;
+  for (int i = 0; i < n && !why; i++) {
+    const int j = job[i];
+    if (j < 0 || j >= M) { why = "jobs_patch: a row outside the job table"; break; }
+    if (h->jpSeen[j]) { why = "jobs_patch: a row named twice"; break; }
+    h->jpSeen[j] = 1; bad = i + 1;
+    if (node[i] < -1 || node[i] >= (h->nodesSet ? h->N : 0)) why = "jobs_patch: node outside [-1, N)";   // (no node table: only -1)
+    else if (node[i] >= 0 && h->jAway[j]) { why = "jobs_patch: a cross-pool away row may only lose its run"; code = ASCHED_ERR_UNSUPPORTED; }
+    else if (h->jQueue[j] >= 0) nT++;
+  }
+  if (why) { for (int i = 0; i < bad; i++) h->jpSeen[job[i]] = 0; return fail(h, code, why); }
+  for (int i = 0; i < n; i++) h->jpSeen[job[i]] = 0;
+  // one scratch block, kept and only ever grown: the entries | the sort array | the kept rows.  Sized before anything changes: running out of device memory here is a refusal too
+  const int total = h->ordOffHost.empty() ? 0 : h->ordOffHost[std::min<size_t>((size_t)h->ordQueues, h->ordOffHost.size() - 1)];
+  int nb2 = n;
+  if (nT > 0) { nb2 = JP_TILE; while (nb2 < n) nb2 <<= 1; }
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t oTs = up(sizeof(int32_t) * 3 * (size_t)n), oKeys = oTs + up(sizeof(int64_t) * (size_t)n), oKept = oKeys + (nT > 0 ? up(sizeof(JpKey) * (size_t)nb2) : 0),
+               need = oKept + (nT > 0 ? up(sizeof(int32_t) * (size_t)total) : 0);
+  if (n > 0 && h->jpScratchBytes < need) {
+    h->jpBufs.freeAll(); h->jpScratch = nullptr; h->jpScratchBytes = 0;
+    h->jpScratch = (char*)plat_malloc(need + need / 4);
+    if (!h->jpScratch) { (void)plat_take_failure(); return fail(h, ASCHED_ERR_DEVICE, "jobs_patch: out of device memory for the patch scratch; the handle is as it was"); }
+    h->jpBufs.ptrs.push_back({h->jpScratch, need + need / 4});
+    h->jpScratchBytes = need + need / 4;
+  }
+  // ---- what jobs_set resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the job table half patched: asched_jobs_set before anything else)
+  h->haveRoundResult = false; h->stateEpoch++;
+  { h->dev.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
+    int32_t zero = 0;
+    plat_h2d(&h->dev.rs->fastActive, &zero, sizeof zero);
+    plat_h2d(&h->dev.rs->l0SaveCount, &zero, sizeof zero); }
+  h->prepared = false;
+  Dev& d = h->dev;
+  for (int k = 0; k < 4; k++) h->jpMs[k] = 0;
+  if (n > 0) {
+    // the host mirrors (round_prepare's host aggregation path reads jNode)
+    for (int i = 0; i < n; i++) {
+      const int j = job[i];
+      h->jNode[j] = node[i]; h->jRunPrio[j] = scheduled_at_priority ? scheduled_at_priority[i] : 0; h->jRunTsHost[j] = run_timestamp ? run_timestamp[i] : 0;
+    }
+    if (!h->jp.built) {   // first patch of this job table: the order-key inputs become resident (the run timestamps as patched above)
+      h->jp.qprio = h->jobBufs.upload(h->jQPrioHost); h->jp.submit = h->jobBufs.upload(h->jSubmitHost); h->jp.runTs = h->jobBufs.upload(h->jRunTsHost);
+      h->jp.keep = h->jobBufs.allocRaw<uint8_t>(M); plat_memset(h->jp.keep, 1, (size_t)M);
+      h->jp.ordSpare = h->jobBufs.allocRaw<int32_t>(total);
+      h->jp.built = true;
+    }
+    JpArgs a; memset(&a, 0, sizeof a);
+    a.M = M; a.n = n; a.nT = nT; a.total = total; a.nb2 = nb2;
+    std::vector<int32_t> prioZero; std::vector<int64_t> tsZero;
+    if (!scheduled_at_priority) { prioZero.assign(n, 0); scheduled_at_priority = prioZero.data(); }
+    if (!run_timestamp) { tsZero.assign(n, 0); run_timestamp = tsZero.data(); }
+    int32_t* e32 = (int32_t*)h->jpScratch; int64_t* e64 = (int64_t*)(h->jpScratch + oTs);
+    plat_h2d(e32, job, sizeof(int32_t) * (size_t)n); plat_h2d(e32 + n, node, sizeof(int32_t) * (size_t)n); plat_h2d(e32 + 2 * (size_t)n, scheduled_at_priority, sizeof(int32_t) * (size_t)n);
+    plat_h2d(e64, run_timestamp, sizeof(int64_t) * (size_t)n);
+    a.pJob = e32; a.pNode = e32 + n; a.pPrio = e32 + 2 * (size_t)n; a.pTs = e64;
+    a.keep = h->jp.keep; a.jQPrio = h->jp.qprio; a.jSubmit = h->jp.submit; a.jRunTs = h->jp.runTs;
+    int32_t* keptBuf = nullptr;
+    if (nT > 0) { a.keys = (JpKey*)(h->jpScratch + oKeys); keptBuf = (int32_t*)(h->jpScratch + oKept); a.out = h->jp.ordSpare; }
+    int prc = plat_take_failure() ? -1 : plat_jobs_patch(d, a, keptBuf);
+    if (prc) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+    if (nT > 0) { std::swap(d.ordAll, h->jp.ordSpare); }
+    plat_jobs_patch_ms(h->jpMs);
+    if (const char* e = getenv("ASCHED_JP_TIMES")) if (e[0] == '1')
+      fprintf(stderr, "[asched jobs_patch] jobs %d entries %d in the order %d: scatter %.4f ms, remove %.4f ms, sort %.4f ms, merge %.4f ms\n", M, n, nT, h->jpMs[0], h->jpMs[1], h->jpMs[2], h->jpMs[3]);
+  }
+  // job dynamic state: everything unbound until round_prepare, as at the end of jobs_set — what CMD_UPSERT_RESET and CMD_RESET_JOBS do (round_run.h controlMain), with
+  // their per-element passes on the whole grid instead of the control workgroup (B_RESET_JOBS also forgets the failed-selection records: asched_excluded_nodes)
+  d.cfg.Q = 0;
+  h->stateEpoch++;
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  if (plat_bulk(d, B_INIT_ALLOC, h->N) || plat_bulk(d, B_KEYS_ALL, h->N) || plat_bulk(d, B_RESET_JOBS, M)) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  plat_d2h(&h->rsHost, d.rs, sizeof(RoundScalars));
+  if (h->rsHost.error) {
+    int e = h->rsHost.error;
+    char buf[128]; snprintf(buf, sizeof buf, "device raised error %d (detail %d)", e, h->rsHost.errorDetail);
+    int32_t zero[2] = {0, 0};
+    plat_h2d(&d.rs->error, zero, sizeof zero);
+    return fail(h, e, buf);
+  }
+  h->rsHost.fastActive = 0; h->rsHost.evictedTableSize = 0; h->rsHost.fairIndexValid = 0; h->rsHost.ftValid = 0; h->rsHost.txnActive = 0; h->rsHost.undoCount = 0;
+  plat_h2d(d.rs, &h->rsHost, sizeof(RoundScalars));
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  h->allocPristine = h->nodesSet;
+  h->evictedDirty = false;
+  return 0;
 }
 
 int32_t asched_txn_begin(asched_t* h) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat); h->allocPristine = false; return runControl(h, CMD_TXN_BEGIN); }

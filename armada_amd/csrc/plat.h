@@ -84,6 +84,11 @@ static int plat_preempt_join(Dev& d, const PjArgs& a);
 struct EvrArgs;
 static int plat_evict_report(Dev& d, const EvrArgs& a, int pass);
 static void plat_evict_report_ms(double* out /*[3]*/);   // measurement hook: device ms of the passes of the last round (events around them when ASCHED_EVR_TIMES=1, else zeros)
+// the run-state patch of the resident job table (kernels_jobs_patch.h): scatter + keys, remove (plat_compact into keptBuf [a.total]), sort, merge by rank into a.out;
+// fills a.kept / a.nKept.  Synchronous: the new order is complete on return.  The CPU build's definition sits in kernels_jobs_patch.h.
+struct JpArgs;
+static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf);
+static void plat_jobs_patch_ms(double* out /*[4]*/);   // measurement hook: device ms of scatter / remove / sort / merge of the last call (events around them when ASCHED_JP_TIMES=1, else zeros)
 static int plat_run_fit_capacity(Dev& d, const std::vector<int32_t>& shapes, std::vector<int32_t>& firstNode, std::vector<long long>& capacity, const int32_t* nodeByRankHost);
 static int plat_run_submit_gangs(Dev& d, const std::vector<int32_t>& off, const std::vector<int32_t>& jobs, std::vector<int32_t>& out);
 static double plat_last_fit_ms();

@@ -32,6 +32,7 @@ struct PlatCtx {
   std::chrono::steady_clock::time_point roundT0;
   hipEvent_t rEv0 = nullptr, rEv1 = nullptr;
   hipEvent_t evrEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool evrTimed[3] = {false, false, false};   // ASCHED_EVR_TIMES=1: around the passes of the evictor report
+  hipEvent_t jpEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool jpTimed = false;   // ASCHED_JP_TIMES=1: around the passes of the job-table patch
   float roundTotalMs = 0.f, roundControlMs = 0.f; int roundLaunches = 0;
   int32_t* cmpScratch = nullptr; size_t cmpScratchInts = 0;   // block counts + total of the grid-wide compaction
   int optIndexN = -1, optIndexM = -1;   // sizes the optimiser's node -> jobs index in the scratch was built for (asched_host.inc decides when it may be reused)
@@ -248,6 +249,7 @@ static void plat_close(PlatCtx* c) {
   if (c->stream) (void)hipStreamDestroy(c->stream);
   for (hipEvent_t e : {c->ev0, c->ev1, c->fitEv0, c->fitEv1, c->litEvMid, c->rEv0, c->rEv1}) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->evrEv) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->jpEv) if (e) (void)hipEventDestroy(e);
   if (c->helpBox) (void)hipFree(c->helpBox);
   if (c->cmpScratch) (void)hipFree(c->cmpScratch);
   if (c->optScratch) (void)hipFree(c->optScratch);
@@ -858,6 +860,48 @@ static int plat_evict_report(Dev& d, const EvrArgs& a, int pass) {
 static void plat_evict_report_ms(double* out) {
   hipEvent_t* ev = evrEvents();
   for (int k = 0; k < 3; k++) { float ms = 0.f; if (ev && t_ctx->evrTimed[k] && hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
+}
+// the run-state patch of the resident job table (kernels_jobs_patch.h; kernels in armada_sched_mgpu.hip): scatter + keys, the compaction of the untouched rows (its count
+// comes back to the host: the merge is sized by it), the sort, the merge.  ASCHED_JP_TIMES=1 puts events around the four passes (tools/probe_jobs_patch.py).
+#include "kernels_jobs_patch.h"
+extern "C" int asched_internal_jp_scatter(const Dev* d, const JpArgs* a, hipStream_t s);
+extern "C" int asched_internal_jp_sort(const JpArgs* a, hipStream_t s);
+extern "C" int asched_internal_jp_merge(const Dev* d, const JpArgs* a, hipStream_t s);
+static hipEvent_t* jpEvents() {
+  static const bool on = [] { const char* e = getenv("ASCHED_JP_TIMES"); return e && e[0] == '1'; }();
+  PlatCtx* c = t_ctx;
+  if (!on) return nullptr;
+  if (!c->jpEv[4]) for (int i = 0; i < 5; i++) if (!c->jpEv[i] && hipEventCreate(&c->jpEv[i]) != hipSuccess) { c->jpEv[i] = nullptr; return nullptr; }
+  return c->jpEv;
+}
+static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf) {
+  PlatCtx* c = t_ctx;
+  hipStream_t st = c->stream;
+  hipEvent_t* ev = jpEvents();
+  c->jpTimed = false;
+  if (ev) (void)hipEventRecord(ev[0], st);
+  bool ok = asched_internal_jp_scatter(&d, &a, st) == 0;
+  if (ev) (void)hipEventRecord(ev[1], st);
+  a.kept = keptBuf; a.nKept = 0;
+  if (ok && a.nT > 0) {
+    int nk = 0;
+    if (plat_compact(d, d.ordAll, a.total, a.keep, keptBuf, nullptr, nullptr, 0, nullptr, &nk)) return -1;
+    a.nKept = nk;
+    if (a.nT + a.nKept != a.total) { c->err = "jobs_patch: the job order lost or gained rows"; return -1; }
+    if (ev) (void)hipEventRecord(ev[2], st);
+    ok = asched_internal_jp_sort(&a, st) == 0;
+  } else if (ev) (void)hipEventRecord(ev[2], st);
+  if (ev) (void)hipEventRecord(ev[3], st);
+  ok = ok && asched_internal_jp_merge(&d, &a, st) == 0;
+  if (ev) (void)hipEventRecord(ev[4], st);
+  ok = ok && hipOk(hipGetLastError(), "k_jp launch") && hipOk(hipStreamSynchronize(st), "k_jp");
+  if (!ok) { if (c->err.empty()) c->err = "k_jp launch failed"; return -1; }
+  c->jpTimed = ev != nullptr;
+  return 0;
+}
+static void plat_jobs_patch_ms(double* out) {
+  hipEvent_t* ev = jpEvents();
+  for (int k = 0; k < 4; k++) { float ms = 0.f; if (ev && t_ctx->jpTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
 }
 // a caller-side buffer may be memory of this handle's GPU (a tensor the collective reduces in place: used directly) or host memory (staged)
 static bool plat_is_device_ptr(const void* p) {

@@ -222,3 +222,53 @@ def run_cycles(lib, sim: SimulatorInput, max_cycles: int = 1000):
         t += sim.cycle_period_s
     s.close()
     return out
+
+
+def run_cycles_patched(lib, sim: SimulatorInput, max_cycles: int = 1000):
+    """run_cycles with ONE jobs_set: the workload's jobs are uploaded once, and between two cycles only the run state of the rows that changed is patched on the
+    device (Scheduler.jobs_patch: the jobs the last round leased or preempted, the runs that ended since).  Row = job id for the whole run; a finished job stays
+    in the table as a row without a run that is in no queued list, which takes no part in a round.  Same records as run_cycles."""
+    from .binding import Scheduler
+    wl = sim.workload
+    m = wl.num_jobs
+    node = np.full(m, -1, np.int32)
+    run_prio = np.zeros(m, np.int32)
+    started = np.full(m, -1.0)
+    done = np.zeros(m, bool)
+    out = []
+    s = Scheduler(lib, wl.config)
+    s.nodes_upsert(wl.node_total, id_rank=wl.node_id_rank)
+    s.jobs_set(wl.job_req, queue=wl.job_queue, pc=wl.job_pc, submit_time=wl.job_submit, node=node, scheduled_at_priority=run_prio, run_timestamp=np.zeros(m, np.int64))
+    changed = np.zeros(m, bool)                       # rows whose run state differs from what the handle holds
+    t = 0.0
+    for _ in range(max_cycles):
+        finished = (node >= 0) & (started >= 0) & (started + sim.job_runtime_s <= t)
+        done |= finished
+        node[finished] = -1
+        changed |= finished
+        if done.all():
+            break
+        rows = np.nonzero(changed)[0].astype(np.int32)
+        if len(rows):
+            running = node[rows] >= 0
+            s.jobs_patch(rows, node[rows], np.where(running, run_prio[rows], 0), np.where(running, np.maximum(started[rows], 0) * 1e9, 0).astype(np.int64))
+            changed[:] = False
+        queued = [np.array([j for j in q if not done[j] and node[j] < 0], dtype=np.int32) for q in wl.queued]
+        nq = wl.num_queues
+        s.round_prepare(wl.queue_weight, queued, global_tokens=float(wl.global_burst), global_burst=wl.global_burst, global_rate_inf=wl.rate_inf,
+                        queue_tokens=[float(wl.queue_burst)] * nq, queue_burst=[wl.queue_burst] * nq, queue_rate_inf=[wl.rate_inf] * nq)
+        r = s.schedule_round()
+        sched = {int(j): int(n) for j, n in r.scheduled.items()}
+        pre = {int(j): int(n) for j, n in r.preempted.items()}
+        for j, n in sched.items():
+            node[j], started[j], run_prio[j] = n, t, r.scheduled_priority[j]
+            changed[j] = True
+        for j in pre:
+            node[j], started[j] = -1, -1.0
+            changed[j] = True
+        out.append({"time_s": t, "scheduled": sched, "preempted": pre, "termination_reason": r.termination_reason})
+        if not sched and not pre and not (node >= 0).any():
+            break   # nothing runs and nothing can be placed: the rest never will
+        t += sim.cycle_period_s
+    s.close()
+    return out

@@ -372,6 +372,21 @@ int32_t ASCHED_FN(nodes_upsert)(asched_t*, const asched_nodes* nodes);
 int32_t ASCHED_FN(set_label_value_ints)(asched_t*, int32_t n, const int32_t* value_ids, const int64_t* ints);
 /* registers the job + requirement tables referenced by job id in the calls below */
 int32_t ASCHED_FN(jobs_set)(asched_t*, const asched_jobs* jobs, const asched_req_classes* classes);
+/* jobdb.Txn.Upsert for run-state changes between two scheduling cycles: txn.Upsert(preemptedJobs) / txn.Upsert(scheduledJobs) (scheduling/scheduling_algo.go:280-283, the
+   jobs built at :956-981), after which jobdb/jobdb.go:572-700 re-seats only those jobs in the per-queue sorted sets (SchedulingOrderCompare, jobdb/comparison.go:49-107).
+   entry i: job[i] (row of the job table) now has its active run on node[i] at scheduled_at_priority[i], leased at run_timestamp[i] (ns);
+   node[i] == -1: the job has no active run any more (preempted, finished, lease returned).  Whether such a job is queued again is, as always,
+   what the queued lists of the next round_prepare say; a row that is neither running nor in a queued list takes no part in a round.
+   scheduled_at_priority / run_timestamp NULL: zeros.
+   After a successful call the handle is in the state asched_jobs_set would have left, given the same job table with node, scheduled_at_priority and run_timestamp
+   replaced in the named rows and the same requirement classes — for every entry point, including everything jobs_set resets (the caller goes on with round_prepare).
+   The work is on the device and proportional to the job order, not a rebuild: no static masks, no job-record upload, no sort of all jobs; the fast structure stays.
+   n == 0 performs the resets only.  Refused before anything changes — ASCHED_ERR_INVALID: no job table, a row outside [0, M), a row named twice, a node outside
+   [-1, N); ASCHED_ERR_UNSUPPORTED: the job set carries the market order (uploaded with bid prices or after asched_set_market), an entry gives a cross-pool away row
+   (asched_jobs.away) a node >= 0.  On a handle without a node table N is 0: only node -1 is accepted.  ASCHED_ERR_DEVICE (a failed launch or copy, as from any
+   other entry point) is NOT such a refusal: the job table may be half patched, and the handle needs asched_jobs_set before anything else.
+   Rows cannot be appended or deleted and no other field changes: asched_jobs_set. */
+int32_t ASCHED_FN(jobs_patch)(asched_t*, int32_t n, const int32_t* job, const int32_t* node, const int32_t* scheduled_at_priority, const int64_t* run_timestamp);
 
 int32_t ASCHED_FN(txn_begin)(asched_t*);    /* nodeDb.Txn(true) (nodedb.go:353) */
 int32_t ASCHED_FN(txn_commit)(asched_t*);

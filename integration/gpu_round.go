@@ -98,6 +98,7 @@ type GpuRound struct {
 	nodes    []*internaltypes.Node
 	nodePos  map[string]int32
 	jobs     []*jobdb.Job
+	jobRow   map[string]int32 // job id -> row of the uploaded job table (PatchJobs)
 	classes  map[string]int32 // requirement class key -> index
 	// poolConfig.GetDefaultJobTolerations() (scheduling_algo.go:773): part of every requirement class (UploadJobs)
 	defaultTolerations []v1.Toleration
@@ -476,6 +477,7 @@ func (g *GpuRound) UploadJobs(jobs []*jobdb.Job, queueIndex map[string]int32) er
 	jobs = append([]*jobdb.Job(nil), jobs...)
 	sort.SliceStable(jobs, func(a, b int) bool { return jobs[a].Id() < jobs[b].Id() })
 	g.jobs = jobs
+	g.jobRow = nil // (PatchJobs builds it when first called)
 	queue, pc, reqClassIdx := make([]int32, m), make([]int32, m), make([]int32, m)
 	qprio := make([]uint32, m)
 	submit, runTs := make([]int64, m), make([]int64, m)
@@ -680,6 +682,61 @@ func (g *GpuRound) UploadJobs(jobs []*jobdb.Job, queueIndex map[string]int32) er
 		return err
 	}
 	return g.check(C.asched_jobs_set(g.h, &in, &cls))
+}
+
+// PatchJobs tells the library the run-state changes of a finished cycle without re-describing the job set (asched_jobs_patch): what
+// txn.Upsert(preemptedJobs) / txn.Upsert(scheduledJobs) apply to the jobDb (scheduling_algo.go:280-283, the jobs built at :956-981).  scheduled: the
+// result's ScheduledJobs (PodSchedulingContext.NodeId / ScheduledAtPriority), leased at leasedAt — the run timestamp the new runs get; preempted: its
+// PreemptedJobs; ended: ids of jobs whose run finished or whose lease was returned since.  Every job must be one of the last UploadJobs (rows do not
+// change: a new submission needs UploadJobs), a market-driven pool is refused by the library (the market order depends on run state too).  g.jobs keeps the
+// jobDb objects of UploadJobs: the caller's jobDb holds the updated ones.  The next call is Schedule, as after UploadJobs.
+func (g *GpuRound) PatchJobs(scheduled, preempted []*schedulercontext.JobSchedulingContext, ended []string, leasedAt time.Time) error {
+	if g.jobRow == nil {
+		g.jobRow = make(map[string]int32, len(g.jobs))
+		for i, j := range g.jobs {
+			g.jobRow[j.Id()] = int32(i)
+		}
+	}
+	n := len(scheduled) + len(preempted) + len(ended)
+	if n == 0 {
+		return g.check(C.asched_jobs_patch(g.h, 0, nil, nil, nil, nil))
+	}
+	job, node, prio, ts := make([]int32, 0, n), make([]int32, 0, n), make([]int32, 0, n), make([]int64, 0, n)
+	add := func(id string, nd, sp int32, t int64) error {
+		row, ok := g.jobRow[id]
+		if !ok {
+			return fmt.Errorf("PatchJobs: job %s is not one of the uploaded jobs", id)
+		}
+		job, node, prio, ts = append(job, row), append(node, nd), append(prio, sp), append(ts, t)
+		return nil
+	}
+	for _, jctx := range scheduled {
+		pctx := jctx.PodSchedulingContext
+		if pctx == nil {
+			return fmt.Errorf("PatchJobs: scheduled job %s without a pod scheduling context", jctx.JobId)
+		}
+		p, ok := g.nodePos[pctx.NodeId]
+		if !ok {
+			return fmt.Errorf("PatchJobs: job %s scheduled on unknown node %s", jctx.JobId, pctx.NodeId)
+		}
+		if err := add(jctx.JobId, p, pctx.ScheduledAtPriority, leasedAt.UnixNano()); err != nil {
+			return err
+		}
+	}
+	for _, jctx := range preempted {
+		if err := add(jctx.JobId, -1, 0, 0); err != nil {
+			return err
+		}
+	}
+	for _, id := range ended {
+		if err := add(id, -1, 0, 0); err != nil {
+			return err
+		}
+	}
+	var pins runtime.Pinner
+	defer pins.Unpin()
+	pins.Pin(&job[0]); pins.Pin(&node[0]); pins.Pin(&prio[0]); pins.Pin(&ts[0])
+	return g.check(C.asched_jobs_patch(g.h, C.int32_t(n), i32p(job), i32p(node), i32p(prio), i64p(ts)))
 }
 
 // uploadLabelValueInts tells the library which interned strings are integers (strconv.ParseInt(v, 10, 64), what
