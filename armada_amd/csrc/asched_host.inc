@@ -672,6 +672,7 @@ int buildFast(asched* h, const std::vector<uint64_t>& classMask) {
     if (d.qsKey && !(e && e[0] == '0')) {
       MgDev m; memset(&m, 0, sizeof m);
       m.cap = QCAPF * QS_CMAX + QCAPF;
+      { const char* l = getenv("ASCHED_STREAM_LIMIT"); m.limitOff = (l && l[0] == '0') ? 1 : 0; }   // ASCHED_STREAM_LIMIT=0: a bulk-merged run ends where a queue's stream ends at its rate-limit tokens (round 6)
       m.q = h->fastBufs.alloc<MgQ>(QCAPF); m.key = h->fastBufs.allocRaw<WideKey>((size_t)m.cap); m.own = h->fastBufs.allocRaw<int32_t>((size_t)m.cap); m.rank = h->fastBufs.allocRaw<int32_t>((size_t)m.cap);
       m.merged = h->fastBufs.allocRaw<MgEnt>((size_t)m.cap); m.cmax = h->fastBufs.allocRaw<WideKey>((size_t)QCAPF * MG_CPQ); m.stop = h->fastBufs.alloc<uint32_t>(4); m.cut = h->fastBufs.alloc<WideKey>(1); m.cutPick = h->fastBufs.alloc<uint32_t>(1);
       d.mg = h->fastBufs.upload(std::vector<MgDev>{m});

@@ -275,11 +275,11 @@ struct WideDev {
 // round_wide.h W_RANK, on the stream representation of round_fast.h); the control wave then only stages the merged order for the node engine.
 struct MgQ {   // one queue of the heap as the merge sees it, written by the control wave before the passes (HBM: the helper workgroups read it)
   int32_t start, len, kind, base;      // stream elements [start, len) are still to come; kind bit 0: evicted stream (d.evKey[base + e]), else queued (d.qsKey[q][e]); bit 1: folded (skip mode)
-  int32_t flags, off, total, nameRank; // flags 1: stream, 2: barrier (a head the run cannot serve: ONE entry under its heap key), 4: open (the queue goes on behind its last element under a key not known here), 8: skip mode (keys must not decrease)
+  int32_t flags, off, total, nameRank; // flags 1: stream, 2: barrier (a head the run cannot serve: ONE entry under its heap key), 4: open (the queue goes on behind its last element under a key not known here), 8: skip mode (keys must not decrease), 32: the last element is the queue's limit element (len counts it; round_merge.h MG_F_LIMIT)
   double budget; int64_t pad_;
   WideKey eff, head;                   // skip mode: the running maximum the queue's keys start from; the heap key of a barrier head
 };
-struct MgEnt { int32_t job, qk, e, ci; };   // merged position -> job, queue | 1 << 30 for an evicted job, stream position, compact index (its key: MgDev.key[ci])
+struct MgEnt { int32_t job, qk, e, ci; };   // merged position -> job, queue | 1 << 30 for an evicted job (| 1 << 29 as well: a limit element), stream position, compact index (its key: MgDev.key[ci])
 struct MgDev {
   MgQ* q;            // [QCAPF]
   WideKey* key;      // [cap] running-maximum packed keys, compact: queue q's entries at q.off .. + q.total
@@ -290,7 +290,8 @@ struct MgDev {
   uint32_t* stop;    // [4] first merged position that is NOT valid (atomic min); total entries; W_MG_CUT: entries the run can serve at most; 1 = the cut is on
   WideKey* cut;      // [1] W_MG_CUT: K* — entries above it are left out of this run's merged order
   uint32_t* cutPick; // [1] W_MG_CUT: (samples at or below the key) << 16 | sample, atomic min over the samples that cover the need
-  int32_t cap, pad;
+  int32_t cap;
+  int32_t limitOff;  // ASCHED_STREAM_LIMIT=0: a stream that ends at its queue's rate-limit tokens stays open and ends the run, as before round 7
 };
 #define MG_CHUNK 64
 #define MG_CPQ (QS_CMAX / MG_CHUNK)

@@ -76,6 +76,7 @@ struct alignas(16) EngineBox {
 #define RJOB(i) (((int32_t*)FL.winJob)[(i) & (RING_N - 1)])
 #define RQ(i) (((int32_t*)FL.winIdx)[(i) & (RING_N - 1)])
 #define RQ_EV 0x100   // ring entry of an evicted stream: nothing for the engine to do
+#define RQ_LIMIT 0x200   // (with RQ_EV) a queue's limit element (round_merge.h): nothing for the engine to do either; the control wave settles the queue when the run ends (fastStreamRun: queueRateLimited)
 #ifndef MG_MIN_ENTRIES_DEFAULT
 #define MG_MIN_ENTRIES_DEFAULT 2048   // (round_merge.h MG_MIN_ENTRIES)
 #endif
@@ -984,6 +985,36 @@ DEV void fastLoadHead(KREF k, int q, int job, QHot& f) {
 
 DEV void qlPutWin(int q, const QHot& f) { QHot& o = FL.hot[q]; o.winKind = f.winKind; o.winStart = f.winStart; o.winCount = f.winCount; }
 
+// QueueRateLimitExceeded for the head `job` (a single queued job) of queue q, whose tokens are used up — the queue-side event of fastIter, shared with the settling of a
+// bulk-merged run that carried the head as the queue's limit element (fastStreamRun).  0 = the generic code must take the iteration (nothing changed but the window).
+DEV int queueRateLimited(Dev& d, KREF k, FastS& S, const FastCtx& fc, int q, QHot& f, int job) {
+  if (S.numUnfeasible > 0 || f.itStage == 0) return 0;
+  bool lookback = fc.maxLookback != 0 && !f.itGangOnlyEv && (uint32_t)f.itJobsSeen >= fc.maxLookback;
+  int nextJob = -1;
+  if (!lookback && !f.itJobOnlyEv && f.itQi < f.qEnd) {
+    int pos = f.itQi;
+    if (!(f.winKind == 1 && pos >= f.winStart && pos < f.winStart + f.winCount)) {
+      int cnt = f.qEnd - pos; if (cnt > WIN) cnt = WIN;
+      winRefill(k, q, 1, pos, cnt);
+      f.winKind = 1; f.winStart = pos; f.winCount = cnt;
+      S.statRefills++;
+    }
+    int w = pos - f.winStart;
+    if (UNI32(FL.winRec[q][w].gang) >= 0) { qlPutWin(q, f); return 0; }  // the generic iterator assembles gangs (only the window moved: harmless)
+    nextJob = UNI32(FL.winJob[q][w]);
+    f.itQi = pos + 1; f.itJobsSeen++;
+  }
+  if (FLANE == 0) { k.jcReason[job] = ASCHED_REASON_QUEUE_RATE_LIMIT; k.jobFlags[job] = F_UNSUCCESSFUL; }
+  d.itStashed[q] = nextJob; d.onlyEvByQueue[q] = 1;
+  f.itGangOnlyEv = 1; f.itJobOnlyEv = 1;
+  f.itNext = -1; f.gctx = -1; f.headFast = 0; f.proposed = f.current = f.size = 0;
+  FL.inHeap[q] = 0;
+  QHot& o = FL.hot[q];
+  o.itQi = f.itQi; o.itJobsSeen = f.itJobsSeen; o.itNext = -1; o.gctx = -1; o.headFast = 0; o.proposed = o.current = o.size = 0;
+  o.itGangOnlyEv = 1; o.itJobOnlyEv = 1; o.winKind = f.winKind; o.winStart = f.winStart; o.winCount = f.winCount;
+  return 1;
+}
+
 // One QueueScheduler iteration (queue_scheduler.go:94-304 body) for the head of queue `top` when it is a single job that
 // (a) is queued and fits at priority -2 or (b) is a phase-1-evicted job returning to its node.  Returns 0 WITHOUT side
 // effects when the iteration needs the generic code (any constraint failing, preemption, gangs, ...); 1 = done;
@@ -1050,30 +1081,7 @@ DEV int fastIter(Dev& d, KREF k, FastS& S, const FastCtx& fc, int top, KeyOut* k
       // constraint check, takes it out again and records it as failed (gang_scheduler.go:63-98: net effect = the job's reason and
       // "unsuccessful" flag), pops the queue's item, which peeks the next job, and then restricts the queue to evicted jobs: the
       // peeked job is stashed and the queue leaves the heap (queue_scheduler.go:213-220, 338-350, 546-566).
-      if (S.numUnfeasible > 0 || f.itStage == 0) return 0;
-      bool lookback = fc.maxLookback != 0 && !f.itGangOnlyEv && (uint32_t)f.itJobsSeen >= fc.maxLookback;
-      int nextJob = -1;
-      if (!lookback && !f.itJobOnlyEv && f.itQi < f.qEnd) {
-        int pos = f.itQi;
-        if (!(f.winKind == 1 && pos >= f.winStart && pos < f.winStart + f.winCount)) {
-          int cnt = f.qEnd - pos; if (cnt > WIN) cnt = WIN;
-          winRefill(k, q, 1, pos, cnt);
-          f.winKind = 1; f.winStart = pos; f.winCount = cnt;
-          S.statRefills++;
-        }
-        int w = pos - f.winStart;
-        if (UNI32(FL.winRec[q][w].gang) >= 0) { qlPutWin(q, f); return 0; }  // the generic iterator assembles gangs (only the window moved: harmless)
-        nextJob = UNI32(FL.winJob[q][w]);
-        f.itQi = pos + 1; f.itJobsSeen++;
-      }
-      if (FLANE == 0) { k.jcReason[job] = ASCHED_REASON_QUEUE_RATE_LIMIT; k.jobFlags[job] = F_UNSUCCESSFUL; }
-      d.itStashed[q] = nextJob; d.onlyEvByQueue[q] = 1;
-      f.itGangOnlyEv = 1; f.itJobOnlyEv = 1;
-      f.itNext = -1; f.gctx = -1; f.headFast = 0; f.proposed = f.current = f.size = 0;
-      FL.inHeap[q] = 0;
-      QHot& o = FL.hot[q];
-      o.itQi = f.itQi; o.itJobsSeen = f.itJobsSeen; o.itNext = -1; o.gctx = -1; o.headFast = 0; o.proposed = o.current = o.size = 0;
-      o.itGangOnlyEv = 1; o.itJobOnlyEv = 1; o.winKind = f.winKind; o.winStart = f.winStart; o.winCount = f.winCount;
+      if (!queueRateLimited(d, k, S, fc, q, f, job)) return 0;
       ko->valid = 0;
       return 1;
     }
@@ -1410,6 +1418,7 @@ DEV_NOINLINE SkipDelta fastDrain(Dev& d, int Q) {
 // prefix sums, round_run.h B_QSKEYS), the engine executes the entries in emission order, and integer accounting is order independent.
 struct StreamIn { double globalTokens; int64_t globalBurst; int32_t globalRateInf, engSeq; int32_t skip, haveLast; uint32_t lastA, lastN; uint64_t lastX, lastY; int32_t resume; int32_t bulkV; };   // skip / last*: skip mode is on, key of the entry served last; bulkV > 0: the run's merged order has been computed by the bulk passes (round_merge.h), that many entries of it are valid
 struct StreamOut { int executed, executedEv, pend, dropped, engSeq, emitted, refills, evicted, maxConsumed, failed, lastQ; uint32_t lastA, lastN; uint64_t lastX, lastY;
+                   int limits;             // (round 7) queues settled at their limit element: one loop iteration each, nothing scheduled
                    int gangJobs, gangs;    // gangs placed INSIDE the run (round 5) and their members: the caller accounts them like fastGangRun's (ReserveN, one scheduled gang each)
                    int event, evT; };      // event != 0: the run is PARKED at one of its two rare events (streamNestSettle / streamNestGang on queue evT) — the caller runs it and calls again with in.resume
 // streams persist between runs: head of queue q == element sPos of its stream, elements [sPos, sLen) are still to come.  A queue's stream is dropped
@@ -1674,6 +1683,11 @@ DEV_NOINLINE StreamOut fastStreamRun(Dev& d, FastCtx fc, int Q, StreamIn in) {
     uniQHot(f);
     if (f.sLen == 0) continue;
     int start = SL_GET(sl, start, q), cq = UNI32(FL.tmpQ[q]), moved = SL_GET(sl, pos, q) - start, kind = SL_GET(sl, kind, q) & 1;
+    // (round 7) more entries done than the stream has elements: the last one was the queue's limit element (round_merge.h) — the elements are settled as ever, which makes
+    // the limit element the queue's head (fastAdvance), and the head then gets what the per-job iteration gives it (queueRateLimited)
+    const bool limAck = !kind && start + cq > f.sLen;
+    const int limPos = f.itQi - 1 - start + f.sLen;   // its place in the queue's list
+    if (limAck) cq = f.sLen - start;
     int pos = start + cq;                          // the new head
     bool more = pos < f.sLen;
 #ifdef ASCHED_HOSTSIM
@@ -1706,7 +1720,26 @@ DEV_NOINLINE StreamOut fastStreamRun(Dev& d, FastCtx fc, int Q, StreamIn in) {
       if (!f.rateInf && 1 <= f.burst) f.tokens -= (double)cq;
     }
     KeyOut ko;
-    if (!fastAdvance(d, k, S, fc, q, f, &ko)) out.pend = q;
+    const bool advanced = fastAdvance(d, k, S, fc, q, f, &ko);
+    if (!advanced) out.pend = q;
+    if (limAck) {
+      QHot h = FL.hot[q];
+      uniQHot(h);
+      // The later entries of the run have spent their global tokens by now, so this must not be left to the per-job iteration (it would see the global tokens of the
+      // end of the run and could give this job the global reason): mgPrepare carries a limit element only where everything below holds for certain — the stream's own
+      // conditions (fastStreamPrepare) give the head, the queue and the tokens; no key known to be unfeasible and no gang member behind the head (mgPrepare) make
+      // queueRateLimited take the job.  If it ever does not, the round ends with an error (the CPU build stops).
+      const bool settled = advanced && UNI32(FL.inHeap[q]) && h.gctx >= 0 && h.headFast && h.headKind == 1 && h.itQi - 1 == limPos && UNI32(k.queuedJobs[limPos]) == h.gctx && !h.cordoned &&
+                           h.burst >= 1 && h.tokens < 1 && queueRateLimited(d, k, S, fc, q, h, h.gctx);
+      if (settled) out.limits++;
+      else {   // never a wrong round: the round ends with ASCHED_ERR_INTERNAL (fastRun leaves its loop on RS.error)
+#ifdef ASCHED_HOSTSIM
+        fprintf(stderr, "hostsim: queue %d's limit element (list position %d) was carried through the run and is not settled\n", q, limPos); abort();
+#endif
+        if (FLANE == 0 && RS.error == 0) { RS.error = ASCHED_ERR_INTERNAL; RS.errorDetail = 540; }
+        LANE0_PUBLISHED();
+      }
+    }
   }
   doneQ += doneQmid; if (maxMid > out.maxConsumed) out.maxConsumed = maxMid;
   out.executed = doneQ; out.executedEv = doneEv; out.engSeq = engSeq; out.emitted = emittedPrev + emitted; out.refills = S.statRefills; out.evicted = S.numEvictedJobs;
@@ -1789,7 +1822,7 @@ DEV RunState streamMerge(Dev& d, FastCtx fc, int Q, int skip, int nest, RunState
       pqPopPush(pq, ko, t);
       SEG(10);
     } else {
-      bool listEnds = !(kind & 1) && UNI32(d.qsLen[2 * t + 1]);
+      bool listEnds = !(kind & 1) && (UNI32(d.qsLen[2 * t + 1]) & 1);   // (bit 1: a limit element waits behind the stream — bulk-merged runs only, round_merge.h; here the stream is open)
       if (listEnds) { pqPopPush(pq, ko, t); continue; }     // the queue's list ends where its stream ends: it leaves the heap
       // the queue goes on beyond its stream (its queued jobs after the evicted ones / more of its list): the next key is not known here ...
       bool gangNext = false;
@@ -1838,9 +1871,9 @@ DEV RunState streamStaged(Dev& d, FastCtx fc, int Q, int skip, int V, RunState m
       for (int x = 0; x < n4; x++) {
         const uint64_t v = UNI64(FL.tmpX[g + x]), w = UNI64(FL.tmpY[g + x]);
         const int job = (int)(uint32_t)v, qk = (int)(uint32_t)(v >> 32), e = (int)(uint32_t)w;
-        const int ev = (qk >> 30) & 1, q = qk & 0xffffff;
-        if (!ev && emittedQ >= allowed) { over = true; break; }   // no global token left for another new job (constraints.go:129-141)
-        if (FLANE == 0) { RJOB(emitted + put) = job; RQ(emitted + put) = q | (ev ? RQ_EV : 0); FL.tmpA[q] = (uint32_t)(e + 1); }
+        const int ev = (qk >> 30) & 1, lim = (qk >> 29) & 1, q = qk & 0xffffff;
+        if ((!ev || lim) && emittedQ >= allowed) { over = true; break; }   // no global token left for another new job (constraints.go:129-141) — the global check comes before the queue's: a limit element ends the run here like a new job, and costs no token when it passes
+        if (FLANE == 0) { RJOB(emitted + put) = job; RQ(emitted + put) = q | (ev ? RQ_EV : 0) | (lim ? RQ_LIMIT : 0); FL.tmpA[q] = (uint32_t)(e + 1); }
         LANE0_PUBLISHED();
         put++; if (!ev) emittedQ++;
         lastQ = q; lastCi = (int)(uint32_t)(w >> 32);
@@ -2102,7 +2135,7 @@ DEV __attribute__((always_inline)) int fastPreemptIter(Dev& d, Ctl& c, FastCtx f
 // is stopped for the passes (mgPrepare asks again, exactly).
 DEV bool mgWorth(Dev& d, int Q) {
 #ifdef ASCHED_HOSTSIM
-  static const int minEntries = getenv("HS_MG_MIN") ? atoi(getenv("HS_MG_MIN")) : MG_MIN_ENTRIES_DEFAULT;
+  const int minEntries = getenv("HS_MG_MIN") ? atoi(getenv("HS_MG_MIN")) : MG_MIN_ENTRIES_DEFAULT;
   if (getenv("HS_NO_MERGE")) return false;
 #else
   const int minEntries = d.f.mgMin;
@@ -2133,7 +2166,7 @@ DEV bool mgWorth(Dev& d, int Q) {
       const QHot& f = FL.hot[q];
       if (f.sLen > f.sPos) {
         const bool kd = FL.sKind[q] != 0;
-        if (!kd && !d.qsLen[2 * q + 1] && !f.effValid) { const int nx = f.itQi - 1 - f.sPos + f.sLen; if (nx < f.qEnd && d.jGang[k.queuedJobs[nx]] >= 0) b2 = 1; }
+        if (!kd && !(d.qsLen[2 * q + 1] & 1) && !f.effValid) { const int nx = f.itQi - 1 - f.sPos + f.sLen; if (nx < f.qEnd && d.jGang[k.queuedJobs[nx]] >= 0) b2 = 1; }
         if (!kd && f.sLen > QS_CMAX) b2 = 1;
       } else if (f.gctx < -1) b2 = 1;
     }
@@ -2314,7 +2347,7 @@ DEV_NOINLINE int fastRun(Dev& d, Ctl& c, const PassCfg& pc, int mode, int* count
           S.loopIterations += so.gangs; S.statFastIters += so.gangs;
         }
         E += so.executedEv;
-        S.loopIterations += E; S.statFastIters += E;
+        S.loopIterations += E + so.limits; S.statFastIters += E + so.limits;   // (a settled limit element is the iteration that failed its queue's rate limit)
         S.statRefills += so.refills; S.numEvictedJobs += so.evicted;
         if (FLANE == 0) { RS.statStreamRuns++; RS.statStreamJobs += E; RS.statStreamEmitted += so.emitted; }
         LANE0_PUBLISHED();
@@ -2322,6 +2355,7 @@ DEV_NOINLINE int fastRun(Dev& d, Ctl& c, const PassCfg& pc, int mode, int* count
         
         pqBuild(pq, Q);
         if (so.pend >= 0) pend = so.pend;
+        if (UNI32(RS.error)) break;   // (a carried limit element that could not be settled: fastStreamRun)
         if (c.skipActive && so.emitted > 0) {
           if (!so.failed) { lastTop = so.lastQ; refK.A = so.lastA; refK.X = so.lastX; refK.Y = so.lastY; refN = so.lastN; haveRef = 1; }   // every emitted entry was served
           else {   // served: the entries before the one that found no node, all of them ordering before it; it is the head of the heap again (nothing emitted after it was done)

@@ -24,6 +24,11 @@
 // node, cancel).  Stopping early is always exact: a run may end anywhere between two entries (fastStreamRun's settling produces every queue's next head from its
 // then-current allocation).
 //
+// (Round 7) A queued stream that was cut at its queue's rate-limit tokens is not open: it goes on with ONE more element, the queue's limit element (MG_F_LIMIT) — the job
+// that gets QueueRateLimitExceeded, after which the queue leaves the heap (fastIter, f.tokens < 1).  Its key was made with the stream's (round_run.h B_QSKEYS); it is packed,
+// ranked and scattered like any element, counts on top of the tokens for the cut like an evicted entry, and is marked in the merged order (MG_QK_LIMIT): streamStaged puts
+// it through the ring as "nothing to select or bind" and the end of the run settles the queue (fastStreamRun, queueRateLimited).  DESIGN.md 3.1 round 7 has the argument.
+//
 // The CPU build replays the heap merge literally after the passes and aborts on the first difference (mgCheck).
 #pragma once
 
@@ -37,6 +42,8 @@ enum { W_MG_PACK = 32, W_MG_FIX, W_MG_RANK, W_MG_SCATTER, W_MG_CUT };
 #define MG_F_OPEN 4
 #define MG_F_SKIP 8
 #define MG_F_PREFER_LARGE 16
+#define MG_F_LIMIT 32   // the stream's last element is the queue's limit element (round 7): ranked like any element, staged as "nothing to select or bind", never placed
+#define MG_QK_LIMIT (1 << 29)   // MgEnt.qk of a limit element (on top of 1 << 30: to the ring it is an entry like a returning evicted job's)
 #ifndef MG_MIN_ENTRIES
 #define MG_MIN_ENTRIES MG_MIN_ENTRIES_DEFAULT   // below this a run is merged by the control wave as before (the passes cost a few hand-shakes with the helper workgroups, and the node engine stops for them)
 #endif
@@ -143,6 +150,7 @@ DEV_COLD void mergeBulkAny(Dev& d, int kind, int i) {
       }
       const int pos = s.start + e;
       MgEnt en; en.job = mgCost(d, s, q, pos).job; en.qk = q | ((s.kind & 1) ? (1 << 30) : 0); en.e = pos; en.ci = i;
+      if (e == s.total - 1 && (s.flags & MG_F_LIMIT)) en.qk |= (1 << 30) | MG_QK_LIMIT;
       mg.merged[rank] = en;
       if (e == s.total - 1 && (s.flags & MG_F_OPEN)) atomicMinU32(&mg.stop[0], (uint32_t)(rank + 1));
       if (dec && (s.flags & MG_F_SKIP)) atomicMinU32(&mg.stop[0], (uint32_t)rank);
@@ -192,6 +200,10 @@ static void mgCheck(Dev& d, const FastCtx& fc, int Q, int skip, int V) {
         fprintf(stderr, "hostsim: bulk merge disagrees with the heap merge at position %d of %d: merged (queue %d, element %d), heap (queue %d, element %d); skip %d\n", n, V, en.qk & 0xffffff, en.e, t, h[t].pos, skip);
         abort();
       }
+      if (((en.qk & MG_QK_LIMIT) != 0) != ((s.flags & MG_F_LIMIT) && h[t].pos == s.len - 1)) {
+        fprintf(stderr, "hostsim: bulk merge position %d (queue %d, element %d of %d): limit mark %d, stream flags %d\n", n, t, h[t].pos, s.len, (en.qk & MG_QK_LIMIT) != 0, s.flags);
+        abort();
+      }
     }
     n++;
     h[t].pos++;
@@ -214,13 +226,22 @@ static void mgCheck(Dev& d, const FastCtx& fc, int Q, int skip, int V) {
 DEV_NOINLINE int mgPrepare(Dev& d, FastCtx fc, int Q, int skip, int need) {   // need: queued jobs the run can serve at most (the global tokens), INT32_MAX = no such bound
 #ifdef ASCHED_HOSTSIM
   { static const bool off = getenv("HS_NO_MERGE") != nullptr; if (off) return 0; }
-  static const int minEntries = getenv("HS_MG_MIN") ? atoi(getenv("HS_MG_MIN")) : MG_MIN_ENTRIES;
+  const int minEntries = getenv("HS_MG_MIN") ? atoi(getenv("HS_MG_MIN")) : MG_MIN_ENTRIES;   // (read per call: tests set it per case)
 #else
   const int minEntries = d.f.mgMin;
 #endif
   if (!d.mg || fc.replay || Q > QCAPF) return 0;
   const FastK k = fastKRef(d);
   MgDev& mg = *d.mg;
+  // (round 7) a queued stream that was cut at its queue's rate-limit tokens goes on with the queue's limit element (fastStreamPrepare made its key; when the run ends the
+  // queue gets what the per-job iteration does with that head: fastStreamRun, queueRateLimited) ONLY where that iteration takes its rate-limit branch for certain.  The
+  // settling comes after the later entries of the run have spent their global tokens, so it must not decline: a declined head would meet the per-job iteration with the
+  // global tokens of the END of the run.  queueRateLimited declines while any scheduling key is known to be unfeasible (whatever skipKnown is) and when the job it peeks
+  // behind the head is a gang member (describe below); neither changes during a run.
+  bool limOk = !UNI32(mg.limitOff) && UNI32(RS.numUnfeasible) == 0 && !k.hasPcLimit && !k.anyRoundLimit;
+#ifdef ASCHED_HOSTSIM
+  if (getenv("HS_NO_STREAM_LIMIT")) limOk = false;
+#endif
   // per queue: what the merge sees of it (lane q); the compact offsets are a prefix sum over the queues' entry counts (through LDS)
   auto describe = [&](int q, int off) {
     const QHot& f = FL.hot[q];
@@ -233,8 +254,12 @@ DEV_NOINLINE int mgPrepare(Dev& d, FastCtx fc, int Q, int skip, int need) {   //
         s.kind = kd | (f.effValid ? 2 : 0); s.start = f.sPos; s.len = f.sLen; s.total = f.sLen - f.sPos;
         s.base = (kd ? f.itEi : f.itQi) - 1 - f.sPos;
         s.flags = MG_F_STREAM | (skip ? MG_F_SKIP : 0) | (fc.preferLarge ? MG_F_PREFER_LARGE : 0);
-        const bool listEnds = !kd && d.qsLen[2 * q + 1] != 0;
-        if (!listEnds) {
+        const int ends = kd ? 0 : d.qsLen[2 * q + 1];
+        const bool listEnds = (ends & 1) != 0;
+        bool lim = (ends & 2) && limOk && f.itStage == 1 && f.sLen == d.qsLen[2 * q] && f.sLen < QS_CMAX;
+        if (lim) { const int nx = s.base + f.sLen + 1; if (nx < f.qEnd && d.jGang[k.queuedJobs[nx]] >= 0) lim = false; }   // the job behind the limit element, which the settling peeks, is a gang member: it would decline (the stream stays open)
+        if (lim) { s.len++; s.total++; s.flags |= MG_F_LIMIT; }
+        else if (!listEnds) {
           s.flags |= MG_F_OPEN;
           // the element behind a queued stream is a gang member: streamMerge settles the queue and goes on (streamNest) — such runs stay with it
           if (!kd && !f.effValid) { const int nx = s.base + f.sLen; if (nx < f.qEnd && d.jGang[k.queuedJobs[nx]] >= 0) bad = 1; }
@@ -252,12 +277,14 @@ DEV_NOINLINE int mgPrepare(Dev& d, FastCtx fc, int Q, int skip, int need) {   //
   };
   FOR_LANES(q, QCAPF) { FL.tmpQ[q] = 0; FL.tmpN[q] = 0; }
   LANE0_PUBLISHED();
-  FOR_LANES(q, Q) { const MgQ s = describe(q, 0); FL.tmpQ[q] = s.total; FL.tmpN[q] = (uint32_t)s.pad_; }
+  FOR_LANES(q, Q) { const MgQ s = describe(q, 0); FL.tmpQ[q] = s.total; FL.tmpN[q] = (uint32_t)s.pad_ | (uint32_t)(s.flags & MG_F_LIMIT); }   // (tmpN: bit 0 bad, MG_F_LIMIT as in the flags)
   LANE0_PUBLISHED();
   int total = 0, bad = 0, streams = 0;
   long long needAll = need;   // the cut (W_MG_CUT): evicted entries cost no token — all of them count on top of `need`
   for (int q = 0; q < Q; q++) {
-    const int t = UNI32(FL.tmpQ[q]); bad |= (int)UNI32(FL.tmpN[q]); if (FLANE == 0) FL.tmpA[q] = (uint32_t)total; total += t; if (t > 1) streams++;
+    const int t = UNI32(FL.tmpQ[q]), fq = (int)UNI32(FL.tmpN[q]);
+    bad |= fq & 1; if (fq & MG_F_LIMIT) needAll++;   // (a limit element costs no token either)
+    if (FLANE == 0) FL.tmpA[q] = (uint32_t)total; total += t; if (t > 1) streams++;
     if (UNI32(FL.sKind[q]) && UNI32(FL.inHeap[q]) && UNI32(FL.hot[q].sLen) > UNI32(FL.hot[q].sPos)) needAll += t;
   }
   LANE0_PUBLISHED();
@@ -293,7 +320,8 @@ DEV_NOINLINE int mgPrepare(Dev& d, FastCtx fc, int Q, int skip, int need) {   //
 #ifdef ASCHED_HOSTSIM
   mgCheck(d, fc, Q, skip, V);
   if (getenv("HS_MG_TRACE")) {
-    fprintf(stderr, "bulk merge: %d entries of %d queues, valid %d, skip %d, cut %d (need %lld)", total, streams, V, skip, (int)mg.stop[3], needAll);
+    int limits = 0; for (int q = 0; q < Q; q++) if (mg.q[q].flags & MG_F_LIMIT) limits++;
+    fprintf(stderr, "bulk merge: %d entries of %d queues, valid %d, skip %d, cut %d (need %lld), limit elements %d", total, streams, V, skip, (int)mg.stop[3], needAll, limits);
     for (int q = 0; q < Q; q++) { const MgQ& s = mg.q[q]; if (!s.total) continue;
       if ((s.flags & MG_F_BARRIER) && mg.rank[s.off] == (int)stop) fprintf(stderr, " | barrier q%d gctx %d headKind %d headFast %d stage %d itEi %d evEnd %d itQi %d qEnd %d tokens %.0f eff %d sLen %d", q, FL.hot[q].gctx, FL.hot[q].headKind, FL.hot[q].headFast, FL.hot[q].itStage, FL.hot[q].itEi, FL.hot[q].evEnd, FL.hot[q].itQi, FL.hot[q].qEnd, FL.hot[q].tokens, FL.hot[q].effValid, FL.hot[q].sLen);
       if ((s.flags & MG_F_STREAM)) { int last = mg.rank[s.off + s.total - 1]; if ((s.flags & MG_F_OPEN) && last + 1 == (int)stop) fprintf(stderr, " | open q%d total %d kind %d", q, s.total, s.kind);

@@ -212,15 +212,20 @@ DEV void bulkElem(Dev& d, int kind, int i) {
         for (int r = 0; r < MAXR; r++) { int64_t s = part[r]; part[r] = run[r]; run[r] += s; }
         if (barrier != INT32_MAX) { len = barrier; cut = true; break; }
       }
-      if (in.pad) break;   // a kept stream: its length and end flag stand
+      if (in.pad & 1) break;   // a kept stream: its length and end flags stand
+      if (in.pad & 2) {   // in.len counts the queue's limit element (fastStreamPrepare): it is one unless the stream was cut in front of it or it is itself a barrier
+        d.qsLen[2 * i] = cut ? len : len - 1;
+        d.qsLen[2 * i + 1] = cut ? 0 : 2;   // bit 1: the element behind the stream is the queue's limit element, its key is qsKey[len]
+        break;
+      }
       d.qsLen[2 * i] = len;
-      d.qsLen[2 * i + 1] = (!cut && in.len > 0 && in.base + in.len == d.queuedOff[i + 1]) ? 1 : 0;   // the queue's list ends where the stream ends
+      d.qsLen[2 * i + 1] = (!cut && in.len > 0 && in.base + in.len == d.queuedOff[i + 1]) ? 1 : 0;   // bit 0: the queue's list ends where the stream ends
     } break;
     case B_QSKEYS: {
       int q = i / QS_CPQ, ch = i % QS_CPQ;
       const QsIn& in = d.qsIn[q];
       if (in.len == 0) break;   // no new stream for this queue (a kept one stays as it is)
-      int len = d.qsLen[2 * q];
+      int len = d.qsLen[2 * q] + ((d.qsLen[2 * q + 1] & 2) ? 1 : 0);   // (the limit element's key is made like any element's: the allocation in front of it is the whole stream's)
       int e0 = ch * QS_CHUNK, e1 = e0 + QS_CHUNK < len ? e0 + QS_CHUNK : len;
       if (e0 >= e1) break;
       const int64_t* carry = d.qsPart + (size_t)i * (MAXR + 2);
@@ -651,6 +656,14 @@ DEV_NOINLINE int fastStreamPrepare(Dev& d, FastCtx fc, int Q, int allowed, int a
     if (FLANE == 0) { FL.hot[q].headFast = 1; FL.hot[q].headKind = f.headKind; FL.hot[q].headIdx = f.headIdx; FL.hot[q].headPos = f.headPos; }
     LANE0_PUBLISHED();
   }
+  // (round 7) a queued stream that ends at the queue's own rate-limit tokens carries the element behind the last token as the queue's LIMIT ELEMENT (round_merge.h): what the
+  // per-job iteration does with it (fastIter, f.tokens < 1) depends on nothing the node side produces.  Only where that branch is taken for certain: no per-class caps, no round
+  // limit, no scheduling key known to be unfeasible, the element within the lookback limit and not a gang member (B_QSSUM's barrier), room for its key.  Whether the
+  // element is carried is decided when the run starts (round_merge.h mgPrepare, which also looks at the job behind it); here only its key is made.
+  bool limOn = d.mg != nullptr && !UNI32(d.mg->limitOff) && UNI32(RS.numUnfeasible) == 0 && !k.hasPcLimit && !k.anyRoundLimit;
+#ifdef ASCHED_HOSTSIM
+  if (getenv("HS_NO_STREAM_LIMIT")) limOn = false;
+#endif
   FOR_LANES(q, QCAPF) FL.tmpQ[q] = 0;
   FOR_LANES(q, Q) {
     QHot& f = FL.hot[q];
@@ -669,13 +682,16 @@ DEV_NOINLINE int fastStreamPrepare(Dev& d, FastCtx fc, int Q, int allowed, int a
                  f.evApplied == f.evDone && f.itQi >= 1 && f.itQi <= f.qEnd && k.queuedJobs[f.itQi - 1] == f.gctx) {   // (a stashed job is not at the list position before the cursor)
         int len = f.qEnd - (f.itQi - 1);
         if (len > cap) len = cap;
-        if (!f.rateInf && f.tokens < (double)len) len = (int)f.tokens;
+        bool byTokens = false;
+        if (!f.rateInf && f.tokens < (double)len) { len = (int)f.tokens; byTokens = true; }
         if (fc.maxLookback != 0 && !f.itGangOnlyEv) {   // element e >= 1 is peeked when itJobsSeen = seen + e - 1 < maxLookback (queue_scheduler.go:434-444)
           int64_t lim = (int64_t)fc.maxLookback - f.itJobsSeen + 1;
           if (lim < 1) lim = 1;
+          if (len >= lim) byTokens = false;   // (the limit element is element len: beyond the lookback limit it is never peeked)
           if (len > lim) len = (int)lim;
         }
         in.base = f.itQi - 1; in.len = len; in.pad = 0;
+        if (limOn && byTokens && len < QS_CMAX) { in.len = len + 1; in.pad = 2; }
         status = 2;
       }
     }
