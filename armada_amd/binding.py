@@ -247,14 +247,14 @@ ALL_SYMBOLS = [
     "excluded_nodes", "set_excluded_nodes",
     "round_preemption_causes", "preemption_join",
     "set_evictor_report", "round_evictor_report",
-    "jobs_patch",
+    "jobs_patch", "jobs_append", "jobs_append_stats",
 ]
 # entry points the CPU oracle does not implement (it is the single-process checker): the communicator and the collectives that run on it, and the join of a
 # round's result lists into preemption causes (a function of lists the oracle already delivers; tests/test_z_preemption_causes.py restates it)
 OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_destroy", "comm_rank", "fit_select_batch_sharded", "round_exchange", "shard_round", "shard_exchanges", "shard_area", "shard_open", "shard_peers",
                     "round_preemption_causes", "preemption_join",
                     "set_evictor_report", "round_evictor_report",   # (recorded by passes between the launches of the split round: tests/test_z_evictor_report.py restates it)
-                    "jobs_patch"}   # (an incremental jobs_set: the oracle is given the whole table; tests/test_z_jobs_patch.py)
+                    "jobs_patch", "jobs_append", "jobs_append_stats"}   # (an incremental jobs_set: the oracle is given the whole table; tests/test_z_jobs_patch.py, test_z_jobs_append.py)
 PREEMPTION_UNKNOWN, PREEMPTION_UNKNOWN_GANG, PREEMPTION_FAIRSHARE, PREEMPTION_URGENCY, PREEMPTION_OPTIMISER = 1, 2, 3, 4, 5   # ASCHED_PREEMPTION_* (context.PreemptionType)
 # ASCHED_EVR_* bits of asched_evictor_report.node_reasons, in bit order: the reference's reason strings in alphabetical order (makeNodePreemptiblityStats sorts them)
 EVICTOR_REASONS = ("all_jobs_preemptible", "below_protected_fair_share", "invalid_queue", "job_not_preemptible", "node_empty", "node_unschedulable")
@@ -449,6 +449,8 @@ class Library:
         f("set_evictor_report", C.c_int32, [C.c_void_p, C.c_int32])
         f("round_evictor_report", C.c_int32, [C.c_void_p, C.POINTER(CEvictorReport)])
         f("jobs_patch", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _i64p])
+        f("jobs_append", C.c_int32, [C.c_void_p, C.POINTER(CJobs)])
+        f("jobs_append_stats", C.c_int32, [C.c_void_p, _i32p])
         f("round_preemption_causes", C.c_int32, [C.c_void_p, C.POINTER(CPreemptionCause), C.c_int32, _i32p, C.c_int32, _i32p])
         f("preemption_join", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, C.c_int32, _i32p, _i32p, _i32p, _u8p, C.POINTER(CPreemptionCause), _i32p, C.c_int32, _i32p])
 
@@ -721,6 +723,42 @@ class Scheduler:
         sp = None if scheduled_at_priority is None else _arr(np.broadcast_to(np.asarray(scheduled_at_priority, dtype=np.int32), (n,)), np.int32)
         ts = None if run_timestamp is None else _arr(np.broadcast_to(np.asarray(run_timestamp, dtype=np.int64), (n,)), np.int64)
         self._check(fn(self.h, n, _ptr(jb, C.c_int32), _ptr(nd, C.c_int32), _ptr(sp, C.c_int32), _ptr(ts, C.c_int64)))
+
+    def jobs_append(self, req, *, queue=None, pc=None, queue_priority=None, submit_time=None, req_class=None, gang_id=None, gang_cardinality=None,
+                    gang_uniformity_label=None, node=None, scheduled_at_priority=None, run_timestamp=None, away=None, bid_price=None):
+        """syncState's upsert of newly submitted jobs: the rows are added behind the resident job table (new job ids num_jobs ..), in ascending job-id order, with the
+        requirement classes of the last jobs_set.  Keywords as for jobs_set; queued jobs only (node / scheduled_at_priority / run_timestamp / away / bid_price exist so
+        that the library's refusals can be reached).  submit_time defaults to the row's job id, as jobs_set's does.  Leaves the handle as jobs_set of the concatenated
+        table would; go on with round_prepare."""
+        fn = self._preemption_fn("jobs_append")
+        req = _arr(req, np.int64).reshape(-1, self.R)
+        m = req.shape[0]
+        s = CJobs()
+        s.m = m
+        keep = [req]
+        s.req = _ptr(req, C.c_int64)
+        for name, val, dtype, ctype in (("queue", np.zeros(m) if queue is None else queue, np.int32, C.c_int32), ("pc", np.zeros(m) if pc is None else pc, np.int32, C.c_int32),
+                                        ("queue_priority", queue_priority, np.uint32, C.c_uint32),
+                                        ("submit_time", self.num_jobs + np.arange(m) if submit_time is None else submit_time, np.int64, C.c_int64),
+                                        ("req_class", req_class, np.int32, C.c_int32), ("gang_id", gang_id, np.int32, C.c_int32), ("gang_cardinality", gang_cardinality, np.int32, C.c_int32),
+                                        ("gang_uniformity_label", gang_uniformity_label, np.int32, C.c_int32), ("node", node, np.int32, C.c_int32),
+                                        ("scheduled_at_priority", scheduled_at_priority, np.int32, C.c_int32), ("run_timestamp", run_timestamp, np.int64, C.c_int64),
+                                        ("away", away, np.uint8, C.c_uint8), ("bid_price", bid_price, np.float64, C.c_double)):
+            if val is None:
+                continue
+            a = _arr(val, dtype)
+            assert a.shape[0] == m, name
+            keep.append(a)
+            setattr(s, name, _ptr(a, ctype))
+        self._check(fn(self.h, C.byref(s)))
+        self.num_jobs += m
+
+    def jobs_append_stats(self):
+        """how the last jobs_append ran: rows, rows that entered the order, new shapes, new gangs, re-allocated, masks and fast structure rebuilt, capacity"""
+        fn = self._preemption_fn("jobs_append_stats")
+        out = np.zeros(8, np.int32)
+        self._check(fn(self.h, _ptr(out, C.c_int32)))
+        return dict(rows=int(out[0]), in_order=int(out[1]), new_shapes=int(out[2]), new_gangs=int(out[3]), reallocated=int(out[4]), rebuilt=int(out[5]), capacity=int(out[6]))
 
     def txn_begin(self): self._check(self.lib.txn_begin(self.h))
     def txn_commit(self): self._check(self.lib.txn_commit(self.h))

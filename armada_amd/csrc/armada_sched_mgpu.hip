@@ -457,3 +457,15 @@ extern "C" int asched_internal_jp_merge(const Dev* d, const JpArgs* a, hipStream
   if (work > 0) hipLaunchKernelGGL(k_jp_merge, dim3(mgBlocks(work)), dim3(MG_THREADS), 0, st, *d, *a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// ------------------------------------------------------------------------------------------------ newly submitted jobs behind the resident job table (kernels_jobs_append.h)
+// row fill + keys; the sort and the merge by rank are the patch's (asched_internal_jp_sort / _jp_merge on JaArgs::p)
+#include "kernels_jobs_append.h"
+__global__ __launch_bounds__(MG_THREADS) void k_ja_fill(Dev d, JaArgs a) {
+  long long i = MG_IDX();
+  if (i < a.nb2) jaFill(d, a, (int)i);
+}
+extern "C" int asched_internal_ja_fill(const Dev* d, const JaArgs* a, hipStream_t st) {
+  if (a->nb2 > 0) hipLaunchKernelGGL(k_ja_fill, dim3(mgBlocks(a->nb2)), dim3(MG_THREADS), 0, st, *d, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}

@@ -28,6 +28,7 @@
 #include "kernels_preempt_join.h"   // PjArgs and, in the CPU build of the tests, plat_preempt_join
 #include "kernels_evict_report.h"   // EvrArgs and, in the CPU build of the tests, plat_evict_report
 #include "kernels_jobs_patch.h"     // JpArgs and, in the CPU build of the tests, plat_jobs_patch
+#include "kernels_jobs_append.h"    // JaArgs and, in the CPU build of the tests, plat_jobs_append
 
 namespace {
 
@@ -234,6 +235,15 @@ struct asched {
   std::vector<uint32_t> jQPrioHost; std::vector<int64_t> jSubmitHost, jRunTsHost;
   struct { bool built = false; uint8_t* keep = nullptr; uint32_t* qprio = nullptr; int64_t* submit = nullptr; int64_t* runTs = nullptr; int32_t* ordSpare = nullptr; } jp;
   std::vector<uint8_t> jpSeen;       // [M] all zero between calls: a row named twice in one patch
+  // ---- asched_jobs_append (kernels_jobs_append.h).  Capacities of the job table's device arrays, in elements: jobs_set allocates exactly what the table needs (capacity ==
+  // size); an append that does not fit grows to max(needed, 1.25 x capacity).  ordCap / ordSpareCap: dev.ordAll and jp.ordSpare (they swap).
+  size_t jobCap = 0, gangCap = 0, gangArrCap = 0, gangJobsCap = 0, gangOffCap = 0, ordCap = 0, ordSpareCap = 0, ordOffCap = 0;
+  std::map<std::pair<int32_t, int32_t>, int32_t> gangMap;   // (queue, gang id) -> dense gang id, as jobs_set numbered them
+  std::vector<int32_t> gangOffHost;  // host copy of dev.gangOff [G + 2]
+  std::vector<int32_t> shapeRow;     // [S] first row of each scheduling-key shape (a new row's JobRec is copied from it on the device)
+  std::vector<int32_t> shapeTable; std::vector<uint64_t> shapeHash;   // open-addressing table over the shapes, built by the first append of a job table
+  int32_t jaStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_append_stats
+  double jaMs[3] = {0, 0, 0};        // device ms of row fill / sort / merge of the last append (ASCHED_JA_TIMES=1)
   DevBufs jpBufs; char* jpScratch = nullptr; size_t jpScratchBytes = 0;   // the entries, the sort array and the kept list of a patch: one block, kept between calls and only ever grown
   double jpMs[4] = {0, 0, 0, 0};     // device ms of the four passes of the last patch (ASCHED_JP_TIMES=1)
   double roundTotalMs = 0, roundControlMs = 0, roundPhaseMs[4] = {0, 0, 0, 0};   // split round: whole sequence / persistent passes / evict-1, evict-3, final bulk phases (host clock)
@@ -372,14 +382,15 @@ static void exclSetup(asched* h) {
   ExclDev& x = h->exclHost;
   x.cap = h->exclCap; x.W = h->dev.cfg.W;
   x.dynCap = (int32_t)std::min<long long>((long long)1 << 20, std::max<long long>(4096, 4ll * h->N));
-  char* base = h->exclBufs.alloc<char>(EXCL_HDR + (size_t)h->M * 4);   // the header, then the per-job slots (dev.h EXCL())
+  const size_t jcap = std::max((size_t)h->M, h->jobCap);   // (room for the rows asched_jobs_append may still add: the job table's capacity)
+  char* base = h->exclBufs.alloc<char>(EXCL_HDR + jcap * 4);   // the header, then the per-job slots (dev.h EXCL())
   x.jobSlot = (int32_t*)(base + EXCL_HDR);
-  plat_memset(x.jobSlot, 0xff, (size_t)h->M * 4);
+  plat_memset(x.jobSlot, 0xff, jcap * 4);
   x.rec = h->exclBufs.alloc<ExclRec>(x.cap);
   x.bits = h->exclBufs.alloc<uint64_t>((size_t)x.cap * x.W);
   x.fbits = (h->dev.cfg.disableUrgency && !h->dev.cfg.disableFair) ? h->exclBufs.alloc<uint64_t>((size_t)x.cap * x.W) : x.bits;   // (gate-passed records exist only with urgency preemption disabled; never read otherwise)
   x.dyn = h->exclBufs.alloc<ExclDyn>(x.dynCap);
-  x.pinAvail = h->exclBufs.alloc<int64_t>(h->M);
+  x.pinAvail = h->exclBufs.alloc<int64_t>(jcap);
   static_assert(sizeof(ExclDev) <= EXCL_HDR, "ExclDev header");
   plat_h2d(base, &x, sizeof x);
   h->dev.excl = x.jobSlot;
@@ -645,7 +656,8 @@ int buildFast(asched* h, const std::vector<uint64_t>& classMask) {
     }
   });
   prof.lap("JobRec fill");
-  d.jrec = (JobRec*)h->fastBufs.alloc<unsigned char>(sizeof(JobRec) * (size_t)std::max(M, 1));
+  const size_t jcap = std::max((size_t)M, h->jobCap);   // (the job table's capacity: asched_jobs_append writes the records of new rows behind the M uploaded here)
+  d.jrec = (JobRec*)h->fastBufs.alloc<unsigned char>(sizeof(JobRec) * std::max<size_t>(jcap, 1));
   if (M) plat_h2d(d.jrec, recs, sizeof(JobRec) * (size_t)M);
   prof.lap("JobRec upload");
   d.shapeTab = h->fastBufs.upload(fitTab);
@@ -658,7 +670,7 @@ int buildFast(asched* h, const std::vector<uint64_t>& classMask) {
   d.baseKey = h->fastBufs.alloc<uint64_t>(Nb2);
   d.baseNode = h->fastBufs.alloc<int32_t>(Npad); d.baseExtra = h->fastBufs.alloc<int64_t>(Npad * MAXE); d.baseCls = h->fastBufs.alloc<uint64_t>(Npad);
   d.baseRemoved = h->fastBufs.alloc<uint8_t>(Npad); d.posOf = h->fastBufs.alloc<int32_t>(Npad); d.l0Slot = h->fastBufs.alloc<int32_t>(Npad);
-  d.evIdxByPos = h->fastBufs.alloc<int32_t>(M); d.evKey = h->fastBufs.alloc<EvKey>(M); d.evCheap = h->fastBufs.alloc<uint8_t>(4104 + (size_t)M + 8);   // [0, 4098): per queue; from 4104: per evicted-list position (round_fast.h EV_EXCL)
+  d.evIdxByPos = h->fastBufs.alloc<int32_t>(jcap); d.evKey = h->fastBufs.alloc<EvKey>(jcap); d.evCheap = h->fastBufs.alloc<uint8_t>(4104 + jcap + 8);   // [0, 4098): per queue; from 4104: per evicted-list position (round_fast.h EV_EXCL)
   d.evChunks = 1024; d.evPart = h->fastBufs.alloc<int64_t>((size_t)d.evChunks * (2 * MAXR + 4));
   d.evMono = h->fastBufs.alloc<uint8_t>(4096 + 2); d.evEdge = h->fastBufs.alloc<uint64_t>((size_t)d.evChunks * 8); d.l0Save = h->fastBufs.alloc<int32_t>(L0CAP); d.candPosSave = h->fastBufs.alloc<int32_t>(SMAX);
   d.qsKey = nullptr; d.qsIn = nullptr; d.qsPart = nullptr; d.qsLen = nullptr; d.qsSave = nullptr;
@@ -965,108 +977,34 @@ int32_t asched_nodes_upsert(asched_t* h, const asched_nodes* in) { if (!h) retur
   return rebuildMasks(h);
 }
 
-int32_t asched_set_label_value_ints(asched_t* h, int32_t n, const int32_t* ids, const int64_t* ints) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
-  if (n < 0 || (n > 0 && (!ids || !ints))) return fail(h, ASCHED_ERR_INVALID, "set_label_value_ints: bad arguments");
-  h->valueInts.clear();
-  for (int i = 0; i < n; i++) h->valueInts[ids[i]] = ints[i];
-  return 0;
-}
-int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_classes* c) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
-  if (h) { h->haveRoundResult = false; h->stateEpoch++; }
-  fastInvalidate(h);
-  h->jobBufs.freeAll();
-  h->jp = {};   // (its buffers lived in jobBufs)
-  HostProf prof("jobs_set");
+// the per-job state of a round (everything indexed by job or by a position of a per-job list), zeroed, with room for `cap` rows: jobs_set takes exactly M,
+// asched_jobs_append a capacity (DESIGN 3.10).  Static per-job arrays (what jobs_set uploads) are not here: an append moves them.
+static void allocJobState(asched* h, size_t cap) {
   Dev& d = h->dev;
-  int M = h->M = j->m, R = h->R;
-  d.cfg.M = M;
-  auto cp32 = [&](const int32_t* s, int32_t def) { std::vector<int32_t> v(M, def); if (s) v.assign(s, s + M); return v; };
-  h->jQueue = cp32(j->queue, 0); h->jPc = cp32(j->pc, 0); h->jReqClass = cp32(j->req_class, 0);
-  std::vector<int32_t> gangId = cp32(j->gang_id, -1), gangCard = cp32(j->gang_cardinality, 1), gangUni = cp32(j->gang_uniformity_label, -1);
-  h->jNode = cp32(j->node, -1); h->jRunPrio = cp32(j->scheduled_at_priority, 0);
-  h->jAway.assign(M, 0); h->anyAway = false;
-  if (j->away) for (int i = 0; i < M; i++) if (j->away[i]) { h->jAway[i] = 1; h->anyAway = true; }
-  std::vector<uint32_t> qprio(M, 0); if (j->queue_priority) qprio.assign(j->queue_priority, j->queue_priority + M);
-  std::vector<int64_t> submit(M, 0), runTs(M, 0);
-  if (j->submit_time) submit.assign(j->submit_time, j->submit_time + M);
-  if (j->run_timestamp) runTs.assign(j->run_timestamp, j->run_timestamp + M);
-  h->jReq.assign(j->req, j->req + (size_t)M * R);
-  int nc = c ? c->n : 0;
-  h->C = std::max(nc, 1);
-  h->clsTol.assign(h->C, {}); h->clsSel.assign(h->C, {}); h->clsAff.clear();
-  if (c && c->has_affinity) h->clsAff.assign(h->C, {});
-  for (int i = 0; i < nc; i++) {
-    if (c->tol_off) for (int k = c->tol_off[i]; k < c->tol_off[i + 1]; k++) h->clsTol[i].push_back({c->tol_key[k], c->tol_op[k], c->tol_value[k], c->tol_effect[k]});
-    if (c->sel_off) for (int k = c->sel_off[i]; k < c->sel_off[i + 1]; k++) h->clsSel[i].push_back({c->sel_key[k], c->sel_value[k]});
-    if (c->has_affinity && c->has_affinity[i]) {
-      h->clsAff[i].present = true;
-      for (int t = c->aff_term_off[i]; t < c->aff_term_off[i + 1]; t++) {
-        std::vector<HAffExpr> term;
-        for (int x = c->aff_expr_off[t]; x < c->aff_expr_off[t + 1]; x++) {
-          HAffExpr ex; ex.key = c->aff_expr_key[x]; ex.op = c->aff_expr_op[x];
-          if (ex.op < ASCHED_AFFINITY_OP_IN || ex.op > ASCHED_AFFINITY_OP_LT) return fail(h, ASCHED_ERR_UNSUPPORTED, "unknown node affinity operator");
-          ex.values.assign(c->aff_values + c->aff_value_off[x], c->aff_values + c->aff_value_off[x + 1]);
-          term.push_back(ex);
-        }
-        h->clsAff[i].terms.push_back(term);
-      }
-    }
-  }
-  d.cfg.C = h->C;
-  prof.lap("copy-in + classes");
-  // scheduling-key shapes (podutils.go:52-72): (requirement class, priority class, requests)
-  // (first occurrence numbers the shape; an open-addressing table over (class, priority class, requests) replaces an ordered map)
-  h->jShape.assign(M, 0); h->shapeClass.clear(); h->shapeReq.clear(); h->shapePc.clear();
-  std::vector<uint8_t> aligned(M, 1);
-  bool anyAway = false;
-  int maxQueue = -1;
-  {
-    size_t cap = 1024;
-    std::vector<int32_t> table(cap, -1);
-    auto hashOf = [&](int i) {
-      uint64_t x = 0x9e3779b97f4a7c15ull ^ ((uint64_t)(uint32_t)h->jReqClass[i] << 32 | (uint32_t)h->jPc[i]);
-      for (int r = 0; r < R; r++) { x ^= (uint64_t)h->jReq[(size_t)i * R + r]; x *= 0xff51afd7ed558ccdull; x ^= x >> 29; }
-      return x;
-    };
-    auto same = [&](int sidx, int i) {
-      if (h->shapeClass[sidx] != h->jReqClass[i] || h->shapePc[sidx] != h->jPc[i]) return false;
-      for (int r = 0; r < R; r++) if (h->shapeReq[(size_t)sidx * R + r] != h->jReq[(size_t)i * R + r]) return false;
-      return true;
-    };
-    std::vector<uint64_t> shapeHash;
-    for (int i = 0; i < M; i++) {
-      if (h->jReqClass[i] < 0 || h->jReqClass[i] >= h->C) return fail(h, ASCHED_ERR_INVALID, "req_class out of range");
-      if (h->jPc[i] < 0 || h->jPc[i] >= h->npc) return fail(h, ASCHED_ERR_INVALID, "pc out of range");
-      if (h->jNode[i] >= h->N && h->nodesSet) return fail(h, ASCHED_ERR_INVALID, "running job on unknown node");
-      if (!h->pcAway[h->jPc[i]].empty()) anyAway = true;
-      uint64_t hv = hashOf(i);
-      size_t pos = hv & (cap - 1);
-      while (table[pos] >= 0 && !(shapeHash[table[pos]] == hv && same(table[pos], i))) pos = (pos + 1) & (cap - 1);
-      if (table[pos] < 0) {
-        int32_t sidx = (int32_t)h->shapeClass.size();
-        table[pos] = sidx;
-        shapeHash.push_back(hv);
-        h->shapeClass.push_back(h->jReqClass[i]); h->shapePc.push_back(h->jPc[i]);
-        for (int r = 0; r < R; r++) h->shapeReq.push_back(h->jReq[(size_t)i * R + r]);
-        if ((size_t)(sidx + 1) * 2 > cap) {  // keep the load factor under one half
-          cap *= 4;
-          table.assign(cap, -1);
-          for (int32_t t = 0; t <= sidx; t++) { size_t p2 = shapeHash[t] & (cap - 1); while (table[p2] >= 0) p2 = (p2 + 1) & (cap - 1); table[p2] = t; }
-          pos = hv & (cap - 1);
-          while (table[pos] != sidx) pos = (pos + 1) & (cap - 1);
-        }
-      }
-      h->jShape[i] = table[pos];
-      for (int cix = 0; cix < h->K; cix++)
-        if (h->jReq[(size_t)i * R + h->indexedCol[cix]] % h->indexedRes[cix]) aligned[i] = 0;
-      maxQueue = std::max(maxQueue, h->jQueue[i]);
-    }
-  }
-  prof.lap("shapes");
-  d.cfg.hasAway = anyAway ? 1 : 0;
-  h->S = (int)h->shapeClass.size(); d.cfg.S = h->S;
-  h->shapeUnaligned.assign(h->S, 0);
-  for (int i = 0; i < M; i++) if (!aligned[i]) h->shapeUnaligned[h->jShape[i]] = 1;
+  auto A32 = [&](size_t n) { return h->jobBufs.alloc<int32_t>(n); };
+  auto A8 = [&](size_t n) { return h->jobBufs.alloc<uint8_t>(n); };
+  const size_t M = cap;
+  d.schedAtPrio = A32(M); d.jobNode = A32(M); d.jobCutoff = A32(M); d.jobEvictedOnNode = A8(M); d.jobFlags = A8(M);
+  d.optSched = A8(M); d.optPre = A8(M); d.optGhost = A32(M);
+  d.jcEvicted = A8(M); d.jcAssigned = A32(M); d.jcReason = A32(M); d.jcHasPctx = A8(M);
+  d.pcNode = A32(M); d.pcSap = A32(M); d.pcPap = A32(M); d.pcMethod = A32(M); d.jcGangCard = A32(M); d.jcPreempted = A8(M);
+  d.jcUniValue = A32(M); d.jcStagedBy = A32(M); d.jcPreSib = A32(M);
+  d.inPreempted = A8(M); d.inScheduled = A8(M); d.inSchedAndEvicted = A8(M); d.preemptedNode = A32(M);
+  d.evList = A32(M); d.evSortKey = h->jobBufs.alloc<uint32_t>(M + 1); d.evTabJob = A32(M); d.evTabAlive = A8(M); d.evIndexOfJob = A32(M);
+  d.fairEnt = A32(M); d.fairEntJob = A32(M);
+  d.evFlag = A8(M); d.preList = A32(M);
+  d.resJob = A32(M); d.resNode = A32(M); d.resPrio = A32(M); d.resMethod = A32(M); d.resPreJob = A32(M); d.resPreNode = A32(M);
+}
+// the per-gang state: G gangs + the scratch gang of schedule_many; arrLen: gangOff[G + 1], the members of every gang and of the scratch gang
+static void allocGangState(asched* h, size_t G, size_t arrLen) {
+  Dev& d = h->dev;
+  d.gangSeen = h->jobBufs.alloc<int32_t>(G + 1); d.gangArr = h->jobBufs.alloc<int32_t>(arrLen); d.gangTotal = h->jobBufs.alloc<int64_t>((G + 1) * (size_t)h->R);
+  d.gangAllEvicted = h->jobBufs.alloc<uint8_t>(G + 1);
+}
+// the away rows of the shape table (jobs_set, and jobs_append when a new shape arrives): the derived requirement classes behind the C real ones, one mask row per
+// (shape, away entry of its priority class).  Derived classes are numbered in shape order, so the same shape table gives the same rows.
+static void deriveAwayRows(asched* h, bool anyAway) {
+  const int R = h->R;
   // away attempts (nodedb.go:677-722) match statically with the job's tolerations + one toleration per taint of the well-known
   // node type: a derived requirement class per (class, well-known type), one extra mask row per (shape, away entry)
   h->clsTol.resize(h->C); h->clsSel.resize(h->C); if (!h->clsAff.empty()) h->clsAff.resize(h->C);
@@ -1123,8 +1061,113 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
     h->awayRowOff[h->S] = (int32_t)h->awayRowClass.size();
   }
   h->Cext = (int)h->clsTol.size();
+}
+
+int32_t asched_set_label_value_ints(asched_t* h, int32_t n, const int32_t* ids, const int64_t* ints) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
+  if (n < 0 || (n > 0 && (!ids || !ints))) return fail(h, ASCHED_ERR_INVALID, "set_label_value_ints: bad arguments");
+  h->valueInts.clear();
+  for (int i = 0; i < n; i++) h->valueInts[ids[i]] = ints[i];
+  return 0;
+}
+int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_classes* c) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
+  if (h) { h->haveRoundResult = false; h->stateEpoch++; }
+  fastInvalidate(h);
+  h->jobBufs.freeAll();
+  h->jp = {};   // (its buffers lived in jobBufs)
+  HostProf prof("jobs_set");
+  Dev& d = h->dev;
+  int M = h->M = j->m, R = h->R;
+  d.cfg.M = M;
+  auto cp32 = [&](const int32_t* s, int32_t def) { std::vector<int32_t> v(M, def); if (s) v.assign(s, s + M); return v; };
+  h->jQueue = cp32(j->queue, 0); h->jPc = cp32(j->pc, 0); h->jReqClass = cp32(j->req_class, 0);
+  std::vector<int32_t> gangId = cp32(j->gang_id, -1), gangCard = cp32(j->gang_cardinality, 1), gangUni = cp32(j->gang_uniformity_label, -1);
+  h->jNode = cp32(j->node, -1); h->jRunPrio = cp32(j->scheduled_at_priority, 0);
+  h->jAway.assign(M, 0); h->anyAway = false;
+  if (j->away) for (int i = 0; i < M; i++) if (j->away[i]) { h->jAway[i] = 1; h->anyAway = true; }
+  std::vector<uint32_t> qprio(M, 0); if (j->queue_priority) qprio.assign(j->queue_priority, j->queue_priority + M);
+  std::vector<int64_t> submit(M, 0), runTs(M, 0);
+  if (j->submit_time) submit.assign(j->submit_time, j->submit_time + M);
+  if (j->run_timestamp) runTs.assign(j->run_timestamp, j->run_timestamp + M);
+  h->jReq.assign(j->req, j->req + (size_t)M * R);
+  int nc = c ? c->n : 0;
+  h->C = std::max(nc, 1);
+  h->clsTol.assign(h->C, {}); h->clsSel.assign(h->C, {}); h->clsAff.clear();
+  if (c && c->has_affinity) h->clsAff.assign(h->C, {});
+  for (int i = 0; i < nc; i++) {
+    if (c->tol_off) for (int k = c->tol_off[i]; k < c->tol_off[i + 1]; k++) h->clsTol[i].push_back({c->tol_key[k], c->tol_op[k], c->tol_value[k], c->tol_effect[k]});
+    if (c->sel_off) for (int k = c->sel_off[i]; k < c->sel_off[i + 1]; k++) h->clsSel[i].push_back({c->sel_key[k], c->sel_value[k]});
+    if (c->has_affinity && c->has_affinity[i]) {
+      h->clsAff[i].present = true;
+      for (int t = c->aff_term_off[i]; t < c->aff_term_off[i + 1]; t++) {
+        std::vector<HAffExpr> term;
+        for (int x = c->aff_expr_off[t]; x < c->aff_expr_off[t + 1]; x++) {
+          HAffExpr ex; ex.key = c->aff_expr_key[x]; ex.op = c->aff_expr_op[x];
+          if (ex.op < ASCHED_AFFINITY_OP_IN || ex.op > ASCHED_AFFINITY_OP_LT) return fail(h, ASCHED_ERR_UNSUPPORTED, "unknown node affinity operator");
+          ex.values.assign(c->aff_values + c->aff_value_off[x], c->aff_values + c->aff_value_off[x + 1]);
+          term.push_back(ex);
+        }
+        h->clsAff[i].terms.push_back(term);
+      }
+    }
+  }
+  d.cfg.C = h->C;
+  prof.lap("copy-in + classes");
+  // scheduling-key shapes (podutils.go:52-72): (requirement class, priority class, requests)
+  // (first occurrence numbers the shape; an open-addressing table over (class, priority class, requests) replaces an ordered map)
+  h->jShape.assign(M, 0); h->shapeClass.clear(); h->shapeReq.clear(); h->shapePc.clear(); h->shapeRow.clear(); h->shapeTable.clear(); h->shapeHash.clear();
+  std::vector<uint8_t> aligned(M, 1);
+  bool anyAway = false;
+  int maxQueue = -1;
+  {
+    size_t cap = 1024;
+    std::vector<int32_t> table(cap, -1);
+    auto hashOf = [&](int i) {
+      uint64_t x = 0x9e3779b97f4a7c15ull ^ ((uint64_t)(uint32_t)h->jReqClass[i] << 32 | (uint32_t)h->jPc[i]);
+      for (int r = 0; r < R; r++) { x ^= (uint64_t)h->jReq[(size_t)i * R + r]; x *= 0xff51afd7ed558ccdull; x ^= x >> 29; }
+      return x;
+    };
+    auto same = [&](int sidx, int i) {
+      if (h->shapeClass[sidx] != h->jReqClass[i] || h->shapePc[sidx] != h->jPc[i]) return false;
+      for (int r = 0; r < R; r++) if (h->shapeReq[(size_t)sidx * R + r] != h->jReq[(size_t)i * R + r]) return false;
+      return true;
+    };
+    std::vector<uint64_t> shapeHash;
+    for (int i = 0; i < M; i++) {
+      if (h->jReqClass[i] < 0 || h->jReqClass[i] >= h->C) return fail(h, ASCHED_ERR_INVALID, "req_class out of range");
+      if (h->jPc[i] < 0 || h->jPc[i] >= h->npc) return fail(h, ASCHED_ERR_INVALID, "pc out of range");
+      if (h->jNode[i] >= h->N && h->nodesSet) return fail(h, ASCHED_ERR_INVALID, "running job on unknown node");
+      if (!h->pcAway[h->jPc[i]].empty()) anyAway = true;
+      uint64_t hv = hashOf(i);
+      size_t pos = hv & (cap - 1);
+      while (table[pos] >= 0 && !(shapeHash[table[pos]] == hv && same(table[pos], i))) pos = (pos + 1) & (cap - 1);
+      if (table[pos] < 0) {
+        int32_t sidx = (int32_t)h->shapeClass.size();
+        table[pos] = sidx;
+        shapeHash.push_back(hv);
+        h->shapeClass.push_back(h->jReqClass[i]); h->shapePc.push_back(h->jPc[i]); h->shapeRow.push_back(i);
+        for (int r = 0; r < R; r++) h->shapeReq.push_back(h->jReq[(size_t)i * R + r]);
+        if ((size_t)(sidx + 1) * 2 > cap) {  // keep the load factor under one half
+          cap *= 4;
+          table.assign(cap, -1);
+          for (int32_t t = 0; t <= sidx; t++) { size_t p2 = shapeHash[t] & (cap - 1); while (table[p2] >= 0) p2 = (p2 + 1) & (cap - 1); table[p2] = t; }
+          pos = hv & (cap - 1);
+          while (table[pos] != sidx) pos = (pos + 1) & (cap - 1);
+        }
+      }
+      h->jShape[i] = table[pos];
+      for (int cix = 0; cix < h->K; cix++)
+        if (h->jReq[(size_t)i * R + h->indexedCol[cix]] % h->indexedRes[cix]) aligned[i] = 0;
+      maxQueue = std::max(maxQueue, h->jQueue[i]);
+    }
+  }
+  prof.lap("shapes");
+  d.cfg.hasAway = anyAway ? 1 : 0;
+  h->S = (int)h->shapeClass.size(); d.cfg.S = h->S;
+  h->shapeUnaligned.assign(h->S, 0);
+  for (int i = 0; i < M; i++) if (!aligned[i]) h->shapeUnaligned[h->jShape[i]] = 1;
+  deriveAwayRows(h, anyAway);
   // gangs: dense id per (queue, gang id), CSR of members (jobRepo.GetGangJobsByGangId)
-  std::map<std::pair<int32_t, int32_t>, int32_t> gmap;
+  std::map<std::pair<int32_t, int32_t>, int32_t>& gmap = h->gangMap; gmap.clear();   // (kept: asched_jobs_append numbers new gangs behind these)
   h->jGangDense.assign(M, -1);
   for (int i = 0; i < M; i++) if (gangId[i] >= 0) {
     auto k = std::make_pair(h->jQueue[i], gangId[i]);
@@ -1257,21 +1300,12 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
     d.ordAllOff = h->jobBufs.upload(off);
     h->ordOffHost = off;
   }
-  auto A32 = [&](size_t n) { return h->jobBufs.alloc<int32_t>(n); };
-  auto A8 = [&](size_t n) { return h->jobBufs.alloc<uint8_t>(n); };
-  d.schedAtPrio = A32(M); d.jobNode = A32(M); d.jobCutoff = A32(M); d.jobEvictedOnNode = A8(M); d.jobFlags = A8(M);
-  d.optSched = A8(M); d.optPre = A8(M); d.optGhost = A32(M);
-  d.jcEvicted = A8(M); d.jcAssigned = A32(M); d.jcReason = A32(M); d.jcHasPctx = A8(M);
-  d.pcNode = A32(M); d.pcSap = A32(M); d.pcPap = A32(M); d.pcMethod = A32(M); d.jcGangCard = A32(M); d.jcPreempted = A8(M);
-  d.jcUniValue = A32(M); d.jcStagedBy = A32(M); d.jcPreSib = A32(M);
-  d.inPreempted = A8(M); d.inScheduled = A8(M); d.inSchedAndEvicted = A8(M); d.preemptedNode = A32(M);
-  d.evList = A32(M); d.evSortKey = h->jobBufs.alloc<uint32_t>(M + 1); d.evTabJob = A32(M); d.evTabAlive = A8(M); d.evIndexOfJob = A32(M);
-  d.fairEnt = A32(M); d.fairEntJob = A32(M);
-  d.evFlag = A8(M); d.preList = A32(M);
-  d.gangSeen = A32(h->G + 1); d.gangArr = A32(gangOff[h->G + 1]); d.gangTotal = h->jobBufs.alloc<int64_t>((size_t)(h->G + 1) * R);
-  d.gangAllEvicted = A8(h->G + 1);
-  d.unfeasible = A8(std::max(h->S, 1)); d.unfeasibleReason = A32(std::max(h->S, 1));
-  d.resJob = A32(M); d.resNode = A32(M); d.resPrio = A32(M); d.resMethod = A32(M); d.resPreJob = A32(M); d.resPreNode = A32(M);
+  allocJobState(h, (size_t)M);
+  allocGangState(h, (size_t)h->G, (size_t)gangOff[h->G + 1]);
+  d.unfeasible = h->jobBufs.alloc<uint8_t>(std::max(h->S, 1)); d.unfeasibleReason = h->jobBufs.alloc<int32_t>(std::max(h->S, 1));
+  h->jobCap = M; h->gangCap = h->G; h->gangArrCap = (size_t)gangOff[h->G + 1]; h->gangJobsCap = gangJobs.size(); h->gangOffCap = gangOff.size();
+  h->ordCap = ord.size(); h->ordSpareCap = 0; h->ordOffCap = h->ordOffHost.size(); h->gangOffHost = gangOff;
+  memset(h->jaStats, 0, sizeof h->jaStats);
   h->jobsSet = true; h->prepared = false;
   h->jQPrioHost.swap(qprio); h->jSubmitHost.swap(submit); h->jRunTsHost.swap(runTs);   // (asched_jobs_patch uploads them when it is first called; nothing is copied here)
   prof.lap("uploads + per-job state allocation");
@@ -1350,8 +1384,8 @@ int32_t asched_jobs_patch(asched_t* h, int32_t n, const int32_t* job, const int3
     }
     if (!h->jp.built) {   // first patch of this job table: the order-key inputs become resident (the run timestamps as patched above)
       h->jp.qprio = h->jobBufs.upload(h->jQPrioHost); h->jp.submit = h->jobBufs.upload(h->jSubmitHost); h->jp.runTs = h->jobBufs.upload(h->jRunTsHost);
-      h->jp.keep = h->jobBufs.allocRaw<uint8_t>(M); plat_memset(h->jp.keep, 1, (size_t)M);
-      h->jp.ordSpare = h->jobBufs.allocRaw<int32_t>(total);
+      h->jp.keep = h->jobBufs.allocRaw<uint8_t>(h->jobCap); plat_memset(h->jp.keep, 1, (size_t)M);
+      h->jp.ordSpare = h->jobBufs.allocRaw<int32_t>(std::max<size_t>((size_t)total, h->ordCap)); h->ordSpareCap = std::max<size_t>((size_t)total, h->ordCap);   // (as long as the order: the two swap)
       h->jp.built = true;
     }
     JpArgs a; memset(&a, 0, sizeof a);
@@ -1368,7 +1402,7 @@ int32_t asched_jobs_patch(asched_t* h, int32_t n, const int32_t* job, const int3
     if (nT > 0) { a.keys = (JpKey*)(h->jpScratch + oKeys); keptBuf = (int32_t*)(h->jpScratch + oKept); a.out = h->jp.ordSpare; }
     int prc = plat_take_failure() ? -1 : plat_jobs_patch(d, a, keptBuf);
     if (prc) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
-    if (nT > 0) { std::swap(d.ordAll, h->jp.ordSpare); }
+    if (nT > 0) { std::swap(d.ordAll, h->jp.ordSpare); std::swap(h->ordCap, h->ordSpareCap); }
     plat_jobs_patch_ms(h->jpMs);
     if (const char* e = getenv("ASCHED_JP_TIMES")) if (e[0] == '1')
       fprintf(stderr, "[asched jobs_patch] jobs %d entries %d in the order %d: scatter %.4f ms, remove %.4f ms, sort %.4f ms, merge %.4f ms\n", M, n, nT, h->jpMs[0], h->jpMs[1], h->jpMs[2], h->jpMs[3]);
@@ -1392,6 +1426,355 @@ int32_t asched_jobs_patch(asched_t* h, int32_t n, const int32_t* job, const int3
   if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
   h->allocPristine = h->nodesSet;
   h->evictedDirty = false;
+  return 0;
+}
+
+// ---- asched_jobs_append (kernels_jobs_append.h): syncState's upsert of the newly submitted jobs (scheduler.go:478-535; jobdb/jobdb.go:572-700, the insertion into the
+// per-queue sorted set at :691-700).  Rows M .. M+m-1 behind the resident ones, on the device; the handle is left as asched_jobs_set of the concatenated table would
+// leave it.  Two paths, chosen per call: every row's scheduling-key shape is already in the table — nothing jobs_set derives per shape changes, so no mask is rebuilt and
+// the fast structure stays; or some row brings a new shape — the per-row work is the same and the shape-dependent tables are re-derived by the code jobs_set ends with.
+static uint64_t jaShapeHash(int32_t cls, int32_t pc, const int64_t* req, int R) {   // (jobs_set's hash over (requirement class, priority class, requests))
+  uint64_t x = 0x9e3779b97f4a7c15ull ^ ((uint64_t)(uint32_t)cls << 32 | (uint32_t)pc);
+  for (int r = 0; r < R; r++) { x ^= (uint64_t)req[r]; x *= 0xff51afd7ed558ccdull; x ^= x >> 29; }
+  return x;
+}
+static void jaShapeTableBuild(asched* h, size_t room) {   // over the shapes the handle holds, with a load factor under one half for `room` shapes
+  const int R = h->R; const size_t S = h->shapeClass.size();
+  size_t cap = 1024; while (cap < 2 * (std::max(room, S) + 1)) cap *= 4;
+  h->shapeTable.assign(cap, -1); h->shapeHash.resize(S);
+  for (size_t s = 0; s < S; s++) {
+    h->shapeHash[s] = jaShapeHash(h->shapeClass[s], h->shapePc[s], &h->shapeReq[s * R], R);
+    size_t pos = h->shapeHash[s] & (cap - 1);
+    while (h->shapeTable[pos] >= 0) pos = (pos + 1) & (cap - 1);
+    h->shapeTable[pos] = (int32_t)s;
+  }
+}
+// one device array of the job table that moves into a larger (or first) block: allocated before anything changes, filled and swapped in afterwards
+struct JaBlock { DevBufs* owner; void** slot; size_t bytes, copyBytes; const void* host; int fill; bool keepOld; void* fresh; };
+
+int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
+  if (!h) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  const int M = h->M, R = h->R;
+  Dev& d = h->dev;
+  // ---- every refusal before anything changes
+  if (!h->jobsSet || h->jQPrioHost.size() != (size_t)M || h->jSubmitHost.size() != (size_t)M || h->jRunTsHost.size() != (size_t)M || h->jNode.size() != (size_t)M)
+    return fail(h, ASCHED_ERR_INVALID, "jobs_append: no job table on this handle (jobs_set first)");
+  if (!rows || rows->m < 0) return fail(h, ASCHED_ERR_INVALID, "jobs_append: bad arguments");
+  const int m = rows->m;
+  if (h->mkJobsBuilt) return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_append: the job set carries the market order, which ranks every job against every other (jobs_set instead)");
+  if (m > 0 && !rows->req) return fail(h, ASCHED_ERR_INVALID, "jobs_append: req is missing");
+  if (m > 0 && rows->bid_price) return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_append: bid prices belong to the market order (jobs_set instead)");
+  if ((long long)M + m > (1ll << 30)) return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_append: more than 2^30 rows");
+  const int M1 = M + m, S0 = h->S, G0 = h->G;
+  std::vector<int32_t> aQueue(m), aPc(m), aCls(m), aShape(m), aGang(m, -1), aGangCard(m, 1), aGangUni(m, -1), aSrc(m, -1), aUniKey(m, -1);
+  std::vector<uint8_t> aAligned(m, 1);
+  std::map<std::pair<int32_t, int32_t>, int32_t> newGangs;
+  int nT = 0, maxQueue = -1;
+  bool anyAway = d.cfg.hasAway != 0;
+  for (int i = 0; i < m; i++) {
+    const int q = rows->queue ? rows->queue[i] : 0, pc = rows->pc ? rows->pc[i] : 0, cls = rows->req_class ? rows->req_class[i] : 0;
+    if (cls < 0 || cls >= h->C) return fail(h, ASCHED_ERR_INVALID, "jobs_append: req_class out of range (the requirement classes are those of the last jobs_set)");
+    if (pc < 0 || pc >= h->npc) return fail(h, ASCHED_ERR_INVALID, "jobs_append: pc out of range");
+    if (q < -1) return fail(h, ASCHED_ERR_INVALID, "jobs_append: a queue below -1");
+    if ((rows->node && rows->node[i] != -1) || (rows->scheduled_at_priority && rows->scheduled_at_priority[i] != 0) || (rows->run_timestamp && rows->run_timestamp[i] != 0))
+      return fail(h, ASCHED_ERR_INVALID, "jobs_append: a row has a run (append the queued job, then jobs_patch gives it its run)");
+    if (rows->away && rows->away[i]) return fail(h, ASCHED_ERR_INVALID, "jobs_append: a row is flagged away (a cross-pool away job is a running job: jobs_set)");
+    aQueue[i] = q; aPc[i] = pc; aCls[i] = cls;
+    if (q >= 0) nT++;
+    maxQueue = std::max(maxQueue, q);
+    if (!h->pcAway[pc].empty()) anyAway = true;
+    const int32_t gid = rows->gang_id ? rows->gang_id[i] : -1;
+    if (rows->gang_cardinality) aGangCard[i] = rows->gang_cardinality[i];
+    const int32_t uni = rows->gang_uniformity_label ? rows->gang_uniformity_label[i] : -1;
+    if (gid >= 0) {
+      auto key = std::make_pair((int32_t)q, gid);
+      if (h->gangMap.count(key)) return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_append: a row joins a gang that already has rows in the table (a gang is submitted in one piece; jobs_set instead)");
+      auto it = newGangs.find(key);
+      if (it == newGangs.end()) it = newGangs.emplace(key, G0 + (int32_t)newGangs.size()).first;
+      aGang[i] = it->second;
+      if (uni >= 0) {
+        aUniKey[i] = uni;
+        auto ls = std::find(h->labelSlots.begin(), h->labelSlots.end(), uni);
+        aGangUni[i] = h->indexedLabels.count(uni) && ls != h->labelSlots.end() ? (int32_t)(ls - h->labelSlots.begin()) : -2;
+      }
+    }
+    for (int c = 0; c < h->K; c++) if (rows->req[(size_t)i * R + h->indexedCol[c]] % h->indexedRes[c]) aAligned[i] = 0;
+  }
+  const int G1 = G0 + (int)newGangs.size();
+  // the shape of every row: a hash over the shapes the handle holds; new shapes get the next ids in order of first occurrence (undone by `undo` on a later refusal)
+  if (m > 0 && h->shapeTable.empty()) jaShapeTableBuild(h, (size_t)S0);
+  for (int i = 0; i < m; i++) {
+    const int64_t* req = rows->req + (size_t)i * R;
+    const uint64_t hv = jaShapeHash(aCls[i], aPc[i], req, R);
+    size_t cap = h->shapeTable.size(), pos = hv & (cap - 1);
+    auto same = [&](int32_t s) {
+      if (h->shapeHash[s] != hv || h->shapeClass[s] != aCls[i] || h->shapePc[s] != aPc[i]) return false;
+      for (int r = 0; r < R; r++) if (h->shapeReq[(size_t)s * R + r] != req[r]) return false;
+      return true;
+    };
+    while (h->shapeTable[pos] >= 0 && !same(h->shapeTable[pos])) pos = (pos + 1) & (cap - 1);
+    if (h->shapeTable[pos] < 0) {
+      const int32_t s = (int32_t)h->shapeClass.size();
+      h->shapeTable[pos] = s; h->shapeHash.push_back(hv);
+      h->shapeClass.push_back(aCls[i]); h->shapePc.push_back(aPc[i]); h->shapeRow.push_back(M + i); h->shapeUnaligned.push_back(0);
+      for (int r = 0; r < R; r++) h->shapeReq.push_back(req[r]);
+      aShape[i] = s;
+      if ((size_t)(s + 1) * 2 > cap) jaShapeTableBuild(h, (size_t)(s + 1) * 2);
+    } else aShape[i] = h->shapeTable[pos];
+    if (!aAligned[i]) h->shapeUnaligned[aShape[i]] = 1;   // (a property of the shape: a resident shape's flag is already what this row says)
+    if (aShape[i] < S0) aSrc[i] = h->shapeRow[aShape[i]];
+  }
+  const int S1 = (int)h->shapeClass.size();
+  const bool newShapes = S1 > S0;
+  const DevCfg cfgSaved = d.cfg; const bool keyWideSaved = h->keyWide, keyCoarseSaved = h->keyCoarse;
+  bool mirrorsGrown = false;
+  auto undo = [&]() {   // a refusal after the shape lookup: the handle exactly as it was
+    if (!newShapes) return;
+    h->shapeClass.resize(S0); h->shapePc.resize(S0); h->shapeReq.resize((size_t)S0 * R); h->shapeRow.resize(S0); h->shapeUnaligned.resize(S0);
+    h->shapeTable.clear(); h->shapeHash.clear();
+    if (mirrorsGrown) {
+      h->jReq.resize((size_t)M * R); h->M = M; h->S = S0;
+      d.cfg = cfgSaved; h->keyWide = keyWideSaved; h->keyCoarse = keyCoarseSaved;
+      deriveAwayRows(h, cfgSaved.hasAway != 0);
+    }
+  };
+  if (newShapes) {
+    // what the rebuild can refuse, checked on the host first: the key layout of the grown table (layoutKeys) and LIT_TMAX for a new row on the literal iteration path
+    h->jReq.insert(h->jReq.end(), rows->req, rows->req + (size_t)m * R); h->M = M1; h->S = S1; mirrorsGrown = true;
+    deriveAwayRows(h, anyAway);
+    if (h->nodesSet) {
+      if (int lrc = layoutKeys(h)) { std::string why = h->err; undo(); return fail(h, lrc, "jobs_append: " + why); }
+      for (int s = S0; s < S1; s++) {
+        std::vector<int32_t> classes{h->shapeClass[s]};
+        for (int k = h->awayRowOff[s]; k < h->awayRowOff[s + 1]; k++) classes.push_back(h->awayRowClass[k]);
+        for (int32_t c : classes) {
+          size_t nTypes = 0;
+          for (size_t t = 0; t < h->types.size(); t++) if (h->types[t].numNodes > 0 && classMatchesType(h, c, h->types[t])) nTypes++;
+          const bool literal = h->shapeUnaligned[s] || (nTypes > 1 && !(h->allocAligned && h->idRankMonotone));
+          if (literal && nTypes > LIT_TMAX) { undo(); return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_append: a requirement class on the literal iteration path matches more than LIT_TMAX node types"); }
+        }
+      }
+    }
+  }
+  // ---- sizes, and every new device block before anything changes: running out of device memory here is a refusal too
+  const int total = h->ordOffHost.empty() ? 0 : h->ordOffHost[std::min<size_t>((size_t)h->ordQueues, h->ordOffHost.size() - 1)];
+  const int total1 = total + nT;
+  const int Qj1 = std::max(h->ordQueues, maxQueue + 1);
+  int nb2 = m;
+  if (nT > 0) { nb2 = JP_TILE; while (nb2 < m) nb2 <<= 1; }
+  const bool grow = (size_t)M1 > h->jobCap;
+  const size_t cap1 = grow ? std::max<size_t>((size_t)M1, h->jobCap + (h->jobCap + 3) / 4) : h->jobCap;   // max(M + m, 1.25 x capacity)
+  // the new gangs' CSR tail
+  std::vector<int32_t> gangOff1, gangTail;
+  if (m > 0) {
+    if (h->gangOffHost.size() != (size_t)G0 + 2) { undo(); return fail(h, ASCHED_ERR_INVALID, "jobs_append: no job table on this handle (jobs_set first)"); }
+    gangOff1.assign(h->gangOffHost.begin(), h->gangOffHost.begin() + G0 + 1);
+    gangOff1.resize((size_t)G1 + 2, 0);
+    std::vector<int32_t> cnt(G1 - G0, 0);
+    for (int i = 0; i < m; i++) if (aGang[i] >= 0) cnt[aGang[i] - G0]++;
+    for (int g = G0; g < G1; g++) gangOff1[g + 1] = gangOff1[g] + cnt[g - G0];
+    gangTail.assign((size_t)(gangOff1[G1] - gangOff1[G0]), 0);
+    { std::vector<int32_t> fill2(gangOff1.begin() + G0, gangOff1.begin() + G1);
+      for (int i = 0; i < m; i++) if (aGang[i] >= 0) gangTail[(size_t)(fill2[aGang[i] - G0]++ - gangOff1[G0])] = M + i; }
+    gangOff1[G1 + 1] = gangOff1[G1] + std::max(M1, 1);   // scratch gang slot for schedule_many
+  }
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t o64 = up(sizeof(int32_t) * 8 * (size_t)m), oReq = o64 + up(sizeof(int64_t) * (size_t)m), oAl = oReq + up(sizeof(int64_t) * (size_t)m * R), oKeys = oAl + up((size_t)m),
+               need = oKeys + (nT > 0 ? up(sizeof(JpKey) * (size_t)nb2) : 0);
+  char* scratchNew = nullptr;
+  if (m > 0 && h->jpScratchBytes < need) {
+    scratchNew = (char*)plat_malloc(need + need / 4);
+    if (!scratchNew) { (void)plat_take_failure(); undo(); return fail(h, ASCHED_ERR_DEVICE, "jobs_append: out of device memory for the append scratch; the handle is as it was"); }
+  }
+  std::vector<JaBlock> blocks;
+  auto stage = [&](DevBufs* owner, void* slot, size_t bytes, size_t copyBytes, const void* host, int fill, bool keepOld = false) {
+    blocks.push_back({owner, (void**)slot, std::max<size_t>(bytes, 1), copyBytes, host, fill, keepOld, nullptr});
+  };
+  const bool buildJp = m > 0 && !h->jp.built;
+  const size_t gangOffCap1 = (size_t)G1 + 2 > h->gangOffCap ? std::max<size_t>((size_t)G1 + 2, h->gangOffCap + h->gangOffCap / 4) : h->gangOffCap;
+  const size_t ordOffCap1 = std::max(h->ordOffCap, (size_t)std::max(Qj1, 1) + 4096 + 2);   // (the queue count outgrew the 4 096 padding)
+  const bool growRec = grow && d.f.structOk && d.jrec && !newShapes;   // (a new shape: rebuildMasks -> buildFast allocates the fast structure at the new capacity)
+  int32_t* ordTarget = nullptr; int32_t* ordNext = nullptr;
+  if (m > 0) {
+    if (grow) {
+      const size_t c = cap1, o = (size_t)M;
+      stage(&h->jobBufs, &d.jQueue, c * 4, o * 4, nullptr, -1); stage(&h->jobBufs, &d.jPc, c * 4, o * 4, nullptr, -1); stage(&h->jobBufs, &d.jShape, c * 4, o * 4, nullptr, -1);
+      stage(&h->jobBufs, &d.jGang, c * 4, o * 4, nullptr, -1); stage(&h->jobBufs, &d.jGangCard, c * 4, o * 4, nullptr, -1); stage(&h->jobBufs, &d.jGangUni, c * 4, o * 4, nullptr, -1);
+      stage(&h->jobBufs, &d.jNode0, c * 4, o * 4, nullptr, -1); stage(&h->jobBufs, &d.jRunPrio, c * 4, o * 4, nullptr, -1);
+      if (d.jAway) stage(&h->jobBufs, &d.jAway, c, o, nullptr, -1);
+      stage(&h->jobBufs, &d.jReq, c * 8 * R, o * 8 * R, nullptr, -1); stage(&h->jobBufs, &d.jAligned, c, o, nullptr, -1); stage(&h->jobBufs, &d.jLeaseMs, c * 8, o * 8, nullptr, -1);
+      if (growRec) {
+        stage(&h->fastBufs, &d.jrec, sizeof(JobRec) * c, sizeof(JobRec) * o, nullptr, -1);
+        stage(&h->fastBufs, &d.evIdxByPos, c * 4, 0, nullptr, 0); stage(&h->fastBufs, &d.evKey, sizeof(EvKey) * c, 0, nullptr, 0); stage(&h->fastBufs, &d.evCheap, 4104 + c + 8, 0, nullptr, 0);
+      }
+    }
+    if (buildJp) {   // first append or patch of this job table: the order-key inputs become resident
+      stage(&h->jobBufs, &h->jp.qprio, cap1 * 4, (size_t)M * 4, h->jQPrioHost.data(), -1); stage(&h->jobBufs, &h->jp.submit, cap1 * 8, (size_t)M * 8, h->jSubmitHost.data(), -1);
+      stage(&h->jobBufs, &h->jp.runTs, cap1 * 8, (size_t)M * 8, h->jRunTsHost.data(), -1); stage(&h->jobBufs, &h->jp.keep, cap1, 0, nullptr, 1);
+    } else if (grow) {
+      stage(&h->jobBufs, &h->jp.qprio, cap1 * 4, (size_t)M * 4, nullptr, -1); stage(&h->jobBufs, &h->jp.submit, cap1 * 8, (size_t)M * 8, nullptr, -1);
+      stage(&h->jobBufs, &h->jp.runTs, cap1 * 8, (size_t)M * 8, nullptr, -1); stage(&h->jobBufs, &h->jp.keep, cap1, 0, nullptr, 1);
+    }
+    // the two order buffers (they swap): the merge's target and the spare it leaves must both hold the grown order
+    if (h->ordSpareCap < (size_t)total1 || !h->jp.ordSpare) stage(&h->jobBufs, &ordTarget, cap1 * 4, 0, nullptr, -1, true);
+    if (h->ordCap < (size_t)total1) stage(&h->jobBufs, &ordNext, cap1 * 4, 0, nullptr, -1, true);
+    if ((size_t)gangOff1[G1] > h->gangJobsCap) stage(&h->jobBufs, &d.gangJobs, std::max<size_t>((size_t)gangOff1[G1], h->gangJobsCap + h->gangJobsCap / 4) * 4, (size_t)gangOff1[G0] * 4, nullptr, -1);
+    if (gangOffCap1 > h->gangOffCap) stage(&h->jobBufs, &d.gangOff, gangOffCap1 * 4, 0, nullptr, -1);
+    if (ordOffCap1 > h->ordOffCap) stage(&h->jobBufs, &d.ordAllOff, ordOffCap1 * 4, 0, nullptr, -1);
+  }
+  // the per-job and per-gang state of a round: allocated fresh (zeroed) where the capacity grows, as jobs_set allocates it
+  const size_t gangJobsCap1 = m > 0 && (size_t)gangOff1[G1] > h->gangJobsCap ? std::max<size_t>((size_t)gangOff1[G1], h->gangJobsCap + h->gangJobsCap / 4) : h->gangJobsCap;
+  const bool growGang = m > 0 && ((size_t)G1 > h->gangCap || (size_t)gangOff1[G1] + (size_t)std::max(M1, 1) > h->gangArrCap);
+  const size_t gangCap1 = growGang ? std::max<size_t>((size_t)G1, h->gangCap + (h->gangCap + 3) / 4) : h->gangCap;
+  const size_t gangArrCap1 = growGang ? std::max<size_t>(gangJobsCap1 + std::max<size_t>(cap1, 1), (size_t)gangOff1[G1] + (size_t)std::max(M1, 1)) : h->gangArrCap;
+  if (growGang) {
+    stage(&h->jobBufs, &d.gangSeen, (gangCap1 + 1) * 4, 0, nullptr, 0); stage(&h->jobBufs, &d.gangArr, gangArrCap1 * 4, 0, nullptr, 0);
+    stage(&h->jobBufs, &d.gangTotal, (gangCap1 + 1) * (size_t)R * 8, 0, nullptr, 0); stage(&h->jobBufs, &d.gangAllEvicted, gangCap1 + 1, 0, nullptr, 0);
+  }
+  if (newShapes) { stage(&h->jobBufs, &d.unfeasible, (size_t)S1, 0, nullptr, 0); stage(&h->jobBufs, &d.unfeasibleReason, (size_t)S1 * 4, 0, nullptr, 0); }
+  if (grow) {
+    const size_t c = cap1;
+    void* s32[] = {&d.schedAtPrio, &d.jobNode, &d.jobCutoff, &d.optGhost, &d.jcAssigned, &d.jcReason, &d.pcNode, &d.pcSap, &d.pcPap, &d.pcMethod, &d.jcGangCard, &d.jcUniValue, &d.jcStagedBy, &d.jcPreSib,
+                   &d.preemptedNode, &d.evList, &d.evTabJob, &d.evIndexOfJob, &d.fairEnt, &d.fairEntJob, &d.preList, &d.resJob, &d.resNode, &d.resPrio, &d.resMethod, &d.resPreJob, &d.resPreNode};
+    void* s8[] = {&d.jobEvictedOnNode, &d.jobFlags, &d.optSched, &d.optPre, &d.jcEvicted, &d.jcHasPctx, &d.jcPreempted, &d.inPreempted, &d.inScheduled, &d.inSchedAndEvicted, &d.evTabAlive, &d.evFlag};
+    for (void* sl : s32) stage(&h->jobBufs, sl, c * 4, 0, nullptr, 0);
+    for (void* sl : s8) stage(&h->jobBufs, sl, c, 0, nullptr, 0);
+    stage(&h->jobBufs, &d.evSortKey, (c + 1) * 4, 0, nullptr, 0);
+  }
+  for (auto& b : blocks) {
+    b.fresh = plat_malloc(b.bytes);
+    if (!b.fresh) {
+      (void)plat_take_failure();
+      for (auto& x : blocks) if (x.fresh) plat_free(x.fresh);
+      if (scratchNew) plat_free(scratchNew);
+      undo();
+      return fail(h, ASCHED_ERR_DEVICE, "jobs_append: out of device memory for the grown job table; the handle is as it was");
+    }
+  }
+  // ---- what jobs_set resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the job table half appended: asched_jobs_set before anything else)
+  h->haveRoundResult = false; h->stateEpoch++;
+  if (newShapes) fastInvalidate(h);
+  else { h->dev.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
+    int32_t zero = 0;
+    plat_h2d(&h->dev.rs->fastActive, &zero, sizeof zero);
+    plat_h2d(&h->dev.rs->l0SaveCount, &zero, sizeof zero); }
+  h->prepared = false; h->evrSized = false;
+  for (int k = 0; k < 3; k++) h->jaMs[k] = 0;
+  if (scratchNew) { h->jpBufs.freeAll(); h->jpScratch = scratchNew; h->jpScratchBytes = need + need / 4; h->jpBufs.ptrs.push_back({scratchNew, need + need / 4}); }
+  if (m > 0) {
+    // the blocks: copies and fills queued on the handle's stream, the old blocks released once they are through
+    std::vector<std::pair<DevBufs*, void*>> old;
+    for (auto& b : blocks) {
+      if (b.fill >= 0) plat_memset(b.fresh, b.fill, b.bytes);
+      if (b.host) { if (b.copyBytes) plat_h2d(b.fresh, b.host, b.copyBytes); }
+      else if (b.copyBytes && *b.slot) plat_d2d(b.fresh, *b.slot, b.copyBytes);
+      if (!b.keepOld && *b.slot) old.push_back({b.owner, *b.slot});
+      *b.slot = b.fresh;
+      b.owner->ptrs.push_back({b.fresh, b.bytes});
+    }
+    auto release = [&](DevBufs* owner, void* p) {
+      for (size_t k = 0; k < owner->ptrs.size(); k++) if (owner->ptrs[k].first == p) { owner->ptrs.erase(owner->ptrs.begin() + k); break; }
+      plat_free(p);
+    };
+    plat_sync();
+    for (auto& o : old) release(o.first, o.second);
+    h->jp.built = true;
+    h->jobCap = cap1; h->gangCap = gangCap1; h->gangArrCap = gangArrCap1; h->gangJobsCap = gangJobsCap1;
+    h->gangOffCap = gangOffCap1; h->ordOffCap = ordOffCap1;
+    // the host mirrors
+    h->jQueue.insert(h->jQueue.end(), aQueue.begin(), aQueue.end()); h->jPc.insert(h->jPc.end(), aPc.begin(), aPc.end()); h->jReqClass.insert(h->jReqClass.end(), aCls.begin(), aCls.end());
+    h->jShape.insert(h->jShape.end(), aShape.begin(), aShape.end()); h->jNode.resize(M1, -1); h->jRunPrio.resize(M1, 0); h->jGangDense.insert(h->jGangDense.end(), aGang.begin(), aGang.end());
+    h->jAway.resize(M1, 0); h->jGangUniKey.insert(h->jGangUniKey.end(), aUniKey.begin(), aUniKey.end());
+    if (!mirrorsGrown) h->jReq.insert(h->jReq.end(), rows->req, rows->req + (size_t)m * R);
+    std::vector<uint32_t> aQPrio(m, 0); std::vector<int64_t> aSubmit(m, 0);
+    if (rows->queue_priority) aQPrio.assign(rows->queue_priority, rows->queue_priority + m);
+    if (rows->submit_time) aSubmit.assign(rows->submit_time, rows->submit_time + m);
+    h->jQPrioHost.insert(h->jQPrioHost.end(), aQPrio.begin(), aQPrio.end()); h->jSubmitHost.insert(h->jSubmitHost.end(), aSubmit.begin(), aSubmit.end()); h->jRunTsHost.resize(M1, 0);
+    for (auto& g : newGangs) h->gangMap.insert(g);
+    h->gangOffHost = gangOff1;
+    h->M = M1; h->G = G1; h->S = S1; d.cfg.M = M1; d.cfg.G = G1; d.cfg.S = S1; d.cfg.hasAway = anyAway ? 1 : 0;
+    // the per-row inputs: the only upload proportional to anything
+    int32_t* e32 = (int32_t*)h->jpScratch; const size_t mm = (size_t)m;
+    const std::vector<int32_t>* cols[7] = {&aQueue, &aPc, &aShape, &aGang, &aGangCard, &aGangUni, &aSrc};
+    for (int k = 0; k < 7; k++) plat_h2d(e32 + k * mm, cols[k]->data(), mm * 4);
+    plat_h2d(e32 + 7 * mm, aQPrio.data(), mm * 4);
+    plat_h2d(h->jpScratch + o64, aSubmit.data(), mm * 8); plat_h2d(h->jpScratch + oReq, rows->req, mm * 8 * R); plat_h2d(h->jpScratch + oAl, aAligned.data(), mm);
+    JaArgs a; memset(&a, 0, sizeof a);
+    a.M = M; a.m = m; a.nb2 = nb2; a.R = R; a.writeRec = (!newShapes && d.f.structOk && d.jrec) ? 1 : 0;
+    a.aQueue = e32; a.aPc = e32 + mm; a.aShape = e32 + 2 * mm; a.aGang = e32 + 3 * mm; a.aGangCard = e32 + 4 * mm; a.aGangUni = e32 + 5 * mm; a.aSrc = e32 + 6 * mm;
+    a.aQPrio = (const uint32_t*)(e32 + 7 * mm); a.aSubmit = (const int64_t*)(h->jpScratch + o64); a.aReq = (const int64_t*)(h->jpScratch + oReq); a.aAligned = (const uint8_t*)(h->jpScratch + oAl);
+    a.jQPrio = h->jp.qprio; a.jSubmit = h->jp.submit;
+    a.p.M = M1; a.p.n = 0; a.p.nb2 = nb2; a.p.nT = nT; a.p.nKept = total; a.p.total = total1;
+    a.p.keep = h->jp.keep; a.p.jQPrio = h->jp.qprio; a.p.jSubmit = h->jp.submit; a.p.jRunTs = h->jp.runTs;
+    int32_t* target = ordTarget ? ordTarget : h->jp.ordSpare;
+    if (nT > 0) { a.p.keys = (JpKey*)(h->jpScratch + oKeys); a.p.kept = d.ordAll; a.p.out = target; }
+    int prc = plat_take_failure() ? -1 : plat_jobs_append(d, a);
+    if (prc) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+    plat_jobs_append_ms(h->jaMs);
+    // the order buffers: the target becomes the order; the spare is the old order where that is long enough, else the second new block
+    { int32_t* oldAll = d.ordAll; int32_t* oldSpare = h->jp.ordSpare;
+      const size_t oldAllCap = h->ordCap, oldSpareCap = h->ordSpareCap;
+      if (nT > 0) {
+        d.ordAll = target; h->ordCap = ordTarget ? cap1 : oldSpareCap;
+        if (ordTarget && oldSpare) release(&h->jobBufs, oldSpare);
+        if (ordNext) { h->jp.ordSpare = ordNext; h->ordSpareCap = cap1; release(&h->jobBufs, oldAll); }
+        else { h->jp.ordSpare = oldAll; h->ordSpareCap = oldAllCap; }
+      } else {   // the order stays; the spare is whatever is long enough
+        if (ordTarget) { if (oldSpare) release(&h->jobBufs, oldSpare); h->jp.ordSpare = ordTarget; h->ordSpareCap = cap1; }
+        if (ordNext) { release(&h->jobBufs, ordNext); }
+      } }
+    if (gangTail.size()) plat_h2d(d.gangJobs + gangOff1[G0], gangTail.data(), gangTail.size() * 4);
+    plat_h2d(d.gangOff, gangOff1.data(), gangOff1.size() * 4);
+    { std::vector<int32_t> off((size_t)std::max(Qj1, 1) + 4096 + 2, total1), add((size_t)Qj1 + 2, 0);
+      for (int i = 0; i < m; i++) if (aQueue[i] >= 0) add[(size_t)aQueue[i] + 1]++;
+      for (int q = 0; q <= Qj1; q++) {
+        if (q > 0) add[q] += add[q - 1];   // new rows of the queues below q
+        off[q] = ((size_t)q < h->ordOffHost.size() && q <= h->ordQueues ? h->ordOffHost[q] : total) + add[q];
+      }
+      plat_h2d(d.ordAllOff, off.data(), off.size() * 4);
+      h->ordOffHost.swap(off); h->ordQueues = Qj1; }
+    if (const char* e = getenv("ASCHED_JA_TIMES")) if (e[0] == '1')
+      fprintf(stderr, "[asched jobs_append] jobs %d rows %d in the order %d: fill %.4f ms, sort %.4f ms, merge %.4f ms\n", M, m, nT, h->jaMs[0], h->jaMs[1], h->jaMs[2]);
+  }
+  h->jaStats[0] = m; h->jaStats[1] = nT; h->jaStats[2] = S1 - S0; h->jaStats[3] = G1 - G0; h->jaStats[4] = (m > 0 && grow) ? 1 : 0; h->jaStats[5] = newShapes ? 1 : 0;
+  h->jaStats[6] = (int32_t)h->jobCap; h->jaStats[7] = 0;
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  d.cfg.Q = 0;
+  if (newShapes) {   // the shape-dependent tables, by the code jobs_set ends with (the key layout was decided above)
+    int rc = rebuildMasks(h);
+    if (rc) return rc;
+    rc = runControl(h, CMD_UPSERT_RESET);
+    if (rc) return rc;
+    rc = runControl(h, CMD_RESET_JOBS);
+    h->allocPristine = h->nodesSet;
+    h->evictedDirty = false;
+    return rc;
+  }
+  if (m > 0 && grow && h->nodesSet) exclSetup(h);   // (the failed-selection records' per-job slots: sized by the capacity)
+  // job dynamic state: everything unbound until round_prepare, as asched_jobs_patch leaves it
+  h->stateEpoch++;
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  if (plat_bulk(d, B_INIT_ALLOC, h->N) || plat_bulk(d, B_KEYS_ALL, h->N) || plat_bulk(d, B_RESET_JOBS, M1)) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  plat_d2h(&h->rsHost, d.rs, sizeof(RoundScalars));
+  if (h->rsHost.error) {
+    int e = h->rsHost.error;
+    char buf[128]; snprintf(buf, sizeof buf, "device raised error %d (detail %d)", e, h->rsHost.errorDetail);
+    int32_t zero[2] = {0, 0};
+    plat_h2d(&d.rs->error, zero, sizeof zero);
+    return fail(h, e, buf);
+  }
+  h->rsHost.fastActive = 0; h->rsHost.evictedTableSize = 0; h->rsHost.fairIndexValid = 0; h->rsHost.ftValid = 0; h->rsHost.txnActive = 0; h->rsHost.undoCount = 0;
+  plat_h2d(d.rs, &h->rsHost, sizeof(RoundScalars));
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  h->allocPristine = h->nodesSet;
+  h->evictedDirty = false;
+  return 0;
+}
+int32_t asched_jobs_append_stats(asched_t* h, int32_t* out) {
+  if (!h || !out) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  for (int k = 0; k < 8; k++) out[k] = h->jaStats[k];
   return 0;
 }
 

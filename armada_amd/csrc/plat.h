@@ -28,6 +28,7 @@ static void* plat_malloc(size_t n);
 static void plat_free(void* p);
 static void plat_memset(void* p, int v, size_t n);
 static void plat_h2d(void* d, const void* s, size_t n);
+static void plat_d2d(void* d, const void* s, size_t n);   // device to device, ordered with the context's other work (asched_jobs_append moves the static per-job arrays into larger blocks)
 static void plat_d2h(void* d, const void* s, size_t n);
 static void plat_d2h_async(void* d, const void* s, size_t n);
 static void plat_sync();
@@ -89,6 +90,11 @@ static void plat_evict_report_ms(double* out /*[3]*/);   // measurement hook: de
 struct JpArgs;
 static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf);
 static void plat_jobs_patch_ms(double* out /*[4]*/);   // measurement hook: device ms of scatter / remove / sort / merge of the last call (events around them when ASCHED_JP_TIMES=1, else zeros)
+// newly submitted jobs behind the resident job table (kernels_jobs_append.h): row fill + keys, the patch's sort, the patch's merge by rank of the old order (a.p.kept) and the
+// sorted new keys into a.p.out.  Synchronous: rows and order are complete on return.  The CPU build's definition sits in kernels_jobs_append.h.
+struct JaArgs;
+static int plat_jobs_append(Dev& d, JaArgs& a);
+static void plat_jobs_append_ms(double* out /*[3]*/);   // measurement hook: device ms of row fill / sort / merge of the last call (events around them when ASCHED_JA_TIMES=1, else zeros)
 static int plat_run_fit_capacity(Dev& d, const std::vector<int32_t>& shapes, std::vector<int32_t>& firstNode, std::vector<long long>& capacity, const int32_t* nodeByRankHost);
 static int plat_run_submit_gangs(Dev& d, const std::vector<int32_t>& off, const std::vector<int32_t>& jobs, std::vector<int32_t>& out);
 static double plat_last_fit_ms();

@@ -32,6 +32,7 @@ struct PlatCtx {
   std::chrono::steady_clock::time_point roundT0;
   hipEvent_t rEv0 = nullptr, rEv1 = nullptr;
   hipEvent_t evrEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool evrTimed[3] = {false, false, false};   // ASCHED_EVR_TIMES=1: around the passes of the evictor report
+  hipEvent_t jaEv[4] = {nullptr, nullptr, nullptr, nullptr}; bool jaTimed = false;   // ASCHED_JA_TIMES=1: around the passes of the job-table append
   hipEvent_t jpEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool jpTimed = false;   // ASCHED_JP_TIMES=1: around the passes of the job-table patch
   float roundTotalMs = 0.f, roundControlMs = 0.f; int roundLaunches = 0;
   int32_t* cmpScratch = nullptr; size_t cmpScratchInts = 0;   // block counts + total of the grid-wide compaction
@@ -250,6 +251,7 @@ static void plat_close(PlatCtx* c) {
   for (hipEvent_t e : {c->ev0, c->ev1, c->fitEv0, c->fitEv1, c->litEvMid, c->rEv0, c->rEv1}) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->evrEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->jpEv) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->jaEv) if (e) (void)hipEventDestroy(e);
   if (c->helpBox) (void)hipFree(c->helpBox);
   if (c->cmpScratch) (void)hipFree(c->cmpScratch);
   if (c->optScratch) (void)hipFree(c->optScratch);
@@ -271,6 +273,10 @@ static void plat_memset(void* p, int v, size_t n) { if (!p) { hipOk(hipErrorInva
 static void plat_h2d(void* d, const void* s, size_t n) {
   if (!d) { hipOk(hipErrorInvalidValue, "upload into a failed allocation"); return; }
   if (hipOk(hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, t_ctx->stream), "hipMemcpyAsync (h2d)")) hipOk(hipStreamSynchronize(t_ctx->stream), "h2d sync");
+}
+static void plat_d2d(void* d, const void* s, size_t n) {
+  if (!d || !s) { hipOk(hipErrorInvalidValue, "device copy of a failed allocation"); return; }
+  if (n) hipOk(hipMemcpyAsync(d, s, n, hipMemcpyDeviceToDevice, t_ctx->stream), "hipMemcpyAsync (d2d)");
 }
 // pinned host memory + asynchronous downloads on the handle's stream (the round's result arrays: one wait for all of them)
 static void* plat_pinned(size_t n) { void* p = nullptr; if (!hipOk(hipHostMalloc(&p, n, hipHostMallocDefault), "hipHostMalloc")) return nullptr; return p; }
@@ -902,6 +908,38 @@ static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf) {
 static void plat_jobs_patch_ms(double* out) {
   hipEvent_t* ev = jpEvents();
   for (int k = 0; k < 4; k++) { float ms = 0.f; if (ev && t_ctx->jpTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
+}
+// newly submitted jobs behind the resident job table (kernels_jobs_append.h; k_ja_fill in armada_sched_mgpu.hip, the sort and the merge are the patch's kernels).
+// ASCHED_JA_TIMES=1 puts events around the three passes (tools/probe_jobs_append.py).
+#include "kernels_jobs_append.h"
+extern "C" int asched_internal_ja_fill(const Dev* d, const JaArgs* a, hipStream_t s);
+static hipEvent_t* jaEvents() {
+  static const bool on = [] { const char* e = getenv("ASCHED_JA_TIMES"); return e && e[0] == '1'; }();
+  PlatCtx* c = t_ctx;
+  if (!on) return nullptr;
+  if (!c->jaEv[3]) for (int i = 0; i < 4; i++) if (!c->jaEv[i] && hipEventCreate(&c->jaEv[i]) != hipSuccess) { c->jaEv[i] = nullptr; return nullptr; }
+  return c->jaEv;
+}
+static int plat_jobs_append(Dev& d, JaArgs& a) {
+  PlatCtx* c = t_ctx;
+  hipStream_t st = c->stream;
+  hipEvent_t* ev = jaEvents();
+  c->jaTimed = false;
+  if (ev) (void)hipEventRecord(ev[0], st);
+  bool ok = asched_internal_ja_fill(&d, &a, st) == 0;
+  if (ev) (void)hipEventRecord(ev[1], st);
+  if (ok && a.p.nT > 0) ok = asched_internal_jp_sort(&a.p, st) == 0;
+  if (ev) (void)hipEventRecord(ev[2], st);
+  if (ok && a.p.nT > 0) ok = asched_internal_jp_merge(&d, &a.p, st) == 0;
+  if (ev) (void)hipEventRecord(ev[3], st);
+  ok = ok && hipOk(hipGetLastError(), "k_ja launch") && hipOk(hipStreamSynchronize(st), "k_ja");
+  if (!ok) { if (c->err.empty()) c->err = "k_ja launch failed"; return -1; }
+  c->jaTimed = ev != nullptr;
+  return 0;
+}
+static void plat_jobs_append_ms(double* out) {
+  hipEvent_t* ev = jaEvents();
+  for (int k = 0; k < 3; k++) { float ms = 0.f; if (ev && t_ctx->jaTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
 }
 // a caller-side buffer may be memory of this handle's GPU (a tensor the collective reduces in place: used directly) or host memory (staged)
 static bool plat_is_device_ptr(const void* p) {

@@ -272,3 +272,87 @@ def run_cycles_patched(lib, sim: SimulatorInput, max_cycles: int = 1000):
         t += sim.cycle_period_s
     s.close()
     return out
+
+
+def arrival_cycles(sim: SimulatorInput, per_cycle: Optional[int] = None) -> np.ndarray:
+    """the cycle in which each row enters the job table, non-decreasing in the row: `per_cycle` rows a cycle in row order, or (None) the first cycle at or after the
+    row's submit time — syncState sees a submission in the cycle after it happened (scheduler.go:478-535)"""
+    wl = sim.workload
+    m = wl.num_jobs
+    if per_cycle is not None:
+        return (np.arange(m) // max(1, int(per_cycle))).astype(np.int64)
+    c = np.ceil(np.asarray(wl.job_submit, dtype=np.float64) / 1e9 / sim.cycle_period_s).astype(np.int64)
+    return np.maximum.accumulate(np.maximum(c, 0))   # (row = arrival order: a row never arrives before the one in front of it)
+
+
+def _run_cycles_arriving(lib, sim: SimulatorInput, per_cycle, max_cycles, appended):
+    from .binding import Scheduler
+    wl = sim.workload
+    m = wl.num_jobs
+    arrive = arrival_cycles(sim, per_cycle)
+    node = np.full(m, -1, np.int32)
+    run_prio = np.zeros(m, np.int32)
+    started = np.full(m, -1.0)
+    done = np.zeros(m, bool)
+    changed = np.zeros(m, bool)
+    out = []
+    s = Scheduler(lib, wl.config)
+    s.nodes_upsert(wl.node_total, id_rank=wl.node_id_rank)
+    have = 0                                          # rows in the handle's table: the jobs that have arrived, in arrival order, finished ones included
+    t = 0.0
+    for cycle in range(max_cycles):
+        finished = (node >= 0) & (started >= 0) & (started + sim.job_runtime_s <= t)
+        done |= finished
+        node[finished] = -1
+        changed |= finished
+        if done.all():
+            break
+        upto = int(np.searchsorted(arrive, cycle, side="right"))
+        if appended:
+            if cycle == 0:                            # the first cycle: jobs_set
+                s.jobs_set(wl.job_req[:upto], queue=wl.job_queue[:upto], pc=wl.job_pc[:upto], submit_time=wl.job_submit[:upto], node=node[:upto],
+                           scheduled_at_priority=run_prio[:upto], run_timestamp=np.zeros(upto, np.int64))
+            elif upto > have:                         # the submissions since the last cycle
+                s.jobs_append(wl.job_req[have:upto], queue=wl.job_queue[have:upto], pc=wl.job_pc[have:upto], submit_time=wl.job_submit[have:upto])
+            rows = np.nonzero(changed)[0].astype(np.int32)
+            if len(rows):                             # then the run state of the rows that changed
+                running = node[rows] >= 0
+                s.jobs_patch(rows, node[rows], np.where(running, run_prio[rows], 0), np.where(running, np.maximum(started[rows], 0) * 1e9, 0).astype(np.int64))
+        else:
+            running = node[:upto] >= 0
+            s.jobs_set(wl.job_req[:upto], queue=wl.job_queue[:upto], pc=wl.job_pc[:upto], submit_time=wl.job_submit[:upto], node=node[:upto],
+                       scheduled_at_priority=np.where(running, run_prio[:upto], 0), run_timestamp=np.where(running, np.maximum(started[:upto], 0) * 1e9, 0).astype(np.int64))
+        changed[:] = False
+        have = upto
+        queued = [np.array([j for j in q if j < have and not done[j] and node[j] < 0], dtype=np.int32) for q in wl.queued]
+        nq = wl.num_queues
+        s.round_prepare(wl.queue_weight, queued, global_tokens=float(wl.global_burst), global_burst=wl.global_burst, global_rate_inf=wl.rate_inf,
+                        queue_tokens=[float(wl.queue_burst)] * nq, queue_burst=[wl.queue_burst] * nq, queue_rate_inf=[wl.rate_inf] * nq)
+        r = s.schedule_round()
+        sched = {int(j): int(n) for j, n in r.scheduled.items()}
+        pre = {int(j): int(n) for j, n in r.preempted.items()}
+        for j, n in sched.items():
+            node[j], started[j], run_prio[j] = n, t, r.scheduled_priority[j]
+            changed[j] = True
+        for j in pre:
+            node[j], started[j] = -1, -1.0
+            changed[j] = True
+        out.append({"time_s": t, "scheduled": sched, "preempted": pre, "termination_reason": r.termination_reason, "rows": have})
+        if have == m and not sched and not pre and not (node >= 0).any():
+            break   # everything has arrived, nothing runs and nothing can be placed: the rest never will
+        t += sim.cycle_period_s
+    s.close()
+    return out
+
+
+def run_cycles_arriving(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000):
+    """run_cycles_patched with the workload's jobs ENTERING the table as they are submitted instead of all at once: the first cycle's arrivals by jobs_set, every later
+    cycle's by Scheduler.jobs_append (syncState's upsert of the new jobs), then the run-state patch, round_prepare and the round.  Row = arrival order (the workload's
+    rows are in submission order); arrival_cycles says which cycle a row arrives in.  Records as run_cycles, plus the table's row count."""
+    return _run_cycles_arriving(lib, sim, per_cycle, max_cycles, True)
+
+
+def run_cycles_arriving_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000):
+    """the rebuilt counterpart of run_cycles_arriving: jobs_set of the grown table (every row that has arrived, with its run state) in every cycle — what any library,
+    the oracle included, can run.  Same rows, same records."""
+    return _run_cycles_arriving(lib, sim, per_cycle, max_cycles, False)

@@ -385,8 +385,31 @@ int32_t ASCHED_FN(jobs_set)(asched_t*, const asched_jobs* jobs, const asched_req
    [-1, N); ASCHED_ERR_UNSUPPORTED: the job set carries the market order (uploaded with bid prices or after asched_set_market), an entry gives a cross-pool away row
    (asched_jobs.away) a node >= 0.  On a handle without a node table N is 0: only node -1 is accepted.  ASCHED_ERR_DEVICE (a failed launch or copy, as from any
    other entry point) is NOT such a refusal: the job table may be half patched, and the handle needs asched_jobs_set before anything else.
-   Rows cannot be appended or deleted and no other field changes: asched_jobs_set. */
+   No other field changes and rows cannot be deleted (a finished job stays as a row without a run: asched_jobs_set drops it when the caller chooses); newly submitted
+   rows are appended with asched_jobs_append. */
 int32_t ASCHED_FN(jobs_patch)(asched_t*, int32_t n, const int32_t* job, const int32_t* node, const int32_t* scheduled_at_priority, const int64_t* run_timestamp);
+/* syncState's upsert of the newly submitted jobs into the jobDb at the start of a cycle (scheduler.go:478-535; jobdb/jobdb.go:572-700, the insertion into the per-queue
+   sorted set at :691-700): rows->m rows are added behind the M rows the handle holds; the new job ids are M .. M+m-1.  Rows must stay in ascending job-id order, as for
+   jobs_set (newly submitted ULIDs sort after the resident ones; the caller sorts the batch).  The requirement classes are those of the last jobs_set.
+   After a successful call the handle is in the state asched_jobs_set would have left, given the concatenated table and the same requirement classes — for every entry
+   point (rounds, scheduling_order, the NodeDb-level calls, the submit check, the optimiser, a later jobs_patch that names old and new rows), including everything jobs_set
+   and jobs_patch reset; the caller goes on with round_prepare.  m == 0 performs the resets only.
+   Accepted rows: queued jobs only (node NULL or all -1; scheduled_at_priority / run_timestamp NULL or 0; away NULL or 0; bid_price NULL); any queue index >= -1, a
+   queue the table has no job of and an index above every earlier one included; any priority class; req_class below the table's number of classes; a gang member only
+   when its (queue, gang_id) is not in the table yet — a gang is submitted in one piece, and new gangs get the next dense ids in order of first occurrence; any request
+   vector.  Where every row's scheduling-key shape (req_class, pc, req) is already in the table the work is on the device and proportional to the batch and the job
+   order: no static masks, no job-record upload, the fast structure stays.  A row with a new shape gets the next shape id and the shape-dependent tables (key layout,
+   masks, fast structure) are rebuilt as jobs_set builds them.  The per-job device arrays have a capacity: an append that does not fit moves them to blocks of
+   max(M + m, 1.25 x capacity) rows; a handle that never appends allocates exactly M.
+   Refused before anything changes — ASCHED_ERR_INVALID: no job table, m < 0, req missing, req_class or pc out of range, a queue below -1, a row with a run, a row flagged
+   away; ASCHED_ERR_UNSUPPORTED: the job set carries the market order, bid_price is given, a row joins a gang that already has rows in the table, M + m exceeds 2^30,
+   whatever the rebuild for a new shape would refuse (a key beyond 128 bits, more than LIT_TMAX node types on the literal path); ASCHED_ERR_DEVICE with "the handle is as
+   it was" in last_error: out of device memory while sizing the new blocks.  Any other ASCHED_ERR_DEVICE (a failed launch or copy) is NOT such a refusal: the handle
+   then needs asched_jobs_set, as documented for jobs_patch. */
+int32_t ASCHED_FN(jobs_append)(asched_t*, const asched_jobs* rows);
+/* how the last jobs_append ran: out[0] rows of the call, [1] rows that entered the order (queue >= 0), [2] new shapes, [3] new gangs, [4] 1 = the per-job arrays were
+   re-allocated, [5] 1 = masks and fast structure were rebuilt, [6] capacity (rows) after the call, [7] 0 (reserved).  Zeros after jobs_set. */
+int32_t ASCHED_FN(jobs_append_stats)(asched_t*, int32_t* out /*[8]*/);
 
 int32_t ASCHED_FN(txn_begin)(asched_t*);    /* nodeDb.Txn(true) (nodedb.go:353) */
 int32_t ASCHED_FN(txn_commit)(asched_t*);

@@ -99,6 +99,7 @@ type GpuRound struct {
 	nodePos  map[string]int32
 	jobs     []*jobdb.Job
 	jobRow   map[string]int32 // job id -> row of the uploaded job table (PatchJobs)
+	gangIds  map[string]int32 // queue + "\x00" + gang id -> the gang id the library was given (UploadJobs; AppendJobs numbers new gangs behind these)
 	classes  map[string]int32 // requirement class key -> index
 	// poolConfig.GetDefaultJobTolerations() (scheduling_algo.go:773): part of every requirement class (UploadJobs)
 	defaultTolerations []v1.Toleration
@@ -467,6 +468,58 @@ type reqClass struct {
 	hasA bool
 }
 
+// classKey interns the static requirements of one job: the key of its requirement class and the class itself (UploadJobs, AppendJobs)
+func (g *GpuRound) classKey(j *jobdb.Job) (string, reqClass) {
+	var rc reqClass
+	key := ""
+	// the pool's default job tolerations (SchedulingOptions.DefaultTolerations, nodedb.go:383-393) are appended to every job's tolerations for
+	// every node selection (:561-562): folded into the class here, once (g.defaultTolerations = poolConfig.GetDefaultJobTolerations())
+	for _, t := range append(append([]v1.Toleration{}, j.Tolerations()...), g.defaultTolerations...) {
+		k := int32(-1)
+		if t.Key != "" {
+			k = g.strs.id(t.Key)
+		}
+		op := int32(C.ASCHED_TOLERATION_OP_EQUAL)
+		if t.Operator == v1.TolerationOpExists {
+			op = C.ASCHED_TOLERATION_OP_EXISTS
+		}
+		rc.tol = append(rc.tol, [4]int32{k, op, g.strs.id(t.Value), effectOf(t.Effect)})
+		key += "t" + t.Key + "\x00" + string(t.Operator) + "\x00" + t.Value + "\x00" + string(t.Effect) + "\x01"
+	}
+	sel := j.NodeSelector()
+	keys := make([]string, 0, len(sel))
+	for k := range sel {
+		keys = append(keys, k)
+	}
+	sort.Strings(keys)
+	for _, k := range keys {
+		rc.sel = append(rc.sel, [2]int32{g.strs.id(k), g.strs.id(sel[k])})
+		key += "s" + k + "\x00" + sel[k] + "\x01"
+	}
+	if a := j.Affinity(); a != nil && a.NodeAffinity != nil && a.NodeAffinity.RequiredDuringSchedulingIgnoredDuringExecution != nil {
+		rc.hasA = true
+		for _, term := range a.NodeAffinity.RequiredDuringSchedulingIgnoredDuringExecution.NodeSelectorTerms {
+			var exprs [][3]interface{}
+			key += "a("
+			for _, e := range term.MatchExpressions {
+				vals := make([]int32, len(e.Values))
+				for i, v := range e.Values {
+					vals[i] = g.strs.id(v)
+				}
+				exprs = append(exprs, [3]interface{}{g.strs.id(e.Key), string(e.Operator), vals})
+				key += e.Key + "\x00" + string(e.Operator) + "\x00"
+				for _, v := range e.Values {
+					key += v + "\x02"
+				}
+				key += "\x01"
+			}
+			key += ")"
+			rc.aff = append(rc.aff, exprs)
+		}
+	}
+	return key, rc
+}
+
 // UploadJobs registers the jobDb view of the round: every non-terminal job of the pool, queued or running (the accessors
 // calculateJobSchedulingInfo reads, scheduling_algo.go:591-698).  queueIndex maps queue names to dense indices (name order).
 func (g *GpuRound) UploadJobs(jobs []*jobdb.Job, queueIndex map[string]int32) error {
@@ -486,57 +539,9 @@ func (g *GpuRound) UploadJobs(jobs []*jobdb.Job, queueIndex map[string]int32) er
 	node, runPrio := make([]int32, m), make([]int32, m)
 	away, anyAway := make([]uint8, m), false
 	gangIds := map[string]int32{}
+	g.gangIds = gangIds
 	var classes []reqClass
-	classKey := func(j *jobdb.Job) (string, reqClass) {
-		var rc reqClass
-		key := ""
-		// the pool's default job tolerations (SchedulingOptions.DefaultTolerations, nodedb.go:383-393) are appended to every job's tolerations for
-		// every node selection (:561-562): folded into the class here, once (g.defaultTolerations = poolConfig.GetDefaultJobTolerations())
-		for _, t := range append(append([]v1.Toleration{}, j.Tolerations()...), g.defaultTolerations...) {
-			k := int32(-1)
-			if t.Key != "" {
-				k = g.strs.id(t.Key)
-			}
-			op := int32(C.ASCHED_TOLERATION_OP_EQUAL)
-			if t.Operator == v1.TolerationOpExists {
-				op = C.ASCHED_TOLERATION_OP_EXISTS
-			}
-			rc.tol = append(rc.tol, [4]int32{k, op, g.strs.id(t.Value), effectOf(t.Effect)})
-			key += "t" + t.Key + "\x00" + string(t.Operator) + "\x00" + t.Value + "\x00" + string(t.Effect) + "\x01"
-		}
-		sel := j.NodeSelector()
-		keys := make([]string, 0, len(sel))
-		for k := range sel {
-			keys = append(keys, k)
-		}
-		sort.Strings(keys)
-		for _, k := range keys {
-			rc.sel = append(rc.sel, [2]int32{g.strs.id(k), g.strs.id(sel[k])})
-			key += "s" + k + "\x00" + sel[k] + "\x01"
-		}
-		if a := j.Affinity(); a != nil && a.NodeAffinity != nil && a.NodeAffinity.RequiredDuringSchedulingIgnoredDuringExecution != nil {
-			rc.hasA = true
-			for _, term := range a.NodeAffinity.RequiredDuringSchedulingIgnoredDuringExecution.NodeSelectorTerms {
-				var exprs [][3]interface{}
-				key += "a("
-				for _, e := range term.MatchExpressions {
-					vals := make([]int32, len(e.Values))
-					for i, v := range e.Values {
-						vals[i] = g.strs.id(v)
-					}
-					exprs = append(exprs, [3]interface{}{g.strs.id(e.Key), string(e.Operator), vals})
-					key += e.Key + "\x00" + string(e.Operator) + "\x00"
-					for _, v := range e.Values {
-						key += v + "\x02"
-					}
-					key += "\x01"
-				}
-				key += ")"
-				rc.aff = append(rc.aff, exprs)
-			}
-		}
-		return key, rc
-	}
+	classKey := g.classKey
 	if _, ok := g.classes[""]; !ok { // class 0 must exist: no tolerations, no selector
 		g.classes[""] = 0
 	}
@@ -684,11 +689,105 @@ func (g *GpuRound) UploadJobs(jobs []*jobdb.Job, queueIndex map[string]int32) er
 	return g.check(C.asched_jobs_set(g.h, &in, &cls))
 }
 
+// ErrNeedsUpload is what AppendJobs answers for a batch the resident job table cannot take: the caller falls back to UploadJobs of the whole job set.
+var ErrNeedsUpload = fmt.Errorf("the job table has to be uploaded again")
+
+// AppendJobs adds the jobs submitted since the last cycle behind the uploaded job table (asched_jobs_append): what syncState's upsert of the new jobs does to the
+// jobDb (scheduler.go:478-535; jobdb/jobdb.go:572-700).  The shim's cycle is AppendJobs(new submissions), PatchJobs(run-state changes), Schedule.  jobs: queued jobs
+// only, none of them uploaded before; sorted here by id — newly submitted ULIDs sort after the resident ones, and the batch's rows follow the table's.  A finished
+// job stays as a row without a run (it is in no queued list and takes no part in a round).  ErrNeedsUpload — UploadJobs instead — where the library would refuse or
+// the shim cannot know the row: the first cycle (no table), a market-driven pool, a job with a run, a job whose requirement class the last UploadJobs did not see
+// (the classes are those of the last asched_jobs_set), a job that joins a gang already in the table (a gang is submitted in one piece), an id that sorts in front
+// of a resident one.  Now and then the caller uploads anyway, to drop the rows of finished jobs.
+func (g *GpuRound) AppendJobs(jobs []*jobdb.Job, queueIndex map[string]int32) error {
+	if g.jobs == nil || g.gangIds == nil || (g.market != nil && g.market.Enabled) {
+		return ErrNeedsUpload
+	}
+	m, R := len(jobs), len(g.resNames)
+	var in C.asched_jobs
+	if m == 0 {
+		return g.check(C.asched_jobs_append(g.h, &in))
+	}
+	jobs = append([]*jobdb.Job(nil), jobs...)
+	sort.SliceStable(jobs, func(a, b int) bool { return jobs[a].Id() < jobs[b].Id() })
+	if n := len(g.jobs); n > 0 && jobs[0].Id() <= g.jobs[n-1].Id() {
+		return ErrNeedsUpload
+	}
+	queue, pc, reqClassIdx := make([]int32, m), make([]int32, m), make([]int32, m)
+	qprio := make([]uint32, m)
+	submit := make([]int64, m)
+	req := make([]int64, m*R)
+	gangId, gangCard, gangUni := make([]int32, m), make([]int32, m), make([]int32, m)
+	newGangs := map[string]int32{}
+	for i, j := range jobs {
+		if !j.Queued() {
+			return ErrNeedsUpload
+		}
+		if qi, ok := queueIndex[j.Queue()]; ok {
+			queue[i] = qi
+		} else {
+			queue[i] = -1
+		}
+		pc[i] = g.pcIndex[j.PriorityClassName()]
+		qprio[i] = j.Priority()
+		submit[i] = j.SubmitTime().UnixNano()
+		copy(req[i*R:], g.vec(j.AllResourceRequirements()))
+		key, _ := g.classKey(j)
+		ci, ok := g.classes[key]
+		if !ok {
+			return ErrNeedsUpload
+		}
+		reqClassIdx[i] = ci
+		gangId[i], gangCard[i], gangUni[i] = -1, 1, -1
+		if gi := j.GetGangInfo(); gi.IsGang() {
+			k := j.Queue() + "\x00" + gi.Id()
+			if _, resident := g.gangIds[k]; resident {
+				return ErrNeedsUpload
+			}
+			id, ok := newGangs[k]
+			if !ok {
+				id = int32(len(g.gangIds) + len(newGangs))
+				newGangs[k] = id
+			}
+			gangId[i], gangCard[i] = id, int32(gi.Cardinality())
+			if gi.NodeUniformity() != "" {
+				gangUni[i] = g.strs.id(gi.NodeUniformity())
+			}
+		}
+	}
+	var pins runtime.Pinner
+	defer pins.Unpin()
+	pin32 := func(s []int32) *C.int32_t {
+		pins.Pin(&s[0])
+		return i32p(s)
+	}
+	in.m = C.int32_t(m)
+	pins.Pin(&qprio[0]); pins.Pin(&submit[0]); pins.Pin(&req[0])
+	in.queue, in.pc, in.req_class = pin32(queue), pin32(pc), pin32(reqClassIdx)
+	in.queue_priority = (*C.uint32_t)(unsafe.Pointer(&qprio[0]))
+	in.submit_time, in.req = i64p(submit), i64p(req)
+	in.gang_id, in.gang_cardinality, in.gang_uniformity_label = pin32(gangId), pin32(gangCard), pin32(gangUni)
+	if err := g.check(C.asched_jobs_append(g.h, &in)); err != nil {
+		return err
+	}
+	base := int32(len(g.jobs))
+	g.jobs = append(g.jobs, jobs...)
+	if g.jobRow != nil {
+		for i, j := range jobs {
+			g.jobRow[j.Id()] = base + int32(i)
+		}
+	}
+	for k, id := range newGangs {
+		g.gangIds[k] = id
+	}
+	return nil
+}
+
 // PatchJobs tells the library the run-state changes of a finished cycle without re-describing the job set (asched_jobs_patch): what
 // txn.Upsert(preemptedJobs) / txn.Upsert(scheduledJobs) apply to the jobDb (scheduling_algo.go:280-283, the jobs built at :956-981).  scheduled: the
 // result's ScheduledJobs (PodSchedulingContext.NodeId / ScheduledAtPriority), leased at leasedAt — the run timestamp the new runs get; preempted: its
-// PreemptedJobs; ended: ids of jobs whose run finished or whose lease was returned since.  Every job must be one of the last UploadJobs (rows do not
-// change: a new submission needs UploadJobs), a market-driven pool is refused by the library (the market order depends on run state too).  g.jobs keeps the
+// PreemptedJobs; ended: ids of jobs whose run finished or whose lease was returned since.  Every job must be one of the last UploadJobs or of an AppendJobs since
+// (rows do not change; new submissions are appended first), a market-driven pool is refused by the library (the market order depends on run state too).  g.jobs keeps the
 // jobDb objects of UploadJobs: the caller's jobDb holds the updated ones.  The next call is Schedule, as after UploadJobs.
 func (g *GpuRound) PatchJobs(scheduled, preempted []*schedulercontext.JobSchedulingContext, ended []string, leasedAt time.Time) error {
 	if g.jobRow == nil {
