@@ -2511,6 +2511,7 @@ int32_t asched_round_prepare(asched_t* h, const asched_queues* in) { if (!h) ret
   // (after the oversubscribed evictor, which does evict them) runs on the generic code when the job set holds any: round_run.h controlMain / runRound.  (Round 3: iterOk = 0.)
   { const char* e = getenv("ASCHED_ENGINE"); d.f.engine = !(e && e[0] == '0'); }
   { const char* e = getenv("ASCHED_ENGINE_HC"); d.f.engineHc = d.f.engine && d.fitBits != nullptr && !d.f.maskMode && d.f.guardMask != 0 && d.f.F <= 128 && !(e && e[0] == '0'); }   // (guard bits: its fit test is the one-subtraction form)
+  { const char* e = getenv("ASCHED_HC_SHORT"); d.f.hcShort = !(e && e[0] == '0'); }   // (engine_hc.h: off = every shape's clean-side bound reads 0, the per-job loop is the same code)
   { const char* e = getenv("ASCHED_RELOC_ALL"); d.f.relocAll = e && e[0] == '1'; }
   { const char* e = getenv("ASCHED_DEBUG_HANG"); d.f.debugHang = e ? atoi(e) : 0; }
   { const char* e = getenv("ASCHED_MERGE_MIN"); d.f.mgMin = e && atoi(e) >= 16 ? atoi(e) : MG_MIN_ENTRIES_DEFAULT; }
@@ -3175,7 +3176,8 @@ int32_t asched_round_stats(asched_t* h, int32_t* out) { if (!h) return ASCHED_ER
   const RoundScalars& r = h->rsHost;
   for (int i = 0; i < 24; i++) out[i] = 0;
   out[20] = r.statHybrid;
-  // out[21..23]: reserved, always 0
+  out[21] = r.statHcShort;
+  // out[22..23]: reserved, always 0
   out[0] = r.statFastIters; out[1] = r.statGenericIters; out[2] = r.statScanSteps; out[3] = r.statRefills; out[4] = r.statL0Max;
   out[5] = r.statFastReplay; out[6] = r.fastOverflow; out[7] = r.fastActive;
   out[16] = r.statStreamRuns; out[17] = r.statStreamJobs; out[18] = r.statStreamPrepared; out[19] = r.statStreamEmitted;

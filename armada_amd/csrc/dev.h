@@ -148,6 +148,7 @@ struct FastCfg {
   int debugHang;              // tests only (ASCHED_DEBUG_HANG=<n>): the cold-set wave stops answering at its n-th command of a ring session, as a protocol defect would make it — every wait must still end
   int mgMin;                  // round_merge.h: a run of at least this many entries is merged by the bulk passes (MG_MIN_ENTRIES_DEFAULT; ASCHED_MERGE_MIN=<n> for soaks: small rounds through the bulk merge and the split node engine)
   int engineHc;               // the ring session of a bulk-merged stream run uses the split level-0 structure (engine_hc.h): hot set / cold set / clean front; ASCHED_ENGINE_HC=1 turns it on
+  int hcShort;                // engine_hc.h: a pick the hot set wins outright skips the general body of the per-job loop (same decisions, fewer instructions); ASCHED_HC_SHORT=0 turns it off
   int engine;                 // queued-job iterations run on two waves (round_fast.h "two-wave iteration"); ASCHED_ENGINE=0 turns it off
   int E; int extraCol[MAXE];  // non-indexed columns
   uint64_t fieldMask[MAXK];   // in-place mask of each packed key field
@@ -191,7 +192,8 @@ struct RoundScalars {
   // kernels keep their stores to the two flags (nothing reads them any more): their code is instruction for instruction what it was.  Compacting the struct and
   // dropping the stores is a change of its own, measured on its own.
   int32_t ftWanted, ftValid;   // written, never read
-  int32_t reserved[3];         // always 0
+  int32_t statHcShort;         // picks the node engine's short path took (engine_hc.h; device only): round_stats hc_short_picks.  (The first of three reserved words: the layout stays.)
+  int32_t reserved[2];         // always 0
   int64_t statSeg[40];       // [24..39]: (profiling builds) segments of the generic iteration
   int64_t gsT;                     // (profiling builds) shader-clock ticks per segment of a fast iteration
   int64_t statClk[8];        // shader-clock ticks per phase of the round (device builds): evict, replay, pass 1, oversub evict, pass 2, unbind+results

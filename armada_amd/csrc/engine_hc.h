@@ -259,8 +259,18 @@ struct HcHot { unsigned long long key, cls; long long ex0, ex1; int node, state,
 enum { SC_NONE = 0, SC_SCAN = 1, SC_HEAD = 2 };
 // The SPARE (pos2 >= 0): the candidate behind the head — the next set bit of the same bitmap word, fetched in the head's round trip.  A consumed head is replaced by it
 // without a memory access (half of the fetches of a headline round, profiles/r06z_spare_candidates.txt); a spare whose node another shape takes is dropped.
+// bk: the key the shape's clean side can offer at best, in the per-job loop's own terms (SC_HEAD: key, SC_SCAN: lb, SC_NONE: ~0) — hcShapesBound, read by the short path.
 struct HcShapes { int pos[2], st[2], node[2], wIdx[2]; unsigned long long w[2], key[2], cls[2], lb[2]; long long ex0[2], ex1[2];
-                  int pos2[2], node2[2]; unsigned long long key2[2], cls2[2]; long long ex02[2], ex12[2]; };
+                  int pos2[2], node2[2]; unsigned long long key2[2], cls2[2]; long long ex02[2], ex12[2]; unsigned long long bk[2]; };
+// bk of every shape from its state as it stands: called wherever st / key / lb change (hcShapesLoad, hcShapesFetch, hcShapesUsed — the general path only).  `on` is
+// ~0, or 0 with the short path switched off (ASCHED_HC_SHORT=0): every bound is 0 then and no hot candidate ever lies below it.
+__device__ static inline void hcShapesBound(HcShapes& sc, unsigned long long on) {
+#pragma unroll
+  for (int x = 0; x < 2; x++) {
+    const unsigned long long b = sc.st[x] == SC_HEAD ? sc.key[x] : (sc.st[x] == SC_SCAN ? sc.lb[x] : ~0ull);
+    sc.bk[x] = b & on;
+  }
+}
 __device__ static inline void hcShapesLoad(KREF k, HcShapes& sc) {   // from the LDS cursors, as the serial engine left them
   const int lane = threadIdx.x & 63;
 #pragma unroll
@@ -392,13 +402,23 @@ __device__ static inline void hcPostA(int& cmdPub, int type, int a) {
   hcStoreI32(&HCB.cmdPub, cmdPub);
 }
 
+// the bind's effect on the level-0 entry in lane hLane of H, in place: key and extras go down; an entry that can no longer host anything is dropped (returns 1: it died)
+__device__ static inline int hcHotBind(HcHot& h, int hLane, const HcJobV& j, unsigned long long G, unsigned long long MFM, long long ME0, long long ME1) {
+  const unsigned long long nk = h.key - j.keyDelta; const long long n0 = h.ex0 - j.ex0, n1 = h.ex1 - j.ex1;
+  const bool alive = ((((nk | G) - MFM) & G) == G) & (ME0 <= n0) & (ME1 <= n1);
+  const bool me = (int)(threadIdx.x & 63) == hLane;
+  h.key = me ? (alive ? nk : ~0ull) : h.key; h.ex0 = me ? n0 : h.ex0; h.ex1 = me ? n1 : h.ex1; h.state = me ? (alive ? 1 : 0) : h.state; h.cls = (me & !alive) ? 0ull : h.cls;
+  return __ballot(me & !alive) ? 1 : 0;
+}
+#define HC_ERR_SHORT 610   // errorDetail of the checking build (-DASCHED_HC_CHECK): the general body decided a short-path job differently, or asked / fetched for it
+
 // One ring session with the split structure.  Same contract as the ENG_STREAM walk of engineLoop: entry i is ready when ringPub > i; the chosen node goes into the
 // ring entry (the bind wave issues the HBM side); ringAck counts the entries placed; ringFail 1 = entry ringAck found no node, 2 = the list overflowed.
 // The loop is written around two costs measured on the MI355X (profiles/r06g_hc_engine_segments.txt): ~8 shader clocks per instruction of a lone wave, ~140 per
 // dependent LDS round trip.  Per job: ONE batch of LDS reads for the next entry and the cold set's answer (issued before the tests, used after them).
 // (A function of its own, not inlined: inside engineLoop its loop shared the register allocation of the serial engine's paths and lived partly in AGPRs.  Its constants
 // and counters are copied in and out: nothing in the loop goes through the references.)
-struct HcOut { int engSeq, statScanSteps, statL0Max; long long segT, eseg[8]; };
+struct HcOut { int engSeq, statScanSteps, statL0Max, hcShort; long long segT, eseg[8]; };
 template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamHcT(Dev& d, const FastK k, const int engSeq0, const int statScan0, const int statL0Max0, const long long segT0) {
   // (every argument BY VALUE: a reference to the caller's constants or counters would put them in memory over there — the serial engine's loops read them too;
   //  measured: 20 % on gang-heavy rounds, profiles/r06v)
@@ -420,7 +440,9 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
   hcStoreI32(&g_fl.eng.hcGen, __builtin_amdgcn_readfirstlane(g_fl.eng.hcGen) + 1);
   int cmdPub = 0, insSeq = 0, rrNext = 0, qSeq = 0, inFlight = 0;   // inFlight: lanes of H whose entry has been handed to C and not yet been taken in
   HcHot h; h.key = ~0ull; h.cls = 0; h.ex0 = h.ex1 = 0; h.node = -1; h.state = 0; h.seq = 0;
-  HcShapes sc; hcShapesLoad(k, sc);
+  const unsigned long long shortOn = d.f.hcShort ? ~0ull : 0ull;   // (read once per session; used on the general path only)
+  HcShapes sc; hcShapesLoad(k, sc); hcShapesBound(sc, shortOn);
+  int nShort = 0;   // picks the short path took: round_stats hc_short_picks
   int total = __builtin_amdgcn_readfirstlane(g_fl.l0Count);   // dirty nodes alive (H + C): the list's high-water mark for round_stats
   int i = 0, fail = 0;
   // (bounded waits, round_kernel.h: a turn of a wait here reads the launch's `abandon` word — 0 or 1 — and leaves through an exit the loop has anyway; NO flag is carried
@@ -428,6 +450,9 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
   HcJobV cur; bool haveCur = false;
 #ifdef ASCHED_FASTPROF
   int pSrc[4] = {0, 0, 0, 0}, pFetch = 0, pDry = 0, pAsk = 0;
+#endif
+#ifdef ASCHED_HC_CHECK
+  int chkNode = -1, chkQ = 0, chkScan = 0;   // the short path's pick of the job at hand (-1: it does not qualify); questions and fetch rounds before its general walk
 #endif
   for (;;) {
     if (!haveCur) {   // the ring ran dry (or the session starts): wait for entry i
@@ -462,13 +487,9 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
     const bool fitH = hcFits<E>(G, q, h.key, h.cls, h.ex0, h.ex1);   // (an empty lane has class bits 0: it fits nothing)
     int hLane;
     unsigned long long hk = hcMinKey(fitH ? h.key : ~0ull, &hLane);
-    // ---- the shape's clean candidate as it stands
     const int shape = __builtin_amdgcn_readfirstlane(cur.shape), sl = shape & 63;
     const bool hiSet = cur.shape >= 64;   // (the same in every lane: a select per word, then ONE v_readlane — no branch on the set)
-    int cst = __builtin_amdgcn_readlane(hiSet ? sc.st[1] : sc.st[0], sl);
-    unsigned long long cKey = hcRead64(hiSet ? sc.key[1] : sc.key[0], sl);        // (SC_HEAD: the candidate's key)
-    const unsigned long long cLb = hcRead64(hiSet ? sc.lb[1] : sc.lb[0], sl);     // (SC_SCAN: a lower bound)
-    ESEG(1);   // [17] H test, clean candidate
+    ESEG(1);   // [17] H test
     int insDone = __builtin_amdgcn_readfirstlane(rIns);
     if (insDone < 0) { fail = 2; break; }   // the cold list overflowed
     if (inFlight > 0) {   // entries whose hand-over wave 3 has taken in leave H: the bound read behind the counter covers them.  The best lane among them: ask C (it has that very entry)
@@ -479,6 +500,42 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
       const bool drop = hLane >= 0 && ((rb >> hLane) & 1);
       hLane = drop ? -1 : hLane; hk = drop ? ~0ull : hk;
     }
+    // ---- the SHORT PATH: a pick the hot set wins outright (74 % of the headline round's placements) skips the general body below.  Taken iff, all wave-uniform:
+    //   (a) !(rLb < hk)   the cold set's lower bound does not lie below the hot candidate (an unknown bound, 0, fails this);
+    //   (b) hk < bkS      the hot candidate lies below the best the shape's clean side can offer (hcShapesBound: head key / scan bound / ~0).  This implies that there
+    //                     IS a hot candidate: hLane >= 0, since hk == ~0 without one; and with the switch off bkS is 0 and (b) never holds;
+    //   (c) lane hLane holds an entry (state 1), not a hand-over in flight (state 2: the general body takes the insert back with HC_C).
+    // Why the general body would decide the same.  By (b) its `known` is hk (a head's key is not below hk).  By (a) `ckLb < known` fails: no question, ck = ~0, no
+    // release of lanes beyond the one above, lk = hk.  A scanning shape has cLb = bkS, so `lk < cLb` holds by (b): no fetch.  Its `bk` is bkS by construction, so
+    // dirtyWins = hk < bkS is true and src = (hk < ~0) ? 0 : 1 = 0: the node of lane hLane.  src 0 posts no HC_D, and by (c) no HC_C.  Keys are unique, so every
+    // strict comparison above has the same outcome whichever side it is read from.  What is left of the body is what stands here: the node into the ring entry, the
+    // ack, the in-place update of the lane (hcHotBind, shared with the general body), the next entry.  `sc` is not touched, nothing is posted to wave 3.
+    // (-DASCHED_HC_CHECK, tools/build_variant.sh, never the product: a job that qualifies walks the general body too, which must come to src 0 and the same node
+    //  without a question or a fetch — else ASCHED_ERR_INTERNAL / HC_ERR_SHORT and the session ends.)
+    {
+      const unsigned long long bkS = hcRead64(hiSet ? sc.bk[1] : sc.bk[0], sl);
+      const int stH = __builtin_amdgcn_readlane(h.state, hLane & 63);   // (no hot candidate: some lane's state, and (b) fails)
+#ifdef ASCHED_HC_CHECK
+      chkNode = -1; chkQ = qSeq; chkScan = ES.statScanSteps;
+      if (!(rLb < hk) & (hk < bkS) & (stH == 1)) chkNode = __builtin_amdgcn_readlane(h.node, hLane & 63);
+#else
+      if (!(rLb < hk) & (hk < bkS) & (stH == 1)) {   // (a scalar branch on a v_readfirstlane of this was measured the same: 217.2 / 217.7 against 216.1 / 217.8 ms)
+        RREC(i).node0 = __builtin_amdgcn_readlane(h.node, hLane & 63);   // (every lane stores the same word)
+        LDS_ORDER();
+        i++;
+        hcStoreI32(&g_fl.eng.ringAck, i);
+        total -= hcHotBind(h, hLane, cur, G, MFM, ME0, ME1);
+        nShort++;
+        cur = nxt; haveCur = __builtin_amdgcn_readfirstlane(nxt.pub) > i;
+        ESEG(6);   // [22] the short path: its test, the pick, the lane's update
+        continue;
+      }
+#endif
+    }
+    // ---- the shape's clean candidate as it stands
+    int cst = __builtin_amdgcn_readlane(hiSet ? sc.st[1] : sc.st[0], sl);
+    unsigned long long cKey = hcRead64(hiSet ? sc.key[1] : sc.key[0], sl);        // (SC_HEAD: the candidate's key)
+    const unsigned long long cLb = hcRead64(hiSet ? sc.lb[1] : sc.lb[0], sl);     // (SC_SCAN: a lower bound)
     // ---- does the cold set matter?  Only when its bound lies below both the hot candidate and the clean candidate at hand: then the exact answer, synchronously (rare)
     const unsigned long long ckLb = UNI64(rLb);
     const unsigned long long known = cst == SC_HEAD && cKey < hk ? cKey : hk;
@@ -510,6 +567,7 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
       pFetch++;
 #endif
       hcShapesFetch(k, ES, sc, shape);
+      hcShapesBound(sc, shortOn);
       cst = __builtin_amdgcn_readlane(hiSet ? sc.st[1] : sc.st[0], sl);
       cKey = hcRead64(hiSet ? sc.key[1] : sc.key[0], sl);
       // (the cold set needs no second look: it was asked above unless its bound lies at or above the hot candidate, and then it cannot win whatever the base offers)
@@ -525,6 +583,12 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
     const int nH = __builtin_amdgcn_readlane(h.node, hLane & 63), nB = __builtin_amdgcn_readlane(hiSet ? sc.node[1] : sc.node[0], sl);
     int n = dirtyWins ? nH : nB;
     if (src == 1) n = __builtin_amdgcn_readfirstlane(g_fl.l0Node[cSlot]);
+#ifdef ASCHED_HC_CHECK
+    if (chkNode >= 0) {
+      if ((src != 0) | (n != chkNode) | (qSeq != chkQ) | (ES.statScanSteps != chkScan)) { if (lane == 0 && RS.error == 0) { RS.error = ASCHED_ERR_INTERNAL; RS.errorDetail = HC_ERR_SHORT; } LANE0_PUBLISHED(); fail = 1; break; }
+      nShort++;
+    }
+#endif
 #ifdef ASCHED_FASTPROF
     pSrc[src & 3]++;
 #endif
@@ -540,11 +604,7 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
     ESEG(4);   // [20] verdict, commands
     // ---- the bind's effect on the node's level-0 entry: key and extras go down; an entry that can no longer host anything is dropped
     if (src == 0) {   // in place, in its lane
-      const unsigned long long nk = h.key - cur.keyDelta; const long long n0 = h.ex0 - cur.ex0, n1 = h.ex1 - cur.ex1;
-      const bool alive = ((((nk | G) - MFM) & G) == G) & (ME0 <= n0) & (ME1 <= n1);
-      const bool me = lane == hLane;
-      h.key = me ? (alive ? nk : ~0ull) : h.key; h.ex0 = me ? n0 : h.ex0; h.ex1 = me ? n1 : h.ex1; h.state = me ? (alive ? 1 : 0) : h.state; h.cls = (me & !alive) ? 0ull : h.cls;
-      if (__ballot(me & !alive)) total--;
+      total -= hcHotBind(h, hLane, cur, G, MFM, ME0, ME1);
     } else {
       unsigned long long okey, ocls; long long oex0, oex1;
       if (src == 1) { okey = ck; ocls = UNI64(g_fl.l0Cls[cSlot]); oex0 = (long long)UNI64(g_fl.l0Ex0[cSlot]); oex1 = (long long)UNI64(g_fl.l0Ex1[cSlot]); }
@@ -556,6 +616,7 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
         const int usedPos = __builtin_amdgcn_readlane(hiSet ? sc.pos[1] : sc.pos[0], sl);
         baseMarkRemoved(k, ES, usedPos);   // a clean entry is used up (fastAfterBind's base branch): its flag and bitmap bits; the shapes' cursors are in registers here
         hcShapesUsed(sc, usedPos);
+        hcShapesBound(sc, shortOn);
       }
       const unsigned long long nk = okey - UNI64(cur.keyDelta); const long long n0 = oex0 - (long long)UNI64(cur.ex0), n1 = oex1 - (long long)UNI64(cur.ex1);
       const bool alive = ((((nk | G) - MFM) & G) == G) && ME0 <= n0 && ME1 <= n1;
@@ -595,7 +656,7 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
   bool gaveUp = waitAbandoned();   // the session ends without its hand-shakes
   if (gaveUp) fail = 1;
 #ifdef ASCHED_FASTPROF
-  if (lane == 0) { g_rs.statSeg[29] += pSrc[0] * 1000ll; g_rs.statSeg[30] += pSrc[1] * 1000ll; g_rs.statSeg[31] += pSrc[2] * 1000ll; g_rs.statSeg[33] += pFetch * 1000ll; g_rs.statSeg[35] += pDry * 1000ll; g_rs.statSeg[36] += pAsk * 1000ll; }   // picks from H / C / the base; clean-candidate fetches; ring-dry waits; questions put to the cold set
+  if (lane == 0) { g_rs.statSeg[29] += pSrc[0] * 1000ll; g_rs.statSeg[30] += pSrc[1] * 1000ll; g_rs.statSeg[31] += pSrc[2] * 1000ll; g_rs.statSeg[33] += pFetch * 1000ll; g_rs.statSeg[35] += pDry * 1000ll; g_rs.statSeg[36] += pAsk * 1000ll; g_rs.statSeg[32] += nShort * 1000ll; }   // picks from H / C / the base (general body only); clean-candidate fetches; ring-dry waits; questions put to the cold set; [32] picks of the short path (all from H)
 #endif
   // ---- session end: the shapes' cursors go back to LDS; C compacts the LDS list; H's entries are appended; a pending failure is reported after the structure is whole again
   hcShapesStore(k, sc);
@@ -620,7 +681,7 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
   }
   if (fail == 3) fail = 2;
   if (fail) { LDS_ORDER(); hcStoreI32(&g_fl.eng.ringFail, fail); }
-  HcOut o; o.engSeq = ES.engSeq; o.statScanSteps = ES.statScanSteps; o.statL0Max = ES.statL0Max; o.segT = ES.segT;
+  HcOut o; o.engSeq = ES.engSeq; o.statScanSteps = ES.statScanSteps; o.statL0Max = ES.statL0Max; o.hcShort = nShort; o.segT = ES.segT;
   for (int x = 0; x < 8; x++) o.eseg[x] = 0;
 #ifdef ASCHED_FASTPROF
   for (int x = 0; x < 8; x++) o.eseg[x] = ES.eseg[x];
@@ -631,6 +692,8 @@ __device__ static inline void engineStreamHc(Dev& d, KREF k, FastS& ES) {
   HcOut o;
   if (k.E == 0) o = engineStreamHcT<0>(d, k, ES.engSeq, ES.statScanSteps, ES.statL0Max, ES.segT); else if (k.E == 1) o = engineStreamHcT<1>(d, k, ES.engSeq, ES.statScanSteps, ES.statL0Max, ES.segT); else o = engineStreamHcT<2>(d, k, ES.engSeq, ES.statScanSteps, ES.statL0Max, ES.segT);
   ES.engSeq = o.engSeq; ES.statScanSteps = o.statScanSteps; ES.statL0Max = o.statL0Max;
+  if ((threadIdx.x & 63) == 0) g_rs.statHcShort += o.hcShort;   // (this wave's word of the round's scalars: nothing else writes it)
+  LANE0_PUBLISHED();
 #ifdef ASCHED_FASTPROF
   ES.segT = o.segT; for (int x = 0; x < 8; x++) ES.eseg[x] += o.eseg[x];
 #endif
