@@ -100,6 +100,13 @@ class CNodes(C.Structure):
     ]
 
 
+class CNodesPatch(C.Structure):  # asched_nodes_patch_rows
+    _fields_ = [
+        ("n", C.c_int32), ("node", _i32p), ("allocatable", _i64p), ("unschedulable", _u8p), ("over_allocated", _u8p),
+        ("taint_off", _i32p), ("taint_key", _i32p), ("taint_value", _i32p), ("taint_effect", _i32p),
+    ]
+
+
 class CReqClasses(C.Structure):
     _fields_ = [
         ("n", C.c_int32), ("tol_off", _i32p), ("tol_key", _i32p), ("tol_op", _i32p), ("tol_value", _i32p),
@@ -248,13 +255,15 @@ ALL_SYMBOLS = [
     "round_preemption_causes", "preemption_join",
     "set_evictor_report", "round_evictor_report",
     "jobs_patch", "jobs_append", "jobs_append_stats",
+    "nodes_patch", "nodes_patch_stats",
 ]
 # entry points the CPU oracle does not implement (it is the single-process checker): the communicator and the collectives that run on it, and the join of a
 # round's result lists into preemption causes (a function of lists the oracle already delivers; tests/test_z_preemption_causes.py restates it)
 OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_destroy", "comm_rank", "fit_select_batch_sharded", "round_exchange", "shard_round", "shard_exchanges", "shard_area", "shard_open", "shard_peers",
                     "round_preemption_causes", "preemption_join",
                     "set_evictor_report", "round_evictor_report",   # (recorded by passes between the launches of the split round: tests/test_z_evictor_report.py restates it)
-                    "jobs_patch", "jobs_append", "jobs_append_stats"}   # (an incremental jobs_set: the oracle is given the whole table; tests/test_z_jobs_patch.py, test_z_jobs_append.py)
+                    "jobs_patch", "jobs_append", "jobs_append_stats",   # (an incremental jobs_set: the oracle is given the whole table; tests/test_z_jobs_patch.py, test_z_jobs_append.py)
+                    "nodes_patch", "nodes_patch_stats"}                  # (an incremental nodes_upsert, likewise: tests/test_z_nodes_patch.py)
 PREEMPTION_UNKNOWN, PREEMPTION_UNKNOWN_GANG, PREEMPTION_FAIRSHARE, PREEMPTION_URGENCY, PREEMPTION_OPTIMISER = 1, 2, 3, 4, 5   # ASCHED_PREEMPTION_* (context.PreemptionType)
 # ASCHED_EVR_* bits of asched_evictor_report.node_reasons, in bit order: the reference's reason strings in alphabetical order (makeNodePreemptiblityStats sorts them)
 EVICTOR_REASONS = ("all_jobs_preemptible", "below_protected_fair_share", "invalid_queue", "job_not_preemptible", "node_empty", "node_unschedulable")
@@ -451,6 +460,8 @@ class Library:
         f("jobs_patch", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _i64p])
         f("jobs_append", C.c_int32, [C.c_void_p, C.POINTER(CJobs)])
         f("jobs_append_stats", C.c_int32, [C.c_void_p, _i32p])
+        f("nodes_patch", C.c_int32, [C.c_void_p, C.POINTER(CNodesPatch)])
+        f("nodes_patch_stats", C.c_int32, [C.c_void_p, _i32p])
         f("round_preemption_causes", C.c_int32, [C.c_void_p, C.POINTER(CPreemptionCause), C.c_int32, _i32p, C.c_int32, _i32p])
         f("preemption_join", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, C.c_int32, _i32p, _i32p, _i32p, _u8p, C.POINTER(CPreemptionCause), _i32p, C.c_int32, _i32p])
 
@@ -759,6 +770,41 @@ class Scheduler:
         out = np.zeros(8, np.int32)
         self._check(fn(self.h, _ptr(out, C.c_int32)))
         return dict(rows=int(out[0]), in_order=int(out[1]), new_shapes=int(out[2]), new_gangs=int(out[3]), reallocated=int(out[4]), rebuilt=int(out[5]), capacity=int(out[6]))
+
+    def nodes_patch(self, node, allocatable=None, unschedulable=None, over_allocated=None, taints=None):
+        """what populateNodeDb re-reads per node every cycle: rows `node` of the resident node table get a new `allocatable` ([n][R]), `unschedulable` / `over_allocated`
+        flag ([n]; a scalar is given to every row) or taint list (`taints`: per row a list of (key, value, effect), without the unschedulable taint); None leaves the
+        field as it is.  Leaves the handle as nodes_upsert of the patched table would; go on with round_prepare."""
+        fn = self._preemption_fn("nodes_patch")
+        nd = _arr(node, np.int32).reshape(-1)
+        n = len(nd)
+        s = CNodesPatch()
+        s.n = n
+        keep = [nd]
+        s.node = _ptr(nd, C.c_int32)
+        if allocatable is not None:
+            al = _arr(allocatable, np.int64).reshape(n, self.R)
+            keep.append(al)
+            s.allocatable = _ptr(al, C.c_int64)
+        for name, val in (("unschedulable", unschedulable), ("over_allocated", over_allocated)):
+            if val is not None:
+                a = _arr(np.broadcast_to(np.asarray(val, dtype=np.uint8), (n,)), np.uint8)
+                keep.append(a)
+                setattr(s, name, _ptr(a, C.c_uint8))
+        if taints is not None:
+            assert len(taints) == n, "taints"
+            off, (tk, tv, te) = _csr(taints, 3)
+            keep += [off, tk, tv, te]
+            s.taint_off, s.taint_key, s.taint_value, s.taint_effect = (_ptr(x, C.c_int32) for x in (off, tk, tv, te))
+        self._check(fn(self.h, C.byref(s)))
+
+    def nodes_patch_stats(self):
+        """how the last nodes_patch ran: entries, rows whose node type changed, whether the rebuild path ran and why (0 none, 1 a node type the table did not have,
+        2 a node type emptied or newly populated, 3 key layout / divisor / alignment)"""
+        fn = self._preemption_fn("nodes_patch_stats")
+        out = np.zeros(8, np.int32)
+        self._check(fn(self.h, _ptr(out, C.c_int32)))
+        return [int(x) for x in out]   # [0] entries, [1] type changed, [2] rebuilt, [3] reason, [4..7] 0: the C array as it is
 
     def txn_begin(self): self._check(self.lib.txn_begin(self.h))
     def txn_commit(self): self._check(self.lib.txn_commit(self.h))

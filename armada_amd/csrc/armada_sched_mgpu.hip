@@ -469,3 +469,24 @@ extern "C" int asched_internal_ja_fill(const Dev* d, const JaArgs* a, hipStream_
   if (a->nb2 > 0) hipLaunchKernelGGL(k_ja_fill, dim3(mgBlocks(a->nb2)), dim3(MG_THREADS), 0, st, *d, *a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// ------------------------------------------------------------------------------------------------ cordons and capacity changes of resident nodes (kernels_nodes_patch.h)
+#define NP_FN __device__ static inline
+#include "kernels_nodes_patch.h"
+__global__ __launch_bounds__(MG_THREADS) void k_np_scatter(Dev d, NpArgs a) {
+  long long i = MG_IDX();
+  if (i < a.n) npScatter(d, a, (int)i);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_np_mask(Dev d, NpArgs a, long long work) {
+  long long t = MG_IDX();
+  if (t < work) npMaskWord(d, a, t);
+}
+extern "C" int asched_internal_np_scatter(const Dev* d, const NpArgs* a, hipStream_t st) {
+  if (a->n > 0) hipLaunchKernelGGL(k_np_scatter, dim3(mgBlocks(a->n)), dim3(MG_THREADS), 0, st, *d, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_np_mask(const Dev* d, const NpArgs* a, hipStream_t st) {
+  const long long work = (long long)(a->Cext + a->Sext + a->T) * a->nW;
+  if (work > 0) hipLaunchKernelGGL(k_np_mask, dim3(mgBlocks(work)), dim3(MG_THREADS), 0, st, *d, *a, work);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}

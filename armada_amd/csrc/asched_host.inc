@@ -29,6 +29,7 @@
 #include "kernels_evict_report.h"   // EvrArgs and, in the CPU build of the tests, plat_evict_report
 #include "kernels_jobs_patch.h"     // JpArgs and, in the CPU build of the tests, plat_jobs_patch
 #include "kernels_jobs_append.h"    // JaArgs and, in the CPU build of the tests, plat_jobs_append
+#include "kernels_nodes_patch.h"    // NpArgs and, in the CPU build of the tests, plat_nodes_patch
 
 namespace {
 
@@ -246,6 +247,17 @@ struct asched {
   double jaMs[3] = {0, 0, 0};        // device ms of row fill / sort / merge of the last append (ASCHED_JA_TIMES=1)
   DevBufs jpBufs; char* jpScratch = nullptr; size_t jpScratchBytes = 0;   // the entries, the sort array and the kept list of a patch: one block, kept between calls and only ever grown
   double jpMs[4] = {0, 0, 0, 0};     // device ms of the four passes of the last patch (ASCHED_JP_TIMES=1)
+  // ---- asched_nodes_patch (kernels_nodes_patch.h).  What nodes_upsert was given and no other mirror holds (index, allocatable, over_allocated: N x (9 + 8R) bytes;
+  // total, id_rank, unschedulable, taints and labels are nodeTotal, nodeIdRank, nodeUnsched, nodeTaints and nodeLabels above): the rebuild path of a patch runs
+  // nodes_upsert's own code on the patched table.  typeByCanon: canonical string of a node type -> position in `types`
+  std::vector<uint64_t> nodeIndexHost; std::vector<int64_t> nodeAllocHost; std::vector<uint8_t> nodeOverAlloc;
+  std::unordered_map<std::string, int> typeByCanon;
+  bool hasTypeOverride = false, uploadedAllocByPrio = false;   // the table came with node_type_override / alloc_by_prio: asched_nodes_patch refuses it
+  uint64_t* dClassMask = nullptr; int32_t* dShapeClass = nullptr;   // [Cext][W], [Sext] in maskBufs (rebuildMasks): the resident class mask and the class of every mask row
+  std::vector<uint8_t> npSeen;       // [N] all zero between calls: a node named twice in one patch
+  DevBufs npBufs; char* npScratch = nullptr; size_t npScratchBytes = 0;   // the entries of a patch: one block, kept between calls and only ever grown
+  int32_t npStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_nodes_patch_stats
+  double npMs[2] = {0, 0};           // device ms of scatter / mask words of the last patch (ASCHED_NP_TIMES=1)
   double roundTotalMs = 0, roundControlMs = 0, roundPhaseMs[4] = {0, 0, 0, 0};   // split round: whole sequence / persistent passes / evict-1, evict-3, final bulk phases (host clock)
   int submitWideUnits = 0, submitWidePasses = 0, submitSeqUnits = 0, submitGangUnits = 0, submitNodePasses = 0, submitLitUnits = 0;   // how the last submit_check ran (submit_stats)
 };
@@ -497,6 +509,7 @@ int layoutKeys(asched* h) {
 int rebuildMasks(asched* h) {
   if (!h->nodesSet || !h->jobsSet) return 0;
   h->maskBufs.freeAll();
+  h->dClassMask = nullptr; h->dShapeClass = nullptr;
   Dev& d = h->dev;
   int W = d.cfg.W;
   // Exactness of the packed-key argmin: (A) the request is a multiple of the index resolution on every indexed column (else the
@@ -513,7 +526,7 @@ int rebuildMasks(asched* h) {
   for (int c = 0; c < h->Cext; c++)
     for (int n = 0; n < h->N; n++)
       if (classMatchesNode(h, c, n)) classMask[(size_t)c * W + (n >> 6)] |= 1ull << (n & 63);
-  uint64_t* dClassMask = h->maskBufs.upload(classMask);
+  uint64_t* dClassMask = h->dClassMask = h->maskBufs.upload(classMask);   // (kept: asched_nodes_patch rewrites the words of patched nodes)
   int Sext = h->S + (int)h->awayRowClass.size();
   d.shapeMask = h->maskBufs.alloc<uint64_t>((size_t)std::max(Sext, 1) * W);
   std::vector<int32_t> shapeClassExt = h->shapeClass;
@@ -522,7 +535,7 @@ int rebuildMasks(asched* h) {
     shapeClassExt.push_back(h->awayRowClass[k]);
     for (int r = 0; r < h->R; r++) shapeReqExt.push_back(h->shapeReq[(size_t)h->awayRowShape[k] * h->R + r]);
   }
-  int32_t* dShapeClass = h->maskBufs.upload(shapeClassExt);
+  int32_t* dShapeClass = h->dShapeClass = h->maskBufs.upload(shapeClassExt);
   d.shapeReq = h->maskBufs.upload(shapeReqExt);
   d.awayRowOff = h->maskBufs.upload(h->awayRowOff);
   {
@@ -579,6 +592,11 @@ int buildFast(asched* h, const std::vector<uint64_t>& classMask) {
   h->fastBufs.freeAll();
   h->qsOrig.valid = false;   // the parked QCAPF-sized stream buffers of a wide round lived in fastBufs: gone with it (a later round_prepare must not put them back)
   d.baseKey = nullptr; d.jrec = nullptr;
+  // (and everything else that lived in fastBufs: a table that loses the fast structure — allocatable above total after a nodes_upsert or the rebuild path of
+  //  asched_nodes_patch — must not leave pointers behind that the round tests for existence, d.evCheap in evictPhaseSplit)
+  d.shapeTab = nullptr; d.nodeCls = nullptr; d.baseNode = nullptr; d.baseExtra = nullptr; d.baseCls = nullptr; d.baseRemoved = nullptr; d.posOf = nullptr; d.l0Slot = nullptr;
+  d.evIdxByPos = nullptr; d.evKey = nullptr; d.evCheap = nullptr; d.evPart = nullptr; d.evMono = nullptr; d.evEdge = nullptr; d.l0Save = nullptr; d.candPosSave = nullptr;
+  d.qsKey = nullptr; d.qsIn = nullptr; d.qsPart = nullptr; d.qsLen = nullptr; d.qsSave = nullptr; d.mg = nullptr; d.fitBits = nullptr;
   int R = h->R, K = h->K, N = h->N, M = h->M, S = h->S, W = d.cfg.W;
   std::vector<int> extra;
   for (int r = 0; r < R; r++) { bool idx = false; for (int c = 0; c < K; c++) idx = idx || h->indexedCol[c] == r; if (!idx) extra.push_back(r); }
@@ -824,7 +842,7 @@ asched_t* asched_create(const asched_config* c) {
 void asched_destroy(asched_t* h) {
   if (!h) return;
   plat_enter(h->plat);
-  h->nodeBufs.freeAll(); h->jobBufs.freeAll(); h->queueBufs.freeAll(); h->maskBufs.freeAll(); h->fastBufs.freeAll(); h->pjBufs.freeAll(); h->evrBufs.freeAll(); h->exclBufs.freeAll(); h->jpBufs.freeAll();
+  h->nodeBufs.freeAll(); h->jobBufs.freeAll(); h->queueBufs.freeAll(); h->maskBufs.freeAll(); h->fastBufs.freeAll(); h->pjBufs.freeAll(); h->evrBufs.freeAll(); h->exclBufs.freeAll(); h->jpBufs.freeAll(); h->npBufs.freeAll();
   plat_pinned_free(h->resPin); plat_free(h->commStatus); plat_free(h->dev.rs); plat_free(h->dev.cmdIO); plat_free(h->dev.scanResult); plat_free(h->dev.undo);
   plat_close(h->plat);
   delete h;
@@ -839,8 +857,23 @@ static void fastInvalidate(asched* h) {  // inputs are being replaced: the level
   plat_h2d(&h->dev.rs->l0SaveCount, &zero, sizeof zero);
 }
 
-int32_t asched_nodes_upsert(asched_t* h, const asched_nodes* in) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
-  if (h) { h->haveRoundResult = false; h->stateEpoch++; }
+}  // extern "C"
+namespace {
+// NewNodeType (internaltypes/node_type.go:68-131) of a node with these taints (the unschedulable taint included) and labels: the type and its canonical string
+void nodeTypeOf(asched* h, const std::vector<HTaint>& taints, const std::vector<HSel>& labels, HType& t, std::string& canon) {
+  for (auto& x : taints) if (h->indexAllTaints || h->indexedTaints.count(x.key)) t.taints.push_back(x);
+  std::stable_sort(t.taints.begin(), t.taints.end(), [](const HTaint& a, const HTaint& b) { return a.key < b.key; });
+  for (auto& l : labels) if (h->indexedLabels.count(l.key)) t.labels.push_back(l);
+  std::sort(t.labels.begin(), t.labels.end(), [](const HSel& a, const HSel& b) { return a.key < b.key; });
+  for (int32_t k : h->indexedLabels) { bool has = false; for (auto& l : t.labels) if (l.key == k) has = true; if (!has) t.unset.push_back(k); }
+  for (auto& x : t.taints) canon += "t" + std::to_string(x.key) + "=" + std::to_string(x.value) + ":" + std::to_string(x.effect) + "$";
+  canon += "&";
+  for (auto& l : t.labels) canon += std::to_string(l.key) + "=" + std::to_string(l.value) + "$";
+}
+
+// asched_nodes_upsert, and the rebuild path of asched_nodes_patch on the patched table
+int nodesUpsertBody(asched* h, const asched_nodes* in) {
+  h->haveRoundResult = false; h->stateEpoch++;
   fastInvalidate(h);
   h->nodeBufs.freeAll();
   Dev& d = h->dev;
@@ -849,7 +882,10 @@ int32_t asched_nodes_upsert(asched_t* h, const asched_nodes* in) { if (!h) retur
   d.cfg.N = N; d.cfg.Npad = Npad; d.cfg.W = Npad / 64;
   h->nodeTaints.assign(N, {}); h->nodeLabels.assign(N, {}); h->nodeType.assign(N, 0); h->types.clear(); h->typeId.clear();
   h->nodeTotal.assign(in->total, in->total + (size_t)N * R);
-  std::map<std::string, int> typeByCanon;
+  h->nodeAllocHost.assign(in->allocatable, in->allocatable + (size_t)N * R); h->nodeIndexHost.assign(in->index, in->index + N);
+  if (in->over_allocated) h->nodeOverAlloc.assign(in->over_allocated, in->over_allocated + N); else h->nodeOverAlloc.assign(N, 0);
+  h->hasTypeOverride = in->node_type_override != nullptr; h->uploadedAllocByPrio = in->alloc_by_prio != nullptr;
+  auto& typeByCanon = h->typeByCanon; typeByCanon.clear();
   std::vector<int64_t> totalRes((size_t)R * Npad, 0), allocatable((size_t)R * Npad, 0), alloc0;
   if (in->alloc_by_prio) alloc0.assign((size_t)P * R * Npad, 0);
   std::vector<uint8_t> flags(N, 0);
@@ -862,20 +898,10 @@ int32_t asched_nodes_upsert(asched_t* h, const asched_nodes* in) { if (!h) retur
     if (in->label_off) for (int k = in->label_off[i]; k < in->label_off[i + 1]; k++) h->nodeLabels[i].push_back({in->label_key[k], in->label_value[k]});
     flags[i] = (unsched && in->over_allocated && in->over_allocated[i]) ? 1 : 0;
     h->nodeUnsched[i] = unsched ? 1 : 0;
-    // NewNodeType (internaltypes/node_type.go:68-131)
     HType t; std::string canon;
     int64_t ov = in->node_type_override ? in->node_type_override[i] : -1;
     if (ov >= 0) canon = "o" + std::to_string(ov);
-    else {
-      for (auto& x : h->nodeTaints[i]) if (h->indexAllTaints || h->indexedTaints.count(x.key)) t.taints.push_back(x);
-      std::stable_sort(t.taints.begin(), t.taints.end(), [](const HTaint& a, const HTaint& b) { return a.key < b.key; });
-      for (auto& l : h->nodeLabels[i]) if (h->indexedLabels.count(l.key)) t.labels.push_back(l);
-      std::sort(t.labels.begin(), t.labels.end(), [](const HSel& a, const HSel& b) { return a.key < b.key; });
-      for (int32_t k : h->indexedLabels) { bool has = false; for (auto& l : t.labels) if (l.key == k) has = true; if (!has) t.unset.push_back(k); }
-      for (auto& x : t.taints) canon += "t" + std::to_string(x.key) + "=" + std::to_string(x.value) + ":" + std::to_string(x.effect) + "$";
-      canon += "&";
-      for (auto& l : t.labels) canon += std::to_string(l.key) + "=" + std::to_string(l.value) + "$";
-    }
+    else nodeTypeOf(h, h->nodeTaints[i], h->nodeLabels[i], t, canon);
     auto it = typeByCanon.find(canon);
     if (it == typeByCanon.end()) { it = typeByCanon.emplace(canon, (int)h->types.size()).first; h->types.push_back(t); h->typeId.push_back(ov); }
     h->nodeType[i] = it->second;
@@ -975,6 +1001,39 @@ int32_t asched_nodes_upsert(asched_t* h, const asched_nodes* in) { if (!h) retur
   int rc = runControl(h, CMD_UPSERT_RESET);
   if (rc) return rc;
   return rebuildMasks(h);
+}
+
+// node and job dynamic state as at the end of jobs_set: everything unbound until round_prepare — what CMD_UPSERT_RESET and CMD_RESET_JOBS do (round_run.h controlMain), with
+// their per-element passes on the whole grid instead of the control workgroup (B_RESET_JOBS also forgets the failed-selection records: asched_excluded_nodes).  The tail of
+// asched_jobs_patch, asched_jobs_append and asched_nodes_patch; M: rows of the job table
+int resetDynamicState(asched* h, int M) {
+  Dev& d = h->dev;
+  h->stateEpoch++;
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  if (plat_bulk(d, B_INIT_ALLOC, h->N) || plat_bulk(d, B_KEYS_ALL, h->N) || plat_bulk(d, B_RESET_JOBS, M)) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  plat_d2h(&h->rsHost, d.rs, sizeof(RoundScalars));
+  if (h->rsHost.error) {
+    int e = h->rsHost.error;
+    char buf[128]; snprintf(buf, sizeof buf, "device raised error %d (detail %d)", e, h->rsHost.errorDetail);
+    int32_t zero[2] = {0, 0};
+    plat_h2d(&d.rs->error, zero, sizeof zero);
+    return fail(h, e, buf);
+  }
+  h->rsHost.fastActive = 0; h->rsHost.evictedTableSize = 0; h->rsHost.fairIndexValid = 0; h->rsHost.ftValid = 0; h->rsHost.txnActive = 0; h->rsHost.undoCount = 0;
+  plat_h2d(d.rs, &h->rsHost, sizeof(RoundScalars));
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  h->allocPristine = h->nodesSet;
+  h->evictedDirty = false;
+  return 0;
+}
+}  // namespace
+extern "C" {
+
+int32_t asched_nodes_upsert(asched_t* h, const asched_nodes* in) {
+  if (!h) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  memset(h->npStats, 0, sizeof h->npStats);
+  return nodesUpsertBody(h, in);
 }
 
 // the per-job state of a round (everything indexed by job or by a position of a per-job list), zeroed, with room for `cap` rows: jobs_set takes exactly M,
@@ -1407,26 +1466,9 @@ int32_t asched_jobs_patch(asched_t* h, int32_t n, const int32_t* job, const int3
     if (const char* e = getenv("ASCHED_JP_TIMES")) if (e[0] == '1')
       fprintf(stderr, "[asched jobs_patch] jobs %d entries %d in the order %d: scatter %.4f ms, remove %.4f ms, sort %.4f ms, merge %.4f ms\n", M, n, nT, h->jpMs[0], h->jpMs[1], h->jpMs[2], h->jpMs[3]);
   }
-  // job dynamic state: everything unbound until round_prepare, as at the end of jobs_set — what CMD_UPSERT_RESET and CMD_RESET_JOBS do (round_run.h controlMain), with
-  // their per-element passes on the whole grid instead of the control workgroup (B_RESET_JOBS also forgets the failed-selection records: asched_excluded_nodes)
+  // job dynamic state: everything unbound until round_prepare, as at the end of jobs_set
   d.cfg.Q = 0;
-  h->stateEpoch++;
-  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
-  if (plat_bulk(d, B_INIT_ALLOC, h->N) || plat_bulk(d, B_KEYS_ALL, h->N) || plat_bulk(d, B_RESET_JOBS, M)) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
-  plat_d2h(&h->rsHost, d.rs, sizeof(RoundScalars));
-  if (h->rsHost.error) {
-    int e = h->rsHost.error;
-    char buf[128]; snprintf(buf, sizeof buf, "device raised error %d (detail %d)", e, h->rsHost.errorDetail);
-    int32_t zero[2] = {0, 0};
-    plat_h2d(&d.rs->error, zero, sizeof zero);
-    return fail(h, e, buf);
-  }
-  h->rsHost.fastActive = 0; h->rsHost.evictedTableSize = 0; h->rsHost.fairIndexValid = 0; h->rsHost.ftValid = 0; h->rsHost.txnActive = 0; h->rsHost.undoCount = 0;
-  plat_h2d(d.rs, &h->rsHost, sizeof(RoundScalars));
-  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
-  h->allocPristine = h->nodesSet;
-  h->evictedDirty = false;
-  return 0;
+  return resetDynamicState(h, M);
 }
 
 // ---- asched_jobs_append (kernels_jobs_append.h): syncState's upsert of the newly submitted jobs (scheduler.go:478-535; jobdb/jobdb.go:572-700, the insertion into the
@@ -1753,28 +1795,227 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
   }
   if (m > 0 && grow && h->nodesSet) exclSetup(h);   // (the failed-selection records' per-job slots: sized by the capacity)
   // job dynamic state: everything unbound until round_prepare, as asched_jobs_patch leaves it
-  h->stateEpoch++;
-  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
-  if (plat_bulk(d, B_INIT_ALLOC, h->N) || plat_bulk(d, B_KEYS_ALL, h->N) || plat_bulk(d, B_RESET_JOBS, M1)) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
-  plat_d2h(&h->rsHost, d.rs, sizeof(RoundScalars));
-  if (h->rsHost.error) {
-    int e = h->rsHost.error;
-    char buf[128]; snprintf(buf, sizeof buf, "device raised error %d (detail %d)", e, h->rsHost.errorDetail);
-    int32_t zero[2] = {0, 0};
-    plat_h2d(&d.rs->error, zero, sizeof zero);
-    return fail(h, e, buf);
-  }
-  h->rsHost.fastActive = 0; h->rsHost.evictedTableSize = 0; h->rsHost.fairIndexValid = 0; h->rsHost.ftValid = 0; h->rsHost.txnActive = 0; h->rsHost.undoCount = 0;
-  plat_h2d(d.rs, &h->rsHost, sizeof(RoundScalars));
-  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
-  h->allocPristine = h->nodesSet;
-  h->evictedDirty = false;
-  return 0;
+  return resetDynamicState(h, M1);
 }
 int32_t asched_jobs_append_stats(asched_t* h, int32_t* out) {
   if (!h || !out) return ASCHED_ERR_INVALID;
   plat_enter(h->plat);
   for (int k = 0; k < 8; k++) out[k] = h->jaStats[k];
+  return 0;
+}
+
+// ---- asched_nodes_patch (kernels_nodes_patch.h): what populateNodeDb re-reads per node every cycle (scheduling_algo.go:1069-1095) for a few rows of the resident node
+// table.  The handle is left as asched_nodes_upsert of the patched table would leave it.  Two paths, chosen per call: nothing the host derives from the WHOLE table can
+// change (the set of populated node types, the aggregates of the key layout) — the entries are scattered on the device and the touched mask words rewritten; or the
+// patched table goes through nodes_upsert's own code (nodesUpsertBody).
+int32_t asched_nodes_patch(asched_t* h, const asched_nodes_patch_rows* rows) {
+  if (!h) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  if (!rows) return fail(h, ASCHED_ERR_INVALID, "nodes_patch: bad arguments");
+  const int N = h->N, R = h->R, K = h->K, n = rows->n;
+  Dev& d = h->dev;
+  // ---- every refusal before anything changes
+  if (!h->nodesSet || h->nodeAllocHost.size() != (size_t)N * R || h->nodeOverAlloc.size() != (size_t)N || h->nodeIndexHost.size() != (size_t)N)
+    return fail(h, ASCHED_ERR_INVALID, "nodes_patch: no node table on this handle (nodes_upsert first)");
+  if (n < 0 || (n > 0 && !rows->node)) return fail(h, ASCHED_ERR_INVALID, "nodes_patch: bad arguments");
+  if (h->uploadedAllocByPrio || h->hasTypeOverride) return fail(h, ASCHED_ERR_UNSUPPORTED, "nodes_patch: the node table was uploaded with alloc_by_prio or node_type_override (nodes_upsert instead)");
+  if (rows->taint_off) {
+    if (n > 0 && rows->taint_off[0] < 0) return fail(h, ASCHED_ERR_INVALID, "nodes_patch: taint_off is not ascending");
+    for (int i = 0; i < n; i++) if (rows->taint_off[i + 1] < rows->taint_off[i]) return fail(h, ASCHED_ERR_INVALID, "nodes_patch: taint_off is not ascending");
+    if (n > 0 && rows->taint_off[n] > 0 && (!rows->taint_key || !rows->taint_value || !rows->taint_effect)) return fail(h, ASCHED_ERR_INVALID, "nodes_patch: bad arguments");
+  }
+  if (h->npSeen.size() != (size_t)N) h->npSeen.assign(N, 0);
+  { int bad = 0; const char* why = nullptr;
+    for (int i = 0; i < n; i++) {
+      const int v = rows->node[i];
+      if (v < 0 || v >= N) { why = "nodes_patch: a node outside the node table"; break; }
+      if (h->npSeen[v]) { why = "nodes_patch: a node named twice"; break; }
+      h->npSeen[v] = 1; bad = i + 1;
+    }
+    for (int i = 0; i < bad; i++) h->npSeen[rows->node[i]] = 0;
+    if (why) return fail(h, ASCHED_ERR_INVALID, why); }
+  // ---- the new state of every entry, and which path serves the call
+  std::vector<std::vector<HTaint>> eTaints(n);   // the node's taints as nodes_upsert keeps them: the listed ones, then the unschedulable taint
+  std::vector<uint8_t> eUns(n), eOver(n);
+  std::vector<int64_t> eAlloc((size_t)n * R);
+  std::vector<int> eType(n, -1);
+  std::vector<HType> newTypes; std::vector<std::string> newCanon;   // node types the table does not have, in order of first occurrence
+  std::vector<int> typeDelta(h->types.size(), 0);
+  int why = 0, typeChanged = 0;
+  for (int i = 0; i < n; i++) {
+    const int v = rows->node[i];
+    eUns[i] = rows->unschedulable ? (rows->unschedulable[i] ? 1 : 0) : h->nodeUnsched[v];
+    eOver[i] = rows->over_allocated ? (rows->over_allocated[i] ? 1 : 0) : h->nodeOverAlloc[v];
+    for (int r = 0; r < R; r++) eAlloc[(size_t)i * R + r] = rows->allocatable ? rows->allocatable[(size_t)i * R + r] : h->nodeAllocHost[(size_t)v * R + r];
+    if (rows->taint_off) for (int k = rows->taint_off[i]; k < rows->taint_off[i + 1]; k++) eTaints[i].push_back({rows->taint_key[k], rows->taint_value[k], rows->taint_effect[k]});
+    else { eTaints[i] = h->nodeTaints[v]; if (h->nodeUnsched[v] && !eTaints[i].empty()) eTaints[i].pop_back(); }
+    if (eUns[i]) eTaints[i].push_back({kUnschedulableTaintKey, 0, ASCHED_EFFECT_NO_SCHEDULE});  // node.go:127-129
+    HType t; std::string canon;
+    nodeTypeOf(h, eTaints[i], h->nodeLabels[v], t, canon);
+    auto it = h->typeByCanon.find(canon);
+    if (it != h->typeByCanon.end()) eType[i] = it->second;
+    else {
+      size_t k = 0;
+      while (k < newCanon.size() && newCanon[k] != canon) k++;
+      if (k == newCanon.size()) { newCanon.push_back(canon); newTypes.push_back(t); }
+      newTypes[k].numNodes++;
+    }
+    if (eType[i] != h->nodeType[v]) { typeChanged++; typeDelta[h->nodeType[v]]--; if (eType[i] >= 0) typeDelta[eType[i]]++; }
+  }
+  if (!newTypes.empty()) why = 1;
+  if (!why) for (size_t t = 0; t < h->types.size(); t++) if ((h->types[t].numNodes > 0) != (h->types[t].numNodes + typeDelta[t] > 0)) { why = 2; break; }
+  if (!why && rows->allocatable)
+    for (int i = 0; i < n && !why; i++) {
+      const int64_t* a = &eAlloc[(size_t)i * R]; const int64_t* tot = &h->nodeTotal[(size_t)rows->node[i] * R];
+      if (h->allocLeTotal) for (int r = 0; r < R; r++) if (!d.cfg.isFloating[r] && (a[r] < 0 || a[r] > tot[r])) why = 3;   // (allocLeTotal keeps its value)
+      for (int c = 0; c < K; c++) {
+        const int64_t v = a[h->indexedCol[c]];
+        if (v > h->keyMaxV[c] || v / h->indexedRes[c] > h->keyMaxQ[c]) why = 3;            // (beyond the widths layoutKeys chose)
+        if (h->keyCoarse && v % d.cfg.indexedRes[c]) why = 3;                                // (the key's fields are exact quotients by the coarser divisor)
+        if (h->allocAligned && v % h->indexedRes[c]) why = 3;                                // (a class matching several types would move to the literal path)
+      }
+    }
+  const int M = h->jobsSet ? h->M : 0;
+  if (why) {
+    // ---- the rebuild path: the patched table, from the handle's mirrors, through nodes_upsert's own code
+    std::vector<int64_t> alloc = h->nodeAllocHost;
+    std::vector<uint8_t> uns = h->nodeUnsched, over = h->nodeOverAlloc;
+    std::vector<int32_t> ofEntry(N, -1);
+    for (int i = 0; i < n; i++) {
+      const int v = rows->node[i];
+      ofEntry[v] = i; uns[v] = eUns[i]; over[v] = eOver[i];
+      for (int r = 0; r < R; r++) alloc[(size_t)v * R + r] = eAlloc[(size_t)i * R + r];
+    }
+    std::vector<int32_t> tOff(N + 1, 0), tKey, tVal, tEff, lOff(N + 1, 0), lKey, lVal;
+    for (int v = 0; v < N; v++) {
+      const std::vector<HTaint>& tv = ofEntry[v] >= 0 ? eTaints[ofEntry[v]] : h->nodeTaints[v];
+      const size_t cnt = tv.size() - (uns[v] ? 1 : 0);   // (without the unschedulable taint: nodes_upsert adds it)
+      for (size_t k = 0; k < cnt; k++) { tKey.push_back(tv[k].key); tVal.push_back(tv[k].value); tEff.push_back(tv[k].effect); }
+      tOff[v + 1] = (int32_t)tKey.size();
+      for (auto& l : h->nodeLabels[v]) { lKey.push_back(l.key); lVal.push_back(l.value); }
+      lOff[v + 1] = (int32_t)lKey.size();
+    }
+    tKey.push_back(0); tVal.push_back(0); tEff.push_back(0); lKey.push_back(0); lVal.push_back(0);
+    // what that code can refuse, decided first: the key layout of the patched table (layoutKeys) and LIT_TMAX for a row on the literal iteration path
+    {
+      const DevCfg cfgSaved = d.cfg; const bool keyWideSaved = h->keyWide, keyCoarseSaved = h->keyCoarse, alignedSaved = h->allocAligned;
+      int64_t maxQ[MAXK], minQ[MAXK], gcdV[MAXK], maxV[MAXK];
+      for (int c = 0; c < MAXK; c++) { maxQ[c] = h->keyMaxQ[c]; minQ[c] = h->keyMinQ[c]; gcdV[c] = h->keyGcdV[c]; maxV[c] = h->keyMaxV[c]; }
+      std::vector<HType> typesSaved; typesSaved.swap(h->types);
+      for (size_t t = 0; t < typesSaved.size(); t++) if (typesSaved[t].numNodes + typeDelta[t] > 0) h->types.push_back(typesSaved[t]);
+      for (auto& t : newTypes) h->types.push_back(t);
+      h->allocAligned = true;
+      for (int c = 0; c < K; c++) {
+        const int64_t res = h->indexedRes[c]; const int col = h->indexedCol[c];
+        int64_t q = 0, g = 0, mv = 0;
+        for (int v = 0; v < N; v++) { const int64_t a = alloc[(size_t)v * R + col]; if (a % res) h->allocAligned = false; q = std::max(q, a / res); g = std::gcd(g, a < 0 ? -a : a); mv = std::max(mv, a); }
+        h->keyMaxQ[c] = q; h->keyMinQ[c] = 0; h->keyGcdV[c] = g; h->keyMaxV[c] = mv;
+      }
+      int rrc = layoutKeys(h);
+      std::string rwhy = rrc ? h->err : std::string();
+      if (!rrc && h->jobsSet) {
+        const int Sext = h->S + (int)h->awayRowClass.size();
+        for (int row = 0; row < Sext && !rrc; row++) {
+          const int shape = row < h->S ? row : h->awayRowShape[row - h->S], cls = row < h->S ? h->shapeClass[row] : h->awayRowClass[row - h->S];
+          size_t nTypes = 0;
+          for (auto& t : h->types) if (classMatchesType(h, cls, t)) nTypes++;
+          const bool literal = h->shapeUnaligned[shape] || (nTypes > 1 && !(h->allocAligned && h->idRankMonotone));
+          if (literal && nTypes > LIT_TMAX) { rrc = ASCHED_ERR_UNSUPPORTED; rwhy = "a requirement class on the literal iteration path matches more than LIT_TMAX node types"; }
+        }
+      }
+      h->types.swap(typesSaved); h->allocAligned = alignedSaved; d.cfg = cfgSaved; h->keyWide = keyWideSaved; h->keyCoarse = keyCoarseSaved;
+      for (int c = 0; c < MAXK; c++) { h->keyMaxQ[c] = maxQ[c]; h->keyMinQ[c] = minQ[c]; h->keyGcdV[c] = gcdV[c]; h->keyMaxV[c] = maxV[c]; }
+      if (rrc) return fail(h, rrc, "nodes_patch: " + rwhy);
+    }
+    std::vector<uint64_t> index = h->nodeIndexHost; std::vector<int64_t> total = h->nodeTotal; std::vector<int32_t> idRank = h->nodeIdRank;
+    asched_nodes in; memset(&in, 0, sizeof in);
+    in.n = N; in.index = index.data(); in.id_rank = idRank.data(); in.total = total.data(); in.allocatable = alloc.data();
+    in.unschedulable = uns.data(); in.over_allocated = over.data();
+    in.taint_off = tOff.data(); in.taint_key = tKey.data(); in.taint_value = tVal.data(); in.taint_effect = tEff.data();
+    in.label_off = lOff.data(); in.label_key = lKey.data(); in.label_value = lVal.data();
+    memset(h->npStats, 0, sizeof h->npStats); h->npMs[0] = h->npMs[1] = 0;
+    int rc = nodesUpsertBody(h, &in);
+    if (rc) return rc;
+    h->npStats[0] = n; h->npStats[1] = typeChanged; h->npStats[2] = 1; h->npStats[3] = why;
+    return M > 0 ? resetDynamicState(h, M) : 0;   // (both paths leave the per-job state as jobs_set does)
+  }
+  // ---- the device path.  One scratch block for the entries, kept and only ever grown, sized before anything changes: running out of device memory here is a refusal too
+  const bool masks = h->jobsSet && h->dClassMask && h->dShapeClass;
+  const int Cext = masks ? h->Cext : 0, CW = std::max(1, (Cext + 63) / 64);
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t oType = up(sizeof(int32_t) * (size_t)n), oWordOff = oType + up(sizeof(int32_t) * (size_t)n), oWordIdx = oWordOff + up(sizeof(int32_t) * ((size_t)n + 1)),
+               oFlags = oWordIdx + up(sizeof(int32_t) * (size_t)n), oAlloc = oFlags + up((size_t)n), oCls = oAlloc + up(sizeof(int64_t) * (size_t)n * R),
+               need = oCls + up(sizeof(uint64_t) * (size_t)n * CW);
+  if (n > 0 && h->npScratchBytes < need) {
+    char* p = (char*)plat_malloc(need + need / 4);
+    if (!p) { (void)plat_take_failure(); return fail(h, ASCHED_ERR_DEVICE, "nodes_patch: out of device memory for the patch entries; the handle is as it was"); }
+    h->npBufs.freeAll();
+    h->npScratch = p; h->npScratchBytes = need + need / 4;
+    h->npBufs.ptrs.push_back({p, need + need / 4});
+  }
+  // ---- what nodes_upsert resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the node table half patched: asched_nodes_upsert before anything else)
+  h->haveRoundResult = false; h->stateEpoch++;
+  { d.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
+    int32_t zero = 0;
+    plat_h2d(&d.rs->fastActive, &zero, sizeof zero);
+    plat_h2d(&d.rs->l0SaveCount, &zero, sizeof zero); }
+  h->prepared = false; h->evrSized = false; h->equalLevels = h->P;
+  memset(h->npStats, 0, sizeof h->npStats); h->npMs[0] = h->npMs[1] = 0;
+  h->npStats[0] = n; h->npStats[1] = typeChanged;
+  if (n > 0) {
+    // the host mirrors, and the totals by difference (addNodeToStats, nodedb.go:44-55)
+    std::vector<int32_t> ord(n);
+    for (int i = 0; i < n; i++) ord[i] = i;
+    std::sort(ord.begin(), ord.end(), [&](int a, int b) { return rows->node[a] < rows->node[b]; });
+    for (int i = 0; i < n; i++) {
+      const int v = rows->node[i];
+      for (int r = 0; r < R; r++) {
+        const int64_t a = eAlloc[(size_t)i * R + r];
+        if (!d.cfg.isFloating[r]) d.cfg.totalResources[r] += a - h->nodeAllocHost[(size_t)v * R + r];
+        h->nodeAllocHost[(size_t)v * R + r] = a;
+      }
+      for (int c = 0; c < K; c++) { const int64_t a = eAlloc[(size_t)i * R + h->indexedCol[c]]; h->keyGcdV[c] = std::gcd(h->keyGcdV[c], a < 0 ? -a : a); }   // (stays a common divisor: layoutKeys of a later jobs_set / jobs_append)
+      h->nodeTaints[v].swap(eTaints[i]); h->nodeUnsched[v] = eUns[i]; h->nodeOverAlloc[v] = eOver[i];
+      h->types[h->nodeType[v]].numNodes--; h->types[eType[i]].numNodes++; h->nodeType[v] = eType[i];
+    }
+    // the entries, ascending by node and grouped by 64-node word; classMatchesNode for these rows only
+    std::vector<int32_t> sNode(n), sType(n), wordOff, wordIdx;
+    std::vector<uint8_t> sFlags(n);
+    std::vector<int64_t> sAlloc((size_t)n * R);
+    std::vector<uint64_t> sCls((size_t)n * CW, 0);
+    for (int k = 0; k < n; k++) {
+      const int i = ord[k], v = rows->node[i];
+      sNode[k] = v; sType[k] = eType[i]; sFlags[k] = (eUns[i] && eOver[i]) ? 1 : 0;
+      for (int r = 0; r < R; r++) sAlloc[(size_t)k * R + r] = eAlloc[(size_t)i * R + r];
+      for (int c = 0; c < Cext; c++) if (classMatchesNode(h, c, v)) sCls[(size_t)k * CW + (c >> 6)] |= 1ull << (c & 63);
+      if (wordIdx.empty() || wordIdx.back() != (v >> 6)) { wordIdx.push_back(v >> 6); wordOff.push_back(k); }
+    }
+    wordOff.push_back(n);
+    NpArgs a; memset(&a, 0, sizeof a);
+    a.n = n; a.nW = (int32_t)wordIdx.size(); a.CW = CW;
+    char* s = h->npScratch;
+    plat_h2d(s, sNode.data(), sizeof(int32_t) * (size_t)n); plat_h2d(s + oType, sType.data(), sizeof(int32_t) * (size_t)n);
+    plat_h2d(s + oWordOff, wordOff.data(), sizeof(int32_t) * wordOff.size()); plat_h2d(s + oWordIdx, wordIdx.data(), sizeof(int32_t) * wordIdx.size());
+    plat_h2d(s + oFlags, sFlags.data(), (size_t)n); plat_h2d(s + oAlloc, sAlloc.data(), sizeof(int64_t) * (size_t)n * R); plat_h2d(s + oCls, sCls.data(), sizeof(uint64_t) * (size_t)n * CW);
+    a.pNode = (const int32_t*)s; a.pType = (const int32_t*)(s + oType); a.wordOff = (const int32_t*)(s + oWordOff); a.wordIdx = (const int32_t*)(s + oWordIdx);
+    a.pFlags = (const uint8_t*)(s + oFlags); a.pAlloc = (const int64_t*)(s + oAlloc); a.pCls = (const uint64_t*)(s + oCls);
+    if (masks) {
+      a.Cext = Cext; a.Sext = h->S + (int)h->awayRowClass.size(); a.T = (int32_t)h->types.size();
+      a.classMask = h->dClassMask; a.shapeClass = h->dShapeClass; a.nodeType = h->dNodeType;
+      if (d.f.structOk && d.nodeCls) { a.nodeCls = d.nodeCls; a.clsLow = h->C >= 64 ? ~0ull : ((1ull << h->C) - 1); }
+    }
+    int prc = plat_take_failure() ? -1 : plat_nodes_patch(d, a);
+    if (prc) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+    plat_nodes_patch_ms(h->npMs);
+    if (const char* e = getenv("ASCHED_NP_TIMES")) if (e[0] == '1')
+      fprintf(stderr, "[asched nodes_patch] nodes %d entries %d words %d mask rows %d: scatter %.4f ms, mask words %.4f ms\n", N, n, a.nW, a.Cext + a.Sext + a.T, h->npMs[0], h->npMs[1]);
+  }
+  return resetDynamicState(h, M);
+}
+int32_t asched_nodes_patch_stats(asched_t* h, int32_t* out) {
+  if (!h || !out) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  for (int k = 0; k < 8; k++) out[k] = h->npStats[k];
   return 0;
 }
 

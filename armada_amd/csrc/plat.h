@@ -95,6 +95,11 @@ static void plat_jobs_patch_ms(double* out /*[4]*/);   // measurement hook: devi
 struct JaArgs;
 static int plat_jobs_append(Dev& d, JaArgs& a);
 static void plat_jobs_append_ms(double* out /*[3]*/);   // measurement hook: device ms of row fill / sort / merge of the last call (events around them when ASCHED_JA_TIMES=1, else zeros)
+// cordons and capacity changes of resident nodes (kernels_nodes_patch.h): the scatter of the entries, then the touched words of the class, shape and type masks.
+// Synchronous: node arrays and masks are complete on return.  The CPU build's definition sits in kernels_nodes_patch.h.
+struct NpArgs;
+static int plat_nodes_patch(Dev& d, const NpArgs& a);
+static void plat_nodes_patch_ms(double* out /*[2]*/);   // measurement hook: device ms of scatter / mask words of the last call (events around them when ASCHED_NP_TIMES=1, else zeros)
 static int plat_run_fit_capacity(Dev& d, const std::vector<int32_t>& shapes, std::vector<int32_t>& firstNode, std::vector<long long>& capacity, const int32_t* nodeByRankHost);
 static int plat_run_submit_gangs(Dev& d, const std::vector<int32_t>& off, const std::vector<int32_t>& jobs, std::vector<int32_t>& out);
 static double plat_last_fit_ms();

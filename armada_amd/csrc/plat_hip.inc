@@ -34,6 +34,7 @@ struct PlatCtx {
   hipEvent_t evrEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool evrTimed[3] = {false, false, false};   // ASCHED_EVR_TIMES=1: around the passes of the evictor report
   hipEvent_t jaEv[4] = {nullptr, nullptr, nullptr, nullptr}; bool jaTimed = false;   // ASCHED_JA_TIMES=1: around the passes of the job-table append
   hipEvent_t jpEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool jpTimed = false;   // ASCHED_JP_TIMES=1: around the passes of the job-table patch
+  hipEvent_t npEv[3] = {nullptr, nullptr, nullptr}; bool npTimed = false;   // ASCHED_NP_TIMES=1: around the passes of the node-table patch
   float roundTotalMs = 0.f, roundControlMs = 0.f; int roundLaunches = 0;
   int32_t* cmpScratch = nullptr; size_t cmpScratchInts = 0;   // block counts + total of the grid-wide compaction
   int optIndexN = -1, optIndexM = -1;   // sizes the optimiser's node -> jobs index in the scratch was built for (asched_host.inc decides when it may be reused)
@@ -252,6 +253,7 @@ static void plat_close(PlatCtx* c) {
   for (hipEvent_t e : c->evrEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->jpEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->jaEv) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->npEv) if (e) (void)hipEventDestroy(e);
   if (c->helpBox) (void)hipFree(c->helpBox);
   if (c->cmpScratch) (void)hipFree(c->cmpScratch);
   if (c->optScratch) (void)hipFree(c->optScratch);
@@ -940,6 +942,37 @@ static int plat_jobs_append(Dev& d, JaArgs& a) {
 static void plat_jobs_append_ms(double* out) {
   hipEvent_t* ev = jaEvents();
   for (int k = 0; k < 3; k++) { float ms = 0.f; if (ev && t_ctx->jaTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
+}
+// cordons and capacity changes of resident nodes (kernels_nodes_patch.h; k_np_scatter / k_np_mask in armada_sched_mgpu.hip).  ASCHED_NP_TIMES=1 puts events around
+// the two passes (tools/probe_nodes_patch.py).
+#include "kernels_nodes_patch.h"
+extern "C" int asched_internal_np_scatter(const Dev* d, const NpArgs* a, hipStream_t s);
+extern "C" int asched_internal_np_mask(const Dev* d, const NpArgs* a, hipStream_t s);
+static hipEvent_t* npEvents() {
+  static const bool on = [] { const char* e = getenv("ASCHED_NP_TIMES"); return e && e[0] == '1'; }();
+  PlatCtx* c = t_ctx;
+  if (!on) return nullptr;
+  if (!c->npEv[2]) for (int i = 0; i < 3; i++) if (!c->npEv[i] && hipEventCreate(&c->npEv[i]) != hipSuccess) { c->npEv[i] = nullptr; return nullptr; }
+  return c->npEv;
+}
+static int plat_nodes_patch(Dev& d, const NpArgs& a) {
+  PlatCtx* c = t_ctx;
+  hipStream_t st = c->stream;
+  hipEvent_t* ev = npEvents();
+  c->npTimed = false;
+  if (ev) (void)hipEventRecord(ev[0], st);
+  bool ok = asched_internal_np_scatter(&d, &a, st) == 0;
+  if (ev) (void)hipEventRecord(ev[1], st);
+  ok = ok && asched_internal_np_mask(&d, &a, st) == 0;
+  if (ev) (void)hipEventRecord(ev[2], st);
+  ok = ok && hipOk(hipGetLastError(), "k_np launch") && hipOk(hipStreamSynchronize(st), "k_np");
+  if (!ok) { if (c->err.empty()) c->err = "k_np launch failed"; return -1; }
+  c->npTimed = ev != nullptr;
+  return 0;
+}
+static void plat_nodes_patch_ms(double* out) {
+  hipEvent_t* ev = npEvents();
+  for (int k = 0; k < 2; k++) { float ms = 0.f; if (ev && t_ctx->npTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
 }
 // a caller-side buffer may be memory of this handle's GPU (a tensor the collective reduces in place: used directly) or host memory (staged)
 static bool plat_is_device_ptr(const void* p) {

@@ -285,7 +285,7 @@ def arrival_cycles(sim: SimulatorInput, per_cycle: Optional[int] = None) -> np.n
     return np.maximum.accumulate(np.maximum(c, 0))   # (row = arrival order: a row never arrives before the one in front of it)
 
 
-def _run_cycles_arriving(lib, sim: SimulatorInput, per_cycle, max_cycles, appended):
+def _run_cycles_arriving(lib, sim: SimulatorInput, per_cycle, max_cycles, appended, node_events=(), nodes_patched=True):
     from .binding import Scheduler
     wl = sim.workload
     m = wl.num_jobs
@@ -298,6 +298,8 @@ def _run_cycles_arriving(lib, sim: SimulatorInput, per_cycle, max_cycles, append
     out = []
     s = Scheduler(lib, wl.config)
     s.nodes_upsert(wl.node_total, id_rank=wl.node_id_rank)
+    allocatable = np.array(wl.node_total, dtype=np.int64)            # the node state the events of run_cycles_cordoning move
+    unschedulable = np.zeros(wl.num_nodes, np.uint8)
     have = 0                                          # rows in the handle's table: the jobs that have arrived, in arrival order, finished ones included
     t = 0.0
     for cycle in range(max_cycles):
@@ -324,6 +326,21 @@ def _run_cycles_arriving(lib, sim: SimulatorInput, per_cycle, max_cycles, append
                        scheduled_at_priority=np.where(running, run_prio[:upto], 0), run_timestamp=np.where(running, np.maximum(started[:upto], 0) * 1e9, 0).astype(np.int64))
         changed[:] = False
         have = upto
+        touched = []                                  # then the node events of this cycle, in the schedule's order
+        for ev in node_events:
+            if ev[0] != cycle:
+                continue
+            kind, n = ev[1], int(ev[2])
+            if kind == "cut":
+                allocatable[n] = np.asarray(ev[3], dtype=np.int64)
+            else:
+                unschedulable[n] = {"cordon": 1, "uncordon": 0}[kind]
+            if n not in touched:
+                touched.append(n)
+        if touched and nodes_patched:
+            s.nodes_patch(touched, allocatable=allocatable[touched], unschedulable=unschedulable[touched])
+        elif touched:
+            s.nodes_upsert(wl.node_total, allocatable, id_rank=wl.node_id_rank, unschedulable=unschedulable)
         queued = [np.array([j for j in q if j < have and not done[j] and node[j] < 0], dtype=np.int32) for q in wl.queued]
         nq = wl.num_queues
         s.round_prepare(wl.queue_weight, queued, global_tokens=float(wl.global_burst), global_burst=wl.global_burst, global_rate_inf=wl.rate_inf,
@@ -356,3 +373,12 @@ def run_cycles_arriving_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[in
     """the rebuilt counterpart of run_cycles_arriving: jobs_set of the grown table (every row that has arrived, with its run state) in every cycle — what any library,
     the oracle included, can run.  Same rows, same records."""
     return _run_cycles_arriving(lib, sim, per_cycle, max_cycles, False)
+
+
+def run_cycles_cordoning(lib, sim: SimulatorInput, node_events, per_cycle: Optional[int] = None, max_cycles: int = 1000, nodes_patched: bool = True, appended: bool = True):
+    """run_cycles_arriving plus a schedule of node events, what populateNodeDb re-reads per node every cycle (scheduling_algo.go:1069-1095): node_events is a list of
+    (cycle, "cordon", node), (cycle, "uncordon", node) and (cycle, "cut", node, allocatable row).  A cycle's events are applied after its job changes and before
+    round_prepare, with ONE Scheduler.nodes_patch of the nodes they name; nodes_patched=False drives the same cycles with nodes_upsert of the whole table instead (the
+    comparison, and with appended=False — jobs_set of the grown table every cycle — what any library, the oracle included, can run).  Jobs stay on a node that is
+    cordoned; a node's capacity may be cut below what its jobs hold.  Records as run_cycles_arriving."""
+    return _run_cycles_arriving(lib, sim, per_cycle, max_cycles, appended, node_events=list(node_events), nodes_patched=nodes_patched)

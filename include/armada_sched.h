@@ -410,6 +410,38 @@ int32_t ASCHED_FN(jobs_append)(asched_t*, const asched_jobs* rows);
 /* how the last jobs_append ran: out[0] rows of the call, [1] rows that entered the order (queue >= 0), [2] new shapes, [3] new gangs, [4] 1 = the per-job arrays were
    re-allocated, [5] 1 = masks and fast structure were rebuilt, [6] capacity (rows) after the call, [7] 0 (reserved).  Zeros after jobs_set. */
 int32_t ASCHED_FN(jobs_append_stats)(asched_t*, int32_t* out /*[8]*/);
+/* the per-cycle changes of resident nodes (populateNodeDb, scheduling_algo.go:1069-1095: IsUnschedulable, WithOverAllocated,
+   MarkResourceUnallocatable; a changed taint set) */
+typedef struct asched_nodes_patch_rows {
+  int32_t n;
+  const int32_t* node;            /* [n] position in the node table, each named at most once */
+  const int64_t* allocatable;     /* [n][R] or NULL = unchanged */
+  const uint8_t* unschedulable;   /* [n] or NULL = unchanged */
+  const uint8_t* over_allocated;  /* [n] or NULL = unchanged */
+  const int32_t* taint_off;       /* [n+1] CSR or NULL = taints unchanged (the unschedulable taint is never listed: the library adds it) */
+  const int32_t* taint_key; const int32_t* taint_value; const int32_t* taint_effect;
+} asched_nodes_patch_rows;
+/* The node table of the last nodes_upsert with the named fields replaced in the named rows: cordon and uncordon, WithOverAllocated, allocatable after
+   MarkResourceUnallocatable, a changed taint set — what populateNodeDb re-reads per node every cycle.
+   After a successful call every entry point answers as it would after asched_nodes_upsert of that table (rounds, the NodeDb-level calls, fit_select_batch, submit_check,
+   iterate_nodes, excluded_nodes, node_types_matching_job, num_nodes, total_resources, the getters, the evictor report, the preemption causes, the optimiser), including
+   everything nodes_upsert resets: no round is prepared and no round result is held, every plane equals allocatable, no job is bound (running jobs stay on a node that
+   becomes unschedulable: round_prepare binds them as always).  The job table, the requirement classes and the fast structure stay; the caller goes on with round_prepare.
+   n == 0 performs the resets only.
+   Two paths, chosen per call (nodes_patch_stats).  Where every patched row's new node type is one the table already has, no type gains its first or loses its last node
+   and every new allocatable value lies inside what the key layout of the table was sized for (within [0, total]; on an indexed column not above the table's largest
+   value, a multiple of the key's divisor, and a multiple of the index resolution where every resident value is one), the work is on the device and proportional to the
+   entries: no host loop over all nodes, no mask rebuild, no job-record upload.  Otherwise the patched table goes through nodes_upsert's own code.
+   Refused before anything changes — ASCHED_ERR_INVALID: no node table, n < 0, n > 0 without node, a node outside [0, N), a node named twice, a taint_off that is not
+   ascending; ASCHED_ERR_UNSUPPORTED: the table was uploaded with alloc_by_prio or node_type_override (test-fixture inputs), whatever the rebuild would refuse (a key
+   beyond 128 bits, more than LIT_TMAX node types on the literal path); ASCHED_ERR_DEVICE with "the handle is as it was" in last_error: out of device memory for the
+   entries.  Any other ASCHED_ERR_DEVICE (a failed launch or copy) is NOT such a refusal: the handle then needs asched_nodes_upsert.
+   Not this call's job, all of them asched_nodes_upsert's: adding or removing rows (the reference's dropping of an unschedulable node that holds no job included,
+   scheduling_algo.go:1070-1077), total, labels, index, id_rank. */
+int32_t ASCHED_FN(nodes_patch)(asched_t*, const asched_nodes_patch_rows* rows);
+/* how the last nodes_patch ran: out[0] entries, [1] rows whose node type changed, [2] 1 = the rebuild path ran, [3] why: 0 none, 1 a node type the table did not
+   have, 2 a node type emptied or newly populated, 3 key layout / divisor / alignment; [4..7] 0.  Zeros after nodes_upsert. */
+int32_t ASCHED_FN(nodes_patch_stats)(asched_t*, int32_t* out /*[8]*/);
 
 int32_t ASCHED_FN(txn_begin)(asched_t*);    /* nodeDb.Txn(true) (nodedb.go:353) */
 int32_t ASCHED_FN(txn_commit)(asched_t*);

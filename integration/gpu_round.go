@@ -838,6 +838,93 @@ func (g *GpuRound) PatchJobs(scheduled, preempted []*schedulercontext.JobSchedul
 	return g.check(C.asched_jobs_patch(g.h, C.int32_t(n), i32p(job), i32p(node), i32p(prio), i64p(ts)))
 }
 
+// ErrNeedsNodeUpload is what PatchNodes answers for a change the resident node table cannot take: the caller falls back to UploadNodes of the whole pool.
+var ErrNeedsNodeUpload = fmt.Errorf("the node table has to be uploaded again")
+
+// PatchNodes tells the library the per-cycle changes of uploaded nodes without re-describing the pool (asched_nodes_patch): what populateNodeDb re-reads per node
+// every cycle (scheduling_algo.go:1069-1095) — IsUnschedulable (cordon and uncordon), WithOverAllocated, the allocatable resources after MarkResourceUnallocatable
+// of what other pools' jobs hold, and the taints.  changed: the new internaltypes.Node objects of nodes UploadNodes has seen, found by id; g.nodes takes them over.
+// Taints are interned as UploadNodes interns them; a taint KEY that no uploaded node carried would get an id behind every earlier one, which is not the reference's
+// lexicographic key order (node_type.go:87-97): such a node, a node UploadNodes has not seen, and a changed total, label set or index are ErrNeedsNodeUpload — the caller
+// then calls UploadNodes with the whole pool.  The reference's dropping of an unschedulable node that holds no job (scheduling_algo.go:1070-1077) removes a row and is
+// UploadNodes' too.  Running jobs stay on a node that becomes unschedulable.  The next call is Schedule, as after UploadNodes.
+func (g *GpuRound) PatchNodes(changed []*internaltypes.Node) error {
+	n, R := len(changed), len(g.resNames)
+	if n == 0 {
+		var none C.asched_nodes_patch_rows
+		return g.check(C.asched_nodes_patch(g.h, &none))
+	}
+	known := make(map[string]bool, len(g.strs.strs))
+	for _, s := range g.strs.strs {
+		known[s] = true
+	}
+	pos, alloc := make([]int32, n), make([]int64, n*R)
+	unsched, over := make([]uint8, n), make([]uint8, n)
+	tOff, tKey, tVal, tEff := make([]int32, 1, n+1), []int32{}, []int32{}, []int32{}
+	for i, node := range changed {
+		p, ok := g.nodePos[node.GetId()]
+		if !ok || node.GetIndex() != g.nodes[p].GetIndex() {
+			return ErrNeedsNodeUpload
+		}
+		old := g.nodes[p]
+		oldTotal, newTotal := g.vec(old.GetTotalResources()), g.vec(node.GetTotalResources())
+		for r := range oldTotal {
+			if oldTotal[r] != newTotal[r] {
+				return ErrNeedsNodeUpload
+			}
+		}
+		oldLabels, newLabels := old.GetLabels(), node.GetLabels()
+		if len(oldLabels) != len(newLabels) {
+			return ErrNeedsNodeUpload
+		}
+		for k, v := range newLabels {
+			if ov, has := oldLabels[k]; !has || ov != v {
+				return ErrNeedsNodeUpload
+			}
+		}
+		pos[i] = p
+		copy(alloc[i*R:], g.vec(node.GetAllocatableResources()))
+		if node.IsUnschedulable() {
+			unsched[i] = 1
+		}
+		if node.IsOverAllocated() {
+			over[i] = 1
+		}
+		for _, t := range node.GetTaints() {
+			if t.Key == "node.kubernetes.io/unschedulable" {
+				continue // the library adds it from `unschedulable` (node.go:127-129)
+			}
+			if !known[t.Key] {
+				return ErrNeedsNodeUpload
+			}
+			tKey, tVal, tEff = append(tKey, g.strs.id(t.Key)), append(tVal, g.strs.id(t.Value)), append(tEff, effectOf(t.Effect))
+		}
+		tOff = append(tOff, int32(len(tKey)))
+	}
+	var pins runtime.Pinner
+	defer pins.Unpin()
+	var in C.asched_nodes_patch_rows
+	in.n = C.int32_t(n)
+	for _, p := range []interface{}{&pos[0], &alloc[0], &unsched[0], &over[0], &tOff[0]} {
+		pins.Pin(p)
+	}
+	for _, s := range [][]int32{tKey, tVal, tEff} {
+		if len(s) > 0 {
+			pins.Pin(&s[0])
+		}
+	}
+	in.node, in.allocatable = i32p(pos), i64p(alloc)
+	in.unschedulable, in.over_allocated = u8p(unsched), u8p(over)
+	in.taint_off, in.taint_key, in.taint_value, in.taint_effect = i32p(tOff), i32p(tKey), i32p(tVal), i32p(tEff)
+	if err := g.check(C.asched_nodes_patch(g.h, &in)); err != nil {
+		return err
+	}
+	for i, node := range changed {
+		g.nodes[pos[i]] = node
+	}
+	return nil
+}
+
 // uploadLabelValueInts tells the library which interned strings are integers (strconv.ParseInt(v, 10, 64), what
 // labels.Requirement.Matches does for Gt / Lt) — asched_set_label_value_ints.  Called before asched_jobs_set / asched_nodes_upsert
 // evaluate affinities (the static masks are rebuilt by whichever of the two comes last).
