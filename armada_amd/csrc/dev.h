@@ -193,7 +193,9 @@ struct RoundScalars {
   // dropping the stores is a change of its own, measured on its own.
   int32_t ftWanted, ftValid;   // written, never read
   int32_t statHcShort;         // picks the node engine's short path took (engine_hc.h; device only): round_stats hc_short_picks.  (The first of three reserved words: the layout stays.)
-  int32_t reserved[2];         // always 0
+  int32_t statNestGangs;       // gangs placed nested inside stream runs (round_fast.h streamNestGang): round_stats nested_gangs.  Filled by the CPU build alone (the device leaves
+                               // it 0: fastRun's loop is register-sensitive and the word is a test's witness, not a measurement).  The second of the three reserved words.
+  int32_t reserved[1];         // always 0
   int64_t statSeg[40];       // [24..39]: (profiling builds) segments of the generic iteration
   int64_t gsT;                     // (profiling builds) shader-clock ticks per segment of a fast iteration
   int64_t statClk[8];        // shader-clock ticks per phase of the round (device builds): evict, replay, pass 1, oversub evict, pass 2, unbind+results

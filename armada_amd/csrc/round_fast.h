@@ -1576,7 +1576,7 @@ DEV_NOINLINE StreamOut fastStreamRun(Dev& d, FastCtx fc, int Q, StreamIn in) {
   StreamOut out; memset(&out, 0, sizeof out); out.pend = -1; out.engSeq = in.engSeq;
   int doneQmid = 0, maxMid = 0, sessLive = 1, emittedPrev = 0;
 #ifdef ASCHED_HOSTSIM
-  static const bool nestOff = getenv("HS_NO_GANG_NEST") != nullptr;
+  const bool nestOff = getenv("HS_NO_GANG_NEST") != nullptr;   // (read per call, like HS_MG_MIN: a test turns the nested path off and on within one process)
 #elif defined(ASCHED_NO_NEST)
   const bool nestOff = true;
 #else
@@ -1942,6 +1942,11 @@ DEV NestIO streamNestGangBody(Dev& d, FastCtx fc, StreamIn in, NestIO st, int t)
   st.go = 0; st.replace = 0; st.relane = 0; st.koValid = 0; st.koA = 0; st.koX = st.koY = 0;
   if (!streamDrain(d, k, st)) return st;
   streamEnd(st.engSeq); st.sessLive = 0;
+  // The run's ring has lain over every queue's prefetch window (RREC / RJOB / RQ), and a queue whose head was the gang when the run began was never settled in it: its
+  // record still calls valid the window that a per-job iteration or the gang's own peek filled.  A gang of two or three members leaves the list position behind it inside
+  // that window, and fastGangRun's fastAdvance then took the "job" and its record from ring entry 4 t + w — an entry of another queue, placed already — as queue t's next
+  // head: the job really there was passed over.  No window outlives a session.
+  FOR_LANES(q, QCAPF) { FL.hot[q].winKind = -1; FL.hot[q].winCount = 0; }
   FOR_LANES(q, QCAPF) FL.tmpN[q] = (uint32_t)FL.tmpQ[q];   // (fastGangRun and fastStreamPrepareOne use tmpQ as scratch: the run's per-queue counts wait in the heap's scatter space)
   LANE0_PUBLISHED();
   StreamIn gi = in;
@@ -2007,6 +2012,10 @@ DEV_NOINLINE GangOut fastGangRun(Dev& d, FastCtx fc, StreamIn in, int t) {
   // CheckJobConstraints for the gang (constraints.go:121-157): anything that fails is the generic code's to report
   if (f.cordoned || in.globalTokens < (double)cnt || in.globalBurst < cnt || f.tokens < (double)cnt || f.burst < cnt) return out;
   if (UNI32((int)d.gangAllEvicted[g])) return out;
+  // the ring overwrites the prefetch windows of the first queues — the member loop below already writes its job words over them, so they are struck HERE, in front of
+  // every return that leaves those words behind (round 12: no window survives a session); they refill on demand
+  FOR_LANES(q, QCAPF) if (q * WIN < cnt + 4) { FL.hot[q].winKind = -1; FL.hot[q].winCount = 0; }
+  if (t * WIN < cnt + 4) { f.winKind = -1; f.winCount = 0; }   // (the register copy of queue t's own record, which fastAdvance below reads and stores back)
   // members: queued jobs untouched in this round (fastGangMember's conditions), no uniformity label
   int bad = 0;
   FOR_LANES(m, cnt) {
@@ -2017,8 +2026,6 @@ DEV_NOINLINE GangOut fastGangRun(Dev& d, FastCtx fc, StreamIn in, int t) {
   FOR_LANES(x, 64) FL.tmpQ[x] = bad; 
   { int any = 0; for (int x = 0; x < 64; x++) any |= UNI32(FL.tmpQ[x]); if (any || RS.awayRowPlus1) return out; }
   FOR_LANES(q, QCAPF) FL.tmpQ[q] = 0;
-  // the ring overwrites the prefetch windows of the first queues: they refill on demand
-  FOR_LANES(q, QCAPF) if (q * WIN < cnt + 4) { FL.hot[q].winKind = -1; FL.hot[q].winCount = 0; }
   if (f.sLen) { if (FLANE == 0) { FL.hot[t].sLen = 0; FL.hot[t].sPos = 0; } LANE0_PUBLISHED(); f.sLen = 0; f.sPos = 0; }
   int engSeq = in.engSeq;
   SEG(26);
@@ -2349,6 +2356,9 @@ DEV_NOINLINE int fastRun(Dev& d, Ctl& c, const PassCfg& pc, int mode, int* count
         E += so.executedEv;
         S.loopIterations += E + so.limits; S.statFastIters += E + so.limits;   // (a settled limit element is the iteration that failed its queue's rate limit)
         S.statRefills += so.refills; S.numEvictedJobs += so.evicted;
+#ifdef ASCHED_HOSTSIM
+        RS.statNestGangs += so.gangs;   // (round_stats nested_gangs: the tests' witness that a round took the nested path)
+#endif
         if (FLANE == 0) { RS.statStreamRuns++; RS.statStreamJobs += E; RS.statStreamEmitted += so.emitted; }
         LANE0_PUBLISHED();
         if (so.dropped) { S.fastActive = 0; fastDrop(d); }

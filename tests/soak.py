@@ -98,6 +98,14 @@ def main():
     orc, hs = libs()
     import scenario
     bad, refused, t0 = 0, 0, time.time()
+
+    def same_and_no_hole(wl, res):
+        """the two rounds are equal, and neither passes a queued job over (scenario.assert_no_job_passed_over: the oracle's round first — the invariant is only
+        applied where the reference itself satisfies it)"""
+        for side, r in zip(("the oracle", "the device code"), res):
+            holes = scenario.jobs_passed_over(wl, r)
+            assert not holes, f"{side} passed queued jobs over: {holes[:10]}"
+        scenario.assert_same_round(res[0], res[1])
     first = int(os.environ.get("SOAK_FIRST", "0"))   # SOAK_FIRST=k: start at seed 100000 + k; SOAK_PROGRESS=1: print every seed before it runs (a hang names its seed)
     for seed in range(100_000 + first, 100_000 + n):
         if os.environ.get("SOAK_PROGRESS"): print("seed", seed, flush=True)
@@ -111,7 +119,7 @@ def main():
                 res = []
                 for lib in (orc, hs):
                     s = W.load(lib, wl); W.prepare(s, wl); res.append(s.schedule_round())
-                scenario.assert_same_round(res[0], res[1])
+                same_and_no_hole(wl, res)
             elif kind == "away":
                 import test_z_cross_pool_away as A
                 wl = A.with_away(seed, prefer_home=seed % 2 == 0, frac=[0.1, 0.3, 0.6][seed % 3])
@@ -129,7 +137,7 @@ def main():
                 res = []
                 for lib in (orc, hs):
                     s = W.load(lib, wl); W.prepare(s, wl, fairshare_preemption_tokens=fp); res.append(s.schedule_round()); s.close()
-                scenario.assert_same_round(res[0], res[1])
+                same_and_no_hole(wl, res)
             elif kind == "offgrid":
                 rng = np.random.default_rng(seed)
                 if seed % 5 == 4:
@@ -164,7 +172,7 @@ def main():
                 res = []
                 for lib in (orc, hs):
                     s = W.load(lib, wl); W.prepare(s, wl); res.append(s.schedule_round()); s.close()
-                scenario.assert_same_round(res[0], res[1])
+                same_and_no_hole(wl, res)
             elif kind == "wide":   # more than 64 queues (round_wide.h): medium rounds, 65 ... 400 queues, evicted jobs returning, gangs, bursts, lookback limits
                 rng = np.random.default_rng(seed)
                 nn, nj, nq = int(rng.integers(60, 1200)), int(rng.integers(1500, 16000)), int(rng.choice([65, 70, 100, 130, 200, 257, 400]))
@@ -178,7 +186,7 @@ def main():
                     if lib is hs and os.environ.get("SOAK_STATS"):
                         st = s.round_stats(); print(seed, nq, {k: st[k] for k in ("fast_iterations", "generic_iterations", "stream_runs", "stream_jobs")}, len(res[-1].scheduled), len(res[-1].preempted))
                     s.close()
-                scenario.assert_same_round(res[0], res[1])
+                same_and_no_hole(wl, res)
             elif kind == "features":
                 import test_z_feature_mix as T
                 scenario.assert_same_round(T.run(orc, seed), T.run(hs, seed))
