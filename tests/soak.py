@@ -9,7 +9,8 @@
     python tests/soak.py market 2000        # market-driven rounds (asched_set_market): tied and distinct bids, gangs, away types, rate limits
     python tests/soak.py away 1500          # crowded rounds with a third of the running jobs cross-pool away jobs and "<queue>-away" contexts (tests/test_z_cross_pool_away.py)
     python tests/soak.py wide 500           # more than 64 queues: wide runs (round_wide.h) — 65 ... 400 queues, evicted jobs returning, gangs, bursts, lookback limits
-    python tests/soak.py features 400       # tests/test_z_feature_mix.py rounds (affinity, conditional away, extra column, limits ...)
+    python tests/soak.py hcedges 250        # tests/test_z_hc_engine_edges.py's recipe at random: 30 ... 1100 live dirty nodes, fragments used up and reopened, 1-8 queues, 0 / 1 / 2 non-indexed columns; bulk merge from 64 entries
+    python tests/soak.py features 400      # tests/test_z_feature_mix.py rounds (affinity, conditional away, extra column, limits ...)
     python tests/soak.py ops 3000           # tests/test_z_nodedb_op_sequences.py NodeDb-level operation sequences
     python tests/soak.py submitcheck 400    # batched SubmitChecker vs the literal sequential restatement (and 3-entry cache)
     python tests/soak.py fit 600            # fit_select_batch at every priority on occupied NodeDbs
@@ -172,6 +173,36 @@ def main():
                 res = []
                 for lib in (orc, hs):
                     s = W.load(lib, wl); W.prepare(s, wl); res.append(s.schedule_round()); s.close()
+                same_and_no_hole(wl, res)
+            elif kind == "hcedges":   # tests/test_z_hc_engine_edges.py's recipe for a chosen number of live dirty nodes, drawn at random; the bulk merge from 64 entries on, so that the split engine (engine_hc.h) serves the run on the device
+                import test_z_hc_engine_edges as T
+                os.environ.setdefault("HS_MG_MIN", "64"); os.environ.setdefault("ASCHED_MERGE_MIN", "64")
+                rng = np.random.default_rng(seed)
+                n_big = int(rng.integers(30, 1101)) if rng.random() < 0.5 else int(rng.choice([rng.integers(30, 130), rng.integers(1000, 1101)]))   # (half of the seeds near H's size or the list's capacity)
+                n_small, nq, E = int(rng.integers(0, 600)), int(rng.integers(1, 9)), int(rng.integers(0, 3))
+                reqs = [T.BIG] * n_big
+                for _ in range(int(rng.integers(0, 200))):   # fragments used up and nodes opened in between: slots of the cold set given up and reused
+                    reqs += [T.FILL] * nq + [T.BIG] * nq if rng.random() < 0.5 else [T.FILL] * int(rng.integers(1, 4))
+                reqs += [T.ONE] * n_small
+                if rng.random() < 0.3:   # a job that fits nowhere ends the session; a second run behind it
+                    reqs += [T.NEVER if rng.random() < 0.5 else [256 * W.Gi, 32_000, 10 * W.Gi, 0]] + [T.ONE] * int(rng.integers(0, 300))
+                n_nodes = sum(1 for r in reqs if r is T.BIG) + int(rng.integers(0, 60))
+                wl = T._pool(n_nodes, reqs, nq, node=(256 * W.Gi, 32_000, 1024 * W.Gi, 2 if E == 2 else 0))
+                if E == 2:
+                    ones = np.nonzero(wl.job_req[:, W.CPU] == 1_000)[0]
+                    wl.job_req[ones[rng.random(len(ones)) < 0.3], W.GPU] = 1
+                    wl.job_req[ones[rng.random(len(ones)) < 0.3], W.EPH] = 200 * W.Gi
+                    T._two_extras(wl)
+                elif E == 0:
+                    T._all_indexed(wl)
+                res = []
+                for lib in (orc, hs):
+                    s = W.load(lib, wl); W.prepare(s, wl)
+                    if lib is hs: s.set_deadline(20.0)
+                    res.append(s.schedule_round())
+                    if lib is hs and os.environ.get("SOAK_STATS"):
+                        st = s.round_stats(); print(seed, n_big, nq, E, {k: st[k] for k in ("l0_max", "l0_overflows", "stream_runs", "stream_jobs", "hc_short_picks")}, len(res[-1].scheduled))
+                    s.close()
                 same_and_no_hole(wl, res)
             elif kind == "wide":   # more than 64 queues (round_wide.h): medium rounds, 65 ... 400 queues, evicted jobs returning, gangs, bursts, lookback limits
                 rng = np.random.default_rng(seed)
