@@ -254,7 +254,7 @@ ALL_SYMBOLS = [
     "excluded_nodes", "set_excluded_nodes",
     "round_preemption_causes", "preemption_join",
     "set_evictor_report", "round_evictor_report",
-    "jobs_patch", "jobs_append", "jobs_append_stats",
+    "jobs_patch", "jobs_append", "jobs_append_stats", "jobs_delete", "jobs_delete_stats",
     "nodes_patch", "nodes_patch_stats",
 ]
 # entry points the CPU oracle does not implement (it is the single-process checker): the communicator and the collectives that run on it, and the join of a
@@ -263,6 +263,7 @@ OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_d
                     "round_preemption_causes", "preemption_join",
                     "set_evictor_report", "round_evictor_report",   # (recorded by passes between the launches of the split round: tests/test_z_evictor_report.py restates it)
                     "jobs_patch", "jobs_append", "jobs_append_stats",   # (an incremental jobs_set: the oracle is given the whole table; tests/test_z_jobs_patch.py, test_z_jobs_append.py)
+                    "jobs_delete", "jobs_delete_stats",                 # (likewise: tests/test_z_jobs_delete.py)
                     "nodes_patch", "nodes_patch_stats"}                  # (an incremental nodes_upsert, likewise: tests/test_z_nodes_patch.py)
 PREEMPTION_UNKNOWN, PREEMPTION_UNKNOWN_GANG, PREEMPTION_FAIRSHARE, PREEMPTION_URGENCY, PREEMPTION_OPTIMISER = 1, 2, 3, 4, 5   # ASCHED_PREEMPTION_* (context.PreemptionType)
 # ASCHED_EVR_* bits of asched_evictor_report.node_reasons, in bit order: the reference's reason strings in alphabetical order (makeNodePreemptiblityStats sorts them)
@@ -460,6 +461,8 @@ class Library:
         f("jobs_patch", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _i64p])
         f("jobs_append", C.c_int32, [C.c_void_p, C.POINTER(CJobs)])
         f("jobs_append_stats", C.c_int32, [C.c_void_p, _i32p])
+        f("jobs_delete", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p])
+        f("jobs_delete_stats", C.c_int32, [C.c_void_p, _i32p])
         f("nodes_patch", C.c_int32, [C.c_void_p, C.POINTER(CNodesPatch)])
         f("nodes_patch_stats", C.c_int32, [C.c_void_p, _i32p])
         f("round_preemption_causes", C.c_int32, [C.c_void_p, C.POINTER(CPreemptionCause), C.c_int32, _i32p, C.c_int32, _i32p])
@@ -770,6 +773,30 @@ class Scheduler:
         out = np.zeros(8, np.int32)
         self._check(fn(self.h, _ptr(out, C.c_int32)))
         return dict(rows=int(out[0]), in_order=int(out[1]), new_shapes=int(out[2]), new_gangs=int(out[3]), reallocated=int(out[4]), rebuilt=int(out[5]), capacity=int(out[6]))
+
+    def jobs_delete(self, rows, want_map=False):
+        """syncState's delete of the jobs in a terminal state: rows `rows` leave the resident job table; the others keep their order and are renumbered densely (new id =
+        old id - deleted rows below it).  Leaves the handle as jobs_set of the reduced table would; go on with round_prepare.  want_map: returns the old -> new id map
+        (int32 [rows before the call], -1 for a deleted row), downloaded from the device."""
+        fn = self._preemption_fn("jobs_delete")
+        jb = _arr(rows, np.int32).reshape(-1)
+        buf = None
+        if want_map:   # downloaded into a buffer this object keeps: the driver's copy into freshly allocated host pages took 25 ms more for 6 MB on the MI355X (profiles/r14_jobs_delete.txt)
+            buf = getattr(self, "_id_map_buf", None)
+            if buf is None or len(buf) < self.num_jobs:
+                buf = self._id_map_buf = np.empty(max(self.num_jobs, 1), np.int32)
+            buf[:self.num_jobs] = -2
+        self._check(fn(self.h, len(jb), _ptr(jb, C.c_int32), _ptr(buf, C.c_int32)))
+        new_id = buf[:self.num_jobs].copy() if want_map else None
+        self.num_jobs -= len(jb)
+        return new_id
+
+    def jobs_delete_stats(self):
+        """how the last jobs_delete ran: rows deleted, rows that left the order, gangs emptied, shapes emptied, rows after the call, capacity"""
+        fn = self._preemption_fn("jobs_delete_stats")
+        out = np.zeros(8, np.int32)
+        self._check(fn(self.h, _ptr(out, C.c_int32)))
+        return dict(rows=int(out[0]), in_order=int(out[1]), gangs_emptied=int(out[2]), shapes_emptied=int(out[3]), num_jobs=int(out[4]), capacity=int(out[5]))
 
     def nodes_patch(self, node, allocatable=None, unschedulable=None, over_allocated=None, taints=None):
         """what populateNodeDb re-reads per node every cycle: rows `node` of the resident node table get a new `allocatable` ([n][R]), `unschedulable` / `over_allocated`

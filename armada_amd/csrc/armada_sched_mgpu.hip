@@ -470,6 +470,47 @@ extern "C" int asched_internal_ja_fill(const Dev* d, const JaArgs* a, hipStream_
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ------------------------------------------------------------------------------------------------ rows leave the resident job table (kernels_jobs_delete.h)
+// mark / unmark, the three gathers (each reads the survivors' list once), the renumbering of a compacted list; the scans are plat_compact's kernels
+#define JD_FN __device__ static inline
+#include "kernels_jobs_delete.h"
+__global__ __launch_bounds__(MG_THREADS) void k_jd_mark(JdArgs a, int value) {
+  long long i = MG_IDX();
+  if (i < a.n) jdMark(a, (int)i, (uint8_t)value);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_jd_narrow(JdArgs a) {
+  long long i = MG_IDX();
+  if (i < a.M1) jdNarrow(a, (int)i);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_jd_req(JdArgs a) {
+  long long e = MG_IDX();
+  if (e < (long long)a.M1 * a.R) jdReq(a, e);
+}
+// eight consecutive lanes move one 128-byte record: a wave reads eight records, each a whole aligned line, and writes 1 KB of consecutive bytes
+__global__ __launch_bounds__(MG_THREADS) void k_jd_rec(JdArgs a) {
+  long long t = MG_IDX();
+  if (t < (long long)a.M1 * 8) jdRec(a, t);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_jd_remap(JdArgs a, int32_t* list, int n) {
+  long long i = MG_IDX();
+  if (i < n) jdRemap(a, list, (int)i);
+}
+extern "C" int asched_internal_jd_mark(const JdArgs* a, int value, hipStream_t st) {
+  if (a->n > 0) hipLaunchKernelGGL(k_jd_mark, dim3(mgBlocks(a->n)), dim3(MG_THREADS), 0, st, *a, value);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_jd_gather(const JdArgs* a, hipStream_t st) {
+  if (a->M1 <= 0) return 0;
+  hipLaunchKernelGGL(k_jd_narrow, dim3(mgBlocks(a->M1)), dim3(MG_THREADS), 0, st, *a);
+  hipLaunchKernelGGL(k_jd_req, dim3(mgBlocks((long long)a->M1 * a->R)), dim3(MG_THREADS), 0, st, *a);
+  if (a->inRec) hipLaunchKernelGGL(k_jd_rec, dim3(mgBlocks((long long)a->M1 * 8)), dim3(MG_THREADS), 0, st, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_jd_remap(const JdArgs* a, int32_t* list, int n, hipStream_t st) {
+  if (n > 0) hipLaunchKernelGGL(k_jd_remap, dim3(mgBlocks(n)), dim3(MG_THREADS), 0, st, *a, list, n);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ------------------------------------------------------------------------------------------------ cordons and capacity changes of resident nodes (kernels_nodes_patch.h)
 #define NP_FN __device__ static inline
 #include "kernels_nodes_patch.h"

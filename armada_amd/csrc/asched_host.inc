@@ -23,12 +23,14 @@
 #include <vector>
 #include <atomic>
 #include <chrono>
+#include <functional>
 #include <thread>
 #include "kernels_fit_lit.h"   // FitLitIdx and, in the CPU build of the tests, plat_run_fit_batch_lit
 #include "kernels_preempt_join.h"   // PjArgs and, in the CPU build of the tests, plat_preempt_join
 #include "kernels_evict_report.h"   // EvrArgs and, in the CPU build of the tests, plat_evict_report
 #include "kernels_jobs_patch.h"     // JpArgs and, in the CPU build of the tests, plat_jobs_patch
 #include "kernels_jobs_append.h"    // JaArgs and, in the CPU build of the tests, plat_jobs_append
+#include "kernels_jobs_delete.h"    // JdArgs and, in the CPU build of the tests, plat_jobs_delete
 #include "kernels_nodes_patch.h"    // NpArgs and, in the CPU build of the tests, plat_nodes_patch
 
 namespace {
@@ -247,6 +249,11 @@ struct asched {
   double jaMs[3] = {0, 0, 0};        // device ms of row fill / sort / merge of the last append (ASCHED_JA_TIMES=1)
   DevBufs jpBufs; char* jpScratch = nullptr; size_t jpScratchBytes = 0;   // the entries, the sort array and the kept list of a patch: one block, kept between calls and only ever grown
   double jpMs[4] = {0, 0, 0, 0};     // device ms of the four passes of the last patch (ASCHED_JP_TIMES=1)
+  // ---- asched_jobs_delete (kernels_jobs_delete.h).  A scheduling-key shape that lost its last row keeps its id with shapeRow[s] == -1 (an append that uses it goes
+  // through the rebuild path); a gang that lost its last row keeps its dense id with no members and leaves gangMap
+  int32_t jdStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_delete_stats
+  double jdMs[5] = {0, 0, 0, 0, 0};  // device ms of mark / scan / gather / order / gang lists of the last delete (ASCHED_JD_TIMES=1)
+  double jdHostMs = 0;               // wall ms of the host's compaction of its mirrors in the last delete
   // ---- asched_nodes_patch (kernels_nodes_patch.h).  What nodes_upsert was given and no other mirror holds (index, allocatable, over_allocated: N x (9 + 8R) bytes;
   // total, id_rank, unschedulable, taints and labels are nodeTotal, nodeIdRank, nodeUnsched, nodeTaints and nodeLabels above): the rebuild path of a patch runs
   // nodes_upsert's own code on the patched table.  typeByCanon: canonical string of a node type -> position in `types`
@@ -1364,7 +1371,7 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
   d.unfeasible = h->jobBufs.alloc<uint8_t>(std::max(h->S, 1)); d.unfeasibleReason = h->jobBufs.alloc<int32_t>(std::max(h->S, 1));
   h->jobCap = M; h->gangCap = h->G; h->gangArrCap = (size_t)gangOff[h->G + 1]; h->gangJobsCap = gangJobs.size(); h->gangOffCap = gangOff.size();
   h->ordCap = ord.size(); h->ordSpareCap = 0; h->ordOffCap = h->ordOffHost.size(); h->gangOffHost = gangOff;
-  memset(h->jaStats, 0, sizeof h->jaStats);
+  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jdStats, 0, sizeof h->jdStats);
   h->jobsSet = true; h->prepared = false;
   h->jQPrioHost.swap(qprio); h->jSubmitHost.swap(submit); h->jRunTsHost.swap(runTs);   // (asched_jobs_patch uploads them when it is first called; nothing is copied here)
   prof.lap("uploads + per-job state allocation");
@@ -1546,6 +1553,7 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
   const int G1 = G0 + (int)newGangs.size();
   // the shape of every row: a hash over the shapes the handle holds; new shapes get the next ids in order of first occurrence (undone by `undo` on a later refusal)
   if (m > 0 && h->shapeTable.empty()) jaShapeTableBuild(h, (size_t)S0);
+  std::vector<int32_t> revived, shapeRowSaved;   // shapes without a resident row that this call gives one, and shapeRow as it was (for `undo`)
   for (int i = 0; i < m; i++) {
     const int64_t* req = rows->req + (size_t)i * R;
     const uint64_t hv = jaShapeHash(aCls[i], aPc[i], req, R);
@@ -1565,14 +1573,19 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
       if ((size_t)(s + 1) * 2 > cap) jaShapeTableBuild(h, (size_t)(s + 1) * 2);
     } else aShape[i] = h->shapeTable[pos];
     if (!aAligned[i]) h->shapeUnaligned[aShape[i]] = 1;   // (a property of the shape: a resident shape's flag is already what this row says)
-    if (aShape[i] < S0) aSrc[i] = h->shapeRow[aShape[i]];
+    if (aShape[i] < S0) {
+      int32_t& first = h->shapeRow[aShape[i]];
+      if (first < 0) { if (revived.empty()) shapeRowSaved = h->shapeRow; revived.push_back(aShape[i]); first = M + i; }   // asched_jobs_delete emptied the shape: no resident row to copy a JobRec from
+      else if (first < M) aSrc[i] = first;
+    }
   }
   const int S1 = (int)h->shapeClass.size();
-  const bool newShapes = S1 > S0;
+  const bool newShapes = S1 > S0 || !revived.empty();   // (a revived shape takes the path of a new one: the records are rebuilt from the mirrors, DESIGN 3.12)
   const DevCfg cfgSaved = d.cfg; const bool keyWideSaved = h->keyWide, keyCoarseSaved = h->keyCoarse;
   bool mirrorsGrown = false;
   auto undo = [&]() {   // a refusal after the shape lookup: the handle exactly as it was
     if (!newShapes) return;
+    if (!revived.empty()) h->shapeRow = shapeRowSaved;
     h->shapeClass.resize(S0); h->shapePc.resize(S0); h->shapeReq.resize((size_t)S0 * R); h->shapeRow.resize(S0); h->shapeUnaligned.resize(S0);
     h->shapeTable.clear(); h->shapeHash.clear();
     if (mirrorsGrown) {
@@ -1801,6 +1814,199 @@ int32_t asched_jobs_append_stats(asched_t* h, int32_t* out) {
   if (!h || !out) return ASCHED_ERR_INVALID;
   plat_enter(h->plat);
   for (int k = 0; k < 8; k++) out[k] = h->jaStats[k];
+  return 0;
+}
+
+// ---- asched_jobs_delete (kernels_jobs_delete.h): syncState's delete of the jobs in a terminal state (scheduler.go:539-549; Txn.BatchDelete / delete,
+// jobdb/jobdb.go:941-990).  The named rows leave the table, the others keep their order and are renumbered densely; the handle is left as asched_jobs_set of the reduced
+// table would leave it.  The device moves every static per-job array, the order and the gang lists; the host compacts its mirrors — the one O(M) host step.  Shape ids,
+// dense gang ids, the key layout and the other aggregates of the table stay: wider than the reduced table needs or equal, never wrong (DESIGN 3.12).
+int32_t asched_jobs_delete(asched_t* h, int32_t n, const int32_t* job, int32_t* new_id) {
+  if (!h) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  const int M = h->M, R = h->R, G = h->G;
+  Dev& d = h->dev;
+  // ---- every refusal before anything changes
+  if (!h->jobsSet || h->jQPrioHost.size() != (size_t)M || h->jSubmitHost.size() != (size_t)M || h->jRunTsHost.size() != (size_t)M || h->jNode.size() != (size_t)M ||
+      h->gangOffHost.size() != (size_t)G + 2)
+    return fail(h, ASCHED_ERR_INVALID, "jobs_delete: no job table on this handle (jobs_set first)");
+  if (n < 0 || (n > 0 && !job)) return fail(h, ASCHED_ERR_INVALID, "jobs_delete: bad arguments");
+  if (h->mkJobsBuilt) return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_delete: the job set carries the market order, which ranks every job against every other (jobs_set instead)");
+  if (h->jpSeen.size() != (size_t)M) h->jpSeen.assign(M, 0);
+  std::vector<uint8_t>& gone = h->jpSeen;   // [M] the rows of this call, until the mirrors are compacted
+  int nT = 0, nGang = 0;
+  { int marked = 0;
+    const char* why = nullptr;
+    for (int i = 0; i < n; i++) {
+      const int j = job[i];
+      if (j < 0 || j >= M) { why = "jobs_delete: a row outside the job table"; break; }
+      if (gone[j]) { why = "jobs_delete: a row named twice"; break; }
+      gone[j] = 1; marked = i + 1;
+      if (h->jQueue[j] >= 0) nT++;
+      if (h->jGangDense[j] >= 0) nGang++;
+    }
+    if (why) { for (int i = 0; i < marked; i++) gone[job[i]] = 0; return fail(h, ASCHED_ERR_INVALID, why); }
+  }
+  if (n > 0 && n == M) {
+    for (int i = 0; i < n; i++) gone[job[i]] = 0;
+    return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_delete: every row of the table is named (a handle holds at least one job: jobs_set of the next table instead)");
+  }
+  const int M1 = M - n;
+  const int total = h->ordOffHost.empty() ? 0 : h->ordOffHost[std::min<size_t>((size_t)h->ordQueues, h->ordOffHost.size() - 1)], total1 = total - nT;
+  const int gangLen = h->gangOffHost[G], gangLen1 = gangLen - nGang;
+  const size_t cap = std::max<size_t>(h->jobCap, (size_t)M);
+  const bool haveRec = d.f.structOk && d.jrec;
+  // ---- the scratch and every new block before anything changes: running out of device memory here is a refusal too.  The scratch: the entries | the survivors' list |
+  // the new ids | the compacted gang lists.  The blocks: one per static per-job array, of the table's capacity (capacities do not shrink); the old ones are released at the end
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t oSrc = up(sizeof(int32_t) * (size_t)n), oNew = oSrc + up(sizeof(int32_t) * (size_t)M), oGang = oNew + up(sizeof(int32_t) * (size_t)M),
+               need = oGang + up(sizeof(int32_t) * (size_t)gangLen);
+  struct Block { DevBufs* owner; void** slot; size_t bytes; void* fresh; };
+  std::vector<Block> blocks;
+  char* scratchNew = nullptr;
+  const bool buildJp = n > 0 && !h->jp.built;
+  const bool needSpare = n > 0 && (!h->jp.ordSpare || h->ordSpareCap < (size_t)total1);
+  int32_t* ordSpareNew = nullptr;   // (its block is the one whose slot is this variable)
+  if (n > 0) {
+    auto stage = [&](DevBufs* owner, void* slot, size_t bytes) { blocks.push_back({owner, (void**)slot, std::max<size_t>(bytes, 1), nullptr}); };
+    void* s32[] = {&d.jQueue, &d.jPc, &d.jShape, &d.jGang, &d.jGangCard, &d.jGangUni, &d.jNode0, &d.jRunPrio, &h->jp.qprio};
+    for (void* sl : s32) stage(&h->jobBufs, sl, cap * 4);
+    if (d.jAway) stage(&h->jobBufs, &d.jAway, cap);
+    stage(&h->jobBufs, &d.jAligned, cap); stage(&h->jobBufs, &d.jLeaseMs, cap * 8); stage(&h->jobBufs, &h->jp.submit, cap * 8); stage(&h->jobBufs, &h->jp.runTs, cap * 8);
+    stage(&h->jobBufs, &d.jReq, cap * 8 * R);
+    if (haveRec) stage(&h->fastBufs, &d.jrec, sizeof(JobRec) * cap);
+    if (buildJp) stage(&h->jobBufs, &h->jp.keep, cap);
+    if (needSpare) stage(&h->jobBufs, &ordSpareNew, std::max<size_t>((size_t)total, h->ordCap) * 4);
+    bool ok = true;
+    if (h->jpScratchBytes < need) { scratchNew = (char*)plat_malloc(need + need / 4); ok = scratchNew != nullptr; }
+    for (auto& b : blocks) { if (!ok) break; b.fresh = plat_malloc(b.bytes); ok = b.fresh != nullptr; }
+    if (!ok) {
+      (void)plat_take_failure();
+      for (auto& b : blocks) if (b.fresh) plat_free(b.fresh);
+      if (scratchNew) plat_free(scratchNew);
+      for (int i = 0; i < n; i++) gone[job[i]] = 0;
+      return fail(h, ASCHED_ERR_DEVICE, "jobs_delete: out of device memory for the scratch and the compacted job table; the handle is as it was");
+    }
+  }
+  // ---- what jobs_set resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the job table half compacted: asched_jobs_set before anything else)
+  h->haveRoundResult = false; h->stateEpoch++;
+  { h->dev.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
+    int32_t zero = 0;
+    plat_h2d(&h->dev.rs->fastActive, &zero, sizeof zero);
+    plat_h2d(&h->dev.rs->l0SaveCount, &zero, sizeof zero); }
+  h->prepared = false; h->evrSized = false;
+  for (int k = 0; k < 5; k++) h->jdMs[k] = 0;
+  h->jdHostMs = 0;
+  int gangsEmptied = 0, shapesEmptied = 0;
+  if (n > 0) {
+    if (scratchNew) { h->jpBufs.freeAll(); h->jpScratch = scratchNew; h->jpScratchBytes = need + need / 4; h->jpBufs.ptrs.push_back({scratchNew, need + need / 4}); }
+    auto fresh = [&](void* slot) -> void* { for (auto& b : blocks) if ((void*)b.slot == slot) return b.fresh; return nullptr; };
+    if (needSpare) ordSpareNew = (int32_t*)fresh(&ordSpareNew);
+    if (buildJp) plat_memset(fresh(&h->jp.keep), 1, cap);   // first incremental call of this job table: the keep flags (the order-key inputs are uploaded below, compacted)
+    JdArgs a; memset(&a, 0, sizeof a);
+    a.M = M; a.M1 = M1; a.n = n; a.R = R; a.total = total; a.total1 = total1; a.gangLen = gangLen; a.gangLen1 = gangLen1;
+    int32_t* e32 = (int32_t*)h->jpScratch;
+    plat_h2d(e32, job, sizeof(int32_t) * (size_t)n);
+    a.job = e32; a.keep = buildJp ? (uint8_t*)fresh(&h->jp.keep) : h->jp.keep;
+    a.src = (int32_t*)(h->jpScratch + oSrc); a.newId = (uint32_t*)(h->jpScratch + oNew);
+    { const int32_t* in[JD_N32] = {d.jQueue, d.jPc, d.jShape, d.jGang, d.jGangCard, d.jGangUni, d.jNode0, d.jRunPrio, buildJp ? nullptr : (const int32_t*)h->jp.qprio};   // (the queue priorities move as the 4-byte words they are)
+      void* sl[JD_N32] = {&d.jQueue, &d.jPc, &d.jShape, &d.jGang, &d.jGangCard, &d.jGangUni, &d.jNode0, &d.jRunPrio, &h->jp.qprio};
+      for (int k = 0; k < JD_N32; k++) { a.in32[k] = in[k]; a.out32[k] = (int32_t*)fresh(sl[k]); } }
+    a.inAway = d.jAway; a.outAway = (uint8_t*)fresh(&d.jAway); a.inAligned = d.jAligned; a.outAligned = (uint8_t*)fresh(&d.jAligned);
+    a.inLease = d.jLeaseMs; a.outLease = (int64_t*)fresh(&d.jLeaseMs);
+    a.inSubmit = buildJp ? nullptr : h->jp.submit; a.outSubmit = (int64_t*)fresh(&h->jp.submit); a.inRunTs = buildJp ? nullptr : h->jp.runTs; a.outRunTs = (int64_t*)fresh(&h->jp.runTs);
+    a.inReq = d.jReq; a.outReq = (int64_t*)fresh(&d.jReq);
+    if (haveRec) { a.inRec = d.jrec; a.outRec = (JobRec*)fresh(&d.jrec); }
+    a.ordIn = d.ordAll; a.ordOut = ordSpareNew ? ordSpareNew : h->jp.ordSpare;
+    a.gangIn = d.gangJobs; a.gangOut = (int32_t*)(h->jpScratch + oGang);
+    int prc = plat_take_failure() ? -1 : plat_jobs_delete(d, a);
+    if (prc) {
+      for (auto& b : blocks) plat_free(b.fresh);
+      gone.assign(M, 0);
+      return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+    }
+    plat_jobs_delete_ms(h->jdMs);
+    if (gangLen1 > 0) plat_d2d(d.gangJobs, a.gangOut, sizeof(int32_t) * (size_t)gangLen1);
+    if (new_id) {   // old -> new: the scan's exclusive prefix, -1 for the rows that left
+      plat_d2h(new_id, a.newId, sizeof(int32_t) * (size_t)M);
+      for (int i = 0; i < n; i++) new_id[job[i]] = -1;
+    }
+    // the blocks: swapped in, the old ones released (plat_jobs_delete has waited for the device)
+    auto release = [&](DevBufs* owner, void* p) {
+      for (size_t k = 0; k < owner->ptrs.size(); k++) if (owner->ptrs[k].first == p) { owner->ptrs.erase(owner->ptrs.begin() + k); break; }
+      plat_free(p);
+    };
+    if (ordSpareNew) { if (h->jp.ordSpare) release(&h->jobBufs, h->jp.ordSpare); h->jp.ordSpare = nullptr; }
+    for (auto& b : blocks) {
+      if ((void*)b.slot != (void*)&ordSpareNew) { if (*b.slot) release(b.owner, *b.slot); *b.slot = b.fresh; }
+      b.owner->ptrs.push_back({b.fresh, b.bytes});
+    }
+    if (ordSpareNew) { h->jp.ordSpare = ordSpareNew; h->ordSpareCap = std::max<size_t>((size_t)total, h->ordCap); }
+    if (total > 0) { std::swap(d.ordAll, h->jp.ordSpare); std::swap(h->ordCap, h->ordSpareCap); }
+    // ---- the host mirrors, compacted in place (row order is kept: every element moves down or stays), one array per host thread; then what the host derives from them
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int32_t> goneOfQueue((size_t)h->ordQueues + 2, 0), goneOfGang((size_t)G + 1, 0);
+    for (int i = 0; i < n; i++) {
+      const int j = job[i];
+      if (h->jQueue[j] >= 0 && h->jQueue[j] < h->ordQueues) goneOfQueue[(size_t)h->jQueue[j] + 1]++;
+      if (h->jGangDense[j] >= 0) goneOfGang[h->jGangDense[j]]++;
+    }
+    { auto squeeze = [&](auto& v, size_t w) {
+        size_t o = 0;
+        for (size_t i = 0; i < (size_t)M; i++) if (!gone[i]) { if (o != i) for (size_t x = 0; x < w; x++) v[o * w + x] = v[i * w + x]; o++; }
+        v.resize((size_t)M1 * w);
+      };
+      std::vector<std::function<void()>> tasks = {
+        [&] { squeeze(h->jQueue, 1); }, [&] { squeeze(h->jPc, 1); }, [&] { squeeze(h->jReqClass, 1); }, [&] { squeeze(h->jShape, 1); }, [&] { squeeze(h->jNode, 1); },
+        [&] { squeeze(h->jRunPrio, 1); }, [&] { squeeze(h->jGangDense, 1); }, [&] { squeeze(h->jAway, 1); }, [&] { squeeze(h->jGangUniKey, 1); }, [&] { squeeze(h->jReq, (size_t)R); },
+        [&] { squeeze(h->jQPrioHost, 1); }, [&] { squeeze(h->jSubmitHost, 1); }, [&] { squeeze(h->jRunTsHost, 1); }};
+      std::atomic<size_t> next{0};
+      auto work = [&] { for (;;) { size_t c = next.fetch_add(1); if (c >= tasks.size()) return; tasks[c](); } };
+      const int T = M < 65536 ? 1 : std::min<int>(hostThreads(), (int)tasks.size());
+      std::vector<std::thread> th;
+      for (int t = 1; t < T; t++) th.emplace_back(work);
+      work();
+      for (auto& x : th) x.join(); }
+    gone.assign(M1, 0);
+    { std::vector<int32_t> row(h->shapeRow.size(), -1);   // the first surviving row of every shape
+      for (int i = 0; i < M1; i++) { int32_t& r = row[h->jShape[i]]; if (r < 0) r = i; }
+      for (size_t s = 0; s < row.size(); s++) if (row[s] < 0 && h->shapeRow[s] >= 0) shapesEmptied++;
+      h->shapeRow.swap(row); }
+    { std::vector<int32_t> off((size_t)G + 2, 0);
+      for (int g = 0; g < G; g++) off[g + 1] = off[g] + (h->gangOffHost[g + 1] - h->gangOffHost[g]) - goneOfGang[g];
+      off[G + 1] = off[G] + std::max(M1, 1);   // scratch gang slot for schedule_many
+      for (auto it = h->gangMap.begin(); it != h->gangMap.end();) {   // an emptied gang: its (queue, gang id) may come again as a new gang
+        const int g = it->second;
+        if (off[g + 1] == off[g] && h->gangOffHost[g + 1] > h->gangOffHost[g]) { it = h->gangMap.erase(it); gangsEmptied++; } else ++it;
+      }
+      plat_h2d(d.gangOff, off.data(), off.size() * 4);
+      h->gangOffHost.swap(off); }
+    { std::vector<int32_t> off(h->ordOffHost.size(), total1);
+      int below = 0;
+      for (int q = 0; q <= h->ordQueues && (size_t)q < off.size(); q++) { below += goneOfQueue[q]; off[q] = h->ordOffHost[q] - below; }
+      plat_h2d(d.ordAllOff, off.data(), off.size() * 4);
+      h->ordOffHost.swap(off); }
+    if (buildJp) {   // the order-key inputs become resident, already compacted
+      plat_h2d(h->jp.qprio, h->jQPrioHost.data(), (size_t)M1 * 4); plat_h2d(h->jp.submit, h->jSubmitHost.data(), (size_t)M1 * 8); plat_h2d(h->jp.runTs, h->jRunTsHost.data(), (size_t)M1 * 8);
+      h->jp.built = true;
+    }
+    h->M = M1; d.cfg.M = M1;
+    h->jdHostMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (const char* e = getenv("ASCHED_JD_TIMES")) if (e[0] == '1')
+      fprintf(stderr, "[asched jobs_delete] jobs %d entries %d in the order %d: mark %.4f ms, scan %.4f ms, gather %.4f ms, order %.4f ms, gang lists %.4f ms, host mirrors %.4f ms\n", M, n, nT,
+              h->jdMs[0], h->jdMs[1], h->jdMs[2], h->jdMs[3], h->jdMs[4], h->jdHostMs);
+  }
+  if (n == 0 && new_id) for (int i = 0; i < M; i++) new_id[i] = i;   // (no pass ran: every row keeps its id)
+  h->jdStats[0] = n; h->jdStats[1] = nT; h->jdStats[2] = gangsEmptied; h->jdStats[3] = shapesEmptied; h->jdStats[4] = M1; h->jdStats[5] = (int32_t)h->jobCap; h->jdStats[6] = h->jdStats[7] = 0;
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  // job dynamic state: everything unbound until round_prepare, as at the end of jobs_set
+  d.cfg.Q = 0;
+  return resetDynamicState(h, M1);
+}
+int32_t asched_jobs_delete_stats(asched_t* h, int32_t* out) {
+  if (!h || !out) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  for (int k = 0; k < 8; k++) out[k] = h->jdStats[k];
   return 0;
 }
 

@@ -95,6 +95,12 @@ static void plat_jobs_patch_ms(double* out /*[4]*/);   // measurement hook: devi
 struct JaArgs;
 static int plat_jobs_append(Dev& d, JaArgs& a);
 static void plat_jobs_append_ms(double* out /*[3]*/);   // measurement hook: device ms of row fill / sort / merge of the last call (events around them when ASCHED_JA_TIMES=1, else zeros)
+// rows leave the resident job table (kernels_jobs_delete.h): mark, scan (plat_compact over the keep flags into a.src / a.newId; its count must be a.M1), the gather of the
+// static per-job arrays into the blocks of a.out*, the compaction and renumbering of the order (a.ordOut) and of the gang lists (a.gangOut), unmark.  Synchronous: everything
+// is complete on return.  The CPU build's definition sits in kernels_jobs_delete.h.
+struct JdArgs;
+static int plat_jobs_delete(Dev& d, JdArgs& a);
+static void plat_jobs_delete_ms(double* out /*[5]*/);   // measurement hook: device ms of mark / scan / gather / order / gang lists of the last call (events around them when ASCHED_JD_TIMES=1, else zeros)
 // cordons and capacity changes of resident nodes (kernels_nodes_patch.h): the scatter of the entries, then the touched words of the class, shape and type masks.
 // Synchronous: node arrays and masks are complete on return.  The CPU build's definition sits in kernels_nodes_patch.h.
 struct NpArgs;

@@ -34,6 +34,7 @@ struct PlatCtx {
   hipEvent_t evrEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool evrTimed[3] = {false, false, false};   // ASCHED_EVR_TIMES=1: around the passes of the evictor report
   hipEvent_t jaEv[4] = {nullptr, nullptr, nullptr, nullptr}; bool jaTimed = false;   // ASCHED_JA_TIMES=1: around the passes of the job-table append
   hipEvent_t jpEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool jpTimed = false;   // ASCHED_JP_TIMES=1: around the passes of the job-table patch
+  hipEvent_t jdEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool jdTimed = false;   // ASCHED_JD_TIMES=1: around the passes of the job-table delete
   hipEvent_t npEv[3] = {nullptr, nullptr, nullptr}; bool npTimed = false;   // ASCHED_NP_TIMES=1: around the passes of the node-table patch
   float roundTotalMs = 0.f, roundControlMs = 0.f; int roundLaunches = 0;
   int32_t* cmpScratch = nullptr; size_t cmpScratchInts = 0;   // block counts + total of the grid-wide compaction
@@ -254,6 +255,7 @@ static void plat_close(PlatCtx* c) {
   for (hipEvent_t e : c->jpEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->jaEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->npEv) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->jdEv) if (e) (void)hipEventDestroy(e);
   if (c->helpBox) (void)hipFree(c->helpBox);
   if (c->cmpScratch) (void)hipFree(c->cmpScratch);
   if (c->optScratch) (void)hipFree(c->optScratch);
@@ -942,6 +944,57 @@ static int plat_jobs_append(Dev& d, JaArgs& a) {
 static void plat_jobs_append_ms(double* out) {
   hipEvent_t* ev = jaEvents();
   for (int k = 0; k < 3; k++) { float ms = 0.f; if (ev && t_ctx->jaTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
+}
+// rows leave the resident job table (kernels_jobs_delete.h; k_jd_* in armada_sched_mgpu.hip, the scans are plat_compact's).  Each compaction brings its count back to the
+// host, which checks it against what the host counted before the next pass is sized by it.  ASCHED_JD_TIMES=1 puts events around the five passes (tools/probe_jobs_delete.py).
+#include "kernels_jobs_delete.h"
+extern "C" int asched_internal_jd_mark(const JdArgs* a, int value, hipStream_t s);
+extern "C" int asched_internal_jd_gather(const JdArgs* a, hipStream_t s);
+extern "C" int asched_internal_jd_remap(const JdArgs* a, int32_t* list, int n, hipStream_t s);
+static hipEvent_t* jdEvents() {
+  static const bool on = [] { const char* e = getenv("ASCHED_JD_TIMES"); return e && e[0] == '1'; }();
+  PlatCtx* c = t_ctx;
+  if (!on) return nullptr;
+  if (!c->jdEv[5]) for (int i = 0; i < 6; i++) if (!c->jdEv[i] && hipEventCreate(&c->jdEv[i]) != hipSuccess) { c->jdEv[i] = nullptr; return nullptr; }
+  return c->jdEv;
+}
+static int plat_jobs_delete(Dev& d, JdArgs& a) {
+  PlatCtx* c = t_ctx;
+  hipStream_t st = c->stream;
+  hipEvent_t* ev = jdEvents();
+  c->jdTimed = false;
+  if (ev) (void)hipEventRecord(ev[0], st);
+  if (asched_internal_jd_mark(&a, 0, st)) { c->err = "k_jd_mark launch failed"; return -1; }
+  if (ev) (void)hipEventRecord(ev[1], st);
+  int m1 = 0;
+  if (plat_compact(d, nullptr, a.M, a.keep, a.src, a.newId, nullptr, 0, nullptr, &m1)) return -1;
+  if (m1 != a.M1) { c->err = "jobs_delete: the scan kept another number of rows than the host counted"; return -1; }
+  if (ev) (void)hipEventRecord(ev[2], st);
+  if (asched_internal_jd_gather(&a, st)) { c->err = "k_jd_gather launch failed"; return -1; }
+  if (ev) (void)hipEventRecord(ev[3], st);
+  if (a.total > 0) {
+    int t1 = 0;
+    if (plat_compact(d, a.ordIn, a.total, a.keep, a.ordOut, nullptr, nullptr, 0, nullptr, &t1)) return -1;
+    if (t1 != a.total1) { c->err = "jobs_delete: the job order lost or gained rows"; return -1; }
+    if (asched_internal_jd_remap(&a, a.ordOut, a.total1, st)) { c->err = "k_jd_remap launch failed"; return -1; }
+  }
+  if (ev) (void)hipEventRecord(ev[4], st);
+  if (a.gangLen > 0) {
+    int g1 = 0;
+    if (plat_compact(d, a.gangIn, a.gangLen, a.keep, a.gangOut, nullptr, nullptr, 0, nullptr, &g1)) return -1;
+    if (g1 != a.gangLen1) { c->err = "jobs_delete: the gang lists lost or gained rows"; return -1; }
+    if (asched_internal_jd_remap(&a, a.gangOut, a.gangLen1, st)) { c->err = "k_jd_remap launch failed"; return -1; }
+  }
+  if (ev) (void)hipEventRecord(ev[5], st);
+  bool ok = asched_internal_jd_mark(&a, 1, st) == 0;
+  ok = ok && hipOk(hipGetLastError(), "k_jd launch") && hipOk(hipStreamSynchronize(st), "k_jd");
+  if (!ok) { if (c->err.empty()) c->err = "k_jd launch failed"; return -1; }
+  c->jdTimed = ev != nullptr;
+  return 0;
+}
+static void plat_jobs_delete_ms(double* out) {
+  hipEvent_t* ev = jdEvents();
+  for (int k = 0; k < 5; k++) { float ms = 0.f; if (ev && t_ctx->jdTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
 }
 // cordons and capacity changes of resident nodes (kernels_nodes_patch.h; k_np_scatter / k_np_mask in armada_sched_mgpu.hip).  ASCHED_NP_TIMES=1 puts events around
 // the two passes (tools/probe_nodes_patch.py).

@@ -375,6 +375,103 @@ def run_cycles_arriving_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[in
     return _run_cycles_arriving(lib, sim, per_cycle, max_cycles, False)
 
 
+def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, every, deleted):
+    from .binding import Scheduler
+    wl = sim.workload
+    m = wl.num_jobs
+    arrive = arrival_cycles(sim, per_cycle)
+    node = np.full(m, -1, np.int32)                   # per JOB (the workload's row), as in _run_cycles_arriving
+    run_prio = np.zeros(m, np.int32)
+    started = np.full(m, -1.0)
+    done = np.zeros(m, bool)
+    changed = np.zeros(m, bool)
+    job_of_row = np.zeros(0, np.int64)                # the driver's own row <-> job map: the table's rows are the jobs that arrived and were not deleted, in job order
+    row_of_job = np.full(m, -1, np.int64)
+    out = []
+    s = Scheduler(lib, wl.config)
+    s.nodes_upsert(wl.node_total, id_rank=wl.node_id_rank)
+    have = 0                                          # jobs that have arrived
+    t = 0.0
+
+    def table_args(jobs):
+        running = node[jobs] >= 0
+        return dict(queue=wl.job_queue[jobs], pc=wl.job_pc[jobs], submit_time=wl.job_submit[jobs], node=node[jobs], scheduled_at_priority=np.where(running, run_prio[jobs], 0),
+                    run_timestamp=np.where(running, np.maximum(started[jobs], 0) * 1e9, 0).astype(np.int64))
+
+    def terminal(jobs):
+        rows = np.nonzero(done[jobs])[0]
+        return rows[:-1] if len(rows) == len(jobs) else rows         # (a table keeps at least one row: jobs_delete refuses to empty it)
+
+    for cycle in range(max_cycles):
+        finished = (node >= 0) & (started >= 0) & (started + sim.job_runtime_s <= t)
+        done |= finished
+        node[finished] = -1
+        changed |= finished
+        if done.all():
+            break
+        upto = int(np.searchsorted(arrive, cycle, side="right"))
+        new = np.arange(have, upto)
+        compact = cycle > 0 and cycle % max(1, int(every)) == 0
+        if deleted:
+            if cycle == 0:                            # the first cycle: jobs_set
+                s.jobs_set(wl.job_req[new], **table_args(new))
+            elif len(new):                            # syncState: the upserts — the submissions since the last cycle, the run state of the rows that changed
+                s.jobs_append(wl.job_req[new], queue=wl.job_queue[new], pc=wl.job_pc[new], submit_time=wl.job_submit[new])
+            row_of_job[new] = len(job_of_row) + np.arange(len(new))
+            job_of_row = np.concatenate([job_of_row, new])
+            jobs = np.nonzero(changed & (row_of_job >= 0))[0]
+            if len(jobs):
+                a = table_args(jobs)
+                s.jobs_patch(row_of_job[jobs].astype(np.int32), a["node"], a["scheduled_at_priority"], a["run_timestamp"])
+            gone = terminal(job_of_row) if compact else np.zeros(0, np.int64)
+            if len(gone):                             # then the delete of the jobs in a terminal state, with the id map applied to the driver's table
+                new_id = s.jobs_delete(gone.astype(np.int32), want_map=True)
+                row_of_job[job_of_row] = new_id
+                job_of_row = job_of_row[new_id >= 0]
+        else:
+            job_of_row = np.concatenate([job_of_row, new])
+            if compact:
+                job_of_row = np.delete(job_of_row, terminal(job_of_row))
+            row_of_job[:] = -1
+            row_of_job[job_of_row] = np.arange(len(job_of_row))
+            s.jobs_set(wl.job_req[job_of_row], **table_args(job_of_row))
+        changed[:] = False
+        have = upto
+        queued = [np.array([row_of_job[j] for j in q if j < have and not done[j] and node[j] < 0], dtype=np.int32) for q in wl.queued]
+        nq = wl.num_queues
+        s.round_prepare(wl.queue_weight, queued, global_tokens=float(wl.global_burst), global_burst=wl.global_burst, global_rate_inf=wl.rate_inf,
+                        queue_tokens=[float(wl.queue_burst)] * nq, queue_burst=[wl.queue_burst] * nq, queue_rate_inf=[wl.rate_inf] * nq)
+        r = s.schedule_round()
+        sched = {int(job_of_row[j]): int(n) for j, n in r.scheduled.items()}              # by job, not by row: rows are renumbered
+        pre = {int(job_of_row[j]): int(n) for j, n in r.preempted.items()}
+        for j, n in r.scheduled.items():
+            k = int(job_of_row[j])
+            node[k], started[k], run_prio[k] = n, t, r.scheduled_priority[j]
+            changed[k] = True
+        for k in pre:
+            node[k], started[k] = -1, -1.0
+            changed[k] = True
+        out.append({"time_s": t, "scheduled": sched, "preempted": pre, "termination_reason": r.termination_reason, "rows": len(job_of_row)})
+        if have == m and not sched and not pre and not (node >= 0).any():
+            break   # everything has arrived, nothing runs and nothing can be placed: the rest never will
+        t += sim.cycle_period_s
+    s.close()
+    return out
+
+
+def run_cycles_compacting(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000, every: int = 1):
+    """run_cycles_arriving with the finished jobs LEAVING the table: every `every` cycles, after the cycle's upserts (jobs_append, jobs_patch), the rows of the jobs in a
+    terminal state are deleted on the device (Scheduler.jobs_delete: syncState's delete, scheduler.go:539-549) and the driver's own row <-> job map follows the id map the
+    call returns.  Records as run_cycles_arriving, with "scheduled" / "preempted" keyed by JOB (the workload's row) and "rows" the table's row count."""
+    return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, every, True)
+
+
+def run_cycles_compacting_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000, every: int = 1):
+    """the rebuilt counterpart of run_cycles_compacting: jobs_set of the live rows (every job that has arrived and was not dropped at a compacting cycle, with its run
+    state) in every cycle — what any library, the oracle included, can run.  Same rows, same records."""
+    return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, every, False)
+
+
 def run_cycles_cordoning(lib, sim: SimulatorInput, node_events, per_cycle: Optional[int] = None, max_cycles: int = 1000, nodes_patched: bool = True, appended: bool = True):
     """run_cycles_arriving plus a schedule of node events, what populateNodeDb re-reads per node every cycle (scheduling_algo.go:1069-1095): node_events is a list of
     (cycle, "cordon", node), (cycle, "uncordon", node) and (cycle, "cut", node, allocatable row).  A cycle's events are applied after its job changes and before

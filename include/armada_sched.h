@@ -385,8 +385,8 @@ int32_t ASCHED_FN(jobs_set)(asched_t*, const asched_jobs* jobs, const asched_req
    [-1, N); ASCHED_ERR_UNSUPPORTED: the job set carries the market order (uploaded with bid prices or after asched_set_market), an entry gives a cross-pool away row
    (asched_jobs.away) a node >= 0.  On a handle without a node table N is 0: only node -1 is accepted.  ASCHED_ERR_DEVICE (a failed launch or copy, as from any
    other entry point) is NOT such a refusal: the job table may be half patched, and the handle needs asched_jobs_set before anything else.
-   No other field changes and rows cannot be deleted (a finished job stays as a row without a run: asched_jobs_set drops it when the caller chooses); newly submitted
-   rows are appended with asched_jobs_append. */
+   No other field changes (a finished job stays as a row without a run until asched_jobs_delete removes it); newly submitted rows are appended with
+   asched_jobs_append. */
 int32_t ASCHED_FN(jobs_patch)(asched_t*, int32_t n, const int32_t* job, const int32_t* node, const int32_t* scheduled_at_priority, const int64_t* run_timestamp);
 /* syncState's upsert of the newly submitted jobs into the jobDb at the start of a cycle (scheduler.go:478-535; jobdb/jobdb.go:572-700, the insertion into the per-queue
    sorted set at :691-700): rows->m rows are added behind the M rows the handle holds; the new job ids are M .. M+m-1.  Rows must stay in ascending job-id order, as for
@@ -410,6 +410,25 @@ int32_t ASCHED_FN(jobs_append)(asched_t*, const asched_jobs* rows);
 /* how the last jobs_append ran: out[0] rows of the call, [1] rows that entered the order (queue >= 0), [2] new shapes, [3] new gangs, [4] 1 = the per-job arrays were
    re-allocated, [5] 1 = masks and fast structure were rebuilt, [6] capacity (rows) after the call, [7] 0 (reserved).  Zeros after jobs_set. */
 int32_t ASCHED_FN(jobs_append_stats)(asched_t*, int32_t* out /*[8]*/);
+/* syncState's delete of the jobs in a terminal state from the jobDb, after the upserts of the same cycle (scheduler.go:539-549; Txn.BatchDelete / delete,
+   jobdb/jobdb.go:941-990): the n rows job[0..n) leave the table.  The remaining rows keep their order and are renumbered densely: new id = old id - number of
+   deleted rows below it.  new_id, when not NULL, receives that map for the M rows the table had before the call, -1 for a deleted row.
+   After a successful call the handle is in the state asched_jobs_set would have left, given the same table without the named rows and the same requirement classes —
+   for every entry point (rounds, scheduling_order, the NodeDb-level calls, the submit check, the optimiser, the preemption causes, the evictor report, a later
+   jobs_patch / jobs_append / nodes_patch in any order), including everything jobs_set resets; the caller goes on with round_prepare.  n == 0 performs the resets only.
+   Any row may be named: queued, running, away, a gang member (the reference deletes gang members one by one, jobdb.go:978-990: the gang goes on with the members it
+   has left; once the last one is gone its (queue, gang_id) may be appended again as a new gang).  The work is on the device and proportional to the table: every
+   static per-job array is moved, the order and the gang lists are compacted; no static masks, no job-record upload, no sort, the fast structure stays.  Capacities do
+   not shrink.  A scheduling-key shape that loses its last row stays known; a later jobs_append that brings it again takes the rebuild path of a new shape.
+   Naming EVERY row is refused (ASCHED_ERR_UNSUPPORTED): a table without rows is not something this call leaves behind — give the next table to asched_jobs_set.
+   Refused before anything changes — ASCHED_ERR_INVALID: no job table, n < 0, n > 0 without job, a row outside [0, M), a row named twice; ASCHED_ERR_UNSUPPORTED: the
+   job set carries the market order, every row is named; ASCHED_ERR_DEVICE with "the handle is as it was" in last_error: out of device memory for the scratch and the
+   compacted arrays (all of it is allocated first).  Any other ASCHED_ERR_DEVICE (a failed launch or copy) is NOT such a refusal: the handle then needs
+   asched_jobs_set, as documented for jobs_patch. */
+int32_t ASCHED_FN(jobs_delete)(asched_t*, int32_t n, const int32_t* job /*[n] rows, each at most once*/, int32_t* new_id /*[M before the call] or NULL*/);
+/* how the last jobs_delete ran: out[0] rows deleted, [1] rows that left the order (queue >= 0), [2] gangs emptied, [3] scheduling-key shapes emptied, [4] M after the
+   call, [5] capacity (rows), [6..7] 0 (reserved).  Zeros after jobs_set. */
+int32_t ASCHED_FN(jobs_delete_stats)(asched_t*, int32_t* out /*[8]*/);
 /* the per-cycle changes of resident nodes (populateNodeDb, scheduling_algo.go:1069-1095: IsUnschedulable, WithOverAllocated,
    MarkResourceUnallocatable; a changed taint set) */
 typedef struct asched_nodes_patch_rows {

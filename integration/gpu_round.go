@@ -838,6 +838,61 @@ func (g *GpuRound) PatchJobs(scheduled, preempted []*schedulercontext.JobSchedul
 	return g.check(C.asched_jobs_patch(g.h, C.int32_t(n), i32p(job), i32p(node), i32p(prio), i64p(ts)))
 }
 
+// DeleteJobs drops the rows of jobs in a terminal state from the uploaded job table (asched_jobs_delete): what syncState does after its upserts, every cycle
+// (scheduler.go:539-549; Txn.BatchDelete / delete, jobdb/jobdb.go:941-990).  The shim's sync step is AppendJobs(new submissions), PatchJobs(run-state changes),
+// DeleteJobs(terminal jobs), then Schedule.  ids: each one of the last UploadJobs or of an AppendJobs since, at most once.  The library renumbers the remaining rows
+// densely and in order; the id map it returns is applied to the shim's own tables here — g.jobs keeps the surviving jobDb objects in row order, g.jobRow their new rows —
+// so a row the caller remembered from before the call is stale.  The entries of g.gangIds stay (their values number the gangs of later batches): a gang whose last
+// member was deleted and whose id is submitted again is ErrNeedsUpload from AppendJobs, although the library itself would take it.  ErrNeedsUpload — UploadJobs instead —
+// on the first cycle, on a market-driven pool and where every row would go (the library keeps at least one).
+func (g *GpuRound) DeleteJobs(ids []string) error {
+	if g.jobs == nil || (g.market != nil && g.market.Enabled) {
+		return ErrNeedsUpload
+	}
+	n := len(ids)
+	if n == 0 {
+		return g.check(C.asched_jobs_delete(g.h, 0, nil, nil))
+	}
+	if n >= len(g.jobs) {
+		return ErrNeedsUpload
+	}
+	if g.jobRow == nil {
+		g.jobRow = make(map[string]int32, len(g.jobs))
+		for i, j := range g.jobs {
+			g.jobRow[j.Id()] = int32(i)
+		}
+	}
+	rows := make([]int32, n)
+	for i, id := range ids {
+		row, ok := g.jobRow[id]
+		if !ok {
+			return fmt.Errorf("DeleteJobs: job %s is not one of the uploaded jobs", id)
+		}
+		rows[i] = row
+	}
+	newId := make([]int32, len(g.jobs))
+	var pins runtime.Pinner
+	defer pins.Unpin()
+	pins.Pin(&rows[0]); pins.Pin(&newId[0])
+	if err := g.check(C.asched_jobs_delete(g.h, C.int32_t(n), i32p(rows), i32p(newId))); err != nil {
+		return err
+	}
+	kept := g.jobs[:0]
+	for i, j := range g.jobs {
+		if newId[i] >= 0 {
+			kept = append(kept, j) // (newId[i] == len(kept) - 1: the map is order-preserving and dense)
+			g.jobRow[j.Id()] = newId[i]
+		} else {
+			delete(g.jobRow, j.Id())
+		}
+	}
+	for i := len(kept); i < len(g.jobs); i++ {
+		g.jobs[i] = nil
+	}
+	g.jobs = kept
+	return nil
+}
+
 // ErrNeedsNodeUpload is what PatchNodes answers for a change the resident node table cannot take: the caller falls back to UploadNodes of the whole pool.
 var ErrNeedsNodeUpload = fmt.Errorf("the node table has to be uploaded again")
 
