@@ -1315,7 +1315,7 @@ class Scheduler:
         self._check(self.lib.round_stats(self.h, out))
         names = ["fast_iterations", "generic_iterations", "base_scan_steps", "window_refills", "l0_max", "fast_replay_steps", "l0_overflows", "fast_active",
                  "kclk_evict", "kclk_replay", "kclk_pass1", "kclk_oversub_evict", "kclk_pass2", "kclk_unbind_results",
-                 "kclk_plane_scans", "kclk_fair_selects", "stream_runs", "stream_jobs", "stream_prepared", "stream_emitted", "preempt_fast_iterations", "hc_short_picks", "nested_gangs"]   # ([23]: reserved)
+                 "kclk_plane_scans", "kclk_fair_selects", "stream_runs", "stream_jobs", "stream_prepared", "stream_emitted", "preempt_fast_iterations", "hc_short_picks", "nested_gangs", "streams_over_cap"]   # (nested_gangs, streams_over_cap: counted by the CPU build alone)
         return {k: out[i] for i, k in enumerate(names)}
 
     def excluded_nodes(self, job: int):

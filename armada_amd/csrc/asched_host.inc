@@ -3625,7 +3625,7 @@ int32_t asched_round_stats(asched_t* h, int32_t* out) { if (!h) return ASCHED_ER
   out[20] = r.statHybrid;
   out[21] = r.statHcShort;
   out[22] = r.statNestGangs;   // (CPU build only: the device leaves it 0)
-  // out[23]: reserved, always 0
+  out[23] = r.statOverCap;     // (CPU build only: the device leaves it 0)
   out[0] = r.statFastIters; out[1] = r.statGenericIters; out[2] = r.statScanSteps; out[3] = r.statRefills; out[4] = r.statL0Max;
   out[5] = r.statFastReplay; out[6] = r.fastOverflow; out[7] = r.fastActive;
   out[16] = r.statStreamRuns; out[17] = r.statStreamJobs; out[18] = r.statStreamPrepared; out[19] = r.statStreamEmitted;

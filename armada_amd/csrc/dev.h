@@ -126,6 +126,7 @@ struct EvKey { double proposed, current, size; int32_t pcPrio; int32_t job; };
 #define QS_CMAX 32768         // stream entries per queue and preparation (round 6: one preparation covers a queue's rate-limit burst, so that a bulk-merged run — round_merge.h — seldom ends because a stream ran out)
 #endif
 #define QS_CHUNK 64           // entries one bulk item covers
+#define QS_GANG_CMAX 4096     // stream entries per queue and preparation in a pool with gangs, where it is below QS_CMAX (round_run.h fastStreamPrepare: a stream is cut at the queue's next gang member, the chunks behind the cut are scanned for nothing)
 #define QS_CPQ (QS_CMAX / QS_CHUNK)
 // a queue's stream as of the last hand-over to the generic code (fastQFlush): taken up again at the next fastQLoad if the generic code left the queue alone
 struct QsSave { int32_t valid, sPos, sLen, itQi, gctx, numUnfeasible; double tokens; int64_t alloc[MAXR]; };
@@ -195,7 +196,8 @@ struct RoundScalars {
   int32_t statHcShort;         // picks the node engine's short path took (engine_hc.h; device only): round_stats hc_short_picks.  (The first of three reserved words: the layout stays.)
   int32_t statNestGangs;       // gangs placed nested inside stream runs (round_fast.h streamNestGang): round_stats nested_gangs.  Filled by the CPU build alone (the device leaves
                                // it 0: fastRun's loop is register-sensitive and the word is a test's witness, not a measurement).  The second of the three reserved words.
-  int32_t reserved[1];         // always 0
+  int32_t statOverCap;         // streams longer than the bulk-merge passes cover that mgWorth / mgPrepare turned away (round_merge.h): round_stats streams_over_cap.  Filled by the
+                               // CPU build alone, like statNestGangs (the device leaves it 0).  The third of the three reserved words.
   int64_t statSeg[40];       // [24..39]: (profiling builds) segments of the generic iteration
   int64_t gsT;                     // (profiling builds) shader-clock ticks per segment of a fast iteration
   int64_t statClk[8];        // shader-clock ticks per phase of the round (device builds): evict, replay, pass 1, oversub evict, pass 2, unbind+results

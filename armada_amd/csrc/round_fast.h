@@ -2174,7 +2174,12 @@ DEV bool mgWorth(Dev& d, int Q) {
       if (f.sLen > f.sPos) {
         const bool kd = FL.sKind[q] != 0;
         if (!kd && !(d.qsLen[2 * q + 1] & 1) && !f.effValid) { const int nx = f.itQi - 1 - f.sPos + f.sLen; if (nx < f.qEnd && d.jGang[k.queuedJobs[nx]] >= 0) b2 = 1; }
-        if (!kd && f.sLen > QS_CMAX) b2 = 1;
+        if (f.sLen - f.sPos > QS_CMAX || (!kd && f.sLen > QS_CMAX)) {   // more entries than the passes cover — an evicted stream is the rest of its queue's eviction list, of any length
+          b2 = 1;
+#ifdef ASCHED_HOSTSIM
+          RS.statOverCap++;   // (round_stats streams_over_cap: the tests' witness that the guard was met)
+#endif
+        }
       } else if (f.gctx < -1) b2 = 1;
     }
 #if defined(ASCHED_HOSTSIM) || !defined(__HIP_DEVICE_COMPILE__)

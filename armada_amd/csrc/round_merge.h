@@ -33,7 +33,9 @@
 #pragma once
 
 enum { W_MG_PACK = 32, W_MG_FIX, W_MG_RANK, W_MG_SCATTER, W_MG_CUT };
-#define MG_SAMPLE 256   // W_MG_CUT: every 256th key of a queue is a sample
+#ifndef MG_SAMPLE
+#define MG_SAMPLE 256   // W_MG_CUT: every 256th key of a queue is a sample (the small-capacity CPU build of tests/hostsim sets 64, with QS_CMAX)
+#endif
 #define MG_SPQ (QS_CMAX / MG_SAMPLE)
 #define MG_PER 16      // other queues one item of the rank pass walks for its element
 #define MG_RG 16       // binary searches that run side by side (independent loads in flight together: a step of the group is one memory round trip)
@@ -50,6 +52,13 @@ enum { W_MG_PACK = 32, W_MG_FIX, W_MG_RANK, W_MG_SCATTER, W_MG_CUT };
 
 DEV EvKey mgCost(const Dev& d, const MgQ& s, int q, int pos) { return (s.kind & 1) ? d.evKey[s.base + pos] : d.qsKey[(size_t)q * QS_CMAX + pos]; }
 
+#ifdef ASCHED_HOSTSIM
+// CPU build: what the passes index stays inside what their grids and arrays cover (a stream of more than QS_CMAX entries described to them would not: mgPrepare's guard)
+#define MG_BOUND(cond, ...) do { if (!(cond)) { fprintf(stderr, "hostsim: bulk merge out of bounds: " __VA_ARGS__); fprintf(stderr, "\n"); abort(); } } while (0)
+#else
+#define MG_BOUND(cond, ...) do { } while (0)
+#endif
+
 DEV_COLD void mergeBulkAny(Dev& d, int kind, int i) {
   MgDev& mg = *d.mg;
   switch (kind) {
@@ -58,8 +67,10 @@ DEV_COLD void mergeBulkAny(Dev& d, int kind, int i) {
       const MgQ s = mg.q[q];
       if ((s.flags & MG_F_BARRIER) && ch == 0) { mg.key[s.off] = s.head; mg.own[s.off] = q; mg.rank[s.off] = 0; }
       if (!(s.flags & MG_F_STREAM)) break;
+      MG_BOUND(ch < MG_CPQ && s.total <= MG_CPQ * MG_CHUNK, "W_MG_PACK queue %d: %d entries, the pass packs %d chunks of %d", q, s.total, MG_CPQ, MG_CHUNK);
       const int e0 = ch * MG_CHUNK, e1 = e0 + MG_CHUNK < s.total ? e0 + MG_CHUNK : s.total;
       if (e0 >= e1) break;
+      MG_BOUND(s.off >= 0 && s.off + e1 <= mg.cap, "W_MG_PACK queue %d: entries up to %d + %d of %d", q, s.off, e1, mg.cap);
       const bool folded = (s.kind & 2) != 0;
       WideKey run; run.a = 0; run.x = 0; run.y = 0;
       if (folded) run = s.eff;
@@ -84,6 +95,8 @@ DEV_COLD void mergeBulkAny(Dev& d, int kind, int i) {
       const int nch = (s.total + MG_CHUNK - 1) / MG_CHUNK;
       for (int ch = 0; ch < nch; ch++) {
         const int e0 = ch * MG_CHUNK, e1 = e0 + MG_CHUNK < s.total ? e0 + MG_CHUNK : s.total;
+        MG_BOUND(ch < MG_CPQ, "W_MG_FIX queue %d: chunk %d of %d entries, a queue has %d chunk maxima", q, ch, s.total, MG_CPQ);
+        MG_BOUND(s.off + e1 <= mg.cap, "W_MG_FIX queue %d: entries up to %d + %d of %d", q, s.off, e1, mg.cap);
         if (ch > 0) for (int e = e0; e < e1; e++) {
           if (!wideKeyLess(out[e], run)) break;   // (the chunk's keys are non-decreasing: the rest is at or above the running maximum)
           out[e] = run;
@@ -159,12 +172,14 @@ DEV_COLD void mergeBulkAny(Dev& d, int kind, int i) {
       const int q = i / MG_SPQ, j = i % MG_SPQ;
       const MgQ s = mg.q[q];
       if (!(s.flags & MG_F_STREAM) || (j + 1) * MG_SAMPLE > s.total) break;
+      MG_BOUND(s.total <= MG_CPQ * MG_CHUNK && s.off + (j + 1) * MG_SAMPLE <= mg.cap, "W_MG_CUT queue %d: %d entries at %d, the pass samples %d chunks of %d, %d entries in all", q, s.total, s.off, MG_CPQ, MG_CHUNK, mg.cap);
       const WideKey ks = mg.key[s.off + j * MG_SAMPLE + MG_SAMPLE - 1];
       const int Q = d.cfg.Q;
       uint32_t cnt = 0;
       for (int q2 = 0; q2 < Q; q2++) {
         const MgQ o = mg.q[q2];
         if (!(o.flags & MG_F_STREAM)) continue;
+        MG_BOUND(o.total <= MG_CPQ * MG_CHUNK, "W_MG_CUT queue %d: %d entries, the pass samples %d chunks of %d", q2, o.total, MG_CPQ, MG_CHUNK);
         int lo = 0, hi = o.total / MG_SAMPLE;   // samples of q2 at or below ks: a prefix (the keys are running maxima)
         while (lo < hi) { const int mid = (lo + hi) >> 1; if (!wideKeyLess(ks, mg.key[o.off + mid * MG_SAMPLE + MG_SAMPLE - 1])) lo = mid + 1; else hi = mid; }
         cnt += (uint32_t)lo;
@@ -222,7 +237,7 @@ static void mgCheck(Dev& d, const FastCtx& fc, int Q, int skip, int V) {
 
 // The merged order of the run that is about to start, for the queues' streams as fastStreamRun will see them.  Control wave, node engine STOPPED (the passes use every
 // wave of the workgroup).  Returns the number of valid merged entries; 0 = this run is merged by the control wave as before (too few entries; a gang the run would nest;
-// a stream longer than the key arrays).
+// a stream, queued or evicted, of more entries than the passes cover).
 DEV_NOINLINE int mgPrepare(Dev& d, FastCtx fc, int Q, int skip, int need) {   // need: queued jobs the run can serve at most (the global tokens), INT32_MAX = no such bound
 #ifdef ASCHED_HOSTSIM
   { static const bool off = getenv("HS_NO_MERGE") != nullptr; if (off) return 0; }
@@ -265,7 +280,9 @@ DEV_NOINLINE int mgPrepare(Dev& d, FastCtx fc, int Q, int skip, int need) {   //
           if (!kd && !f.effValid) { const int nx = s.base + f.sLen; if (nx < f.qEnd && d.jGang[k.queuedJobs[nx]] >= 0) bad = 1; }
         }
         if (s.kind & 2) { s.eff.a = FL.effA[q]; s.eff.x = FL.effX[q]; s.eff.y = FL.effY[q]; }
-        if (!kd && s.len > QS_CMAX) bad = 1;
+        // the passes' grids (Q * MG_CPQ chunks, Q * MG_SPQ samples) and mg.cmax cover QS_CMAX entries of a queue.  A queued stream is prepared within that; an evicted stream
+        // is the rest of its queue's eviction list, which nothing bounds: over the capacity the run stays with the control wave's merge, which reads d.evKey in place
+        if (s.total > QS_CMAX || (!kd && s.len > QS_CMAX)) bad = 1;   // (mgWorth has the same line, and counts it for the CPU build's round_stats)
       } else {
         s.flags = MG_F_BARRIER | (fc.preferLarge ? MG_F_PREFER_LARGE : 0); s.total = 1;
         s.head.a = FL.kA[q]; s.head.x = FL.kX[q]; s.head.y = FL.kY[q];
@@ -321,7 +338,10 @@ DEV_NOINLINE int mgPrepare(Dev& d, FastCtx fc, int Q, int skip, int need) {   //
   mgCheck(d, fc, Q, skip, V);
   if (getenv("HS_MG_TRACE")) {
     int limits = 0; for (int q = 0; q < Q; q++) if (mg.q[q].flags & MG_F_LIMIT) limits++;
-    fprintf(stderr, "bulk merge: %d entries of %d queues, valid %d, skip %d, cut %d (need %lld), limit elements %d", total, streams, V, skip, (int)mg.stop[3], needAll, limits);
+    int decs = 0, decsFix = 0;   // entries whose own key orders before the running maximum in front of them; those of them that are the first of a chunk (W_MG_FIX carried the maximum over)
+    for (int q = 0; q < Q; q++) { const MgQ& s = mg.q[q]; if (!(s.flags & MG_F_STREAM)) continue;
+      for (int e = 0; e < s.total; e++) if ((mg.own[s.off + e] >> 30) & 1) { decs++; if (e % MG_CHUNK == 0) decsFix++; } }
+    fprintf(stderr, "bulk merge: %d entries of %d queues, valid %d, skip %d, cut %d (need %lld), limit elements %d, decreases %d (%d across a chunk boundary)", total, streams, V, skip, (int)mg.stop[3], needAll, limits, decs, decsFix);
     for (int q = 0; q < Q; q++) { const MgQ& s = mg.q[q]; if (!s.total) continue;
       if ((s.flags & MG_F_BARRIER) && mg.rank[s.off] == (int)stop) fprintf(stderr, " | barrier q%d gctx %d headKind %d headFast %d stage %d itEi %d evEnd %d itQi %d qEnd %d tokens %.0f eff %d sLen %d", q, FL.hot[q].gctx, FL.hot[q].headKind, FL.hot[q].headFast, FL.hot[q].itStage, FL.hot[q].itEi, FL.hot[q].evEnd, FL.hot[q].itQi, FL.hot[q].qEnd, FL.hot[q].tokens, FL.hot[q].effValid, FL.hot[q].sLen);
       if ((s.flags & MG_F_STREAM)) { int last = mg.rank[s.off + s.total - 1]; if ((s.flags & MG_F_OPEN) && last + 1 == (int)stop) fprintf(stderr, " | open q%d total %d kind %d", q, s.total, s.kind);

@@ -632,7 +632,7 @@ DEV_NOINLINE int fastStreamPrepare(Dev& d, FastCtx fc, int Q, int allowed, int a
   int skipUnf = fc.skipKnown && RS.numUnfeasible > 0;
   int cap = allowed < QS_CMAX ? allowed : QS_CMAX;
   if (cap > capHint) cap = capHint;
-  if (d.cfg.G > 0 && cap > 4096) cap = 4096;   // a pool with gangs: a stream is cut at the queue's next gang member, and the chunks behind the cut are scanned for nothing (BASELINE configs[3]: 686 -> 838 ms with 32 768)
+  if (d.cfg.G > 0 && cap > QS_GANG_CMAX) cap = QS_GANG_CMAX;   // a pool with gangs: a stream is cut at the queue's next gang member, and the chunks behind the cut are scanned for nothing (BASELINE configs[3]: 686 -> 838 ms with 32 768)
   bool evOk = fc.evStatic && RS.lvl0NonNeg && RS.numPreemptedMarks == 0;
 #ifdef ASCHED_HOSTSIM
   if (getenv("HS_NO_EV_STREAM")) evOk = false;

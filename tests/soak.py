@@ -19,6 +19,8 @@
 
 HS_RING_LAG=<seed> (CPU build): the serial node engine lags behind the merge by a pseudo-random number of ring entries, as on the device (tests/hostsim/fast_serial.h).
 SOAK_LIB=hip (on a GPU box): the same seeds through the product library instead of the CPU build.
+SOAK_LIB=cap64: through the CPU build with a stream capacity of 64 entries per queue (tests/hostsim libhostsim_cap64.so: -DQS_CMAX=64 -DMG_SAMPLE=64), where every stream
+run meets the capacity; with HS_MG_MIN=64 the bulk merge takes every run of a full stream.
 Prints one line per divergence and a summary; exit code 1 if anything diverged.  (Round 1: all clean after the submit-check fix.)
 """
 import os
@@ -42,8 +44,9 @@ def libs():
         torch.cuda.init()
         import armada_amd
         return Library(os.path.join(ROOT, "oracle", "liboracle.so"), "oracle_"), armada_amd.load_library()
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "hostsim")])
-    return Library(os.path.join(ROOT, "oracle", "liboracle.so"), "oracle_"), Library(os.path.join(ROOT, "tests", "hostsim", "libhostsim.so"), "asched_")
+    name = "libhostsim_cap64.so" if os.environ.get("SOAK_LIB") == "cap64" else "libhostsim.so"
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "tests", "hostsim"), name])
+    return Library(os.path.join(ROOT, "oracle", "liboracle.so"), "oracle_"), Library(os.path.join(ROOT, "tests", "hostsim", name), "asched_")
 
 
 def sharded_rounds(lib, wl, fp, world):
