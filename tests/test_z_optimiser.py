@@ -20,9 +20,10 @@ PCS = {"pc0": (0, 1), "pc1": (1, 1), "pc2": (2, 1), "pc2np": (2, 0), "pc3": (3, 
 PC_NAMES = sorted(PCS)
 
 
-def build(lib, nodes, jobs, queues, extra_total=None, extra_alloc=None):
+def build(lib, nodes, jobs, queues, extra_total=None, extra_alloc=None, id_rank=None, allocatable=None, gang_id=None):
     """nodes: [(cpu, mem, taint)], jobs: [(queue, cpu, mem, pc, node or -1, lease_ms)], queues: [(name, priority factor)].
-    Returns a prepared Scheduler (fair shares with unlimited demand, like setUpSctx :202-246)."""
+    Returns a prepared Scheduler (fair shares with unlimited demand, like setUpSctx :202-246).
+    id_rank: the nodes' id order (default: the index); allocatable: [(cpu, mem)] per node (default: the total); gang_id: per job, -1 = no gang (members of cardinality 2)."""
     cfg = Config(num_resources=2, indexed_col=[CPU, MEM], indexed_resolution=[1000, GI], pc_priority=[PCS[n][0] for n in PC_NAMES],
                  pc_preemptible=[PCS[n][1] for n in PC_NAMES], drf_multiplier=[1.0, 1.0], indexed_taint_keys=None)
     nodes = list(nodes)
@@ -31,11 +32,14 @@ def build(lib, nodes, jobs, queues, extra_total=None, extra_alloc=None):
     total = np.array([[m, c] for c, m, _ in nodes], dtype=np.int64)
     total[:, CPU] *= 1000
     s = Scheduler(lib, cfg)
-    s.nodes_upsert(total, taints=[[(5, 1, 1)] if t else [] for _, _, t in nodes])
+    if allocatable is not None:
+        allocatable = np.array([[m, c * 1000] for c, m in allocatable], dtype=np.int64)
+    s.nodes_upsert(total, allocatable, id_rank=id_rank, taints=[[(5, 1, 1)] if t else [] for _, _, t in nodes])
     qn = [q for q, _ in queues]
     req = np.array([[m, c * 1000] for _, c, m, _, _, _ in jobs], dtype=np.int64).reshape(len(jobs), 2)
+    gang = {} if gang_id is None else dict(gang_id=list(gang_id), gang_cardinality=[2 if g >= 0 else 1 for g in gang_id])
     s.jobs_set(req, queue=[qn.index(j[0]) for j in jobs], pc=[PC_NAMES.index(j[3]) for j in jobs], node=[j[4] for j in jobs],
-               scheduled_at_priority=[PCS[j[3]][0] for j in jobs], run_timestamp=[int(j[5]) * 1_000_000 for j in jobs], submit_time=list(range(len(jobs))))
+               scheduled_at_priority=[PCS[j[3]][0] for j in jobs], run_timestamp=[int(j[5]) * 1_000_000 for j in jobs], submit_time=list(range(len(jobs))), **gang)
     npc = len(PC_NAMES)
     alloc = np.zeros((len(qn), npc, 2), dtype=np.int64)
     for i, j in enumerate(jobs):
