@@ -8,7 +8,10 @@
 //
 // What.  The level-0 structure of round_fast.h (sorted base + list of dirty nodes, "L0") split three ways for the length of one ring session:
 //   H   the HOT set: the <= 48 (HC_H_MAX) dirty nodes modified most recently, one per lane of the engine wave, in registers.  A query is one branch-free fit test per
-//       lane (hcFits: requirement class, every key field through the guard bits, the extras) and a 64-lane minimum (two 32-bit DPP reductions); a bind rewrites one lane.
+//       lane (hcFits: requirement class, every key field through the guard bits, the extras) and a look at the lanes' key ORDER, which is kept, not recomputed: each lane
+//       holds the set of lanes with a smaller key (HcHot::below, hc_order.h), so the first-fit lane is the fitting one with none of the fitting lanes below it — two
+//       ballots.  A bind rewrites one lane and its bit in the others' words.  (Until round 9 a 64-lane minimum by two dependent 32-bit DPP reductions, ~300 ticks per job;
+//       -DASCHED_HC_DPPMIN still builds that query, -DASCHED_HC_CHECK compares the two on every job.)
 //   C   the COLD set: every other dirty node = the LDS list itself (FL.l0*), mirrored in the registers of wave 3 (16 rows x 64 lanes).  Wave 3 answers "minimum-key
 //       entry a job fits on", takes the entries H evicts, gives up the ones that are picked — and keeps, per fit shape, a LOWER BOUND of the keys of its entries the
 //       shape fits on (HCB.clb[128]: lowered by every hand-over, refreshed by every answer).  The engine asks only when that bound lies below both the hot and the clean
@@ -28,6 +31,7 @@
 //   HC_E  the session ends: compact the LDS list, publish its length
 // Every wait of this protocol reads the launch's `abandon` word (round_kernel.h "bounded waits") and leaves through an exit its loop has anyway.
 #pragma once
+#include "hc_order.h"
 
 #define HC_CMDS 32
 #define HC_INS 16      // payload slots of entries H hands over (at most HC_INS / 2 are in flight)
@@ -86,6 +90,14 @@ template <int E> __device__ static inline bool hcFits(unsigned long long G, cons
   if (E > 0) ok &= q.ex0 <= ex0;
   if (E > 1) ok &= q.ex1 <= ex1;
   return ok;
+}
+// the lanes hcFits holds in, as a mask: one ballot per condition, joined in scalar registers (a ballot of the joined condition costs a select and a compare more)
+template <int E> __device__ static inline unsigned long long hcFitsMask(unsigned long long G, const HcNeed& q, unsigned long long key, unsigned long long cls, long long ex0, long long ex1) {
+  unsigned long long m = __builtin_amdgcn_ballot_w64(((cls >> q.cls) & 1) != 0);
+  m &= __builtin_amdgcn_ballot_w64((((key | G) - q.fmin) & G) == G);
+  if (E > 0) m &= __builtin_amdgcn_ballot_w64(q.ex0 <= ex0);
+  if (E > 1) m &= __builtin_amdgcn_ballot_w64(q.ex1 <= ex1);
+  return m;
 }
 
 // ------------------------------------------------------------------------------------------------ wave 3: the cold set
@@ -251,7 +263,20 @@ __device__ static void coldLoop(Dev& d) {
 }
 
 // ------------------------------------------------------------------------------------------------ wave 1: hot set + per-shape clean candidates
-struct HcHot { unsigned long long key, cls; long long ex0, ex1; int node, state, seq; };   // state 0 empty, 1 entry, 2 entry handed to C (insert `seq` in flight)
+struct HcHot { unsigned long long key, cls, below; long long ex0, ex1; int node, state, seq; };   // state 0 empty, 1 entry, 2 entry handed to C (insert `seq` in flight); below: the lanes whose entry has a smaller key (hc_order.h)
+// the first-fit lane of H and its key (-1, ~0: no lane fits), wave-uniform: the fitting lane with no fitting lane below it
+__device__ static inline unsigned long long hcOrderPick(const HcHot& h, unsigned long long fitMask, int* laneOut) {
+  const unsigned long long who = __builtin_amdgcn_ballot_w64(hcOrderFirst(true, h.below, fitMask)) & fitMask;   // (the lane's own fit joins as a mask: the ballot is then one compare)
+  const int l = (int)__builtin_ctzll(who | (1ull << 63));
+  const unsigned long long kl = hcRead64(h.key, l);
+  *laneOut = who ? l : -1;
+  return who ? kl : ~0ull;
+}
+// lane L of H takes key nk (~0: its entry died), the same value in every lane: the order words follow (every lane calls this; h.key of lane L may hold the old or the new key)
+__device__ static inline void hcOrderSet(HcHot& h, int L, unsigned long long nk) {
+  const unsigned long long lt = __builtin_amdgcn_ballot_w64(h.key < nk);
+  h.below = hcOrderUpdate(h.below, h.key, (int)(threadIdx.x & 63), __builtin_amdgcn_readfirstlane(L), nk, lt);   // (L in a scalar register: its bit is then a scalar mask, not a shift per lane)
+}
 // The clean side: fastFirstFit's per-shape base cursor (FL.cand, round_fast.h) held in registers for the session, two fit shapes per lane (lane, lane + 64), plus the
 // bitmap word ("clean and fits", d.fitBits) the cursor stands in.  A consumed candidate's successor is then known without a memory access (the next set bit); its
 // fields cost ONE HBM round trip, fetched on demand for every shape that lacks them at once (hcShapesFetch).  st: 0 nothing left, 1 scanning from pos (inclusive), 2 the
@@ -402,15 +427,19 @@ __device__ static inline void hcPostA(int& cmdPub, int type, int a) {
   hcStoreI32(&HCB.cmdPub, cmdPub);
 }
 
-// the bind's effect on the level-0 entry in lane hLane of H, in place: key and extras go down; an entry that can no longer host anything is dropped (returns 1: it died)
+// the bind's effect on the level-0 entry in lane hLane of H, in place: key and extras go down; an entry that can no longer host anything is dropped (returns 1: it died).
+// The lane's new key, read back into scalar registers, serves the order words (hc_order.h) and says whether the entry died (~0): no ballot for that.
 __device__ static inline int hcHotBind(HcHot& h, int hLane, const HcJobV& j, unsigned long long G, unsigned long long MFM, long long ME0, long long ME1) {
   const unsigned long long nk = h.key - j.keyDelta; const long long n0 = h.ex0 - j.ex0, n1 = h.ex1 - j.ex1;
   const bool alive = ((((nk | G) - MFM) & G) == G) & (ME0 <= n0) & (ME1 <= n1);
   const bool me = (int)(threadIdx.x & 63) == hLane;
   h.key = me ? (alive ? nk : ~0ull) : h.key; h.ex0 = me ? n0 : h.ex0; h.ex1 = me ? n1 : h.ex1; h.state = me ? (alive ? 1 : 0) : h.state; h.cls = (me & !alive) ? 0ull : h.cls;
-  return __ballot(me & !alive) ? 1 : 0;
+  const unsigned long long nkL = hcRead64(h.key, hLane);
+  hcOrderSet(h, hLane, nkL);
+  return nkL == ~0ull ? 1 : 0;
 }
 #define HC_ERR_SHORT 610   // errorDetail of the checking build (-DASCHED_HC_CHECK): the general body decided a short-path job differently, or asked / fetched for it
+#define HC_ERR_ORDER 611   // the same build: the order words (hc_order.h) and the 64-lane minimum named different lanes or keys for a job
 
 // One ring session with the split structure.  Same contract as the ENG_STREAM walk of engineLoop: entry i is ready when ringPub > i; the chosen node goes into the
 // ring entry (the bind wave issues the HBM side); ringAck counts the entries placed; ringFail 1 = entry ringAck found no node, 2 = the list overflowed.
@@ -439,7 +468,7 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
   LDS_ORDER();
   hcStoreI32(&g_fl.eng.hcGen, __builtin_amdgcn_readfirstlane(g_fl.eng.hcGen) + 1);
   int cmdPub = 0, insSeq = 0, rrNext = 0, qSeq = 0, inFlight = 0;   // inFlight: lanes of H whose entry has been handed to C and not yet been taken in
-  HcHot h; h.key = ~0ull; h.cls = 0; h.ex0 = h.ex1 = 0; h.node = -1; h.state = 0; h.seq = 0;
+  HcHot h; h.key = ~0ull; h.cls = 0; h.below = 0; h.ex0 = h.ex1 = 0; h.node = -1; h.state = 0; h.seq = 0;
   const unsigned long long shortOn = d.f.hcShort ? ~0ull : 0ull;   // (read once per session; used on the general path only)
   HcShapes sc; hcShapesLoad(k, sc); hcShapesBound(sc, shortOn);
   int nShort = 0;   // picks the short path took: round_stats hc_short_picks
@@ -482,11 +511,22 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
     const int rIns = __hip_atomic_load(&HCB.insDone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     LDS_ORDER();   // (the bound is read behind the counter: a hand-over the counter covers has lowered it already)
     const unsigned long long rLb = HCB.clb[cur.shape & 127];
-    // ---- H: one test per lane, the 64-lane minimum
+    // ---- H: one test per lane, then the fitting lane that has no fitting lane below it in key order (hc_order.h)
     HcNeed q; q.fmin = cur.fmin; q.ex0 = cur.ex0; q.ex1 = cur.ex1; q.cls = cur.cls;
-    const bool fitH = hcFits<E>(G, q, h.key, h.cls, h.ex0, h.ex1);   // (an empty lane has class bits 0: it fits nothing)
-    int hLane;
-    unsigned long long hk = hcMinKey(fitH ? h.key : ~0ull, &hLane);
+    int hLane;   // (an empty lane has class bits 0: it fits nothing)
+#ifdef ASCHED_HC_DPPMIN
+    const bool fitH = hcFits<E>(G, q, h.key, h.cls, h.ex0, h.ex1);
+    unsigned long long hk = hcMinKey(fitH ? h.key : ~0ull, &hLane);   // (A/B and debugging, tools/build_variant.sh: the 64-lane minimum of rounds 6 to 8; the order words are kept all the same)
+#else
+    unsigned long long hk = hcOrderPick(h, hcFitsMask<E>(G, q, h.key, h.cls, h.ex0, h.ex1), &hLane);
+#endif
+#ifdef ASCHED_HC_CHECK
+    {   // the checking build: the order words must name the lane and the key the 64-lane minimum finds, on every job
+      int mLane; const unsigned long long mk = hcMinKey(hcFits<E>(G, q, h.key, h.cls, h.ex0, h.ex1) ? h.key : ~0ull, &mLane);
+      int oLane; const unsigned long long ok = hcOrderPick(h, hcFitsMask<E>(G, q, h.key, h.cls, h.ex0, h.ex1), &oLane);
+      if ((mLane != oLane) | (mk != ok)) { if (lane == 0 && RS.error == 0) { RS.error = ASCHED_ERR_INTERNAL; RS.errorDetail = HC_ERR_ORDER; } LANE0_PUBLISHED(); fail = 1; break; }
+    }
+#endif
     const int shape = __builtin_amdgcn_readfirstlane(cur.shape), sl = shape & 63;
     const bool hiSet = cur.shape >= 64;   // (the same in every lane: a select per word, then ONE v_readlane — no branch on the set)
     ESEG(1);   // [17] H test
@@ -496,6 +536,7 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
       const bool rel = (h.state == 2) & (h.seq < insDone);
       const unsigned long long rb = __ballot(rel);
       h.state = rel ? 0 : h.state; h.cls = rel ? 0ull : h.cls; h.key = rel ? ~0ull : h.key;
+      h.below = hcOrderRelease(h.below, rb);
       inFlight -= __popcll(rb);
       const bool drop = hLane >= 0 && ((rb >> hLane) & 1);
       hLane = drop ? -1 : hLane; hk = drop ? ~0ull : hk;
@@ -555,6 +596,7 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
       const bool rel = (h.state == 2) & (h.seq < insDone);   // the answer counts these hand-overs: the entries are C's now
       const unsigned long long rb = __ballot(rel);
       h.state = rel ? 0 : h.state; h.cls = rel ? 0ull : h.cls; h.key = rel ? ~0ull : h.key;
+      h.below = hcOrderRelease(h.below, rb);
       inFlight -= __popcll(rb);
       const bool drop = hLane >= 0 && ((rb >> hLane) & 1);
       hLane = drop ? -1 : hLane; hk = drop ? ~0ull : hk;
@@ -626,6 +668,7 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
         if (occ == ~0ull) { fail = 2; break; }   // (cannot happen: HC_H_MAX entries + the hand-overs in flight are fewer than the lanes; reported as an overflow if it ever does)
         const int fl = (int)__builtin_ctzll(~occ);
         const bool me = lane == fl;
+        hcOrderSet(h, fl, nk);   // (the lane's old bits are stale: both its word and its bit in the others' are written whole)
         h.key = me ? nk : h.key; h.cls = me ? ocls : h.cls; h.ex0 = me ? n0 : h.ex0; h.ex1 = me ? n1 : h.ex1; h.node = me ? n : h.node; h.state = me ? 1 : h.state;
         if (src != 1) { total++; if (total > ES.statL0Max) ES.statL0Max = total; }
         // H over its size: the next entry in lane order (round robin) goes to C
