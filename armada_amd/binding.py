@@ -255,7 +255,7 @@ ALL_SYMBOLS = [
     "round_preemption_causes", "preemption_join",
     "set_evictor_report", "round_evictor_report",
     "jobs_patch", "jobs_append", "jobs_append_stats", "jobs_delete", "jobs_delete_stats",
-    "nodes_patch", "nodes_patch_stats",
+    "nodes_patch", "nodes_patch_stats", "nodes_delete", "nodes_delete_stats",
 ]
 # entry points the CPU oracle does not implement (it is the single-process checker): the communicator and the collectives that run on it, and the join of a
 # round's result lists into preemption causes (a function of lists the oracle already delivers; tests/test_z_preemption_causes.py restates it)
@@ -264,7 +264,8 @@ OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_d
                     "set_evictor_report", "round_evictor_report",   # (recorded by passes between the launches of the split round: tests/test_z_evictor_report.py restates it)
                     "jobs_patch", "jobs_append", "jobs_append_stats",   # (an incremental jobs_set: the oracle is given the whole table; tests/test_z_jobs_patch.py, test_z_jobs_append.py)
                     "jobs_delete", "jobs_delete_stats",                 # (likewise: tests/test_z_jobs_delete.py)
-                    "nodes_patch", "nodes_patch_stats"}                  # (an incremental nodes_upsert, likewise: tests/test_z_nodes_patch.py)
+                    "nodes_patch", "nodes_patch_stats",                 # (an incremental nodes_upsert, likewise: tests/test_z_nodes_patch.py)
+                    "nodes_delete", "nodes_delete_stats"}                # (likewise: tests/test_z_nodes_delete.py)
 PREEMPTION_UNKNOWN, PREEMPTION_UNKNOWN_GANG, PREEMPTION_FAIRSHARE, PREEMPTION_URGENCY, PREEMPTION_OPTIMISER = 1, 2, 3, 4, 5   # ASCHED_PREEMPTION_* (context.PreemptionType)
 # ASCHED_EVR_* bits of asched_evictor_report.node_reasons, in bit order: the reference's reason strings in alphabetical order (makeNodePreemptiblityStats sorts them)
 EVICTOR_REASONS = ("all_jobs_preemptible", "below_protected_fair_share", "invalid_queue", "job_not_preemptible", "node_empty", "node_unschedulable")
@@ -465,6 +466,8 @@ class Library:
         f("jobs_delete_stats", C.c_int32, [C.c_void_p, _i32p])
         f("nodes_patch", C.c_int32, [C.c_void_p, C.POINTER(CNodesPatch)])
         f("nodes_patch_stats", C.c_int32, [C.c_void_p, _i32p])
+        f("nodes_delete", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p])
+        f("nodes_delete_stats", C.c_int32, [C.c_void_p, _i32p])
         f("round_preemption_causes", C.c_int32, [C.c_void_p, C.POINTER(CPreemptionCause), C.c_int32, _i32p, C.c_int32, _i32p])
         f("preemption_join", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, C.c_int32, _i32p, _i32p, _i32p, _u8p, C.POINTER(CPreemptionCause), _i32p, C.c_int32, _i32p])
 
@@ -832,6 +835,32 @@ class Scheduler:
         out = np.zeros(8, np.int32)
         self._check(fn(self.h, _ptr(out, C.c_int32)))
         return [int(x) for x in out]   # [0] entries, [1] type changed, [2] rebuilt, [3] reason, [4..7] 0: the C array as it is
+
+    def nodes_delete(self, rows, want_map=False):
+        """populateNodeDb's dropping of an unschedulable node that holds no job (and of the nodes of a filtered executor): rows `rows` leave the resident node table; the
+        others keep their order and are renumbered densely (new position = old position - deleted rows below it), and so is the node of every running job of the
+        resident job table.  No running job may be on a deleted row.  Leaves the handle as nodes_upsert of the reduced table would; go on with round_prepare.
+        want_map: returns the old -> new map (int32 [rows before the call], -1 for a deleted row)."""
+        fn = self._preemption_fn("nodes_delete")
+        nd = _arr(rows, np.int32).reshape(-1)
+        buf = None
+        n_before = self.num_nodes
+        if want_map:   # into a buffer this object keeps, as jobs_delete does (fresh host pages cost more than the copy)
+            buf = getattr(self, "_node_map_buf", None)
+            if buf is None or len(buf) < n_before:
+                buf = self._node_map_buf = np.empty(max(n_before, 1), np.int32)
+            buf[:n_before] = -2
+        self._check(fn(self.h, len(nd), _ptr(nd, C.c_int32), _ptr(buf, C.c_int32)))
+        self.num_nodes -= len(nd)
+        return buf[:n_before].copy() if want_map else None
+
+    def nodes_delete_stats(self):
+        """how the last nodes_delete ran: [0] rows deleted, [1] job rows whose node was renumbered, [2] 1 = the rebuild path ran, [3] why (0 none, 2 a node type emptied,
+        4 a value of an indexed label emptied), [4] nodes after the call, [5..7] 0: the C array as it is"""
+        fn = self._preemption_fn("nodes_delete_stats")
+        out = np.zeros(8, np.int32)
+        self._check(fn(self.h, _ptr(out, C.c_int32)))
+        return [int(x) for x in out]
 
     def txn_begin(self): self._check(self.lib.txn_begin(self.h))
     def txn_commit(self): self._check(self.lib.txn_commit(self.h))

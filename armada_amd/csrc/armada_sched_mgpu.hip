@@ -531,3 +531,77 @@ extern "C" int asched_internal_np_mask(const Dev* d, const NpArgs* a, hipStream_
   if (work > 0) hipLaunchKernelGGL(k_np_mask, dim3(mgBlocks(work)), dim3(MG_THREADS), 0, st, *d, *a, work);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// ------------------------------------------------------------------------------------------------ rows leave the resident node table (kernels_nodes_delete.h)
+// mark / unmark, the check of the running jobs, the two gathers, the renumbering of the index order, the bit compaction of the mask rows and the remap of the running
+// jobs' nodes; the scans are plat_compact's kernels
+#define ND_FN __device__ static inline
+#define ND_MIN32(p, v) atomicMin((p), (v))
+#include "kernels_nodes_delete.h"
+__global__ __launch_bounds__(MG_THREADS) void k_nd_mark(NdArgs a, int value) {
+  long long i = MG_IDX();
+  if (i < a.n) ndMark(a, (int)i, (uint8_t)value);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_nd_check(NdArgs a) {
+  long long j = MG_IDX();
+  if (j < a.M) ndCheck(a, (int)j);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_nd_plane(NdArgs a) {
+  long long e = MG_IDX();
+  if (e < (long long)a.R * a.N1) ndPlane(a, e);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_nd_narrow(NdArgs a) {
+  long long i = MG_IDX();
+  if (i < a.N1) ndNarrow(a, (int)i);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_nd_rank(NdArgs a) {
+  long long i = MG_IDX();
+  if (i < a.N1) ndRank(a, (int)i);
+}
+// one wave per output word: the workgroup's four waves take four consecutive words.  Every lane of a wave takes the same branches (w is wave-uniform), so the ballot
+// sees all 64 lanes; src is loaded once per word and the rows are looped inside
+__global__ __launch_bounds__(MG_THREADS) void k_nd_mask(NdArgs a) {
+  const long long t = MG_IDX();
+  const int w = (int)(t >> 6), lane = (int)(threadIdx.x & 63);
+  if (w >= a.W1) return;
+  const int nn = 64 * w + lane;
+  const int s = nn < a.N1 ? a.src[nn] : -1;
+  for (int k = 0; k < ND_MASKS; k++)
+    for (int row = 0; row < a.rows[k]; row++) {
+      const bool b = s >= 0 && ndBit(a.inMask[k] + (size_t)row * a.W, s);
+      const unsigned long long word = __ballot(b);
+      if (lane == 0) a.outMask[k][(size_t)row * a.W1 + w] = word;
+    }
+}
+__global__ __launch_bounds__(MG_THREADS) void k_nd_job(NdArgs a) {
+  long long j = MG_IDX();
+  if (j < a.M) ndJob(a, (int)j);
+}
+extern "C" int asched_internal_nd_mark(const NdArgs* a, int value, hipStream_t st) {
+  if (a->n > 0) hipLaunchKernelGGL(k_nd_mark, dim3(mgBlocks(a->n)), dim3(MG_THREADS), 0, st, *a, value);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_nd_check(const NdArgs* a, hipStream_t st) {
+  if (a->M > 0) hipLaunchKernelGGL(k_nd_check, dim3(mgBlocks(a->M)), dim3(MG_THREADS), 0, st, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_nd_gather(const NdArgs* a, hipStream_t st) {
+  if (a->N1 <= 0) return 0;
+  hipLaunchKernelGGL(k_nd_plane, dim3(mgBlocks((long long)a->R * a->N1)), dim3(MG_THREADS), 0, st, *a);
+  hipLaunchKernelGGL(k_nd_narrow, dim3(mgBlocks(a->N1)), dim3(MG_THREADS), 0, st, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_nd_rank(const NdArgs* a, hipStream_t st) {
+  if (a->N1 > 0) hipLaunchKernelGGL(k_nd_rank, dim3(mgBlocks(a->N1)), dim3(MG_THREADS), 0, st, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_nd_mask(const NdArgs* a, hipStream_t st) {
+  int rows = 0;
+  for (int k = 0; k < ND_MASKS; k++) rows += a->rows[k];
+  if (rows > 0 && a->W1 > 0) hipLaunchKernelGGL(k_nd_mask, dim3(mgBlocks((long long)a->W1 * 64)), dim3(MG_THREADS), 0, st, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_nd_job(const NdArgs* a, hipStream_t st) {
+  if (a->M > 0) hipLaunchKernelGGL(k_nd_job, dim3(mgBlocks(a->M)), dim3(MG_THREADS), 0, st, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}

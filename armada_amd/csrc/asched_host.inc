@@ -32,6 +32,7 @@
 #include "kernels_jobs_append.h"    // JaArgs and, in the CPU build of the tests, plat_jobs_append
 #include "kernels_jobs_delete.h"    // JdArgs and, in the CPU build of the tests, plat_jobs_delete
 #include "kernels_nodes_patch.h"    // NpArgs and, in the CPU build of the tests, plat_nodes_patch
+#include "kernels_nodes_delete.h"   // NdArgs and, in the CPU build of the tests, plat_nodes_delete
 
 namespace {
 
@@ -265,6 +266,13 @@ struct asched {
   DevBufs npBufs; char* npScratch = nullptr; size_t npScratchBytes = 0;   // the entries of a patch: one block, kept between calls and only ever grown
   int32_t npStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_nodes_patch_stats
   double npMs[2] = {0, 0};           // device ms of scatter / mask words of the last patch (ASCHED_NP_TIMES=1)
+  // ---- asched_nodes_delete (kernels_nodes_delete.h).  slotValueCount: nodes that carry slotValues[s][k] — a value that loses its last node takes the rebuild path, as a
+  // node type that loses its last node does (types[].numNodes).  The keep flags are a block of their own, all 1 between calls; the rest of the scratch is kept and only grown
+  std::vector<std::vector<int32_t>> slotValueCount;
+  DevBufs ndBufs; uint8_t* ndKeep = nullptr; size_t ndKeepCap = 0; char* ndScratch = nullptr; size_t ndScratchBytes = 0;
+  std::vector<int32_t> ndMap;        // [N] the old -> new map of the last delete on the host (the remap of the jNode mirror)
+  int32_t ndStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_nodes_delete_stats
+  double ndMs[7] = {0, 0, 0, 0, 0, 0, 0};   // device ms of the passes of the last delete (ASCHED_ND_TIMES=1)
   double roundTotalMs = 0, roundControlMs = 0, roundPhaseMs[4] = {0, 0, 0, 0};   // split round: whole sequence / persistent passes / evict-1, evict-3, final bulk phases (host clock)
   int submitWideUnits = 0, submitWidePasses = 0, submitSeqUnits = 0, submitGangUnits = 0, submitNodePasses = 0, submitLitUnits = 0;   // how the last submit_check ran (submit_stats)
 };
@@ -849,7 +857,7 @@ asched_t* asched_create(const asched_config* c) {
 void asched_destroy(asched_t* h) {
   if (!h) return;
   plat_enter(h->plat);
-  h->nodeBufs.freeAll(); h->jobBufs.freeAll(); h->queueBufs.freeAll(); h->maskBufs.freeAll(); h->fastBufs.freeAll(); h->pjBufs.freeAll(); h->evrBufs.freeAll(); h->exclBufs.freeAll(); h->jpBufs.freeAll(); h->npBufs.freeAll();
+  h->nodeBufs.freeAll(); h->jobBufs.freeAll(); h->queueBufs.freeAll(); h->maskBufs.freeAll(); h->fastBufs.freeAll(); h->pjBufs.freeAll(); h->evrBufs.freeAll(); h->exclBufs.freeAll(); h->jpBufs.freeAll(); h->npBufs.freeAll(); h->ndBufs.freeAll();
   plat_pinned_free(h->resPin); plat_free(h->commStatus); plat_free(h->dev.rs); plat_free(h->dev.cmdIO); plat_free(h->dev.scanResult); plat_free(h->dev.undo);
   plat_close(h->plat);
   delete h;
@@ -876,6 +884,43 @@ void nodeTypeOf(asched* h, const std::vector<HTaint>& taints, const std::vector<
   for (auto& x : t.taints) canon += "t" + std::to_string(x.key) + "=" + std::to_string(x.value) + ":" + std::to_string(x.effect) + "$";
   canon += "&";
   for (auto& l : t.labels) canon += std::to_string(l.key) + "=" + std::to_string(l.value) + "$";
+}
+
+// What nodesUpsertBody would refuse for a table of `N` rows with these populated node types and this allocatable [N][R], decided before anything changes: the key
+// layout of that table (layoutKeys) and LIT_TMAX for a row on the literal iteration path.  Everything the decision touches is saved and put back: the handle is as it
+// was on return.  The rebuild paths of asched_nodes_patch and asched_nodes_delete share it.  0, or the code with the reason in rwhy
+int rebuildRefusal(asched* h, std::vector<HType>& typesAfter, const int64_t* alloc, int N, std::string& rwhy) {
+  Dev& d = h->dev;
+  const int R = h->R, K = h->K;
+  const DevCfg cfgSaved = d.cfg; const bool keyWideSaved = h->keyWide, keyCoarseSaved = h->keyCoarse, alignedSaved = h->allocAligned;
+  const int nSaved = h->N;
+  const std::string errSaved = h->err;
+  int64_t maxQ[MAXK], minQ[MAXK], gcdV[MAXK], maxV[MAXK];
+  for (int c = 0; c < MAXK; c++) { maxQ[c] = h->keyMaxQ[c]; minQ[c] = h->keyMinQ[c]; gcdV[c] = h->keyGcdV[c]; maxV[c] = h->keyMaxV[c]; }
+  h->types.swap(typesAfter);
+  h->N = N;
+  h->allocAligned = true;
+  for (int c = 0; c < K; c++) {
+    const int64_t res = h->indexedRes[c]; const int col = h->indexedCol[c];
+    int64_t q = 0, g = 0, mv = 0;
+    for (int v = 0; v < N; v++) { const int64_t a = alloc[(size_t)v * R + col]; if (a % res) h->allocAligned = false; q = std::max(q, a / res); g = std::gcd(g, a < 0 ? -a : a); mv = std::max(mv, a); }
+    h->keyMaxQ[c] = q; h->keyMinQ[c] = 0; h->keyGcdV[c] = g; h->keyMaxV[c] = mv;
+  }
+  int rrc = layoutKeys(h);
+  rwhy = rrc ? h->err : std::string();
+  if (!rrc && h->jobsSet) {
+    const int Sext = h->S + (int)h->awayRowClass.size();
+    for (int row = 0; row < Sext && !rrc; row++) {
+      const int shape = row < h->S ? row : h->awayRowShape[row - h->S], cls = row < h->S ? h->shapeClass[row] : h->awayRowClass[row - h->S];
+      size_t nTypes = 0;
+      for (auto& t : h->types) if (classMatchesType(h, cls, t)) nTypes++;
+      const bool literal = h->shapeUnaligned[shape] || (nTypes > 1 && !(h->allocAligned && h->idRankMonotone));
+      if (literal && nTypes > LIT_TMAX) { rrc = ASCHED_ERR_UNSUPPORTED; rwhy = "a requirement class on the literal iteration path matches more than LIT_TMAX node types"; }
+    }
+  }
+  h->types.swap(typesAfter); h->N = nSaved; h->allocAligned = alignedSaved; d.cfg = cfgSaved; h->keyWide = keyWideSaved; h->keyCoarse = keyCoarseSaved; h->err = errSaved;
+  for (int c = 0; c < MAXK; c++) { h->keyMaxQ[c] = maxQ[c]; h->keyMinQ[c] = minQ[c]; h->keyGcdV[c] = gcdV[c]; h->keyMaxV[c] = maxV[c]; }
+  return rrc;
 }
 
 // asched_nodes_upsert, and the rebuild path of asched_nodes_patch on the patched table
@@ -970,10 +1015,11 @@ int nodesUpsertBody(asched* h, const asched_nodes* in) {
   // uniformity labels: values present on nodes, per indexed label (nodedb.go:143, addNodeToStats)
   h->labelSlots.assign(h->indexedLabels.begin(), h->indexedLabels.end());
   h->slotValues.assign(h->labelSlots.size(), {});
+  h->slotValueCount.assign(h->labelSlots.size(), {});
   for (size_t s = 0; s < h->labelSlots.size(); s++) {
-    std::set<int32_t> vals;
-    for (int i = 0; i < N; i++) for (auto& l : h->nodeLabels[i]) if (l.key == h->labelSlots[s]) vals.insert(l.value);
-    h->slotValues[s].assign(vals.begin(), vals.end());
+    std::map<int32_t, int32_t> vals;   // value -> nodes that carry it (asched_nodes_delete keeps the counts)
+    for (int i = 0; i < N; i++) for (auto& l : h->nodeLabels[i]) if (l.key == h->labelSlots[s]) vals[l.value]++;
+    for (auto& kv : vals) { h->slotValues[s].push_back(kv.first); h->slotValueCount[s].push_back(kv.second); }
   }
   d.totalRes = h->nodeBufs.upload(totalRes);
   d.allocatable = h->nodeBufs.upload(allocatable);
@@ -1039,7 +1085,7 @@ extern "C" {
 int32_t asched_nodes_upsert(asched_t* h, const asched_nodes* in) {
   if (!h) return ASCHED_ERR_INVALID;
   plat_enter(h->plat);
-  memset(h->npStats, 0, sizeof h->npStats);
+  memset(h->npStats, 0, sizeof h->npStats); memset(h->ndStats, 0, sizeof h->ndStats);
   return nodesUpsertBody(h, in);
 }
 
@@ -2102,36 +2148,13 @@ int32_t asched_nodes_patch(asched_t* h, const asched_nodes_patch_rows* rows) {
       lOff[v + 1] = (int32_t)lKey.size();
     }
     tKey.push_back(0); tVal.push_back(0); tEff.push_back(0); lKey.push_back(0); lVal.push_back(0);
-    // what that code can refuse, decided first: the key layout of the patched table (layoutKeys) and LIT_TMAX for a row on the literal iteration path
+    // what that code can refuse, decided first, with everything put back (rebuildRefusal)
     {
-      const DevCfg cfgSaved = d.cfg; const bool keyWideSaved = h->keyWide, keyCoarseSaved = h->keyCoarse, alignedSaved = h->allocAligned;
-      int64_t maxQ[MAXK], minQ[MAXK], gcdV[MAXK], maxV[MAXK];
-      for (int c = 0; c < MAXK; c++) { maxQ[c] = h->keyMaxQ[c]; minQ[c] = h->keyMinQ[c]; gcdV[c] = h->keyGcdV[c]; maxV[c] = h->keyMaxV[c]; }
-      std::vector<HType> typesSaved; typesSaved.swap(h->types);
-      for (size_t t = 0; t < typesSaved.size(); t++) if (typesSaved[t].numNodes + typeDelta[t] > 0) h->types.push_back(typesSaved[t]);
-      for (auto& t : newTypes) h->types.push_back(t);
-      h->allocAligned = true;
-      for (int c = 0; c < K; c++) {
-        const int64_t res = h->indexedRes[c]; const int col = h->indexedCol[c];
-        int64_t q = 0, g = 0, mv = 0;
-        for (int v = 0; v < N; v++) { const int64_t a = alloc[(size_t)v * R + col]; if (a % res) h->allocAligned = false; q = std::max(q, a / res); g = std::gcd(g, a < 0 ? -a : a); mv = std::max(mv, a); }
-        h->keyMaxQ[c] = q; h->keyMinQ[c] = 0; h->keyGcdV[c] = g; h->keyMaxV[c] = mv;
-      }
-      int rrc = layoutKeys(h);
-      std::string rwhy = rrc ? h->err : std::string();
-      if (!rrc && h->jobsSet) {
-        const int Sext = h->S + (int)h->awayRowClass.size();
-        for (int row = 0; row < Sext && !rrc; row++) {
-          const int shape = row < h->S ? row : h->awayRowShape[row - h->S], cls = row < h->S ? h->shapeClass[row] : h->awayRowClass[row - h->S];
-          size_t nTypes = 0;
-          for (auto& t : h->types) if (classMatchesType(h, cls, t)) nTypes++;
-          const bool literal = h->shapeUnaligned[shape] || (nTypes > 1 && !(h->allocAligned && h->idRankMonotone));
-          if (literal && nTypes > LIT_TMAX) { rrc = ASCHED_ERR_UNSUPPORTED; rwhy = "a requirement class on the literal iteration path matches more than LIT_TMAX node types"; }
-        }
-      }
-      h->types.swap(typesSaved); h->allocAligned = alignedSaved; d.cfg = cfgSaved; h->keyWide = keyWideSaved; h->keyCoarse = keyCoarseSaved;
-      for (int c = 0; c < MAXK; c++) { h->keyMaxQ[c] = maxQ[c]; h->keyMinQ[c] = minQ[c]; h->keyGcdV[c] = gcdV[c]; h->keyMaxV[c] = maxV[c]; }
-      if (rrc) return fail(h, rrc, "nodes_patch: " + rwhy);
+      std::vector<HType> typesAfter;
+      for (size_t t = 0; t < h->types.size(); t++) if (h->types[t].numNodes + typeDelta[t] > 0) typesAfter.push_back(h->types[t]);
+      for (auto& t : newTypes) typesAfter.push_back(t);
+      std::string rwhy;
+      if (int rrc = rebuildRefusal(h, typesAfter, alloc.data(), N, rwhy)) return fail(h, rrc, "nodes_patch: " + rwhy);
     }
     std::vector<uint64_t> index = h->nodeIndexHost; std::vector<int64_t> total = h->nodeTotal; std::vector<int32_t> idRank = h->nodeIdRank;
     asched_nodes in; memset(&in, 0, sizeof in);
@@ -2222,6 +2245,244 @@ int32_t asched_nodes_patch_stats(asched_t* h, int32_t* out) {
   if (!h || !out) return ASCHED_ERR_INVALID;
   plat_enter(h->plat);
   for (int k = 0; k < 8; k++) out[k] = h->npStats[k];
+  return 0;
+}
+
+// ---- asched_nodes_delete (kernels_nodes_delete.h): rows leave the resident node table — what populateNodeDb does every cycle to an unschedulable node that holds no
+// job (scheduling_algo.go:1069-1077) and to the nodes of an executor it filters out (:1100-1169).  The handle is left as asched_nodes_upsert of the table without the
+// named rows would leave it, with every run of the resident job table sent through the old -> new map.  Two paths, chosen per call, as in asched_nodes_patch: nothing
+// the host derives from the WHOLE table can change (no node type and no value of an indexed label loses its last node) — the per-node arrays are gathered and the mask
+// rows bit-compacted on the device; or the reduced table goes through nodes_upsert's own code (nodesUpsertBody) and only the jobs' nodes are remapped on the device.
+int32_t asched_nodes_delete(asched_t* h, int32_t n, const int32_t* node, int32_t* new_id) {
+  if (!h) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  const int N = h->N, R = h->R, P = h->P;
+  Dev& d = h->dev;
+  // ---- every refusal before anything changes
+  if (!h->nodesSet || h->nodeAllocHost.size() != (size_t)N * R || h->nodeOverAlloc.size() != (size_t)N || h->nodeIndexHost.size() != (size_t)N)
+    return fail(h, ASCHED_ERR_INVALID, "nodes_delete: no node table on this handle (nodes_upsert first)");
+  if (n < 0 || (n > 0 && !node)) return fail(h, ASCHED_ERR_INVALID, "nodes_delete: bad arguments");
+  if (h->uploadedAllocByPrio || h->hasTypeOverride) return fail(h, ASCHED_ERR_UNSUPPORTED, "nodes_delete: the node table was uploaded with alloc_by_prio or node_type_override (nodes_upsert instead)");
+  if (h->npSeen.size() != (size_t)N) h->npSeen.assign(N, 0);
+  std::vector<uint8_t>& gone = h->npSeen;   // [N] the rows of this call, until the mirrors are compacted
+  auto ungone = [&](int upTo) { for (int i = 0; i < upTo; i++) gone[node[i]] = 0; };
+  { int marked = 0; const char* why = nullptr;
+    for (int i = 0; i < n; i++) {
+      const int v = node[i];
+      if (v < 0 || v >= N) { why = "nodes_delete: a row outside the node table"; break; }
+      if (gone[v]) { why = "nodes_delete: a row named twice"; break; }
+      gone[v] = 1; marked = i + 1;
+    }
+    if (why) { ungone(marked); return fail(h, ASCHED_ERR_INVALID, why); } }
+  if (n > 0 && n == N) { ungone(n); return fail(h, ASCHED_ERR_UNSUPPORTED, "nodes_delete: every row of the table is named (a handle holds at least one node: nodes_upsert of the next table instead)"); }
+  const int N1 = N - n, M = h->jobsSet ? h->M : 0;
+  const int Npad = d.cfg.Npad, W = d.cfg.W;
+  int Npad1 = ((N1 + 63) / 64) * 64; if (Npad1 == 0) Npad1 = 64;
+  const int W1 = Npad1 / 64;
+  // which path: a node type or a value of an indexed label that loses its last node changes what the host derives from the whole table
+  int why = 0;
+  std::vector<int> typeGone(h->types.size(), 0);
+  std::vector<std::vector<int32_t>> valueGone(h->slotValueCount.size());
+  for (size_t s = 0; s < valueGone.size(); s++) valueGone[s].assign(h->slotValueCount[s].size(), 0);
+  auto slotValueOf = [&](size_t s, int32_t value) { const auto& vs = h->slotValues[s]; return (size_t)(std::lower_bound(vs.begin(), vs.end(), value) - vs.begin()); };
+  for (int i = 0; i < n; i++) {
+    const int v = node[i];
+    typeGone[h->nodeType[v]]++;
+    for (auto& l : h->nodeLabels[v]) for (size_t s = 0; s < h->labelSlots.size(); s++) if (l.key == h->labelSlots[s]) { const size_t k = slotValueOf(s, l.value); if (k < valueGone[s].size()) valueGone[s][k]++; }
+  }
+  // (an indexed label is part of the node type: a value that loses its last node empties a node type as well — the value is the reason reported then)
+  for (size_t s = 0; s < valueGone.size() && !why; s++) for (size_t k = 0; k < valueGone[s].size(); k++) if (valueGone[s][k] > 0 && h->slotValueCount[s][k] - valueGone[s][k] <= 0) { why = 4; break; }
+  for (size_t t = 0; t < h->types.size() && !why; t++) if (h->types[t].numNodes > 0 && h->types[t].numNodes - typeGone[t] <= 0) why = 2;
+  // the reduced table of the rebuild path, and what nodes_upsert's code would refuse for it
+  std::vector<int64_t> rAlloc, rTotal; std::vector<uint8_t> rUns, rOver; std::vector<uint64_t> rIndex; std::vector<int32_t> rIdRank, tOff, tKey, tVal, tEff, lOff, lKey, lVal;
+  if (why) {
+    tOff.push_back(0); lOff.push_back(0);
+    for (int v = 0; v < N; v++) {
+      if (gone[v]) continue;
+      for (int r = 0; r < R; r++) { rAlloc.push_back(h->nodeAllocHost[(size_t)v * R + r]); rTotal.push_back(h->nodeTotal[(size_t)v * R + r]); }
+      rUns.push_back(h->nodeUnsched[v]); rOver.push_back(h->nodeOverAlloc[v]); rIndex.push_back(h->nodeIndexHost[v]); rIdRank.push_back(h->nodeIdRank[v]);
+      const std::vector<HTaint>& tv = h->nodeTaints[v];
+      const size_t cnt = tv.size() - (h->nodeUnsched[v] ? 1 : 0);   // (without the unschedulable taint: nodes_upsert adds it)
+      for (size_t k = 0; k < cnt; k++) { tKey.push_back(tv[k].key); tVal.push_back(tv[k].value); tEff.push_back(tv[k].effect); }
+      tOff.push_back((int32_t)tKey.size());
+      for (auto& l : h->nodeLabels[v]) { lKey.push_back(l.key); lVal.push_back(l.value); }
+      lOff.push_back((int32_t)lKey.size());
+    }
+    tKey.push_back(0); tVal.push_back(0); tEff.push_back(0); lKey.push_back(0); lVal.push_back(0);
+    std::vector<HType> typesAfter;
+    for (size_t t = 0; t < h->types.size(); t++) if (h->types[t].numNodes - typeGone[t] > 0) typesAfter.push_back(h->types[t]);
+    std::string rwhy;
+    if (int rrc = rebuildRefusal(h, typesAfter, rAlloc.data(), N1, rwhy)) { ungone(n); return fail(h, rrc, "nodes_delete: " + rwhy); }
+  }
+  // ---- the scratch and every fresh block before anything changes: running out of device memory here is a refusal too.  The scratch: the entries | the survivors' list |
+  // the new positions | the check word.  The blocks keep the sizes of the ones they replace (block sizes do not shrink); only the strides inside them change
+  const bool masks = !why && h->jobsSet && h->dClassMask && h->dShapeClass;
+  const bool haveFast = !why && h->jobsSet && d.f.structOk && d.nodeCls;
+  const int Sext = masks ? h->S + (int)h->awayRowClass.size() : 0, labelRows = masks && !h->uniOffHost.empty() ? h->uniOffHost.back() : 0;
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t oSrc = up(sizeof(int32_t) * (size_t)n), oNew = oSrc + up(sizeof(int32_t) * (size_t)N), oBad = oNew + up(sizeof(int32_t) * (size_t)N), need = oBad + 256;
+  struct Block { DevBufs* owner; void** slot; size_t bytes; int fill; void* fresh; };
+  std::vector<Block> blocks;
+  char* scratchNew = nullptr; uint8_t* keepNew = nullptr;
+  if (n > 0) {
+    auto stage = [&](DevBufs* owner, void* slot, size_t bytes, int fill = 0) { blocks.push_back({owner, (void**)slot, std::max<size_t>(bytes, 1), fill, nullptr}); };
+    if (!why) {
+      const size_t np = (size_t)Npad;
+      stage(&h->nodeBufs, &d.totalRes, 8 * R * np); stage(&h->nodeBufs, &d.allocatable, 8 * R * np); stage(&h->nodeBufs, &d.alloc, 8 * (size_t)P * R * np);
+      stage(&h->nodeBufs, &d.keys, 8 * 2 * (size_t)P * np, 0xff);
+      stage(&h->nodeBufs, &d.nodeFlags, (size_t)N); stage(&h->nodeBufs, &d.idxRank, 4 * (size_t)N); stage(&h->nodeBufs, &d.nodeByRank, 4 * (size_t)N); stage(&h->nodeBufs, &d.nodeIdRank, 4 * (size_t)N);
+      stage(&h->nodeBufs, &d.accAvail, 8 * np * R); stage(&h->nodeBufs, &d.accStamp, 4 * np); stage(&h->nodeBufs, &d.accStaticFailed, np);
+      stage(&h->nodeBufs, &d.fairOff, 4 * (np + 2)); stage(&h->nodeBufs, &d.nodeOver, 4 * np);
+      if (masks) {
+        stage(&h->maskBufs, &h->dClassMask, 8 * (size_t)h->Cext * W); stage(&h->maskBufs, &d.shapeMask, 8 * (size_t)std::max(Sext, 1) * W);
+        stage(&h->maskBufs, &d.typeMask, 8 * std::max<size_t>(h->types.size(), 1) * W); stage(&h->maskBufs, &d.labelMask, 8 * (size_t)std::max(labelRows, 1) * W);
+        stage(&h->maskBufs, &h->dNodeType, 4 * (size_t)N);
+      }
+      if (haveFast) stage(&h->fastBufs, &d.nodeCls, 8 * (size_t)N);
+    }
+    bool ok = true;
+    if (h->ndScratchBytes < need) { scratchNew = (char*)plat_malloc(need + need / 4); ok = scratchNew != nullptr; }
+    if (ok && h->ndKeepCap < (size_t)N) { keepNew = (uint8_t*)plat_malloc((size_t)N); ok = keepNew != nullptr; }
+    for (auto& b : blocks) { if (!ok) break; b.fresh = plat_malloc(b.bytes); ok = b.fresh != nullptr; }
+    if (!ok) {
+      (void)plat_take_failure();
+      for (auto& b : blocks) if (b.fresh) plat_free(b.fresh);
+      if (scratchNew) plat_free(scratchNew);
+      if (keepNew) plat_free(keepNew);
+      ungone(n);
+      return fail(h, ASCHED_ERR_DEVICE, "nodes_delete: out of device memory for the scratch and the compacted node table; the handle is as it was");
+    }
+    auto adopt = [&](void* fresh, size_t bytes, void* old) {
+      for (size_t k = 0; k < h->ndBufs.ptrs.size(); k++) if (old && h->ndBufs.ptrs[k].first == old) { h->ndBufs.ptrs.erase(h->ndBufs.ptrs.begin() + k); plat_free(old); break; }
+      h->ndBufs.ptrs.push_back({fresh, bytes});
+    };
+    if (scratchNew) { adopt(scratchNew, need + need / 4, h->ndScratch); h->ndScratch = scratchNew; h->ndScratchBytes = need + need / 4; }
+    if (keepNew) { adopt(keepNew, (size_t)N, h->ndKeep); h->ndKeep = keepNew; h->ndKeepCap = (size_t)N; plat_memset(keepNew, 1, (size_t)N); }
+  }
+  // ---- mark and check: a running job on a named row is the last refusal, read from the device before anything else is written
+  NdArgs a; memset(&a, 0, sizeof a);
+  if (n > 0) {
+    a.N = N; a.N1 = N1; a.n = n; a.R = R; a.M = M; a.Npad = Npad; a.Npad1 = Npad1; a.W = W; a.W1 = W1;
+    int32_t* e32 = (int32_t*)h->ndScratch;
+    plat_h2d(e32, node, sizeof(int32_t) * (size_t)n);
+    a.node = e32; a.keep = h->ndKeep; a.src = (int32_t*)(h->ndScratch + oSrc); a.newId = (uint32_t*)(h->ndScratch + oNew); a.bad = (int32_t*)(h->ndScratch + oBad);
+    a.jNode0 = M > 0 ? d.jNode0 : nullptr; a.jrec = (M > 0 && d.f.structOk && d.jrec) ? d.jrec : nullptr;
+    int32_t bad = ND_NONE;
+    const int crc = plat_take_failure() ? -1 : plat_nodes_delete_check(d, a, &bad);
+    if (crc || bad != ND_NONE) {
+      for (auto& b : blocks) plat_free(b.fresh);
+      ungone(n);
+      if (crc) { h->ndBufs.freeAll(); h->ndKeep = nullptr; h->ndKeepCap = 0; h->ndScratch = nullptr; h->ndScratchBytes = 0; return fail(h, ASCHED_ERR_DEVICE, plat_last_error()); }
+      return fail(h, ASCHED_ERR_INVALID, "nodes_delete: job row " + std::to_string(bad) + " runs on a named node (say what became of the run first: jobs_patch with node -1, or jobs_delete)");
+    }
+  }
+  // ---- what nodes_upsert resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the tables half compacted: asched_nodes_upsert and asched_jobs_set before anything else)
+  h->haveRoundResult = false; h->stateEpoch++;
+  { d.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
+    int32_t zero = 0;
+    plat_h2d(&d.rs->fastActive, &zero, sizeof zero);
+    plat_h2d(&d.rs->l0SaveCount, &zero, sizeof zero); }
+  h->prepared = false; h->evrSized = false; h->equalLevels = P;
+  memset(h->ndStats, 0, sizeof h->ndStats); for (int k = 0; k < 7; k++) h->ndMs[k] = 0;
+  int renumbered = 0;
+  if (n > 0) {
+    auto fresh = [&](void* slot) -> void* { for (auto& b : blocks) if ((void*)b.slot == slot) return b.fresh; return nullptr; };
+    for (auto& b : blocks) plat_memset(b.fresh, b.fill, b.bytes);
+    a.jobsOnly = why ? 1 : 0;
+    if (!why) {
+      a.inTotal = d.totalRes; a.outTotal = (int64_t*)fresh(&d.totalRes); a.inAlloc = d.allocatable; a.outAlloc = (int64_t*)fresh(&d.allocatable);
+      a.inFlags = d.nodeFlags; a.outFlags = (uint8_t*)fresh(&d.nodeFlags); a.inIdRank = d.nodeIdRank; a.outIdRank = (int32_t*)fresh(&d.nodeIdRank);
+      a.rankIn = d.nodeByRank; a.rankOut = (int32_t*)fresh(&d.nodeByRank); a.idxRankOut = (int32_t*)fresh(&d.idxRank);
+      if (masks) {
+        a.inType = h->dNodeType; a.outType = (int32_t*)fresh(&h->dNodeType);
+        const uint64_t* in[ND_MASKS] = {h->dClassMask, d.shapeMask, d.typeMask, d.labelMask};
+        void* sl[ND_MASKS] = {&h->dClassMask, &d.shapeMask, &d.typeMask, &d.labelMask};
+        const int rows[ND_MASKS] = {h->Cext, Sext, (int)h->types.size(), labelRows};
+        for (int k = 0; k < ND_MASKS; k++) { a.inMask[k] = in[k]; a.outMask[k] = (uint64_t*)fresh(sl[k]); a.rows[k] = rows[k]; }
+      }
+      if (haveFast) { a.inCls = d.nodeCls; a.outCls = (uint64_t*)fresh(&d.nodeCls); }
+    }
+    const int prc = plat_take_failure() ? -1 : plat_nodes_delete(d, a);
+    if (prc) {
+      for (auto& b : blocks) plat_free(b.fresh);
+      gone.assign(N, 0);
+      h->ndBufs.freeAll(); h->ndKeep = nullptr; h->ndKeepCap = 0; h->ndScratch = nullptr; h->ndScratchBytes = 0;
+      return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+    }
+    plat_nodes_delete_ms(h->ndMs);
+    // the old -> new map on the host: the scan's exclusive prefix, -1 for the rows that left
+    h->ndMap.resize(N);
+    plat_d2h(h->ndMap.data(), a.newId, sizeof(int32_t) * (size_t)N);
+    for (int i = 0; i < n; i++) h->ndMap[node[i]] = -1;
+    if (new_id) memcpy(new_id, h->ndMap.data(), sizeof(int32_t) * (size_t)N);
+    if (M > 0) {   // the jNode mirror, on the host threads asched_jobs_delete uses
+      const int first = *std::min_element(node, node + n);
+      std::atomic<int> cnt{0};
+      parallelChunks((size_t)M, M < 65536 ? 1 : (size_t)hostThreads(), [&](size_t lo, size_t hi) {
+        int c = 0;
+        for (size_t j = lo; j < hi; j++) { const int v = h->jNode[j]; if (v > first && v < N) { h->jNode[j] = h->ndMap[v]; c++; } }
+        cnt += c;
+      });
+      renumbered = cnt;
+    }
+    if (why) {
+      // ---- the rebuild path: the reduced table, from the handle's mirrors, through nodes_upsert's own code (the job table's nodes are already renumbered)
+      gone.assign(N1, 0);
+      asched_nodes in; memset(&in, 0, sizeof in);
+      in.n = N1; in.index = rIndex.data(); in.id_rank = rIdRank.data(); in.total = rTotal.data(); in.allocatable = rAlloc.data();
+      in.unschedulable = rUns.data(); in.over_allocated = rOver.data();
+      in.taint_off = tOff.data(); in.taint_key = tKey.data(); in.taint_value = tVal.data(); in.taint_effect = tEff.data();
+      in.label_off = lOff.data(); in.label_key = lKey.data(); in.label_value = lVal.data();
+      int rc = nodesUpsertBody(h, &in);
+      if (rc) return rc;
+    } else {
+      // ---- the device path: the blocks swapped in, the old ones released (plat_nodes_delete has waited for the device)
+      auto release = [&](DevBufs* owner, void* p) {
+        for (size_t k = 0; k < owner->ptrs.size(); k++) if (owner->ptrs[k].first == p) { owner->ptrs.erase(owner->ptrs.begin() + k); break; }
+        plat_free(p);
+      };
+      for (auto& b : blocks) { if (*b.slot) release(b.owner, *b.slot); *b.slot = b.fresh; b.owner->ptrs.push_back({b.fresh, b.bytes}); }
+      // scratch indexed by node that lives in the fast structure: the start a fresh nodes_upsert + jobs_set gives it (zeros), over the whole block
+      if (haveFast) {
+        void* scr[] = {d.baseKey, d.baseNode, d.baseExtra, d.baseCls, d.baseRemoved, d.posOf, d.l0Slot, d.fitBits};
+        for (void* p : scr) if (p) for (auto& e : h->fastBufs.ptrs) if (e.first == p) { plat_memset(p, 0, e.second); break; }
+      }
+      // the host mirrors, compacted in place (row order is kept: every element moves down or stays); the totals and the counts by difference (addNodeToStats, nodedb.go:44-55)
+      for (int i = 0; i < n; i++) {
+        const int v = node[i];
+        for (int r = 0; r < R; r++) if (!d.cfg.isFloating[r]) d.cfg.totalResources[r] -= h->nodeAllocHost[(size_t)v * R + r];
+      }
+      for (size_t t = 0; t < h->types.size(); t++) h->types[t].numNodes -= typeGone[t];
+      for (size_t s = 0; s < valueGone.size(); s++) for (size_t k = 0; k < valueGone[s].size(); k++) h->slotValueCount[s][k] -= valueGone[s][k];
+      { auto squeeze = [&](auto& v, size_t w) {
+          size_t o = 0;
+          for (size_t i = 0; i < (size_t)N; i++) if (!gone[i]) { if (o != i) for (size_t x = 0; x < w; x++) v[o * w + x] = std::move(v[i * w + x]); o++; }
+          v.resize((size_t)N1 * w);
+        };
+        squeeze(h->nodeTaints, 1); squeeze(h->nodeLabels, 1); squeeze(h->nodeType, 1); squeeze(h->nodeTotal, (size_t)R); squeeze(h->nodeAllocHost, (size_t)R);
+        squeeze(h->nodeIndexHost, 1); squeeze(h->nodeOverAlloc, 1); squeeze(h->nodeUnsched, 1); squeeze(h->nodeIdRank, 1); }
+      { size_t o = 0;
+        for (size_t i = 0; i < (size_t)N; i++) { const int v = h->nodeByRank[i]; if (h->ndMap[v] >= 0) h->nodeByRank[o++] = h->ndMap[v]; }
+        h->nodeByRank.resize(N1); }
+      gone.assign(N1, 0);
+      h->N = N1; d.cfg.N = N1; d.cfg.Npad = Npad1; d.cfg.W = W1;
+      if (haveFast) d.fitW = (N1 + 63) / 64;
+      if (h->jobsSet) exclSetup(h);   // (the [cap][W] bit rows of the failed-selection store: B_RESET_JOBS forgets the records anyway)
+    }
+    if (const char* e = getenv("ASCHED_ND_TIMES")) if (e[0] == '1')
+      fprintf(stderr, "[asched nodes_delete] nodes %d entries %d jobs %d mask rows %d path %s: mark + check %.4f ms, scan %.4f ms, gather %.4f ms, index order %.4f ms, mask rows %.4f ms, job remap %.4f ms, unmark %.4f ms\n",
+              N, n, M, a.rows[0] + a.rows[1] + a.rows[2] + a.rows[3], why ? "rebuild" : "device", h->ndMs[0], h->ndMs[1], h->ndMs[2], h->ndMs[3], h->ndMs[4], h->ndMs[5], h->ndMs[6]);
+  }
+  if (n == 0 && new_id) for (int i = 0; i < N; i++) new_id[i] = i;   // (no pass ran: every row keeps its position)
+  h->ndStats[0] = n; h->ndStats[1] = renumbered; h->ndStats[2] = why ? 1 : 0; h->ndStats[3] = why; h->ndStats[4] = h->N;
+  memset(h->npStats, 0, sizeof h->npStats);
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  return resetDynamicState(h, M);
+}
+int32_t asched_nodes_delete_stats(asched_t* h, int32_t* out) {
+  if (!h || !out) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  for (int k = 0; k < 8; k++) out[k] = h->ndStats[k];
   return 0;
 }
 

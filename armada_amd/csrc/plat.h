@@ -106,6 +106,14 @@ static void plat_jobs_delete_ms(double* out /*[5]*/);   // measurement hook: dev
 struct NpArgs;
 static int plat_nodes_patch(Dev& d, const NpArgs& a);
 static void plat_nodes_patch_ms(double* out /*[2]*/);   // measurement hook: device ms of scatter / mask words of the last call (events around them when ASCHED_NP_TIMES=1, else zeros)
+// rows leave the resident node table (kernels_nodes_delete.h).  plat_nodes_delete_check: mark, then the check of the running jobs; *bad is the lowest job row that runs on
+// a named node or ND_NONE, and in the first case the flags are set again: nothing else was written.  plat_nodes_delete: the scan (its count must be a.N1), the gathers
+// into the blocks of a.out*, the index order, the mask rows, the remap of the running jobs' nodes, unmark.  Synchronous: everything is complete on return.  The CPU
+// build's definitions sit in kernels_nodes_delete.h.
+struct NdArgs;
+static int plat_nodes_delete_check(Dev& d, NdArgs& a, int32_t* bad);
+static int plat_nodes_delete(Dev& d, NdArgs& a);
+static void plat_nodes_delete_ms(double* out /*[7]*/);   // measurement hook: device ms of mark + check / scan / gather / index order / mask rows / job remap / unmark of the last call (events around them when ASCHED_ND_TIMES=1, else zeros)
 static int plat_run_fit_capacity(Dev& d, const std::vector<int32_t>& shapes, std::vector<int32_t>& firstNode, std::vector<long long>& capacity, const int32_t* nodeByRankHost);
 static int plat_run_submit_gangs(Dev& d, const std::vector<int32_t>& off, const std::vector<int32_t>& jobs, std::vector<int32_t>& out);
 static double plat_last_fit_ms();

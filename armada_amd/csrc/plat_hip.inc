@@ -34,6 +34,7 @@ struct PlatCtx {
   hipEvent_t evrEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool evrTimed[3] = {false, false, false};   // ASCHED_EVR_TIMES=1: around the passes of the evictor report
   hipEvent_t jaEv[4] = {nullptr, nullptr, nullptr, nullptr}; bool jaTimed = false;   // ASCHED_JA_TIMES=1: around the passes of the job-table append
   hipEvent_t jpEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool jpTimed = false;   // ASCHED_JP_TIMES=1: around the passes of the job-table patch
+  hipEvent_t ndEv[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool ndTimed = false;   // ASCHED_ND_TIMES=1: around the passes of the node-table delete
   hipEvent_t jdEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool jdTimed = false;   // ASCHED_JD_TIMES=1: around the passes of the job-table delete
   hipEvent_t npEv[3] = {nullptr, nullptr, nullptr}; bool npTimed = false;   // ASCHED_NP_TIMES=1: around the passes of the node-table patch
   float roundTotalMs = 0.f, roundControlMs = 0.f; int roundLaunches = 0;
@@ -256,6 +257,7 @@ static void plat_close(PlatCtx* c) {
   for (hipEvent_t e : c->jaEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->npEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->jdEv) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->ndEv) if (e) (void)hipEventDestroy(e);
   if (c->helpBox) (void)hipFree(c->helpBox);
   if (c->cmpScratch) (void)hipFree(c->cmpScratch);
   if (c->optScratch) (void)hipFree(c->optScratch);
@@ -1026,6 +1028,75 @@ static int plat_nodes_patch(Dev& d, const NpArgs& a) {
 static void plat_nodes_patch_ms(double* out) {
   hipEvent_t* ev = npEvents();
   for (int k = 0; k < 2; k++) { float ms = 0.f; if (ev && t_ctx->npTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
+}
+// rows leave the resident node table (kernels_nodes_delete.h; k_nd_* in armada_sched_mgpu.hip, the scans are plat_compact's).  The check brings its word back to the host
+// before anything is written; each compaction brings its count back.  ASCHED_ND_TIMES=1 puts events around the seven passes (tools/probe_nodes_delete.py).
+#include "kernels_nodes_delete.h"
+extern "C" int asched_internal_nd_mark(const NdArgs* a, int value, hipStream_t s);
+extern "C" int asched_internal_nd_check(const NdArgs* a, hipStream_t s);
+extern "C" int asched_internal_nd_gather(const NdArgs* a, hipStream_t s);
+extern "C" int asched_internal_nd_rank(const NdArgs* a, hipStream_t s);
+extern "C" int asched_internal_nd_mask(const NdArgs* a, hipStream_t s);
+extern "C" int asched_internal_nd_job(const NdArgs* a, hipStream_t s);
+static hipEvent_t* ndEvents() {
+  static const bool on = [] { const char* e = getenv("ASCHED_ND_TIMES"); return e && e[0] == '1'; }();
+  PlatCtx* c = t_ctx;
+  if (!on) return nullptr;
+  if (!c->ndEv[7]) for (int i = 0; i < 8; i++) if (!c->ndEv[i] && hipEventCreate(&c->ndEv[i]) != hipSuccess) { c->ndEv[i] = nullptr; return nullptr; }
+  return c->ndEv;
+}
+static int plat_nodes_delete_check(Dev& d, NdArgs& a, int32_t* bad) {
+  (void)d;
+  PlatCtx* c = t_ctx;
+  hipStream_t st = c->stream;
+  hipEvent_t* ev = ndEvents();
+  c->ndTimed = false;
+  *bad = ND_NONE;
+  const int32_t none = ND_NONE;
+  if (ev) (void)hipEventRecord(ev[0], st);
+  if (!hipOk(hipMemcpyAsync(a.bad, &none, sizeof none, hipMemcpyHostToDevice, st), "nodes_delete check word")) return -1;
+  if (asched_internal_nd_mark(&a, 0, st)) { c->err = "k_nd_mark launch failed"; return -1; }
+  if (asched_internal_nd_check(&a, st)) { c->err = "k_nd_check launch failed"; return -1; }
+  if (ev) (void)hipEventRecord(ev[1], st);
+  int32_t t = ND_NONE;
+  if (!hipOk(hipMemcpyAsync(&t, a.bad, sizeof t, hipMemcpyDeviceToHost, st), "nodes_delete check word") || !hipOk(hipStreamSynchronize(st), "k_nd_check")) return -1;
+  *bad = t;
+  if (t != ND_NONE) {
+    if (asched_internal_nd_mark(&a, 1, st) || !hipOk(hipStreamSynchronize(st), "k_nd_mark")) { if (c->err.empty()) c->err = "k_nd_mark launch failed"; return -1; }
+  }
+  return 0;
+}
+static int plat_nodes_delete(Dev& d, NdArgs& a) {
+  PlatCtx* c = t_ctx;
+  hipStream_t st = c->stream;
+  hipEvent_t* ev = ndEvents();
+  int n1 = 0;
+  if (plat_compact(d, nullptr, a.N, a.keep, a.src, a.newId, nullptr, 0, nullptr, &n1)) return -1;
+  if (n1 != a.N1) { c->err = "nodes_delete: the scan kept another number of rows than the host counted"; return -1; }
+  if (ev) (void)hipEventRecord(ev[2], st);
+  if (!a.jobsOnly && asched_internal_nd_gather(&a, st)) { c->err = "k_nd_gather launch failed"; return -1; }
+  if (ev) (void)hipEventRecord(ev[3], st);
+  if (!a.jobsOnly) {
+    int r1 = 0;
+    if (plat_compact(d, a.rankIn, a.N, a.keep, a.rankOut, nullptr, nullptr, 0, nullptr, &r1)) return -1;
+    if (r1 != a.N1) { c->err = "nodes_delete: the index order lost or gained rows"; return -1; }
+    if (asched_internal_nd_rank(&a, st)) { c->err = "k_nd_rank launch failed"; return -1; }
+  }
+  if (ev) (void)hipEventRecord(ev[4], st);
+  if (!a.jobsOnly && asched_internal_nd_mask(&a, st)) { c->err = "k_nd_mask launch failed"; return -1; }
+  if (ev) (void)hipEventRecord(ev[5], st);
+  if (asched_internal_nd_job(&a, st)) { c->err = "k_nd_job launch failed"; return -1; }
+  if (ev) (void)hipEventRecord(ev[6], st);
+  bool ok = asched_internal_nd_mark(&a, 1, st) == 0;
+  if (ev) (void)hipEventRecord(ev[7], st);
+  ok = ok && hipOk(hipGetLastError(), "k_nd launch") && hipOk(hipStreamSynchronize(st), "k_nd");
+  if (!ok) { if (c->err.empty()) c->err = "k_nd launch failed"; return -1; }
+  c->ndTimed = ev != nullptr;
+  return 0;
+}
+static void plat_nodes_delete_ms(double* out) {
+  hipEvent_t* ev = ndEvents();
+  for (int k = 0; k < 7; k++) { float ms = 0.f; if (ev && t_ctx->ndTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
 }
 // a caller-side buffer may be memory of this handle's GPU (a tensor the collective reduces in place: used directly) or host memory (staged)
 static bool plat_is_device_ptr(const void* p) {

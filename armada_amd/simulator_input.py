@@ -479,3 +479,119 @@ def run_cycles_cordoning(lib, sim: SimulatorInput, node_events, per_cycle: Optio
     comparison, and with appended=False — jobs_set of the grown table every cycle — what any library, the oracle included, can run).  Jobs stay on a node that is
     cordoned; a node's capacity may be cut below what its jobs hold.  Records as run_cycles_arriving."""
     return _run_cycles_arriving(lib, sim, per_cycle, max_cycles, appended, node_events=list(node_events), nodes_patched=nodes_patched)
+
+
+def _run_cycles_draining(lib, sim: SimulatorInput, node_events, per_cycle, max_cycles, drained):
+    from .binding import Scheduler
+    wl = sim.workload
+    m, n0 = wl.num_jobs, wl.num_nodes
+    arrive = arrival_cycles(sim, per_cycle)
+    node = np.full(m, -1, np.int64)                   # per job: the node it runs on, by the workload's node number (positions in the handle's table shift)
+    run_prio = np.zeros(m, np.int32)
+    started = np.full(m, -1.0)
+    done = np.zeros(m, bool)
+    changed = np.zeros(m, bool)
+    unschedulable = np.zeros(n0, np.uint8)
+    node_of_row = np.arange(n0, dtype=np.int64)       # the driver's own position <-> node map
+    row_of_node = np.arange(n0, dtype=np.int64)
+    pending = []                                      # nodes a "drop" event named that still hold a job or are not cordoned
+    id_rank = np.arange(n0) if wl.node_id_rank is None else np.asarray(wl.node_id_rank)
+    out = []
+    s = Scheduler(lib, wl.config)
+    s.nodes_upsert(wl.node_total, id_rank=id_rank)
+    have = 0
+    t = 0.0
+
+    def rows_of(jobs):
+        return np.where(node[jobs] >= 0, row_of_node[np.maximum(node[jobs], 0)], -1).astype(np.int32)
+
+    for cycle in range(max_cycles):
+        finished = (node >= 0) & (started >= 0) & (started + sim.job_runtime_s <= t)
+        done |= finished
+        node[finished] = -1
+        changed |= finished
+        if done.all():
+            break
+        upto = int(np.searchsorted(arrive, cycle, side="right"))
+        if drained:
+            if cycle == 0:
+                s.jobs_set(wl.job_req[:upto], queue=wl.job_queue[:upto], pc=wl.job_pc[:upto], submit_time=wl.job_submit[:upto], node=rows_of(np.arange(upto)),
+                           scheduled_at_priority=run_prio[:upto], run_timestamp=np.zeros(upto, np.int64))
+            elif upto > have:
+                s.jobs_append(wl.job_req[have:upto], queue=wl.job_queue[have:upto], pc=wl.job_pc[have:upto], submit_time=wl.job_submit[have:upto])
+            rows = np.nonzero(changed)[0].astype(np.int32)
+            if len(rows):
+                running = node[rows] >= 0
+                s.jobs_patch(rows, rows_of(rows), np.where(running, run_prio[rows], 0), np.where(running, np.maximum(started[rows], 0) * 1e9, 0).astype(np.int64))
+        changed[:] = False
+        have = upto
+        touched = []                                  # then the node events of this cycle, in the schedule's order
+        for ev in node_events:
+            if ev[0] != cycle:
+                continue
+            kind, n = ev[1], int(ev[2])
+            if kind == "cordon":
+                unschedulable[n] = 1
+                if row_of_node[n] >= 0 and n not in touched:
+                    touched.append(n)
+            elif kind == "drop":
+                if n not in pending:
+                    pending.append(n)
+            else:
+                raise ValueError(f"node event {kind!r}")
+        # populateNodeDb's rule (scheduling_algo.go:1069-1077): a node that is unschedulable and holds no job is left out — from the first cycle in which both hold
+        busy = np.zeros(n0, bool)
+        busy[node[node >= 0]] = True
+        gone = [n for n in pending if row_of_node[n] >= 0 and unschedulable[n] and not busy[n]]
+        gone = gone[:max(0, len(node_of_row) - 1)]    # (a table keeps at least one row)
+        pending = [n for n in pending if n not in gone]
+        if drained:
+            if touched:
+                s.nodes_patch(row_of_node[touched].astype(np.int32), unschedulable=unschedulable[touched])
+            if gone:
+                new_id = s.nodes_delete(row_of_node[gone].astype(np.int32), want_map=True)
+                row_of_node[node_of_row] = new_id
+                node_of_row = node_of_row[new_id >= 0]
+        else:
+            if gone:
+                node_of_row = node_of_row[~np.isin(node_of_row, gone)]
+                row_of_node[:] = -1
+                row_of_node[node_of_row] = np.arange(len(node_of_row))
+            s.nodes_upsert(wl.node_total[node_of_row], id_rank=id_rank[node_of_row], unschedulable=unschedulable[node_of_row])
+            running = node[:upto] >= 0
+            s.jobs_set(wl.job_req[:upto], queue=wl.job_queue[:upto], pc=wl.job_pc[:upto], submit_time=wl.job_submit[:upto], node=rows_of(np.arange(upto)),
+                       scheduled_at_priority=np.where(running, run_prio[:upto], 0), run_timestamp=np.where(running, np.maximum(started[:upto], 0) * 1e9, 0).astype(np.int64))
+        queued = [np.array([j for j in q if j < have and not done[j] and node[j] < 0], dtype=np.int32) for q in wl.queued]
+        nq = wl.num_queues
+        s.round_prepare(wl.queue_weight, queued, global_tokens=float(wl.global_burst), global_burst=wl.global_burst, global_rate_inf=wl.rate_inf,
+                        queue_tokens=[float(wl.queue_burst)] * nq, queue_burst=[wl.queue_burst] * nq, queue_rate_inf=[wl.rate_inf] * nq)
+        r = s.schedule_round()
+        sched = {int(j): int(node_of_row[n]) for j, n in r.scheduled.items()}             # by the workload's node number, not by position: positions are renumbered
+        pre = {int(j): int(node_of_row[n]) for j, n in r.preempted.items()}
+        for j, n in sched.items():
+            node[j], started[j], run_prio[j] = n, t, r.scheduled_priority[j]
+            changed[j] = True
+        for j in pre:
+            node[j], started[j] = -1, -1.0
+            changed[j] = True
+        out.append({"time_s": t, "scheduled": sched, "preempted": pre, "termination_reason": r.termination_reason, "rows": have, "nodes": len(node_of_row)})
+        if have == m and not sched and not pre and not (node >= 0).any():
+            break   # everything has arrived, nothing runs and nothing can be placed: the rest never will
+        t += sim.cycle_period_s
+    s.close()
+    return out
+
+
+def run_cycles_draining(lib, sim: SimulatorInput, node_events, per_cycle: Optional[int] = None, max_cycles: int = 1000):
+    """run_cycles_arriving plus nodes that are drained and LEAVE the table: node_events is a list of (cycle, "cordon", node) and (cycle, "drop", node), nodes by the
+    workload's numbering.  A cordon is one Scheduler.nodes_patch; a drop is applied with the reference's own rule (populateNodeDb, scheduling_algo.go:1069-1077): from
+    the event's cycle on, in the first cycle in which the node is unschedulable and holds no job, after the cycle's job changes, by Scheduler.nodes_delete — the
+    driver's position <-> node map follows the map the call returns.  Records as run_cycles_arriving, with nodes by the workload's numbering and "nodes" the table's
+    row count."""
+    return _run_cycles_draining(lib, sim, list(node_events), per_cycle, max_cycles, True)
+
+
+def run_cycles_draining_rebuilt(lib, sim: SimulatorInput, node_events, per_cycle: Optional[int] = None, max_cycles: int = 1000):
+    """the rebuilt counterpart of run_cycles_draining: nodes_upsert of each cycle's reduced node table and jobs_set of the grown job table, its runs on the reduced
+    table's positions, in every cycle — what any library, the oracle included, can run.  Same rows, same records."""
+    return _run_cycles_draining(lib, sim, list(node_events), per_cycle, max_cycles, False)

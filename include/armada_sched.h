@@ -455,12 +455,36 @@ typedef struct asched_nodes_patch_rows {
    ascending; ASCHED_ERR_UNSUPPORTED: the table was uploaded with alloc_by_prio or node_type_override (test-fixture inputs), whatever the rebuild would refuse (a key
    beyond 128 bits, more than LIT_TMAX node types on the literal path); ASCHED_ERR_DEVICE with "the handle is as it was" in last_error: out of device memory for the
    entries.  Any other ASCHED_ERR_DEVICE (a failed launch or copy) is NOT such a refusal: the handle then needs asched_nodes_upsert.
-   Not this call's job, all of them asched_nodes_upsert's: adding or removing rows (the reference's dropping of an unschedulable node that holds no job included,
-   scheduling_algo.go:1070-1077), total, labels, index, id_rank. */
+   Not this call's job: removing rows is asched_nodes_delete's (the reference's dropping of an unschedulable node that holds no job, scheduling_algo.go:1070-1077);
+   adding rows, total, labels, index and id_rank are asched_nodes_upsert's. */
 int32_t ASCHED_FN(nodes_patch)(asched_t*, const asched_nodes_patch_rows* rows);
 /* how the last nodes_patch ran: out[0] entries, [1] rows whose node type changed, [2] 1 = the rebuild path ran, [3] why: 0 none, 1 a node type the table did not
    have, 2 a node type emptied or newly populated, 3 key layout / divisor / alignment; [4..7] 0.  Zeros after nodes_upsert. */
 int32_t ASCHED_FN(nodes_patch_stats)(asched_t*, int32_t* out /*[8]*/);
+/* populateNodeDb leaves a node that IsUnschedulable() and holds no job out of the NodeDb, "so the resource of the node is not counted for fairshare"
+   (scheduling_algo.go:1069-1077), and so it does with every node of an executor it filters out as stale, lagging or cordoned (:1100-1169): the n rows node[0..n)
+   leave the resident node table.  The remaining rows keep their order and are renumbered densely: new position = old position - number of deleted rows below it.
+   new_id, when not NULL, receives that map for the N rows the table had before the call, -1 for a deleted row.
+   After a successful call every entry point answers as it would after asched_nodes_upsert of the same node table without the named rows, with the resident job table's
+   runs sent through that map (rounds, the NodeDb-level calls, fit_select_batch*, submit_check, iterate_nodes, excluded_nodes, node_types_matching_job, num_nodes,
+   total_resources, indexed_node_label_values, the getters, the evictor report, the preemption causes, the optimiser, a later jobs_patch / jobs_append / jobs_delete /
+   nodes_patch in any order), including everything nodes_upsert resets; the caller goes on with round_prepare.  n == 0 performs the resets only.  Block sizes do not
+   shrink.  The job table's rows, order, shapes, gangs and requirement classes stay, and so does the fast structure.  Aggregates that are bounds (the widths of the key
+   layout, alignment, the gcd of a column) stay conservative: results equal the fresh handle's, internal widths and path choices need not.
+   Two paths, chosen per call (nodes_delete_stats).  Where no node type and no value of an indexed label loses its last node, the work is on the device: the per-node
+   arrays are gathered into blocks with the new stride, every mask row is bit-compacted, the index order is compacted and the running jobs' nodes are renumbered; the
+   host compacts its per-node mirrors.  Otherwise the reduced table goes through nodes_upsert's own code and the jobs' nodes are renumbered on the device.
+   Refused before anything changes — ASCHED_ERR_INVALID: no node table, n < 0, n > 0 without node, a row outside [0, N), a row named twice, a resident job whose run is
+   on a named row (the reference logs "assigned to node ..., but no such node found" and leaves such a job unbound; here the caller says what became of the run first:
+   jobs_patch with node -1, or jobs_delete; last_error names the lowest such job row); ASCHED_ERR_UNSUPPORTED: every row is named (give the next table to
+   asched_nodes_upsert), the table was uploaded with alloc_by_prio or node_type_override, whatever the rebuild would refuse; ASCHED_ERR_DEVICE with "the handle is as
+   it was" in last_error: out of device memory for the scratch and the fresh blocks (all of it is allocated first).  Any other ASCHED_ERR_DEVICE (a failed launch or
+   copy) is NOT such a refusal: the handle then needs asched_nodes_upsert and asched_jobs_set.
+   Not this call's job: adding rows (asched_nodes_upsert). */
+int32_t ASCHED_FN(nodes_delete)(asched_t*, int32_t n, const int32_t* node /*[n] rows, each at most once*/, int32_t* new_id /*[N before the call] or NULL*/);
+/* how the last nodes_delete ran: out[0] rows deleted, [1] job rows whose node was renumbered, [2] 1 = the rebuild path ran, [3] why: 0 none, 2 a node type emptied,
+   4 a value of an indexed label emptied; [4] N after the call, [5..7] 0.  Zeros after nodes_upsert. */
+int32_t ASCHED_FN(nodes_delete_stats)(asched_t*, int32_t* out /*[8]*/);
 
 int32_t ASCHED_FN(txn_begin)(asched_t*);    /* nodeDb.Txn(true) (nodedb.go:353) */
 int32_t ASCHED_FN(txn_commit)(asched_t*);
