@@ -107,6 +107,15 @@ class CNodesPatch(C.Structure):  # asched_nodes_patch_rows
     ]
 
 
+class CNodesAppend(C.Structure):  # asched_nodes_append_rows
+    _fields_ = [
+        ("m", C.c_int32), ("index", _u64p), ("id_rank", _i32p), ("id_rank_all", _i32p), ("total", _i64p), ("allocatable", _i64p),
+        ("unschedulable", _u8p), ("over_allocated", _u8p),
+        ("taint_off", _i32p), ("taint_key", _i32p), ("taint_value", _i32p), ("taint_effect", _i32p),
+        ("label_off", _i32p), ("label_key", _i32p), ("label_value", _i32p),
+    ]
+
+
 class CReqClasses(C.Structure):
     _fields_ = [
         ("n", C.c_int32), ("tol_off", _i32p), ("tol_key", _i32p), ("tol_op", _i32p), ("tol_value", _i32p),
@@ -255,7 +264,7 @@ ALL_SYMBOLS = [
     "round_preemption_causes", "preemption_join",
     "set_evictor_report", "round_evictor_report",
     "jobs_patch", "jobs_append", "jobs_append_stats", "jobs_delete", "jobs_delete_stats",
-    "nodes_patch", "nodes_patch_stats", "nodes_delete", "nodes_delete_stats",
+    "nodes_patch", "nodes_patch_stats", "nodes_delete", "nodes_delete_stats", "nodes_append", "nodes_append_stats",
 ]
 # entry points the CPU oracle does not implement (it is the single-process checker): the communicator and the collectives that run on it, and the join of a
 # round's result lists into preemption causes (a function of lists the oracle already delivers; tests/test_z_preemption_causes.py restates it)
@@ -265,7 +274,8 @@ OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_d
                     "jobs_patch", "jobs_append", "jobs_append_stats",   # (an incremental jobs_set: the oracle is given the whole table; tests/test_z_jobs_patch.py, test_z_jobs_append.py)
                     "jobs_delete", "jobs_delete_stats",                 # (likewise: tests/test_z_jobs_delete.py)
                     "nodes_patch", "nodes_patch_stats",                 # (an incremental nodes_upsert, likewise: tests/test_z_nodes_patch.py)
-                    "nodes_delete", "nodes_delete_stats"}                # (likewise: tests/test_z_nodes_delete.py)
+                    "nodes_delete", "nodes_delete_stats",               # (likewise: tests/test_z_nodes_delete.py)
+                    "nodes_append", "nodes_append_stats"}                # (likewise: tests/test_z_nodes_append.py)
 PREEMPTION_UNKNOWN, PREEMPTION_UNKNOWN_GANG, PREEMPTION_FAIRSHARE, PREEMPTION_URGENCY, PREEMPTION_OPTIMISER = 1, 2, 3, 4, 5   # ASCHED_PREEMPTION_* (context.PreemptionType)
 # ASCHED_EVR_* bits of asched_evictor_report.node_reasons, in bit order: the reference's reason strings in alphabetical order (makeNodePreemptiblityStats sorts them)
 EVICTOR_REASONS = ("all_jobs_preemptible", "below_protected_fair_share", "invalid_queue", "job_not_preemptible", "node_empty", "node_unschedulable")
@@ -468,6 +478,8 @@ class Library:
         f("nodes_patch_stats", C.c_int32, [C.c_void_p, _i32p])
         f("nodes_delete", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p])
         f("nodes_delete_stats", C.c_int32, [C.c_void_p, _i32p])
+        f("nodes_append", C.c_int32, [C.c_void_p, C.POINTER(CNodesAppend)])
+        f("nodes_append_stats", C.c_int32, [C.c_void_p, _i32p])
         f("round_preemption_causes", C.c_int32, [C.c_void_p, C.POINTER(CPreemptionCause), C.c_int32, _i32p, C.c_int32, _i32p])
         f("preemption_join", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, C.c_int32, _i32p, _i32p, _i32p, _u8p, C.POINTER(CPreemptionCause), _i32p, C.c_int32, _i32p])
 
@@ -858,6 +870,59 @@ class Scheduler:
         """how the last nodes_delete ran: [0] rows deleted, [1] job rows whose node was renumbered, [2] 1 = the rebuild path ran, [3] why (0 none, 2 a node type emptied,
         4 a value of an indexed label emptied), [4] nodes after the call, [5..7] 0: the C array as it is"""
         fn = self._preemption_fn("nodes_delete_stats")
+        out = np.zeros(8, np.int32)
+        self._check(fn(self.h, _ptr(out, C.c_int32)))
+        return [int(x) for x in out]
+
+    def nodes_append(self, total, allocatable=None, *, index, id_rank=None, id_rank_all=None, unschedulable=None, over_allocated=None, taints=None, labels=None):
+        """populateNodeDb's inserting of the nodes the healthy executors report (a cluster that scales up, an executor that returns, a drained node uncordoned): the
+        m rows of `total` join the resident node table at positions N .. N + m - 1, with the fields of nodes_upsert; no resident position changes.  `index`: node.index
+        of the new rows, unique against the resident ones.  `id_rank`: [m] in the rank space of the resident rows (None: behind every resident rank, in row order);
+        `id_rank_all`: [N + m], replaces the id rank of every row (ignored when m == 0).  Leaves the handle as nodes_upsert of the grown table would; go on with round_prepare, and tell a run
+        on a new node with jobs_patch or jobs_append."""
+        fn = self._preemption_fn("nodes_append")
+        total = _arr(total, np.int64).reshape(-1, self.R)
+        m = total.shape[0]
+        allocatable = total if allocatable is None else _arr(allocatable, np.int64).reshape(m, self.R)
+        idx = _arr(index, np.uint64).reshape(-1)
+        assert len(idx) == m, "index"
+        s = CNodesAppend()
+        s.m = m
+        keep = [total, allocatable, idx]
+        s.index, s.total, s.allocatable = _ptr(idx, C.c_uint64), _ptr(total, C.c_int64), _ptr(allocatable, C.c_int64)
+        if id_rank is not None:
+            r = _arr(id_rank, np.int32).reshape(-1)
+            assert len(r) == m, "id_rank"
+            keep.append(r)
+            s.id_rank = _ptr(r, C.c_int32)
+        if id_rank_all is not None:
+            r = _arr(id_rank_all, np.int32).reshape(-1)
+            assert len(r) == self.num_nodes + m, "id_rank_all"
+            keep.append(r)
+            s.id_rank_all = _ptr(r, C.c_int32)
+        for name, val in (("unschedulable", unschedulable), ("over_allocated", over_allocated)):
+            if val is not None:
+                a = _arr(np.broadcast_to(np.asarray(val, dtype=np.uint8), (m,)), np.uint8)
+                keep.append(a)
+                setattr(s, name, _ptr(a, C.c_uint8))
+        if taints is not None:
+            assert len(taints) == m, "taints"
+            off, (tk, tv, te) = _csr(taints, 3)
+            keep += [off, tk, tv, te]
+            s.taint_off, s.taint_key, s.taint_value, s.taint_effect = (_ptr(x, C.c_int32) for x in (off, tk, tv, te))
+        if labels is not None:
+            assert len(labels) == m, "labels"
+            off, (lk, lv) = _csr(labels, 2)
+            keep += [off, lk, lv]
+            s.label_off, s.label_key, s.label_value = (_ptr(x, C.c_int32) for x in (off, lk, lv))
+        self._check(fn(self.h, C.byref(s)))
+        self.num_nodes += m
+
+    def nodes_append_stats(self):
+        """how the last nodes_append ran: [0] rows appended, [1] 1 = the per-node blocks changed stride, [2] 1 = the rebuild path ran, [3] why (0 none, 1 a node type the
+        table did not have, 2 a known type newly populated, 3 key layout / divisor / alignment / id order, 4 a new value of an indexed label, 5 the rank field of the
+        key is too narrow), [4] nodes after the call, [5..7] 0: the C array as it is"""
+        fn = self._preemption_fn("nodes_append_stats")
         out = np.zeros(8, np.int32)
         self._check(fn(self.h, _ptr(out, C.c_int32)))
         return [int(x) for x in out]

@@ -605,3 +605,46 @@ extern "C" int asched_internal_nd_job(const NdArgs* a, hipStream_t st) {
   if (a->M > 0) hipLaunchKernelGGL(k_nd_job, dim3(mgBlocks(a->M)), dim3(MG_THREADS), 0, st, *a);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// ------------------------------------------------------------------------------------------------ new rows join the resident node table (kernels_nodes_append.h)
+// the planes, the narrow arrays, the merge of the index order and the mask rows, all into fresh blocks of the new size.  The mask pass is one THREAD per output word:
+// almost every word is a copy, and consecutive lanes copy consecutive words of a row; only the last ceil(m / 64) + 1 words of a row hold new positions, and their
+// thread loops over at most 64 entries (a wave per word would spend 64 lanes on one 8-byte copy: DESIGN 3.14)
+#define NA_FN __device__ static inline
+#include "kernels_nodes_append.h"
+__global__ __launch_bounds__(MG_THREADS) void k_na_plane(NaArgs a) {
+  long long e = MG_IDX();
+  if (e < (long long)a.R * a.N1) naPlane(a, e);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_na_narrow(NaArgs a) {
+  long long i = MG_IDX();
+  if (i < a.N1) naNarrow(a, (int)i);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_na_rank(NaArgs a) {
+  long long i = MG_IDX();
+  if (i < a.N1) naRank(a, (int)i);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_na_mask(NaArgs a, long long work) {
+  long long t = MG_IDX();
+  if (t < work) naMaskWord(a, t);
+}
+extern "C" int asched_internal_na_planes(const NaArgs* a, hipStream_t st) {
+  if (a->N1 <= 0) return 0;
+  hipLaunchKernelGGL(k_na_plane, dim3(mgBlocks((long long)a->R * a->N1)), dim3(MG_THREADS), 0, st, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_na_narrow(const NaArgs* a, hipStream_t st) {
+  if (a->N1 > 0) hipLaunchKernelGGL(k_na_narrow, dim3(mgBlocks(a->N1)), dim3(MG_THREADS), 0, st, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_na_rank(const NaArgs* a, hipStream_t st) {
+  if (a->N1 > 0) hipLaunchKernelGGL(k_na_rank, dim3(mgBlocks(a->N1)), dim3(MG_THREADS), 0, st, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_na_mask(const NaArgs* a, hipStream_t st) {
+  long long rows = 0;
+  for (int k = 0; k < NA_MASKS; k++) rows += a->rows[k];
+  const long long work = rows * a->W1;
+  if (work > 0) hipLaunchKernelGGL(k_na_mask, dim3(mgBlocks(work)), dim3(MG_THREADS), 0, st, *a, work);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}

@@ -33,6 +33,7 @@
 #include "kernels_jobs_delete.h"    // JdArgs and, in the CPU build of the tests, plat_jobs_delete
 #include "kernels_nodes_patch.h"    // NpArgs and, in the CPU build of the tests, plat_nodes_patch
 #include "kernels_nodes_delete.h"   // NdArgs and, in the CPU build of the tests, plat_nodes_delete
+#include "kernels_nodes_append.h"   // NaArgs and, in the CPU build of the tests, plat_nodes_append
 
 namespace {
 
@@ -161,6 +162,7 @@ struct asched {
   std::vector<int64_t> nodeTotal;  // [N][R]
   std::vector<int32_t> nodeByRank;
   bool allocAligned = true, idRankMonotone = true, hasAllocByPrio = false, allocLeTotal = true;
+  bool idRanksGiven = false;   // nodes_upsert was given id ranks (without them id order == index order by definition and nodeIdRank holds the row order: asched_nodes_append)
   int64_t keyMaxV[MAXK] = {0}, keyGcdV[MAXK] = {0};    // per indexed column: the largest value any node offers, the gcd of every node value (layoutKeys: the coarser divisor)
   bool keyCoarse = false;                              // the order key's fields are quotients by a COARSER divisor than the index resolution (layoutKeys): dev.cfg.indexedRes holds it
   int64_t keyMaxQ[MAXK] = {0}, keyMinQ[MAXK] = {0};   // per indexed column: largest / smallest (value / resolution) any node offers (order-key layout, layoutKeys)
@@ -273,6 +275,10 @@ struct asched {
   std::vector<int32_t> ndMap;        // [N] the old -> new map of the last delete on the host (the remap of the jNode mirror)
   int32_t ndStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_nodes_delete_stats
   double ndMs[7] = {0, 0, 0, 0, 0, 0, 0};   // device ms of the passes of the last delete (ASCHED_ND_TIMES=1)
+  // ---- asched_nodes_append (kernels_nodes_append.h).  The entries of an append: one block, kept between calls and only ever grown
+  DevBufs naBufs; char* naScratch = nullptr; size_t naScratchBytes = 0;
+  int32_t naStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_nodes_append_stats
+  double naMs[4] = {0, 0, 0, 0};     // device ms of planes / narrow arrays / index order / mask rows of the last append (ASCHED_NA_TIMES=1)
   double roundTotalMs = 0, roundControlMs = 0, roundPhaseMs[4] = {0, 0, 0, 0};   // split round: whole sequence / persistent passes / evict-1, evict-3, final bulk phases (host clock)
   int submitWideUnits = 0, submitWidePasses = 0, submitSeqUnits = 0, submitGangUnits = 0, submitNodePasses = 0, submitLitUnits = 0;   // how the last submit_check ran (submit_stats)
 };
@@ -857,7 +863,7 @@ asched_t* asched_create(const asched_config* c) {
 void asched_destroy(asched_t* h) {
   if (!h) return;
   plat_enter(h->plat);
-  h->nodeBufs.freeAll(); h->jobBufs.freeAll(); h->queueBufs.freeAll(); h->maskBufs.freeAll(); h->fastBufs.freeAll(); h->pjBufs.freeAll(); h->evrBufs.freeAll(); h->exclBufs.freeAll(); h->jpBufs.freeAll(); h->npBufs.freeAll(); h->ndBufs.freeAll();
+  h->nodeBufs.freeAll(); h->jobBufs.freeAll(); h->queueBufs.freeAll(); h->maskBufs.freeAll(); h->fastBufs.freeAll(); h->pjBufs.freeAll(); h->evrBufs.freeAll(); h->exclBufs.freeAll(); h->jpBufs.freeAll(); h->npBufs.freeAll(); h->ndBufs.freeAll(); h->naBufs.freeAll();
   plat_pinned_free(h->resPin); plat_free(h->commStatus); plat_free(h->dev.rs); plat_free(h->dev.cmdIO); plat_free(h->dev.scanResult); plat_free(h->dev.undo);
   plat_close(h->plat);
   delete h;
@@ -982,7 +988,7 @@ int nodesUpsertBody(asched* h, const asched_nodes* in) {
   std::sort(order.begin(), order.end(), [&](int a, int b) { return in->index[a] < in->index[b]; });
   for (int i = 1; i < N; i++) if (in->index[order[i]] == in->index[order[i - 1]]) return fail(h, ASCHED_ERR_INVALID, "duplicate node index");
   h->nodeByRank = order;
-  h->idRankMonotone = true;
+  h->idRankMonotone = true; h->idRanksGiven = in->id_rank != nullptr;
   for (int i = 0; i < N; i++) { idxRank[order[i]] = i; if (i > 0 && in->id_rank && in->id_rank[order[i]] < in->id_rank[order[i - 1]]) h->idRankMonotone = false; }
   // key packing: field_c = alloc_c/res_c - lo_c in width_c bits; the node-index rank in the low bits (layoutKeys)
   h->allocAligned = true;
@@ -1085,7 +1091,7 @@ extern "C" {
 int32_t asched_nodes_upsert(asched_t* h, const asched_nodes* in) {
   if (!h) return ASCHED_ERR_INVALID;
   plat_enter(h->plat);
-  memset(h->npStats, 0, sizeof h->npStats); memset(h->ndStats, 0, sizeof h->ndStats);
+  memset(h->npStats, 0, sizeof h->npStats); memset(h->ndStats, 0, sizeof h->ndStats); memset(h->naStats, 0, sizeof h->naStats);
   return nodesUpsertBody(h, in);
 }
 
@@ -2483,6 +2489,328 @@ int32_t asched_nodes_delete_stats(asched_t* h, int32_t* out) {
   if (!h || !out) return ASCHED_ERR_INVALID;
   plat_enter(h->plat);
   for (int k = 0; k < 8; k++) out[k] = h->ndStats[k];
+  return 0;
+}
+
+// ---- asched_nodes_append (kernels_nodes_append.h): new rows join the resident node table — what populateNodeDb does every cycle with the nodes the healthy executors
+// report (scheduling_algo.go:1019-1098), an executor that returns from the filters at :1100-1169 and a drained node that is uncordoned.  The handle is left as
+// asched_nodes_upsert of "the N resident rows in their order, then the m new rows" would leave it.  Two paths, chosen per call, as in asched_nodes_patch and
+// asched_nodes_delete: nothing the host derives from the WHOLE table changes — every block that depends on N, Npad or W is written into a fresh block of the new size
+// on the device and swapped in; or the grown table goes through nodes_upsert's own code (nodesUpsertBody).
+int32_t asched_nodes_append(asched_t* h, const asched_nodes_append_rows* rows) {
+  if (!h) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  if (!rows) return fail(h, ASCHED_ERR_INVALID, "nodes_append: bad arguments");
+  HostProf prof("nodes_append");   // ASCHED_HOSTPROF=1: where the host's share of the call goes
+  const int N = h->N, R = h->R, K = h->K, P = h->P, m = rows->m;
+  Dev& d = h->dev;
+  // ---- every refusal before anything changes
+  if (!h->nodesSet || h->nodeAllocHost.size() != (size_t)N * R || h->nodeOverAlloc.size() != (size_t)N || h->nodeIndexHost.size() != (size_t)N)
+    return fail(h, ASCHED_ERR_INVALID, "nodes_append: no node table on this handle (nodes_upsert first)");
+  if (m < 0 || (m > 0 && (!rows->index || !rows->total || !rows->allocatable))) return fail(h, ASCHED_ERR_INVALID, "nodes_append: bad arguments");
+  if (h->uploadedAllocByPrio || h->hasTypeOverride) return fail(h, ASCHED_ERR_UNSUPPORTED, "nodes_append: the node table was uploaded with alloc_by_prio or node_type_override (nodes_upsert instead)");
+  { auto ascending = [&](const int32_t* off) { if (m > 0 && off[0] < 0) return false; for (int i = 0; i < m; i++) if (off[i + 1] < off[i]) return false; return true; };
+    if (rows->taint_off) {
+      if (!ascending(rows->taint_off)) return fail(h, ASCHED_ERR_INVALID, "nodes_append: taint_off is not ascending");
+      if (m > 0 && rows->taint_off[m] > 0 && (!rows->taint_key || !rows->taint_value || !rows->taint_effect)) return fail(h, ASCHED_ERR_INVALID, "nodes_append: bad arguments");
+    }
+    if (rows->label_off) {
+      if (!ascending(rows->label_off)) return fail(h, ASCHED_ERR_INVALID, "nodes_append: label_off is not ascending");
+      if (m > 0 && rows->label_off[m] > 0 && (!rows->label_key || !rows->label_value)) return fail(h, ASCHED_ERR_INVALID, "nodes_append: bad arguments");
+    } }
+  if ((long long)N + m > (1ll << 30)) return fail(h, ASCHED_ERR_UNSUPPORTED, "nodes_append: more than 2^30 nodes");
+  if (m > 0 && !h->idRanksGiven && rows->id_rank && !rows->id_rank_all)
+    return fail(h, ASCHED_ERR_INVALID, "nodes_append: the node table was uploaded without id ranks, so id_rank has no rank space to lie in (id_rank_all, or no ranks)");
+  const int N1 = N + m, M = h->jobsSet ? h->M : 0;
+  const int Npad = d.cfg.Npad, W = d.cfg.W;
+  int Npad1 = ((N1 + 63) / 64) * 64; if (Npad1 == 0) Npad1 = 64;
+  const int W1 = Npad1 / 64;
+  // the index order: the new rows ascending by node.index and each one's insertion point among the resident ranks (the resident rows with a smaller index)
+  std::vector<int32_t> ord(m), ins(m);
+  for (int i = 0; i < m; i++) ord[i] = i;
+  std::sort(ord.begin(), ord.end(), [&](int a, int b) { return rows->index[a] < rows->index[b]; });
+  for (int k = 0; k < m; k++) {
+    const uint64_t x = rows->index[ord[k]];
+    if (k > 0 && rows->index[ord[k - 1]] == x) return fail(h, ASCHED_ERR_INVALID, "nodes_append: two new rows with the same node index");
+    const auto it = std::lower_bound(h->nodeByRank.begin(), h->nodeByRank.end(), x, [&](int32_t v, uint64_t key) { return h->nodeIndexHost[v] < key; });
+    if (it != h->nodeByRank.end() && h->nodeIndexHost[*it] == x) return fail(h, ASCHED_ERR_INVALID, "nodes_append: a new row with the node index of a resident row");
+    ins[k] = (int32_t)(it - h->nodeByRank.begin());
+  }
+  // ---- the state of every new row, and which path serves the call
+  std::vector<std::vector<HTaint>> eTaints(m); std::vector<std::vector<HSel>> eLabels(m);
+  std::vector<uint8_t> eUns(m), eOver(m);
+  std::vector<int> eType(m, -1);
+  std::vector<int32_t> eIdRank(m);
+  std::vector<HType> newTypes; std::vector<std::string> newCanon;   // node types the table does not have, in order of first occurrence
+  std::vector<int> typeAdd(h->types.size(), 0);
+  std::vector<std::vector<int32_t>> valueAdd(h->slotValueCount.size());
+  for (size_t s = 0; s < valueAdd.size(); s++) valueAdd[s].assign(h->slotValueCount[s].size(), 0);
+  const size_t L = h->labelSlots.size();
+  std::vector<int32_t> eLab((size_t)m * std::max<size_t>(L, 1), -1);   // per entry and label slot: the value's position in slotValues, -1
+  bool newValue = false;
+  { int32_t behind = 0;
+    if (!rows->id_rank && !rows->id_rank_all && m > 0) for (int32_t r : h->nodeIdRank) behind = std::max(behind, r < INT32_MAX ? r + 1 : r);
+    for (int i = 0; i < m; i++) {
+      eUns[i] = rows->unschedulable && rows->unschedulable[i] ? 1 : 0;
+      eOver[i] = rows->over_allocated && rows->over_allocated[i] ? 1 : 0;
+      if (rows->taint_off) for (int k = rows->taint_off[i]; k < rows->taint_off[i + 1]; k++) eTaints[i].push_back({rows->taint_key[k], rows->taint_value[k], rows->taint_effect[k]});
+      if (eUns[i]) eTaints[i].push_back({kUnschedulableTaintKey, 0, ASCHED_EFFECT_NO_SCHEDULE});  // node.go:127-129
+      if (rows->label_off) for (int k = rows->label_off[i]; k < rows->label_off[i + 1]; k++) eLabels[i].push_back({rows->label_key[k], rows->label_value[k]});
+      eIdRank[i] = rows->id_rank_all ? rows->id_rank_all[N + i] : rows->id_rank ? rows->id_rank[i] : behind + i;
+      HType t; std::string canon;
+      nodeTypeOf(h, eTaints[i], eLabels[i], t, canon);
+      auto it = h->typeByCanon.find(canon);
+      if (it != h->typeByCanon.end()) { eType[i] = it->second; typeAdd[it->second]++; }
+      else {
+        size_t k = 0;
+        while (k < newCanon.size() && newCanon[k] != canon) k++;
+        if (k == newCanon.size()) { newCanon.push_back(canon); newTypes.push_back(t); }
+        newTypes[k].numNodes++;
+      }
+      for (auto& l : eLabels[i]) for (size_t s = 0; s < L; s++) if (l.key == h->labelSlots[s]) {
+        const auto& vs = h->slotValues[s];
+        const size_t k = (size_t)(std::lower_bound(vs.begin(), vs.end(), l.value) - vs.begin());
+        if (k < vs.size() && vs[k] == l.value && h->slotValueCount[s][k] > 0) { valueAdd[s][k]++; eLab[(size_t)i * L + s] = (int32_t)k; }
+        else newValue = true;
+      }
+    } }
+  int why = 0;
+  // (an indexed label is part of the node type: a new value is a new node type as well — the value is the reason reported then, as asched_nodes_delete does)
+  if (newValue) why = 4;
+  if (!why && !newTypes.empty()) why = 1;
+  if (!why) for (size_t t = 0; t < h->types.size(); t++) if (typeAdd[t] > 0 && h->types[t].numNodes <= 0) { why = 2; break; }
+  if (!why && N1 > 1 && d.cfg.idxBits < 64 && ((uint64_t)(N1 - 1) >> d.cfg.idxBits)) why = 5;   // (the rank field of the key layout holds N + m - 1)
+  if (!why)
+    for (int i = 0; i < m && !why; i++) {   // asched_nodes_patch's condition on a new allocatable row
+      const int64_t* a = rows->allocatable + (size_t)i * R; const int64_t* tot = rows->total + (size_t)i * R;
+      if (h->allocLeTotal) for (int r = 0; r < R; r++) if (!d.cfg.isFloating[r] && (a[r] < 0 || a[r] > tot[r])) why = 3;   // (allocLeTotal keeps its value)
+      for (int c = 0; c < K; c++) {
+        const int64_t v = a[h->indexedCol[c]];
+        if (v > h->keyMaxV[c] || v / h->indexedRes[c] > h->keyMaxQ[c]) why = 3;            // (beyond the widths layoutKeys chose)
+        if (h->keyCoarse && v % d.cfg.indexedRes[c]) why = 3;                                // (the key's fields are exact quotients by the coarser divisor)
+        if (h->allocAligned && v % h->indexedRes[c]) why = 3;                                // (a class matching several types would move to the literal path)
+      }
+    }
+  // id order == index order on the merged index order, decided before anything changes: with id_rank a new row's rank lies between its neighbours'; with id_rank_all
+  // one pass over the N + m ranks
+  // monoGiven: what nodes_upsert of the grown table computes (the rebuild path and its refusals go by it); monoAfter: what the device path keeps
+  bool monoAfter = h->idRankMonotone, monoGiven = h->idRankMonotone;
+  const bool noRanks = !h->idRanksGiven && !rows->id_rank_all;   // the table has no id ranks and gets none: id order == index order by definition, as in nodes_upsert
+  if (m > 0 && rows->id_rank_all) {
+    monoAfter = true;
+    int32_t prev = INT32_MIN; int k = 0;
+    for (int r = 0; r <= N && monoAfter; r++) {
+      for (; k < m && ins[k] == r; k++) { const int32_t x = rows->id_rank_all[N + ord[k]]; if (x < prev) monoAfter = false; prev = x; }
+      if (r < N) { const int32_t x = rows->id_rank_all[h->nodeByRank[r]]; if (x < prev) monoAfter = false; prev = x; }
+    }
+    monoGiven = monoAfter;
+    if (!h->idRankMonotone) monoAfter = false;   // (stays conservative: a layout chosen for literal rows serves the others as well)
+  } else if (monoAfter && !noRanks) {
+    for (int k = 0; k < m && monoAfter; k++) {
+      const int32_t x = eIdRank[ord[k]];
+      if (k > 0 && ins[k - 1] == ins[k]) { if (x < eIdRank[ord[k - 1]]) monoAfter = false; }
+      else if (ins[k] > 0 && x < h->nodeIdRank[h->nodeByRank[ins[k] - 1]]) monoAfter = false;
+      if (!(k + 1 < m && ins[k + 1] == ins[k]) && ins[k] < N && h->nodeIdRank[h->nodeByRank[ins[k]]] < x) monoAfter = false;
+    }
+    monoGiven = monoAfter;
+  }
+  if (!why && h->idRankMonotone && !monoAfter) why = 3;
+  if (why) {
+    // ---- the rebuild path: the grown table, from the handle's mirrors and the new rows, through nodes_upsert's own code
+    std::vector<int64_t> alloc = h->nodeAllocHost, total = h->nodeTotal;
+    std::vector<uint8_t> uns = h->nodeUnsched, over = h->nodeOverAlloc;
+    std::vector<uint64_t> index = h->nodeIndexHost;
+    std::vector<int32_t> idRank = h->nodeIdRank;
+    alloc.insert(alloc.end(), rows->allocatable, rows->allocatable + (size_t)m * R); total.insert(total.end(), rows->total, rows->total + (size_t)m * R);
+    uns.insert(uns.end(), eUns.begin(), eUns.end()); over.insert(over.end(), eOver.begin(), eOver.end());
+    index.insert(index.end(), rows->index, rows->index + m);
+    if (rows->id_rank_all) idRank.assign(rows->id_rank_all, rows->id_rank_all + N1); else idRank.insert(idRank.end(), eIdRank.begin(), eIdRank.end());
+    std::vector<int32_t> tOff(N1 + 1, 0), tKey, tVal, tEff, lOff(N1 + 1, 0), lKey, lVal;
+    for (int v = 0; v < N1; v++) {
+      const std::vector<HTaint>& tv = v < N ? h->nodeTaints[v] : eTaints[v - N];
+      const size_t cnt = tv.size() - (uns[v] ? 1 : 0);   // (without the unschedulable taint: nodes_upsert adds it)
+      for (size_t k = 0; k < cnt; k++) { tKey.push_back(tv[k].key); tVal.push_back(tv[k].value); tEff.push_back(tv[k].effect); }
+      tOff[v + 1] = (int32_t)tKey.size();
+      for (auto& l : (v < N ? h->nodeLabels[v] : eLabels[v - N])) { lKey.push_back(l.key); lVal.push_back(l.value); }
+      lOff[v + 1] = (int32_t)lKey.size();
+    }
+    tKey.push_back(0); tVal.push_back(0); tEff.push_back(0); lKey.push_back(0); lVal.push_back(0);
+    // what that code can refuse, decided first, with everything put back (rebuildRefusal).  Unlike for a reduced table it CAN fire here
+    {
+      std::vector<HType> typesAfter;
+      for (size_t t = 0; t < h->types.size(); t++) if (h->types[t].numNodes + typeAdd[t] > 0) typesAfter.push_back(h->types[t]);
+      for (auto& t : newTypes) typesAfter.push_back(t);
+      std::string rwhy;
+      const bool monoSaved = h->idRankMonotone;
+      h->idRankMonotone = monoGiven;
+      const int rrc = rebuildRefusal(h, typesAfter, alloc.data(), N1, rwhy);
+      h->idRankMonotone = monoSaved;
+      if (rrc) return fail(h, rrc, "nodes_append: " + rwhy);
+    }
+    asched_nodes in; memset(&in, 0, sizeof in);
+    in.n = N1; in.index = index.data(); in.id_rank = noRanks ? nullptr : idRank.data(); in.total = total.data(); in.allocatable = alloc.data();
+    in.unschedulable = uns.data(); in.over_allocated = over.data();
+    in.taint_off = tOff.data(); in.taint_key = tKey.data(); in.taint_value = tVal.data(); in.taint_effect = tEff.data();
+    in.label_off = lOff.data(); in.label_key = lKey.data(); in.label_value = lVal.data();
+    memset(h->naStats, 0, sizeof h->naStats); for (int k = 0; k < 4; k++) h->naMs[k] = 0;
+    memset(h->npStats, 0, sizeof h->npStats); memset(h->ndStats, 0, sizeof h->ndStats);
+    int rc = nodesUpsertBody(h, &in);
+    if (rc) return rc;
+    h->naStats[0] = m; h->naStats[1] = Npad1 != Npad ? 1 : 0; h->naStats[2] = 1; h->naStats[3] = why; h->naStats[4] = h->N;
+    return M > 0 ? resetDynamicState(h, M) : 0;   // (both paths leave the per-job state as jobs_set does)
+  }
+  // ---- the device path.  The scratch for the entries and every fresh block before anything changes: running out of device memory here is a refusal too.  Blocks that
+  // hold the table are always fresh (nothing is changed in place); blocks of node-indexed scratch that are large enough already (block sizes do not shrink) are zeroed
+  prof.lap("refusals and the choice of the path");
+  const bool masks = h->jobsSet && h->dClassMask && h->dShapeClass;
+  const bool haveFast = h->jobsSet && d.f.structOk && d.nodeCls;
+  const int Cext = masks ? h->Cext : 0, CW = std::max(1, (Cext + 63) / 64);
+  const int Sext = masks ? h->S + (int)h->awayRowClass.size() : 0, T = masks ? (int)h->types.size() : 0, labelRows = masks && !h->uniOffHost.empty() ? h->uniOffHost.back() : 0;
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t mm = (size_t)m;
+  const size_t oAlloc = up(8 * mm * R), oIdRank = oAlloc + up(8 * mm * R), oType = oIdRank + up(4 * mm), oIns = oType + up(4 * mm), oInsRow = oIns + up(4 * mm),
+               oLab = oInsRow + up(4 * mm), oCls = oLab + up(4 * mm * std::max<size_t>(L, 1)), oFlags = oCls + up(8 * mm * CW), oAll = oFlags + up(mm),
+               need = oAll + (rows->id_rank_all ? up(4 * (size_t)N1) : 0) + 256;
+  struct Block { DevBufs* owner; void** slot; size_t bytes; int fill; void* fresh; };
+  std::vector<Block> blocks; std::vector<std::pair<void*, size_t>> zeroed;
+  char* scratchNew = nullptr;
+  if (m > 0) {
+    auto stage = [&](DevBufs* owner, void* slot, size_t bytes, int fill = 0) { blocks.push_back({owner, (void**)slot, std::max<size_t>(bytes, 1), fill, nullptr}); };
+    auto scratch = [&](DevBufs* owner, void* slot, size_t bytes) {   // node-indexed scratch: zeros of at least `bytes`
+      void* p = *(void**)slot;
+      for (auto& e : owner->ptrs) if (p && e.first == p && e.second >= bytes) { zeroed.push_back({p, e.second}); return; }
+      stage(owner, slot, bytes);
+    };
+    const size_t np = (size_t)Npad1, n1 = (size_t)N1;
+    stage(&h->nodeBufs, &d.totalRes, 8 * R * np); stage(&h->nodeBufs, &d.allocatable, 8 * R * np); stage(&h->nodeBufs, &d.alloc, 8 * (size_t)P * R * np);
+    stage(&h->nodeBufs, &d.keys, 8 * 2 * (size_t)P * np, 0xff);
+    stage(&h->nodeBufs, &d.nodeFlags, n1); stage(&h->nodeBufs, &d.idxRank, 4 * n1); stage(&h->nodeBufs, &d.nodeByRank, 4 * n1); stage(&h->nodeBufs, &d.nodeIdRank, 4 * n1);
+    scratch(&h->nodeBufs, &d.accAvail, 8 * np * R); scratch(&h->nodeBufs, &d.accStamp, 4 * np); scratch(&h->nodeBufs, &d.accStaticFailed, np);
+    scratch(&h->nodeBufs, &d.fairOff, 4 * (np + 2)); scratch(&h->nodeBufs, &d.nodeOver, 4 * np);
+    if (masks) {
+      stage(&h->maskBufs, &h->dClassMask, 8 * (size_t)std::max(Cext, 1) * W1); stage(&h->maskBufs, &d.shapeMask, 8 * (size_t)std::max(Sext, 1) * W1);
+      stage(&h->maskBufs, &d.typeMask, 8 * (size_t)std::max(T, 1) * W1); stage(&h->maskBufs, &d.labelMask, 8 * (size_t)std::max(labelRows, 1) * W1);
+      stage(&h->maskBufs, &h->dNodeType, 4 * n1);
+    }
+    if (haveFast) {
+      size_t Nb2 = 64;
+      while (Nb2 < n1) Nb2 <<= 1;
+      stage(&h->fastBufs, &d.nodeCls, 8 * n1);
+      scratch(&h->fastBufs, &d.baseKey, 8 * Nb2); scratch(&h->fastBufs, &d.baseNode, 4 * np); scratch(&h->fastBufs, &d.baseExtra, 8 * np * MAXE); scratch(&h->fastBufs, &d.baseCls, 8 * np);
+      scratch(&h->fastBufs, &d.baseRemoved, np); scratch(&h->fastBufs, &d.posOf, 4 * np); scratch(&h->fastBufs, &d.l0Slot, 4 * np);
+      if (d.fitBits) scratch(&h->fastBufs, &d.fitBits, 8 * ((size_t)d.f.F * ((n1 + 63) / 64) + 64));
+    }
+    bool ok = true;
+    if (h->naScratchBytes < need) { scratchNew = (char*)plat_malloc(need + need / 4); ok = scratchNew != nullptr; }
+    for (auto& b : blocks) { if (!ok) break; b.fresh = plat_malloc(b.bytes); ok = b.fresh != nullptr; }
+    if (!ok) {
+      (void)plat_take_failure();
+      for (auto& b : blocks) if (b.fresh) plat_free(b.fresh);
+      if (scratchNew) plat_free(scratchNew);
+      return fail(h, ASCHED_ERR_DEVICE, "nodes_append: out of device memory for the scratch and the grown node table; the handle is as it was");
+    }
+    if (scratchNew) { h->naBufs.freeAll(); h->naScratch = scratchNew; h->naScratchBytes = need + need / 4; h->naBufs.ptrs.push_back({scratchNew, need + need / 4}); }
+  }
+  prof.lap("allocations");
+  // ---- what nodes_upsert resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the handle between two tables: asched_nodes_upsert before anything else)
+  h->haveRoundResult = false; h->stateEpoch++;
+  { d.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
+    int32_t zero = 0;
+    plat_h2d(&d.rs->fastActive, &zero, sizeof zero);
+    plat_h2d(&d.rs->l0SaveCount, &zero, sizeof zero); }
+  h->prepared = false; h->evrSized = false; h->equalLevels = P;
+  memset(h->naStats, 0, sizeof h->naStats); for (int k = 0; k < 4; k++) h->naMs[k] = 0;
+  memset(h->npStats, 0, sizeof h->npStats); memset(h->ndStats, 0, sizeof h->ndStats);
+  if (m > 0) {
+    // the host mirrors first (classMatchesNode reads them); the totals and the counts by addition (addNodeToStats, nodedb.go:44-55)
+    h->nodeTaints.resize(N1); h->nodeLabels.resize(N1); h->nodeType.resize(N1);
+    for (int i = 0; i < m; i++) {
+      h->nodeTaints[N + i].swap(eTaints[i]); h->nodeLabels[N + i].swap(eLabels[i]); h->nodeType[N + i] = eType[i];
+      h->types[eType[i]].numNodes++;
+      for (int r = 0; r < R; r++) if (!d.cfg.isFloating[r]) d.cfg.totalResources[r] += rows->allocatable[(size_t)i * R + r];
+      for (int c = 0; c < K; c++) { const int64_t a = rows->allocatable[(size_t)i * R + h->indexedCol[c]]; h->keyGcdV[c] = std::gcd(h->keyGcdV[c], a < 0 ? -a : a); }   // (stays a common divisor: layoutKeys of a later jobs_set / jobs_append)
+    }
+    for (size_t s = 0; s < valueAdd.size(); s++) for (size_t k = 0; k < valueAdd[s].size(); k++) h->slotValueCount[s][k] += valueAdd[s][k];
+    h->nodeTotal.insert(h->nodeTotal.end(), rows->total, rows->total + (size_t)m * R);
+    h->nodeAllocHost.insert(h->nodeAllocHost.end(), rows->allocatable, rows->allocatable + (size_t)m * R);
+    h->nodeIndexHost.insert(h->nodeIndexHost.end(), rows->index, rows->index + m);
+    h->nodeOverAlloc.insert(h->nodeOverAlloc.end(), eOver.begin(), eOver.end()); h->nodeUnsched.insert(h->nodeUnsched.end(), eUns.begin(), eUns.end());
+    if (rows->id_rank_all) h->nodeIdRank.assign(rows->id_rank_all, rows->id_rank_all + N1); else h->nodeIdRank.insert(h->nodeIdRank.end(), eIdRank.begin(), eIdRank.end());
+    h->idRankMonotone = monoAfter;
+    if (rows->id_rank_all) h->idRanksGiven = true;
+    { std::vector<int32_t> merged(N1);   // nodeByRank, merged as the device merges it
+      int k = 0, o = 0;
+      for (int r = 0; r <= N; r++) { for (; k < m && ins[k] == r; k++) merged[o++] = N + ord[k]; if (r < N) merged[o++] = h->nodeByRank[r]; }
+      h->nodeByRank.swap(merged); }
+    h->npSeen.assign(N1, 0);
+    // the entries: class bits by classMatchesNode for the m rows only, the label rows of each entry
+    std::vector<uint8_t> sFlags(m);
+    std::vector<int32_t> sType(eType.begin(), eType.end()), insRow(m), sLab((size_t)m * std::max<size_t>(L, 1), -1);
+    std::vector<uint64_t> sCls((size_t)m * CW, 0);
+    for (int i = 0; i < m; i++) {
+      sFlags[i] = (eUns[i] && eOver[i]) ? 1 : 0;
+      for (int c = 0; c < Cext; c++) if (classMatchesNode(h, c, N + i)) sCls[(size_t)i * CW + (c >> 6)] |= 1ull << (c & 63);
+      if (masks) for (size_t s = 0; s < L; s++) if (eLab[(size_t)i * L + s] >= 0) sLab[(size_t)i * L + s] = h->uniOffHost[s] + eLab[(size_t)i * L + s];
+    }
+    for (int k = 0; k < m; k++) insRow[k] = N + ord[k];
+    NaArgs a; memset(&a, 0, sizeof a);
+    a.N = N; a.N1 = N1; a.m = m; a.R = R; a.Npad = Npad; a.Npad1 = Npad1; a.W = W; a.W1 = W1; a.CW = CW; a.L = (int32_t)L;
+    for (int r = 0; r < R; r++) if (d.cfg.isFloating[r]) a.floatMask |= 1 << r;
+    a.clsLow = h->C >= 64 ? ~0ull : ((1ull << h->C) - 1);
+    char* s = h->naScratch;
+    plat_h2d(s, rows->total, 8 * mm * R); plat_h2d(s + oAlloc, rows->allocatable, 8 * mm * R); plat_h2d(s + oIdRank, eIdRank.data(), 4 * mm); plat_h2d(s + oType, sType.data(), 4 * mm);
+    plat_h2d(s + oIns, ins.data(), 4 * mm); plat_h2d(s + oInsRow, insRow.data(), 4 * mm); plat_h2d(s + oLab, sLab.data(), 4 * sLab.size()); plat_h2d(s + oCls, sCls.data(), 8 * sCls.size());
+    plat_h2d(s + oFlags, sFlags.data(), mm);
+    if (rows->id_rank_all) { plat_h2d(s + oAll, rows->id_rank_all, 4 * (size_t)N1); a.idRankAll = (const int32_t*)(s + oAll); }
+    a.pTotal = (const int64_t*)s; a.pAlloc = (const int64_t*)(s + oAlloc); a.pIdRank = (const int32_t*)(s + oIdRank); a.pType = (const int32_t*)(s + oType);
+    a.ins = (const int32_t*)(s + oIns); a.insRow = (const int32_t*)(s + oInsRow); a.pLab = (const int32_t*)(s + oLab); a.pCls = (const uint64_t*)(s + oCls); a.pFlags = (const uint8_t*)(s + oFlags);
+    auto fresh = [&](void* slot) -> void* { for (auto& b : blocks) if ((void*)b.slot == slot) return b.fresh; return nullptr; };
+    prof.lap("mirrors, class bits and the upload of the entries");
+    for (auto& b : blocks) plat_memset(b.fresh, b.fill, b.bytes);
+    a.inTotal = d.totalRes; a.outTotal = (int64_t*)fresh(&d.totalRes); a.inAlloc = d.allocatable; a.outAlloc = (int64_t*)fresh(&d.allocatable);
+    a.inFlags = d.nodeFlags; a.outFlags = (uint8_t*)fresh(&d.nodeFlags); a.inIdRank = d.nodeIdRank; a.outIdRank = (int32_t*)fresh(&d.nodeIdRank);
+    a.rankIn = d.nodeByRank; a.rankOut = (int32_t*)fresh(&d.nodeByRank); a.idxRankOut = (int32_t*)fresh(&d.idxRank);
+    if (masks) {
+      a.inType = h->dNodeType; a.outType = (int32_t*)fresh(&h->dNodeType);
+      a.shapeClass = h->dShapeClass; a.shapeReq = d.shapeReq;
+      const uint64_t* in[NA_MASKS] = {h->dClassMask, d.shapeMask, d.typeMask, d.labelMask};
+      void* sl[NA_MASKS] = {&h->dClassMask, &d.shapeMask, &d.typeMask, &d.labelMask};
+      const int nrows[NA_MASKS] = {Cext, Sext, T, labelRows};
+      for (int k = 0; k < NA_MASKS; k++) { a.inMask[k] = in[k]; a.outMask[k] = (uint64_t*)fresh(sl[k]); a.rows[k] = nrows[k]; }
+    }
+    if (haveFast) { a.inCls = d.nodeCls; a.outCls = (uint64_t*)fresh(&d.nodeCls); }
+    const int prc = plat_take_failure() ? -1 : plat_nodes_append(d, a);
+    if (prc) {
+      for (auto& b : blocks) plat_free(b.fresh);
+      return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+    }
+    plat_nodes_append_ms(h->naMs);
+    prof.lap("memsets and the passes");
+    // the blocks swapped in, the old ones released (plat_nodes_append has waited for the device); the node-indexed scratch that stays gets the start a fresh upload gives it
+    auto release = [&](DevBufs* owner, void* p) {
+      for (size_t k = 0; k < owner->ptrs.size(); k++) if (owner->ptrs[k].first == p) { owner->ptrs.erase(owner->ptrs.begin() + k); break; }
+      plat_free(p);
+    };
+    for (auto& b : blocks) { if (*b.slot) release(b.owner, *b.slot); *b.slot = b.fresh; b.owner->ptrs.push_back({b.fresh, b.bytes}); }
+    for (auto& z : zeroed) plat_memset(z.first, 0, z.second);
+    h->N = N1; d.cfg.N = N1; d.cfg.Npad = Npad1; d.cfg.W = W1;
+    if (haveFast) d.fitW = (N1 + 63) / 64;
+    if (h->jobsSet) exclSetup(h);   // (the [cap][W] bit rows of the failed-selection store: B_RESET_JOBS forgets the records anyway)
+    prof.lap("releases and exclSetup");
+    if (const char* e = getenv("ASCHED_NA_TIMES")) if (e[0] == '1')
+      fprintf(stderr, "[asched nodes_append] nodes %d entries %d mask rows %d fresh blocks %zu: planes %.4f ms, narrow arrays %.4f ms, index order %.4f ms, mask rows %.4f ms\n",
+              N, m, a.rows[0] + a.rows[1] + a.rows[2] + a.rows[3], blocks.size(), h->naMs[0], h->naMs[1], h->naMs[2], h->naMs[3]);
+  }
+  h->naStats[0] = m; h->naStats[1] = Npad1 != Npad ? 1 : 0; h->naStats[4] = h->N;
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  const int rc = resetDynamicState(h, M);
+  prof.lap("the reset passes");
+  return rc;
+}
+int32_t asched_nodes_append_stats(asched_t* h, int32_t* out) {
+  if (!h || !out) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  for (int k = 0; k < 8; k++) out[k] = h->naStats[k];
   return 0;
 }
 

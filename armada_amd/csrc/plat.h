@@ -114,6 +114,11 @@ struct NdArgs;
 static int plat_nodes_delete_check(Dev& d, NdArgs& a, int32_t* bad);
 static int plat_nodes_delete(Dev& d, NdArgs& a);
 static void plat_nodes_delete_ms(double* out /*[7]*/);   // measurement hook: device ms of mark + check / scan / gather / index order / mask rows / job remap / unmark of the last call (events around them when ASCHED_ND_TIMES=1, else zeros)
+// new rows join the resident node table (kernels_nodes_append.h): the planes, the narrow arrays, the merge of the index order and the mask rows, all into the fresh
+// blocks of a.out*; nothing the handle points to is written.  Synchronous: everything is complete on return.  The CPU build's definition sits in kernels_nodes_append.h.
+struct NaArgs;
+static int plat_nodes_append(Dev& d, NaArgs& a);
+static void plat_nodes_append_ms(double* out /*[4]*/);   // measurement hook: device ms of planes / narrow arrays / index order / mask rows of the last call (events around them when ASCHED_NA_TIMES=1, else zeros)
 static int plat_run_fit_capacity(Dev& d, const std::vector<int32_t>& shapes, std::vector<int32_t>& firstNode, std::vector<long long>& capacity, const int32_t* nodeByRankHost);
 static int plat_run_submit_gangs(Dev& d, const std::vector<int32_t>& off, const std::vector<int32_t>& jobs, std::vector<int32_t>& out);
 static double plat_last_fit_ms();

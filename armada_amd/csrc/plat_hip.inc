@@ -35,6 +35,7 @@ struct PlatCtx {
   hipEvent_t jaEv[4] = {nullptr, nullptr, nullptr, nullptr}; bool jaTimed = false;   // ASCHED_JA_TIMES=1: around the passes of the job-table append
   hipEvent_t jpEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool jpTimed = false;   // ASCHED_JP_TIMES=1: around the passes of the job-table patch
   hipEvent_t ndEv[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool ndTimed = false;   // ASCHED_ND_TIMES=1: around the passes of the node-table delete
+  hipEvent_t naEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool naTimed = false;   // ASCHED_NA_TIMES=1: around the passes of the node-table append
   hipEvent_t jdEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool jdTimed = false;   // ASCHED_JD_TIMES=1: around the passes of the job-table delete
   hipEvent_t npEv[3] = {nullptr, nullptr, nullptr}; bool npTimed = false;   // ASCHED_NP_TIMES=1: around the passes of the node-table patch
   float roundTotalMs = 0.f, roundControlMs = 0.f; int roundLaunches = 0;
@@ -258,6 +259,7 @@ static void plat_close(PlatCtx* c) {
   for (hipEvent_t e : c->npEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->jdEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ndEv) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->naEv) if (e) (void)hipEventDestroy(e);
   if (c->helpBox) (void)hipFree(c->helpBox);
   if (c->cmpScratch) (void)hipFree(c->cmpScratch);
   if (c->optScratch) (void)hipFree(c->optScratch);
@@ -1097,6 +1099,44 @@ static int plat_nodes_delete(Dev& d, NdArgs& a) {
 static void plat_nodes_delete_ms(double* out) {
   hipEvent_t* ev = ndEvents();
   for (int k = 0; k < 7; k++) { float ms = 0.f; if (ev && t_ctx->ndTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
+}
+// new rows join the resident node table (kernels_nodes_append.h; k_na_* in armada_sched_mgpu.hip).  ASCHED_NA_TIMES=1 puts events around the four passes
+// (tools/probe_nodes_append.py).
+#include "kernels_nodes_append.h"
+extern "C" int asched_internal_na_planes(const NaArgs* a, hipStream_t s);
+extern "C" int asched_internal_na_narrow(const NaArgs* a, hipStream_t s);
+extern "C" int asched_internal_na_rank(const NaArgs* a, hipStream_t s);
+extern "C" int asched_internal_na_mask(const NaArgs* a, hipStream_t s);
+static hipEvent_t* naEvents() {
+  static const bool on = [] { const char* e = getenv("ASCHED_NA_TIMES"); return e && e[0] == '1'; }();
+  PlatCtx* c = t_ctx;
+  if (!on) return nullptr;
+  if (!c->naEv[4]) for (int i = 0; i < 5; i++) if (!c->naEv[i] && hipEventCreate(&c->naEv[i]) != hipSuccess) { c->naEv[i] = nullptr; return nullptr; }
+  return c->naEv;
+}
+static int plat_nodes_append(Dev& d, NaArgs& a) {
+  (void)d;
+  PlatCtx* c = t_ctx;
+  hipStream_t st = c->stream;
+  hipEvent_t* ev = naEvents();
+  c->naTimed = false;
+  if (ev) (void)hipEventRecord(ev[0], st);
+  if (asched_internal_na_planes(&a, st)) { c->err = "k_na_plane launch failed"; return -1; }
+  if (ev) (void)hipEventRecord(ev[1], st);
+  if (asched_internal_na_narrow(&a, st)) { c->err = "k_na_narrow launch failed"; return -1; }
+  if (ev) (void)hipEventRecord(ev[2], st);
+  if (asched_internal_na_rank(&a, st)) { c->err = "k_na_rank launch failed"; return -1; }
+  if (ev) (void)hipEventRecord(ev[3], st);
+  bool ok = asched_internal_na_mask(&a, st) == 0;
+  if (ev) (void)hipEventRecord(ev[4], st);
+  ok = ok && hipOk(hipGetLastError(), "k_na launch") && hipOk(hipStreamSynchronize(st), "k_na");
+  if (!ok) { if (c->err.empty()) c->err = "k_na launch failed"; return -1; }
+  c->naTimed = ev != nullptr;
+  return 0;
+}
+static void plat_nodes_append_ms(double* out) {
+  hipEvent_t* ev = naEvents();
+  for (int k = 0; k < 4; k++) { float ms = 0.f; if (ev && t_ctx->naTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
 }
 // a caller-side buffer may be memory of this handle's GPU (a tensor the collective reduces in place: used directly) or host memory (staged)
 static bool plat_is_device_ptr(const void* p) {

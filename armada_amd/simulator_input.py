@@ -481,7 +481,7 @@ def run_cycles_cordoning(lib, sim: SimulatorInput, node_events, per_cycle: Optio
     return _run_cycles_arriving(lib, sim, per_cycle, max_cycles, appended, node_events=list(node_events), nodes_patched=nodes_patched)
 
 
-def _run_cycles_draining(lib, sim: SimulatorInput, node_events, per_cycle, max_cycles, drained):
+def _run_cycles_draining(lib, sim: SimulatorInput, node_events, per_cycle, max_cycles, drained, joins=False, absent=()):
     from .binding import Scheduler
     wl = sim.workload
     m, n0 = wl.num_jobs, wl.num_nodes
@@ -492,13 +492,15 @@ def _run_cycles_draining(lib, sim: SimulatorInput, node_events, per_cycle, max_c
     done = np.zeros(m, bool)
     changed = np.zeros(m, bool)
     unschedulable = np.zeros(n0, np.uint8)
-    node_of_row = np.arange(n0, dtype=np.int64)       # the driver's own position <-> node map
-    row_of_node = np.arange(n0, dtype=np.int64)
+    node_of_row = np.setdiff1d(np.arange(n0, dtype=np.int64), np.asarray(absent, dtype=np.int64))   # the driver's own position <-> node map
+    index_of = (lambda nodes: np.asarray(nodes) + 1) if joins else (lambda nodes: None)   # node.index: with joins the workload's node number, which a returning node keeps; else the binding's default
+    row_of_node = np.full(n0, -1, dtype=np.int64)
+    row_of_node[node_of_row] = np.arange(len(node_of_row))
     pending = []                                      # nodes a "drop" event named that still hold a job or are not cordoned
     id_rank = np.arange(n0) if wl.node_id_rank is None else np.asarray(wl.node_id_rank)
     out = []
     s = Scheduler(lib, wl.config)
-    s.nodes_upsert(wl.node_total, id_rank=id_rank)
+    s.nodes_upsert(wl.node_total[node_of_row], index=index_of(node_of_row), id_rank=id_rank[node_of_row])
     have = 0
     t = 0.0
 
@@ -525,7 +527,7 @@ def _run_cycles_draining(lib, sim: SimulatorInput, node_events, per_cycle, max_c
                 s.jobs_patch(rows, rows_of(rows), np.where(running, run_prio[rows], 0), np.where(running, np.maximum(started[rows], 0) * 1e9, 0).astype(np.int64))
         changed[:] = False
         have = upto
-        touched = []                                  # then the node events of this cycle, in the schedule's order
+        touched, joining = [], []                     # then the node events of this cycle, in the schedule's order
         for ev in node_events:
             if ev[0] != cycle:
                 continue
@@ -537,6 +539,15 @@ def _run_cycles_draining(lib, sim: SimulatorInput, node_events, per_cycle, max_c
             elif kind == "drop":
                 if n not in pending:
                     pending.append(n)
+            elif kind == "join" and joins:
+                unschedulable[n] = 0                  # (a node comes back uncordoned)
+                if n in pending:
+                    pending.remove(n)
+                if row_of_node[n] >= 0:               # still in the table (its drop was waiting for its jobs): the join is an uncordon
+                    if n not in touched:
+                        touched.append(n)
+                elif n not in joining:
+                    joining.append(n)
             else:
                 raise ValueError(f"node event {kind!r}")
         # populateNodeDb's rule (scheduling_algo.go:1069-1077): a node that is unschedulable and holds no job is left out — from the first cycle in which both hold
@@ -552,12 +563,16 @@ def _run_cycles_draining(lib, sim: SimulatorInput, node_events, per_cycle, max_c
                 new_id = s.nodes_delete(row_of_node[gone].astype(np.int32), want_map=True)
                 row_of_node[node_of_row] = new_id
                 node_of_row = node_of_row[new_id >= 0]
+            if joining:                               # populateNodeDb inserts what the executors report: the new rows go behind the resident ones
+                s.nodes_append(wl.node_total[joining], index=index_of(joining), id_rank=id_rank[joining], unschedulable=unschedulable[joining])
+                row_of_node[joining] = len(node_of_row) + np.arange(len(joining))
+                node_of_row = np.concatenate([node_of_row, np.asarray(joining, dtype=np.int64)])
         else:
-            if gone:
-                node_of_row = node_of_row[~np.isin(node_of_row, gone)]
+            if gone or joining:
+                node_of_row = np.concatenate([node_of_row[~np.isin(node_of_row, gone)], np.asarray(joining, dtype=np.int64)])
                 row_of_node[:] = -1
                 row_of_node[node_of_row] = np.arange(len(node_of_row))
-            s.nodes_upsert(wl.node_total[node_of_row], id_rank=id_rank[node_of_row], unschedulable=unschedulable[node_of_row])
+            s.nodes_upsert(wl.node_total[node_of_row], index=index_of(node_of_row), id_rank=id_rank[node_of_row], unschedulable=unschedulable[node_of_row])
             running = node[:upto] >= 0
             s.jobs_set(wl.job_req[:upto], queue=wl.job_queue[:upto], pc=wl.job_pc[:upto], submit_time=wl.job_submit[:upto], node=rows_of(np.arange(upto)),
                        scheduled_at_priority=np.where(running, run_prio[:upto], 0), run_timestamp=np.where(running, np.maximum(started[:upto], 0) * 1e9, 0).astype(np.int64))
@@ -574,7 +589,8 @@ def _run_cycles_draining(lib, sim: SimulatorInput, node_events, per_cycle, max_c
         for j in pre:
             node[j], started[j] = -1, -1.0
             changed[j] = True
-        out.append({"time_s": t, "scheduled": sched, "preempted": pre, "termination_reason": r.termination_reason, "rows": have, "nodes": len(node_of_row)})
+        out.append({"time_s": t, "scheduled": sched, "preempted": pre, "termination_reason": r.termination_reason, "rows": have, "nodes": len(node_of_row),
+                    **({"joined": len(joining)} if joins else {})})
         if have == m and not sched and not pre and not (node >= 0).any():
             break   # everything has arrived, nothing runs and nothing can be placed: the rest never will
         t += sim.cycle_period_s
@@ -595,3 +611,18 @@ def run_cycles_draining_rebuilt(lib, sim: SimulatorInput, node_events, per_cycle
     """the rebuilt counterpart of run_cycles_draining: nodes_upsert of each cycle's reduced node table and jobs_set of the grown job table, its runs on the reduced
     table's positions, in every cycle — what any library, the oracle included, can run.  Same rows, same records."""
     return _run_cycles_draining(lib, sim, list(node_events), per_cycle, max_cycles, False)
+
+
+def run_cycles_scaling(lib, sim: SimulatorInput, node_events, per_cycle: Optional[int] = None, max_cycles: int = 1000, absent=()):
+    """run_cycles_draining plus nodes that JOIN the table: node_events may also hold (cycle, "join", node).  `absent`: nodes (by the workload's numbering) that are not in
+    the first cycle's table — a cluster that scales up.  A join of a node that is not in the table — absent from the start, or dropped earlier — goes through
+    Scheduler.nodes_append after the cycle's patches and deletes: the node comes back uncordoned, with its old node.index and id rank, at the end of the table, and the
+    driver's position <-> node map follows it.  A join of a node that is still in the table (its drop was waiting for its jobs to finish) cancels the drop and uncordons
+    it.  Records as run_cycles_draining, plus "joined": the rows appended in the cycle."""
+    return _run_cycles_draining(lib, sim, list(node_events), per_cycle, max_cycles, True, joins=True, absent=tuple(absent))
+
+
+def run_cycles_scaling_rebuilt(lib, sim: SimulatorInput, node_events, per_cycle: Optional[int] = None, max_cycles: int = 1000, absent=()):
+    """the rebuilt counterpart of run_cycles_scaling: nodes_upsert of each cycle's node table (the remaining rows in their order, then the joining ones) and jobs_set of
+    the grown job table in every cycle — what any library, the oracle included, can run.  Same rows, same records."""
+    return _run_cycles_draining(lib, sim, list(node_events), per_cycle, max_cycles, False, joins=True, absent=tuple(absent))

@@ -456,7 +456,7 @@ typedef struct asched_nodes_patch_rows {
    beyond 128 bits, more than LIT_TMAX node types on the literal path); ASCHED_ERR_DEVICE with "the handle is as it was" in last_error: out of device memory for the
    entries.  Any other ASCHED_ERR_DEVICE (a failed launch or copy) is NOT such a refusal: the handle then needs asched_nodes_upsert.
    Not this call's job: removing rows is asched_nodes_delete's (the reference's dropping of an unschedulable node that holds no job, scheduling_algo.go:1070-1077);
-   adding rows, total, labels, index and id_rank are asched_nodes_upsert's. */
+   adding rows is asched_nodes_append's; total, labels, index and id_rank of resident rows are asched_nodes_upsert's. */
 int32_t ASCHED_FN(nodes_patch)(asched_t*, const asched_nodes_patch_rows* rows);
 /* how the last nodes_patch ran: out[0] entries, [1] rows whose node type changed, [2] 1 = the rebuild path ran, [3] why: 0 none, 1 a node type the table did not
    have, 2 a node type emptied or newly populated, 3 key layout / divisor / alignment; [4..7] 0.  Zeros after nodes_upsert. */
@@ -480,11 +480,52 @@ int32_t ASCHED_FN(nodes_patch_stats)(asched_t*, int32_t* out /*[8]*/);
    asched_nodes_upsert), the table was uploaded with alloc_by_prio or node_type_override, whatever the rebuild would refuse; ASCHED_ERR_DEVICE with "the handle is as
    it was" in last_error: out of device memory for the scratch and the fresh blocks (all of it is allocated first).  Any other ASCHED_ERR_DEVICE (a failed launch or
    copy) is NOT such a refusal: the handle then needs asched_nodes_upsert and asched_jobs_set.
-   Not this call's job: adding rows (asched_nodes_upsert). */
+   Not this call's job: adding rows (asched_nodes_append). */
 int32_t ASCHED_FN(nodes_delete)(asched_t*, int32_t n, const int32_t* node /*[n] rows, each at most once*/, int32_t* new_id /*[N before the call] or NULL*/);
 /* how the last nodes_delete ran: out[0] rows deleted, [1] job rows whose node was renumbered, [2] 1 = the rebuild path ran, [3] why: 0 none, 2 a node type emptied,
    4 a value of an indexed label emptied; [4] N after the call, [5..7] 0.  Zeros after nodes_upsert. */
 int32_t ASCHED_FN(nodes_delete_stats)(asched_t*, int32_t* out /*[8]*/);
+/* populateNodeDb inserts whatever nodes the healthy executors report (scheduling_algo.go:1019-1098): a cluster that scales up, an executor that was stale, lagging
+   or cordoned and returns (:1100-1169), a drained node that is uncordoned.  The m rows join the resident node table behind the N resident ones, at positions
+   N .. N + m - 1; no resident position changes, so no run of the resident job table is renumbered. */
+typedef struct asched_nodes_append_rows {   /* the fields of asched_nodes, for the m new rows */
+  int32_t m;
+  const uint64_t* index;          /* [m] node.index: unique among the new rows and against the resident ones */
+  const int32_t* id_rank;         /* [m] in the rank space of the resident rows (only the order matters); NULL = behind every resident rank, in row order */
+  const int32_t* id_rank_all;     /* optional [N+m]: replaces the id rank of EVERY row (the caller re-ranked its id strings); overrides id_rank */
+  const int64_t* total;           /* [m][R] */
+  const int64_t* allocatable;     /* [m][R] */
+  const uint8_t* unschedulable;   /* [m] or NULL */
+  const uint8_t* over_allocated;  /* [m] or NULL */
+  const int32_t* taint_off; const int32_t* taint_key; const int32_t* taint_value; const int32_t* taint_effect;   /* CSR or NULL */
+  const int32_t* label_off; const int32_t* label_key; const int32_t* label_value;                               /* CSR or NULL */
+} asched_nodes_append_rows;
+/* After a successful call every entry point answers as it would after asched_nodes_upsert of the table "the N resident rows in their order, then the m new rows"
+   (rounds, the NodeDb-level calls, fit_select_batch*, submit_check, iterate_nodes, excluded_nodes, node_types_matching_job, num_nodes, total_resources,
+   indexed_node_label_values, the getters, the evictor report, the preemption causes, the optimiser, a later jobs_patch / jobs_append / jobs_delete / nodes_patch /
+   nodes_delete in any order), including everything nodes_upsert resets; the caller goes on with round_prepare.  m == 0 performs the resets only.  A run on a new node
+   is told afterwards with jobs_patch or jobs_append, naming the new position.  The job table, its order, shapes, gangs, requirement classes and the fast structure
+   stay.  Aggregates that are bounds (the widths of the key layout, alignment, the gcd of a column, id order == index order) stay conservative: results equal the fresh
+   handle's, internal widths and path choices need not.  Unlike a delete, an append can VIOLATE such a bound: it then takes the rebuild path.
+   Id ranks: a table that asched_nodes_upsert was given WITHOUT id_rank has no rank space (its id order is its index order by definition); it takes appends without
+   ranks, which keep that definition, or with id_rank_all, which gives every row a rank; id_rank alone is refused there.  m == 0 performs the resets only and ignores
+   id_rank_all.
+   Two paths, chosen per call (nodes_append_stats).  The device path where nothing the host derives from the whole table changes: every new row's node type is
+   already populated, every value of an indexed label on a new row is already present, every new allocatable row lies inside what the key layout was chosen for
+   (nodes_patch's condition), N + m - 1 fits the rank field of the key, and id order == index order does not turn false.  Every block that depends on N, its padding
+   or the words of a mask row is written into a fresh block of the new size — the planes, the narrow arrays, the merged index order, every mask row — and swapped
+   in at the end; the host extends its mirrors.  Otherwise the grown table goes through nodes_upsert's own code.
+   Refused before anything changes — ASCHED_ERR_INVALID: no node table, m < 0, m > 0 without index / total / allocatable, an index that a resident row or another
+   new row has, a taint_off or label_off that is not ascending, id_rank without id_rank_all on a table uploaded without id ranks; ASCHED_ERR_UNSUPPORTED: the table was uploaded with alloc_by_prio or node_type_override, N + m above
+   2^30, whatever the rebuild would refuse (a key beyond 128 bits, more than LIT_TMAX node types on the literal path); ASCHED_ERR_DEVICE with "the handle is as it
+   was" in last_error: out of device memory for the scratch and the fresh blocks (all of it is allocated first).  Any other ASCHED_ERR_DEVICE (a failed launch or
+   copy) is NOT such a refusal: the handle then needs asched_nodes_upsert.
+   Not this call's job: inserting rows anywhere but at the end; total, labels or index of resident rows (asched_nodes_upsert). */
+int32_t ASCHED_FN(nodes_append)(asched_t*, const asched_nodes_append_rows* rows);
+/* how the last nodes_append ran: out[0] rows appended, [1] 1 = the per-node blocks changed stride (the padded node count grew), [2] 1 = the rebuild path ran, [3] why:
+   0 none, 1 a node type the table did not have, 2 a known node type newly populated, 3 key layout / divisor / alignment / id order, 4 a new value of an indexed label
+   (reported in preference to 1 or 2), 5 the rank field of the key is too narrow; [4] N after the call, [5..7] 0.  Zeros after nodes_upsert. */
+int32_t ASCHED_FN(nodes_append_stats)(asched_t*, int32_t* out /*[8]*/);
 
 int32_t ASCHED_FN(txn_begin)(asched_t*);    /* nodeDb.Txn(true) (nodedb.go:353) */
 int32_t ASCHED_FN(txn_commit)(asched_t*);

@@ -980,6 +980,103 @@ func (g *GpuRound) PatchNodes(changed []*internaltypes.Node) error {
 	return nil
 }
 
+// AppendNodes tells the library which nodes joined the pool since the last cycle without re-describing the pool (asched_nodes_append): what populateNodeDb inserts
+// for the nodes the healthy executors report (scheduling_algo.go:1019-1098) — a cluster that scales up, an executor that was stale, lagging or cordoned and returns
+// (:1100-1169), a drained node that is uncordoned.  joined: internaltypes.Node objects UploadNodes has not seen (by id); they take the positions behind the uploaded
+// ones, in the order given, and g.nodes / g.nodePos follow.  The id ranks of ALL nodes are re-ranked from the id strings and given as id_rank_all: a new id sorts
+// anywhere among the old ones.  Taints are interned as UploadNodes interns them; a taint KEY that no uploaded node carried would get an id behind every earlier one,
+// which is not the reference's lexicographic key order (node_type.go:87-97): such a node, and a node whose id is already uploaded, are ErrNeedsNodeUpload — the caller
+// then calls UploadNodes with the whole pool.  A job that runs on a new node is told afterwards, by its new position (PatchJobs / AppendJobs).  The next call is
+// Schedule, as after UploadNodes.  (Like the rest of this file it is written out for the maintainer and has not been compiled: the reference's module tree is not
+// vendored here.)
+func (g *GpuRound) AppendNodes(joined []*internaltypes.Node) error {
+	m, R := len(joined), len(g.resNames)
+	if m == 0 {
+		var none C.asched_nodes_append_rows
+		return g.check(C.asched_nodes_append(g.h, &none))
+	}
+	known := make(map[string]bool, len(g.strs.strs))
+	for _, s := range g.strs.strs {
+		known[s] = true
+	}
+	n0 := len(g.nodes)
+	index := make([]uint64, m)
+	total, alloc := make([]int64, m*R), make([]int64, m*R)
+	unsched, over := make([]uint8, m), make([]uint8, m)
+	tOff, tKey, tVal, tEff := make([]int32, 1, m+1), []int32{}, []int32{}, []int32{}
+	lOff, lKey, lVal := make([]int32, 1, m+1), []int32{}, []int32{}
+	ids := make([]string, 0, n0+m)
+	for _, node := range g.nodes {
+		ids = append(ids, node.GetId())
+	}
+	seen := make(map[string]bool, m)
+	for i, node := range joined {
+		if _, ok := g.nodePos[node.GetId()]; ok || seen[node.GetId()] {
+			return ErrNeedsNodeUpload
+		}
+		seen[node.GetId()] = true
+		ids = append(ids, node.GetId())
+		index[i] = node.GetIndex()
+		copy(total[i*R:], g.vec(node.GetTotalResources()))
+		copy(alloc[i*R:], g.vec(node.GetAllocatableResources()))
+		if node.IsUnschedulable() {
+			unsched[i] = 1
+		}
+		if node.IsOverAllocated() {
+			over[i] = 1
+		}
+		for _, t := range node.GetTaints() {
+			if t.Key == "node.kubernetes.io/unschedulable" {
+				continue // the library adds it from `unschedulable` (node.go:127-129)
+			}
+			if !known[t.Key] {
+				return ErrNeedsNodeUpload
+			}
+			tKey, tVal, tEff = append(tKey, g.strs.id(t.Key)), append(tVal, g.strs.id(t.Value)), append(tEff, effectOf(t.Effect))
+		}
+		tOff = append(tOff, int32(len(tKey)))
+		labels := node.GetLabels()
+		keys := make([]string, 0, len(labels))
+		for k := range labels {
+			keys = append(keys, k)
+		}
+		sort.Strings(keys)
+		for _, k := range keys {
+			lKey, lVal = append(lKey, g.strs.id(k)), append(lVal, g.strs.id(labels[k]))
+		}
+		lOff = append(lOff, int32(len(lKey)))
+	}
+	rank := ranks(ids)
+	var pins runtime.Pinner
+	defer pins.Unpin()
+	var in C.asched_nodes_append_rows
+	in.m = C.int32_t(m)
+	for _, p := range []interface{}{&index[0], &rank[0], &total[0], &alloc[0], &unsched[0], &over[0], &tOff[0], &lOff[0]} {
+		pins.Pin(p)
+	}
+	for _, s := range [][]int32{tKey, tVal, tEff, lKey, lVal} {
+		if len(s) > 0 {
+			pins.Pin(&s[0])
+		}
+	}
+	in.index, in.id_rank_all = (*C.uint64_t)(unsafe.Pointer(&index[0])), i32p(rank)
+	in.total, in.allocatable = i64p(total), i64p(alloc)
+	in.unschedulable, in.over_allocated = u8p(unsched), u8p(over)
+	in.taint_off, in.taint_key, in.taint_value, in.taint_effect = i32p(tOff), i32p(tKey), i32p(tVal), i32p(tEff)
+	in.label_off, in.label_key, in.label_value = i32p(lOff), i32p(lKey), i32p(lVal)
+	if err := g.uploadLabelValueInts(); err != nil { // (a new label value may be an integer)
+		return err
+	}
+	if err := g.check(C.asched_nodes_append(g.h, &in)); err != nil {
+		return err
+	}
+	for i, node := range joined {
+		g.nodePos[node.GetId()] = int32(n0 + i)
+	}
+	g.nodes = append(g.nodes, joined...)
+	return nil
+}
+
 // uploadLabelValueInts tells the library which interned strings are integers (strconv.ParseInt(v, 10, 64), what
 // labels.Requirement.Matches does for Gt / Lt) — asched_set_label_value_ints.  Called before asched_jobs_set / asched_nodes_upsert
 // evaluate affinities (the static masks are rebuilt by whichever of the two comes last).
