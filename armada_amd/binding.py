@@ -1405,11 +1405,11 @@ class Scheduler:
                     evr_job_node_ms=out[6], evr_queue_ms=out[7])
 
     def round_stats(self):
-        out = (C.c_int32 * 24)()
+        out = (C.c_int32 * 25)()
         self._check(self.lib.round_stats(self.h, out))
         names = ["fast_iterations", "generic_iterations", "base_scan_steps", "window_refills", "l0_max", "fast_replay_steps", "l0_overflows", "fast_active",
                  "kclk_evict", "kclk_replay", "kclk_pass1", "kclk_oversub_evict", "kclk_pass2", "kclk_unbind_results",
-                 "kclk_plane_scans", "kclk_fair_selects", "stream_runs", "stream_jobs", "stream_prepared", "stream_emitted", "preempt_fast_iterations", "hc_short_picks", "nested_gangs", "streams_over_cap"]   # (nested_gangs, streams_over_cap: counted by the CPU build alone)
+                 "kclk_plane_scans", "kclk_fair_selects", "stream_runs", "stream_jobs", "stream_prepared", "stream_emitted", "preempt_fast_iterations", "hc_short_picks", "nested_gangs", "streams_over_cap", "hc_clean_picks"]   # (nested_gangs, streams_over_cap: counted by the CPU build alone; hc_short_picks, hc_clean_picks: by the device alone)
         return {k: out[i] for i, k in enumerate(names)}
 
     def excluded_nodes(self, job: int):

@@ -4210,11 +4210,12 @@ int32_t asched_gang_schedule(asched_t* h, int32_t n, const int32_t* jobs, int32_
 int32_t asched_round_stats(asched_t* h, int32_t* out) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
   plat_d2h(&h->rsHost, h->dev.rs, sizeof(RoundScalars));
   const RoundScalars& r = h->rsHost;
-  for (int i = 0; i < 24; i++) out[i] = 0;
+  for (int i = 0; i < 25; i++) out[i] = 0;
   out[20] = r.statHybrid;
   out[21] = r.statHcShort;
   out[22] = r.statNestGangs;   // (CPU build only: the device leaves it 0)
   out[23] = r.statOverCap;     // (CPU build only: the device leaves it 0)
+  out[24] = (int32_t)(r.statSeg[HC_CLEAN_SEG] / 1000);   // (device only, engine_hc.h; a -DASCHED_FASTPROF build adds segment ticks to the same word: read statSeg[34] there)
   out[0] = r.statFastIters; out[1] = r.statGenericIters; out[2] = r.statScanSteps; out[3] = r.statRefills; out[4] = r.statL0Max;
   out[5] = r.statFastReplay; out[6] = r.fastOverflow; out[7] = r.fastActive;
   out[16] = r.statStreamRuns; out[17] = r.statStreamJobs; out[18] = r.statStreamPrepared; out[19] = r.statStreamEmitted;

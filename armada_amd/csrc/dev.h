@@ -199,6 +199,10 @@ struct RoundScalars {
   int32_t statOverCap;         // streams longer than the bulk-merge passes cover that mgWorth / mgPrepare turned away (round_merge.h): round_stats streams_over_cap.  Filled by the
                                // CPU build alone, like statNestGangs (the device leaves it 0).  The third of the three reserved words.
   int64_t statSeg[40];       // [24..39]: (profiling builds) segments of the generic iteration
+#define HC_CLEAN_SEG 15      // the statSeg word that carries the picks of the node engine's clean short path (engine_hc.h; device only, kilo-units like its neighbours) to
+                             // round_stats hc_clean_picks: no reserved word is left and the struct keeps its layout.  Nothing else writes word 15 in the product build (the
+                             // always-on words are 0-2, 24-34 and 37-39).  EVERY word of statSeg belongs to some SEG / XSEG / GSEG / WSEG segment of the -DASCHED_FASTPROF builds
+                             // (15: round_fast.h "the ring is full", round_ctl.h GSEG(15)), so in those builds — never shipped — word 24 of round_stats carries ticks as well.
   int64_t gsT;                     // (profiling builds) shader-clock ticks per segment of a fast iteration
   int64_t statClk[8];        // shader-clock ticks per phase of the round (device builds): evict, replay, pass 1, oversub evict, pass 2, unbind+results
 #ifdef ASCHED_RS_PAD

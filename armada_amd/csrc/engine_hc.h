@@ -439,6 +439,7 @@ __device__ static inline int hcHotBind(HcHot& h, int hLane, const HcJobV& j, uns
   return nkL == ~0ull ? 1 : 0;
 }
 #define HC_ERR_SHORT 610   // errorDetail of the checking build (-DASCHED_HC_CHECK): the general body decided a short-path job differently, or asked / fetched for it
+#define HC_ERR_CLEAN 612   // the same build: the text the clean short path skips decided such a job differently (not the shape's clean head), or asked / fetched for it
 #define HC_ERR_ORDER 611   // the same build: the order words (hc_order.h) and the 64-lane minimum named different lanes or keys for a job
 
 // One ring session with the split structure.  Same contract as the ENG_STREAM walk of engineLoop: entry i is ready when ringPub > i; the chosen node goes into the
@@ -447,7 +448,7 @@ __device__ static inline int hcHotBind(HcHot& h, int hLane, const HcJobV& j, uns
 // dependent LDS round trip.  Per job: ONE batch of LDS reads for the next entry and the cold set's answer (issued before the tests, used after them).
 // (A function of its own, not inlined: inside engineLoop its loop shared the register allocation of the serial engine's paths and lived partly in AGPRs.  Its constants
 // and counters are copied in and out: nothing in the loop goes through the references.)
-struct HcOut { int engSeq, statScanSteps, statL0Max, hcShort; long long segT, eseg[8]; };
+struct HcOut { int engSeq, statScanSteps, statL0Max, hcShort, hcClean; long long segT, eseg[8]; };
 template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamHcT(Dev& d, const FastK k, const int engSeq0, const int statScan0, const int statL0Max0, const long long segT0) {
   // (every argument BY VALUE: a reference to the caller's constants or counters would put them in memory over there — the serial engine's loops read them too;
   //  measured: 20 % on gang-heavy rounds, profiles/r06v)
@@ -472,6 +473,7 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
   const unsigned long long shortOn = d.f.hcShort ? ~0ull : 0ull;   // (read once per session; used on the general path only)
   HcShapes sc; hcShapesLoad(k, sc); hcShapesBound(sc, shortOn);
   int nShort = 0;   // picks the short path took: round_stats hc_short_picks
+  int nClean = 0;   // picks the clean short path took: round_stats hc_clean_picks
   int total = __builtin_amdgcn_readfirstlane(g_fl.l0Count);   // dirty nodes alive (H + C): the list's high-water mark for round_stats
   int i = 0, fail = 0;
   // (bounded waits, round_kernel.h: a turn of a wait here reads the launch's `abandon` word — 0 or 1 — and leaves through an exit the loop has anyway; NO flag is carried
@@ -481,7 +483,7 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
   int pSrc[4] = {0, 0, 0, 0}, pFetch = 0, pDry = 0, pAsk = 0;
 #endif
 #ifdef ASCHED_HC_CHECK
-  int chkNode = -1, chkQ = 0, chkScan = 0;   // the short path's pick of the job at hand (-1: it does not qualify); questions and fetch rounds before its general walk
+  int chkNode = -1, chkSrc = 0, chkQ = 0, chkScan = 0;   // the pick of the job at hand by the short path it qualifies for (-1: for neither) and that path's source (0 the hot set, 2 the clean head); questions and fetch rounds before its general walk
 #endif
   for (;;) {
     if (!haveCur) {   // the ring ran dry (or the session starts): wait for entry i
@@ -557,7 +559,7 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
       const unsigned long long bkS = hcRead64(hiSet ? sc.bk[1] : sc.bk[0], sl);
       const int stH = __builtin_amdgcn_readlane(h.state, hLane & 63);   // (no hot candidate: some lane's state, and (b) fails)
 #ifdef ASCHED_HC_CHECK
-      chkNode = -1; chkQ = qSeq; chkScan = ES.statScanSteps;
+      chkNode = -1; chkSrc = 0; chkQ = qSeq; chkScan = ES.statScanSteps;
       if (!(rLb < hk) & (hk < bkS) & (stH == 1)) chkNode = __builtin_amdgcn_readlane(h.node, hLane & 63);
 #else
       if (!(rLb < hk) & (hk < bkS) & (stH == 1)) {   // (a scalar branch on a v_readfirstlane of this was measured the same: 217.2 / 217.7 against 216.1 / 217.8 ms)
@@ -576,11 +578,36 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
     // ---- the shape's clean candidate as it stands
     int cst = __builtin_amdgcn_readlane(hiSet ? sc.st[1] : sc.st[0], sl);
     unsigned long long cKey = hcRead64(hiSet ? sc.key[1] : sc.key[0], sl);        // (SC_HEAD: the candidate's key)
+    // ---- the CLEAN SHORT PATH (round 10): a pick the shape's clean head wins outright skips the body down to the verdict.  Taken iff, all wave-uniform:
+    //   (a') the shape's clean side holds a head (cst == SC_HEAD; with ASCHED_HC_SHORT=0 the state is masked to 0 here and this never holds);
+    //   (b') cKey < hk       the hot candidate lies above the head, or there is none (hk == ~0);
+    //   (c') !(rLb < cKey)   the cold set's lower bound is known (not 0) and does not lie below the head.
+    // Why the skipped text would decide the same.  By (a') and (b') its `known` is cKey, by (c') `ckLb < known` fails: no question, ck = ~0, cSlot = -1, no second
+    // release of lanes.  A fetch needs cst == SC_SCAN: none.  bk = cKey, dirtyWins = hk < cKey is false by (b'), the exit for "no node" needs cst != SC_HEAD,
+    // src = 2, n = nB: the values the skip leaves in place.  Keys are unique: every strict comparison reads the same from either side.  What follows is the general
+    // body's own text, not a copy: the node into the ring entry, the ack, no command (src 2 posts neither HC_D nor HC_C), the src-2 upkeep, the next entry.
+    // The flag lives from here to the end of this turn of the loop, never around it.
+    // (-DASCHED_HC_CHECK: a job that qualifies walks the skipped text too, which must come to src 2 and the same node without a question or a fetch round — else
+    //  ASCHED_ERR_INTERNAL / HC_ERR_CLEAN and the session ends.  -DASCHED_HC_NOCLEAN builds the loop without the skip.)
+#ifdef ASCHED_HC_NOCLEAN
+    const bool cleanS = false;
+#else
+    const bool cleanQ = ((cst & (int)shortOn) == SC_HEAD) & (cKey < hk) & !(rLb < cKey);
+#ifdef ASCHED_HC_CHECK
+    if (cleanQ) { chkNode = __builtin_amdgcn_readlane(hiSet ? sc.node[1] : sc.node[0], sl); chkSrc = 2; }
+    const bool cleanS = false;
+#else
+    const bool cleanS = cleanQ;
+    nClean += cleanS ? 1 : 0;   // (counted here: the flag's last use in the product build is the skip below)
+#endif
+#endif
     const unsigned long long cLb = hcRead64(hiSet ? sc.lb[1] : sc.lb[0], sl);     // (SC_SCAN: a lower bound)
     // ---- does the cold set matter?  Only when its bound lies below both the hot candidate and the clean candidate at hand: then the exact answer, synchronously (rare)
     const unsigned long long ckLb = UNI64(rLb);
     const unsigned long long known = cst == SC_HEAD && cKey < hk ? cKey : hk;
     unsigned long long ck = ~0ull; int cSlot = -1;
+    int src = 2, n = __builtin_amdgcn_readlane(hiSet ? sc.node[1] : sc.node[0], sl);   // (what the clean short path leaves in place)
+    if (!cleanS) {
     if (ckLb < known) {
 #ifdef ASCHED_FASTPROF
       pAsk++;
@@ -620,21 +647,25 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
     // cold set's node, which is rare and in LDS, is fetched under one
     const bool dirtyWins = lk2 < bk;
     if (!dirtyWins & (cst != SC_HEAD)) { fail = 1; break; }
-    const int src = dirtyWins ? (hk < ck ? 0 : 1) : 2;
+    src = dirtyWins ? (hk < ck ? 0 : 1) : 2;
     // ---- the pick: its node goes to the bind wave at once; its level-0 entry after the bind (fastAfterBind) is worked out where it lives
     const int nH = __builtin_amdgcn_readlane(h.node, hLane & 63), nB = __builtin_amdgcn_readlane(hiSet ? sc.node[1] : sc.node[0], sl);
-    int n = dirtyWins ? nH : nB;
+    n = dirtyWins ? nH : nB;
     if (src == 1) n = __builtin_amdgcn_readfirstlane(g_fl.l0Node[cSlot]);
 #ifdef ASCHED_HC_CHECK
     if (chkNode >= 0) {
-      if ((src != 0) | (n != chkNode) | (qSeq != chkQ) | (ES.statScanSteps != chkScan)) { if (lane == 0 && RS.error == 0) { RS.error = ASCHED_ERR_INTERNAL; RS.errorDetail = HC_ERR_SHORT; } LANE0_PUBLISHED(); fail = 1; break; }
-      nShort++;
+      if ((src != chkSrc) | (n != chkNode) | (qSeq != chkQ) | (ES.statScanSteps != chkScan)) { if (lane == 0 && RS.error == 0) { RS.error = ASCHED_ERR_INTERNAL; RS.errorDetail = chkSrc ? HC_ERR_CLEAN : HC_ERR_SHORT; } LANE0_PUBLISHED(); fail = 1; break; }
+      if (chkSrc) nClean++; else nShort++;
     }
 #endif
 #ifdef ASCHED_FASTPROF
     pSrc[src & 3]++;
 #endif
     ESEG(3);   // [19] the three-way minimum (incl. fetching clean candidates)
+    }
+#ifdef ASCHED_FASTPROF
+    else pSrc[2]++;
+#endif
     RREC(i).node0 = n;   // (every lane stores the same word)
     LDS_ORDER();
     i++;
@@ -643,6 +674,9 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
     if (src == 1) hcPostA(cmdPub, HC_D, cSlot);
     if (inFlight > 0 && src == 0 && __builtin_amdgcn_readlane(h.state, hLane) == 2) { hcPostA(cmdPub, HC_C, __builtin_amdgcn_readlane(h.seq, hLane)); inFlight--; }
     const bool haveNext = __builtin_amdgcn_readfirstlane(nxt.pub) > i;
+#ifdef ASCHED_FASTPROF
+    if (!cleanS)
+#endif
     ESEG(4);   // [20] verdict, commands
     // ---- the bind's effect on the node's level-0 entry: key and extras go down; an entry that can no longer host anything is dropped
     if (src == 0) {   // in place, in its lane
@@ -694,12 +728,15 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
       } else if (src == 1) total--;
     }
     cur = nxt; haveCur = haveNext;
+#ifdef ASCHED_FASTPROF
+    if (cleanS) ESEG(7); else   // [23] the clean short path: its test, the pick, the base entry's and H's upkeep
+#endif
     ESEG(5);   // [21] hot-set / base upkeep
   }
   bool gaveUp = waitAbandoned();   // the session ends without its hand-shakes
   if (gaveUp) fail = 1;
 #ifdef ASCHED_FASTPROF
-  if (lane == 0) { g_rs.statSeg[29] += pSrc[0] * 1000ll; g_rs.statSeg[30] += pSrc[1] * 1000ll; g_rs.statSeg[31] += pSrc[2] * 1000ll; g_rs.statSeg[33] += pFetch * 1000ll; g_rs.statSeg[35] += pDry * 1000ll; g_rs.statSeg[36] += pAsk * 1000ll; g_rs.statSeg[32] += nShort * 1000ll; }   // picks from H / C / the base (general body only); clean-candidate fetches; ring-dry waits; questions put to the cold set; [32] picks of the short path (all from H)
+  if (lane == 0) { g_rs.statSeg[29] += pSrc[0] * 1000ll; g_rs.statSeg[30] += pSrc[1] * 1000ll; g_rs.statSeg[31] += pSrc[2] * 1000ll; g_rs.statSeg[33] += pFetch * 1000ll; g_rs.statSeg[35] += pDry * 1000ll; g_rs.statSeg[36] += pAsk * 1000ll; g_rs.statSeg[32] += nShort * 1000ll; g_rs.statSeg[34] += nClean * 1000ll; }   // picks from H / C / the base (not the hot short path's); clean-candidate fetches; ring-dry waits; questions put to the cold set; [32] picks of the short path (all from H); [34] picks of the clean short path (part of [31])
 #endif
   // ---- session end: the shapes' cursors go back to LDS; C compacts the LDS list; H's entries are appended; a pending failure is reported after the structure is whole again
   hcShapesStore(k, sc);
@@ -724,7 +761,7 @@ template <int E> __device__ static __attribute__((noinline)) HcOut engineStreamH
   }
   if (fail == 3) fail = 2;
   if (fail) { LDS_ORDER(); hcStoreI32(&g_fl.eng.ringFail, fail); }
-  HcOut o; o.engSeq = ES.engSeq; o.statScanSteps = ES.statScanSteps; o.statL0Max = ES.statL0Max; o.hcShort = nShort; o.segT = ES.segT;
+  HcOut o; o.engSeq = ES.engSeq; o.statScanSteps = ES.statScanSteps; o.statL0Max = ES.statL0Max; o.hcShort = nShort; o.hcClean = nClean; o.segT = ES.segT;
   for (int x = 0; x < 8; x++) o.eseg[x] = 0;
 #ifdef ASCHED_FASTPROF
   for (int x = 0; x < 8; x++) o.eseg[x] = ES.eseg[x];
@@ -735,7 +772,7 @@ __device__ static inline void engineStreamHc(Dev& d, KREF k, FastS& ES) {
   HcOut o;
   if (k.E == 0) o = engineStreamHcT<0>(d, k, ES.engSeq, ES.statScanSteps, ES.statL0Max, ES.segT); else if (k.E == 1) o = engineStreamHcT<1>(d, k, ES.engSeq, ES.statScanSteps, ES.statL0Max, ES.segT); else o = engineStreamHcT<2>(d, k, ES.engSeq, ES.statScanSteps, ES.statL0Max, ES.segT);
   ES.engSeq = o.engSeq; ES.statScanSteps = o.statScanSteps; ES.statL0Max = o.statL0Max;
-  if ((threadIdx.x & 63) == 0) g_rs.statHcShort += o.hcShort;   // (this wave's word of the round's scalars: nothing else writes it)
+  if ((threadIdx.x & 63) == 0) { g_rs.statHcShort += o.hcShort; g_rs.statSeg[HC_CLEAN_SEG] += o.hcClean * 1000ll; }   // (this wave's words of the round's scalars: nothing else writes them)
   LANE0_PUBLISHED();
 #ifdef ASCHED_FASTPROF
   ES.segT = o.segT; for (int x = 0; x < 8; x++) ES.eseg[x] += o.eseg[x];

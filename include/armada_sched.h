@@ -841,8 +841,9 @@ int32_t ASCHED_FN(round_timing)(asched_t*, double* out /*[8]*/);
    fast structure active at the end, [8..15] kilo-ticks per phase, [16..19] stream runs / entries bound in them / stream entries prepared / emitted,
    [20] iterations whose job needed preemption and stayed in the fast loop, [21] picks the split node engine's short path took
    (device only: the CPU build leaves it 0; ASCHED_HC_SHORT=0 turns the path off), [22] gangs placed nested inside stream runs (the CPU build of the tests only: the device
-   leaves it 0), [23] reserved, always 0}.  The CPU oracle reports zeros. */
-int32_t ASCHED_FN(round_stats)(asched_t*, int32_t* out /*[24]*/);
+   leaves it 0), [23] streams the bulk merge turned away for their length (the CPU build of the tests only), [24] picks the split node engine's clean short path took
+   (device only, like [21], and switched off with it)}.  The CPU oracle reports zeros. */
+int32_t ASCHED_FN(round_stats)(asched_t*, int32_t* out /*[25]*/);
 /* Hard timeout of a round (maxSchedulingDuration, config/scheduler/config.yaml:83; scheduling_algo.go:130-134 wraps the context in
    WithTimeout, queue_scheduler.go:105-112 checks ctx.Done() every loop iteration and returns ctx.Err()).  asched_set_deadline: every
    following schedule_round / schedule_queues is cancelled `seconds` after it starts (0 = none).  asched_cancel = the context's cancel
