@@ -265,6 +265,7 @@ ALL_SYMBOLS = [
     "set_evictor_report", "round_evictor_report",
     "jobs_patch", "jobs_append", "jobs_append_stats", "jobs_delete", "jobs_delete_stats",
     "nodes_patch", "nodes_patch_stats", "nodes_delete", "nodes_delete_stats", "nodes_append", "nodes_append_stats",
+    "round_prepare_resident", "round_queued",
 ]
 # entry points the CPU oracle does not implement (it is the single-process checker): the communicator and the collectives that run on it, and the join of a
 # round's result lists into preemption causes (a function of lists the oracle already delivers; tests/test_z_preemption_causes.py restates it)
@@ -275,7 +276,8 @@ OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_d
                     "jobs_delete", "jobs_delete_stats",                 # (likewise: tests/test_z_jobs_delete.py)
                     "nodes_patch", "nodes_patch_stats",                 # (an incremental nodes_upsert, likewise: tests/test_z_nodes_patch.py)
                     "nodes_delete", "nodes_delete_stats",               # (likewise: tests/test_z_nodes_delete.py)
-                    "nodes_append", "nodes_append_stats"}                # (likewise: tests/test_z_nodes_append.py)
+                    "nodes_append", "nodes_append_stats",               # (likewise: tests/test_z_nodes_append.py)
+                    "round_prepare_resident", "round_queued"}           # (the oracle has no resident table and is always given explicit lists: tests/test_z_round_prepare_resident.py)
 PREEMPTION_UNKNOWN, PREEMPTION_UNKNOWN_GANG, PREEMPTION_FAIRSHARE, PREEMPTION_URGENCY, PREEMPTION_OPTIMISER = 1, 2, 3, 4, 5   # ASCHED_PREEMPTION_* (context.PreemptionType)
 # ASCHED_EVR_* bits of asched_evictor_report.node_reasons, in bit order: the reference's reason strings in alphabetical order (makeNodePreemptiblityStats sorts them)
 EVICTOR_REASONS = ("all_jobs_preemptible", "below_protected_fair_share", "invalid_queue", "job_not_preemptible", "node_empty", "node_unschedulable")
@@ -480,6 +482,8 @@ class Library:
         f("nodes_delete_stats", C.c_int32, [C.c_void_p, _i32p])
         f("nodes_append", C.c_int32, [C.c_void_p, C.POINTER(CNodesAppend)])
         f("nodes_append_stats", C.c_int32, [C.c_void_p, _i32p])
+        f("round_prepare_resident", C.c_int32, [C.c_void_p, C.POINTER(CQueues), C.c_int32, _i32p])
+        f("round_queued", C.c_int32, [C.c_void_p, _i32p, _i32p, C.c_int32])
         f("round_preemption_causes", C.c_int32, [C.c_void_p, C.POINTER(CPreemptionCause), C.c_int32, _i32p, C.c_int32, _i32p])
         f("preemption_join", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, C.c_int32, _i32p, _i32p, _i32p, _u8p, C.POINTER(CPreemptionCause), _i32p, C.c_int32, _i32p])
 
@@ -1329,11 +1333,12 @@ class Scheduler:
         return f, dc, uc
 
     # ---------------------------------------------------------------- round level
-    def round_prepare(self, weight, queued: Sequence[Sequence[int]], *, name_rank=None, allocated_by_pc=None, demand=None,
-                      short_job_penalty=None, cordoned=None, pc_resource_limit_fraction=None,
-                      global_tokens=float("inf"), global_burst=2**62, global_rate_inf=True,
-                      queue_tokens=None, queue_burst=None, queue_rate_inf=None,
-                      fairshare_preemption_tokens=None):
+    def _queues_struct(self, weight, *, name_rank=None, allocated_by_pc=None, demand=None,
+                       short_job_penalty=None, cordoned=None, pc_resource_limit_fraction=None,
+                       global_tokens=float("inf"), global_burst=2**62, global_rate_inf=True,
+                       queue_tokens=None, queue_burst=None, queue_rate_inf=None,
+                       fairshare_preemption_tokens=None):
+        """asched_queues without the queued lists -> (struct, the arrays it points into)"""
         q = len(weight)
         npc = len(self.cfg.pc_priority)
         s = CQueues()
@@ -1367,6 +1372,11 @@ class Scheduler:
         if fairshare_preemption_tokens is not None:
             s.has_fairshare_preemption_limiter = 1
             s.fairshare_preemption_tokens = float(fairshare_preemption_tokens)
+        return s, keep
+
+    def round_prepare(self, weight, queued: Sequence[Sequence[int]], **kw):
+        q = len(weight)
+        s, keep = self._queues_struct(weight, **kw)
         off = np.zeros(q + 1, dtype=np.int32)
         parts = [np.asarray(l, dtype=np.int32).reshape(-1) for l in queued]
         for i, l in enumerate(parts):
@@ -1377,6 +1387,27 @@ class Scheduler:
         self._check(self.lib.round_prepare(self.h, C.byref(s)))
         self.num_queues = q
         self._round_keep = keep
+
+    def round_prepare_resident(self, weight, *, held=None, **kw):
+        """round_prepare with the queued lists derived on the device from the resident job order: the list of queue q is every row of queue q that has no run and is
+        not named in `held` (rows left out of this round only; nothing of it is stored), in SchedulingOrderCompare order.  Takes round_prepare's keyword arguments."""
+        fn = self._preemption_fn("round_prepare_resident")
+        s, keep = self._queues_struct(weight, **kw)
+        hd = None if held is None else _arr(held, np.int32).reshape(-1)
+        self._check(fn(self.h, C.byref(s), 0 if hd is None else len(hd), _ptr(hd, C.c_int32)))
+        self.num_queues = len(weight)
+        self._round_keep = keep
+
+    def round_queued(self):
+        """the queued lists the last round_prepare / round_prepare_resident left on the device: one int32 array per queue"""
+        fn = self._preemption_fn("round_queued")
+        off = np.zeros(max(getattr(self, "num_queues", 0), 0) + 1, np.int32)
+        total = fn(self.h, _ptr(off, C.c_int32), None, 0)
+        if total < 0:
+            self._check(total)
+        jobs = np.zeros(max(total, 1), np.int32)
+        self._check(min(fn(self.h, _ptr(off, C.c_int32), _ptr(jobs, C.c_int32), total), 0))
+        return [jobs[off[i]:off[i + 1]].copy() for i in range(len(off) - 1)]
 
     def gang_schedule(self, jobs: Sequence[int]):
         """GangScheduler.Schedule for one gang -> (ok, reason, [PodResult])."""

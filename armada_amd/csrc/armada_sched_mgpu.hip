@@ -648,3 +648,25 @@ extern "C" int asched_internal_na_mask(const NaArgs* a, hipStream_t st) {
   if (work > 0) hipLaunchKernelGGL(k_na_mask, dim3(mgBlocks(work)), dim3(MG_THREADS), 0, st, *a, work);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
+
+// ------------------------------------------------------------------------------------------------ queued lists from the resident order (kernels_queued_lists.h)
+// mark (a thread per four rows: one 32-bit store of four flag bytes) and hold (a thread per held entry); the compaction is plat_compact's kernels
+#define QL_FN __device__ static inline
+#include "kernels_queued_lists.h"
+__global__ __launch_bounds__(MG_THREADS) void k_ql_mark(QlArgs a, int words) {
+  long long w = MG_IDX();
+  if (w < words) qlMarkWord(a, (int)w);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_ql_hold(QlArgs a) {
+  long long i = MG_IDX();
+  if (i < a.nHeld) qlHold(a, (int)i);
+}
+extern "C" int asched_internal_ql_mark(const QlArgs* a, hipStream_t st) {
+  const int words = (a->M + 3) / 4;
+  if (words > 0) hipLaunchKernelGGL(k_ql_mark, dim3(mgBlocks(words)), dim3(MG_THREADS), 0, st, *a, words);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_ql_hold(const QlArgs* a, hipStream_t st) {
+  if (a->nHeld > 0) hipLaunchKernelGGL(k_ql_hold, dim3(mgBlocks(a->nHeld)), dim3(MG_THREADS), 0, st, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}

@@ -34,6 +34,7 @@
 #include "kernels_nodes_patch.h"    // NpArgs and, in the CPU build of the tests, plat_nodes_patch
 #include "kernels_nodes_delete.h"   // NdArgs and, in the CPU build of the tests, plat_nodes_delete
 #include "kernels_nodes_append.h"   // NaArgs and, in the CPU build of the tests, plat_nodes_append
+#include "kernels_queued_lists.h"   // QlArgs and, in the CPU build of the tests, plat_queued_lists
 
 namespace {
 
@@ -279,6 +280,12 @@ struct asched {
   DevBufs naBufs; char* naScratch = nullptr; size_t naScratchBytes = 0;
   int32_t naStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_nodes_append_stats
   double naMs[4] = {0, 0, 0, 0};     // device ms of planes / narrow arrays / index order / mask rows of the last append (ASCHED_NA_TIMES=1)
+  // ---- asched_round_prepare_resident (kernels_queued_lists.h).  The flag bytes, the prefix words, the lists and their offsets belong to the handle: sized from the
+  // capacities of the job table (jobCap rows, ordCap order entries), kept across rounds and only ever grown; the held rows of a call in a block of their own
+  struct { DevBufs bufs; uint8_t* flag = nullptr; uint32_t* prefix = nullptr; int32_t* list = nullptr; int32_t* off = nullptr; size_t rowCap = 0, ordCap = 0;
+           DevBufs heldBufs; int32_t* held = nullptr; size_t heldCap = 0; } ql;
+  double qlMs[3] = {0, 0, 0};        // device ms of mark / hold / compact of the last round_prepare_resident (ASCHED_QL_TIMES=1)
+  bool queuedValid = false; int queuedTotal = 0;   // dev.queuedOff / dev.queuedJobs are what the last round_prepare / round_prepare_resident left (asched_round_queued)
   double roundTotalMs = 0, roundControlMs = 0, roundPhaseMs[4] = {0, 0, 0, 0};   // split round: whole sequence / persistent passes / evict-1, evict-3, final bulk phases (host clock)
   int submitWideUnits = 0, submitWidePasses = 0, submitSeqUnits = 0, submitGangUnits = 0, submitNodePasses = 0, submitLitUnits = 0;   // how the last submit_check ran (submit_stats)
 };
@@ -863,7 +870,7 @@ asched_t* asched_create(const asched_config* c) {
 void asched_destroy(asched_t* h) {
   if (!h) return;
   plat_enter(h->plat);
-  h->nodeBufs.freeAll(); h->jobBufs.freeAll(); h->queueBufs.freeAll(); h->maskBufs.freeAll(); h->fastBufs.freeAll(); h->pjBufs.freeAll(); h->evrBufs.freeAll(); h->exclBufs.freeAll(); h->jpBufs.freeAll(); h->npBufs.freeAll(); h->ndBufs.freeAll(); h->naBufs.freeAll();
+  h->nodeBufs.freeAll(); h->jobBufs.freeAll(); h->queueBufs.freeAll(); h->maskBufs.freeAll(); h->fastBufs.freeAll(); h->pjBufs.freeAll(); h->evrBufs.freeAll(); h->exclBufs.freeAll(); h->jpBufs.freeAll(); h->npBufs.freeAll(); h->ndBufs.freeAll(); h->naBufs.freeAll(); h->ql.bufs.freeAll(); h->ql.heldBufs.freeAll();
   plat_pinned_free(h->resPin); plat_free(h->commStatus); plat_free(h->dev.rs); plat_free(h->dev.cmdIO); plat_free(h->dev.scanResult); plat_free(h->dev.undo);
   plat_close(h->plat);
   delete h;
@@ -3439,9 +3446,43 @@ static int64_t multiplyResource(int64_t res, double m) {  // resource_list.go:31
 }
 
 static void evrSize(asched* h);   // (the evictor report's buffers, below)
-int32_t asched_round_prepare(asched_t* h, const asched_queues* in) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
-  if (h) { h->haveRoundResult = false; h->stateEpoch++; }
-  if (!h->nodesSet || !h->jobsSet) return fail(h, ASCHED_ERR_INVALID, "round_prepare: nodes_upsert and jobs_set first");
+// the queued lists of round_prepare_resident (kernels_queued_lists.h): mark, hold, compact into the handle's own blocks; dev.queuedOff / dev.queuedJobs point at them
+static int deriveQueuedLists(asched* h, int Q, int32_t nHeld, const int32_t* held, int* total) {
+  Dev& d = h->dev;
+  auto& ql = h->ql;
+  const int M = h->M;
+  const int ordTotal = h->ordOffHost.empty() ? 0 : h->ordOffHost[std::min<size_t>((size_t)Q, h->ordOffHost.size() - 1)];   // entries of queues < Q in the pre-sorted order
+  if (!ql.flag || ql.rowCap < (size_t)M || ql.ordCap < (size_t)ordTotal) {
+    const size_t rows = std::max<size_t>(std::max(h->jobCap, (size_t)M), 1), ords = std::max<size_t>(std::max(h->ordCap, (size_t)ordTotal), 1);
+    ql.bufs.freeAll(); ql.rowCap = ql.ordCap = 0;
+    ql.flag = ql.bufs.allocRaw<uint8_t>(4 * ((rows + 3) / 4)); ql.prefix = ql.bufs.allocRaw<uint32_t>(ords); ql.list = ql.bufs.allocRaw<int32_t>(ords);
+    ql.off = ql.bufs.allocRaw<int32_t>(4096 + 2);
+    if (!ql.flag || !ql.prefix || !ql.list || !ql.off) { ql.bufs.freeAll(); ql.flag = nullptr; return fail(h, ASCHED_ERR_DEVICE, plat_last_error()); }
+    ql.rowCap = rows; ql.ordCap = ords;
+  }
+  if (nHeld > 0 && ql.heldCap < (size_t)nHeld) {
+    const size_t cap = std::max<size_t>((size_t)nHeld + (size_t)nHeld / 4, 256);
+    ql.heldBufs.freeAll(); ql.heldCap = 0;
+    ql.held = ql.heldBufs.allocRaw<int32_t>(cap);
+    if (!ql.held) { ql.heldBufs.freeAll(); return fail(h, ASCHED_ERR_DEVICE, plat_last_error()); }
+    ql.heldCap = cap;
+  }
+  if (nHeld > 0) plat_h2d(ql.held, held, sizeof(int32_t) * (size_t)nHeld);
+  QlArgs a; memset(&a, 0, sizeof a);
+  a.M = M; a.Q = Q; a.nHeld = nHeld > 0 ? nHeld : 0; a.jNode0 = d.jNode0; a.jQueue = d.jQueue; a.held = ql.held; a.flag = ql.flag;
+  a.vec = (((uintptr_t)d.jNode0 | (uintptr_t)d.jQueue) & 15) == 0;
+  if (plat_take_failure() || plat_queued_lists(d, a, ordTotal, ql.list, ql.prefix, ql.off, total)) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  d.queuedOff = ql.off; d.queuedJobs = ql.list;
+  plat_queued_lists_ms(h->qlMs);
+  if (const char* e = getenv("ASCHED_QL_TIMES")) if (e[0] == '1')
+    fprintf(stderr, "[asched round_prepare_resident] rows %d order entries %d queues %d held %d queued %d: mark %.4f ms, hold %.4f ms, compact %.4f ms\n",
+            M, ordTotal, Q, a.nHeld, *total, h->qlMs[0], h->qlMs[1], h->qlMs[2]);
+  return 0;
+}
+// everything round_prepare and round_prepare_resident share: the two differ in where dev.queuedOff / dev.queuedJobs come from (the caller's lists, uploaded; or
+// deriveQueuedLists).  The entry points have checked what they refuse.
+static int roundPrepareBody(asched* h, const asched_queues* in, bool resident, int32_t nHeld, const int32_t* held) {
+  h->queuedValid = false;
   h->queueBufs.recycle();
   h->allocPristine = false;   // populateNodeDb binds the running jobs
   HostProf prof("round_prepare");
@@ -3458,6 +3499,21 @@ int32_t asched_round_prepare(asched_t* h, const asched_queues* in) { if (!h) ret
   // single-launch prepare keep them on the host
   static const bool hostAgg = [] { const char* e = getenv("ASCHED_HOST_AGG"); const char* s1 = getenv("ASCHED_SINGLE_LAUNCH"); return (e && e[0] == '1') || (s1 && s1[0] == '1'); }();
   const bool devAgg = !in->allocated_by_pc && !in->demand && !hostAgg;
+  // the queued lists: the caller's, or derived on the device from the resident order — and read back once where the host sums the queued demand below
+  const int32_t *qOffIn = in->queued_off, *qJobsIn = in->queued_jobs;
+  std::vector<int32_t> queuedOff, queuedJobs;
+  int queuedTotal = 0;
+  if (resident) {
+    if (int rc = deriveQueuedLists(h, Q, nHeld, held, &queuedTotal)) return rc;
+    if (!devAgg && !in->demand) {
+      queuedOff.resize((size_t)Q + 1); queuedJobs.resize((size_t)std::max(queuedTotal, 1));
+      plat_d2h(queuedOff.data(), d.queuedOff, sizeof(int32_t) * ((size_t)Q + 1));
+      if (queuedTotal > 0) plat_d2h(queuedJobs.data(), d.queuedJobs, sizeof(int32_t) * (size_t)queuedTotal);
+      if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+      qOffIn = queuedOff.data(); qJobsIn = queuedJobs.data();
+    }
+    prof.lap("queued lists from the resident order");
+  }
   if (in->allocated_by_pc) allocByPc.assign(in->allocated_by_pc, in->allocated_by_pc + (size_t)Q * npc * R);
   else if (!devAgg) for (int j = 0; j < M; j++) if (h->jNode[j] >= 0 && h->jQueue[j] >= 0 && h->jQueue[j] < Q)
     for (int r = 0; r < R; r++) allocByPc[((size_t)h->jQueue[j] * npc + h->jPc[j]) * R + r] += h->jReq[(size_t)j * R + r];
@@ -3480,8 +3536,8 @@ int32_t asched_round_prepare(asched_t* h, const asched_queues* in) { if (!h) ret
     std::vector<int64_t> byPc((size_t)Q * npc * R, 0);
     for (int q = 0; q < Q; q++) {
       if (in->cordoned && in->cordoned[q]) continue;
-      for (int k = in->queued_off[q]; k < in->queued_off[q + 1]; k++) {
-        int j = in->queued_jobs[k];
+      for (int k = qOffIn[q]; k < qOffIn[q + 1]; k++) {
+        int j = qJobsIn[k];
         for (int r = 0; r < R; r++) byPc[((size_t)q * npc + h->jPc[j]) * R + r] += h->jReq[(size_t)j * R + r];
       }
     }
@@ -3500,8 +3556,11 @@ int32_t asched_round_prepare(asched_t* h, const asched_queues* in) { if (!h) ret
     qTokens[q] = in->queue_tokens ? in->queue_tokens[q] : (double)qBurst[q];
     if (in->cordoned) cordoned[q] = in->cordoned[q];
   }
-  std::vector<int32_t> queuedOff(in->queued_off, in->queued_off + Q + 1);
-  std::vector<int32_t> queuedJobs(in->queued_jobs, in->queued_jobs + queuedOff[Q]);
+  if (!resident) {
+    queuedOff.assign(in->queued_off, in->queued_off + Q + 1);
+    queuedJobs.assign(in->queued_jobs, in->queued_jobs + queuedOff[Q]);
+    queuedTotal = queuedOff[Q];
+  }
   d.qWeight = h->queueBufs.upload(weight); d.qNameRank = h->queueBufs.upload(nameRank);
   d.qAllocByPc = h->queueBufs.upload(allocByPc); d.qAlloc = h->queueBufs.upload(alloc); d.qDemand = h->queueBufs.upload(demand);
   d.qPenalty = h->queueBufs.upload(penalty); d.qPcLimit = h->queueBufs.upload(pcLimit);
@@ -3511,7 +3570,8 @@ int32_t asched_round_prepare(asched_t* h, const asched_queues* in) { if (!h) ret
   d.qTokens = h->queueBufs.upload(qTokens); d.qBurst = h->queueBufs.upload(qBurst); d.qRateInf = h->queueBufs.upload(qRateInf);
   d.qCordoned = h->queueBufs.upload(cordoned);
   d.qFair = h->queueBufs.alloc<double>(Q); d.qDc = h->queueBufs.alloc<double>(Q); d.qUc = h->queueBufs.alloc<double>(Q);
-  d.queuedOff = h->queueBufs.upload(queuedOff); d.queuedJobs = h->queueBufs.upload(queuedJobs);
+  if (!resident) { d.queuedOff = h->queueBufs.upload(queuedOff); d.queuedJobs = h->queueBufs.upload(queuedJobs); }   // (resident: deriveQueuedLists has set them)
+  h->queuedTotal = queuedTotal; h->queuedValid = true;
   d.evOff = h->queueBufs.alloc<int32_t>(Q + 2);
   auto QI = [&]() { return h->queueBufs.alloc<int32_t>(Q + 1); };
   auto Q8 = [&]() { return h->queueBufs.alloc<uint8_t>(Q + 1); };
@@ -3595,7 +3655,7 @@ int32_t asched_round_prepare(asched_t* h, const asched_queues* in) { if (!h) ret
   else {
     if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
     const int ordTotalAgg = h->ordOffHost.empty() ? 0 : h->ordOffHost[std::min<size_t>((size_t)Q, h->ordOffHost.size() - 1)];   // jobs of queues < Q in the pre-sorted order
-    if (devAgg && (plat_agg(d, 0, ordTotalAgg) || plat_agg(d, 1, queuedOff[Q]) || plat_small(d, SM_AGG_FIN, 0))) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+    if (devAgg && (plat_agg(d, 0, ordTotalAgg) || plat_agg(d, 1, queuedTotal) || plat_small(d, SM_AGG_FIN, 0))) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
     if (plat_bulk(d, B_INIT_ALLOC, h->N) || plat_bulk(d, B_RESET_JOBS, M) || plat_bulk(d, B_POPULATE, M) || plat_bulk(d, B_KEYS_ALL, h->N) ||
         plat_bulk(d, B_CLEAR_UNFEASIBLE, h->S) || plat_small(d, SM_PREPARE_FIN, 0))
       return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
@@ -3619,6 +3679,38 @@ int32_t asched_round_prepare(asched_t* h, const asched_queues* in) { if (!h) ret
   }
   if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
   return 0;
+}
+int32_t asched_round_prepare(asched_t* h, const asched_queues* in) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
+  if (h) { h->haveRoundResult = false; h->stateEpoch++; }
+  if (!h->nodesSet || !h->jobsSet) return fail(h, ASCHED_ERR_INVALID, "round_prepare: nodes_upsert and jobs_set first");
+  return roundPrepareBody(h, in, false, 0, nullptr);
+}
+// round_prepare with the queued lists derived from the resident job order (NewQueuedJobsIterator over repo.QueuedJobs, jobiteration.go:144-160).  Every refusal is
+// decided here, before anything on the handle changes
+int32_t asched_round_prepare_resident(asched_t* h, const asched_queues* in, int32_t nHeld, const int32_t* held) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
+  if (!in) return fail(h, ASCHED_ERR_INVALID, "round_prepare_resident: no queues");
+  if (in->queued_off || in->queued_jobs) return fail(h, ASCHED_ERR_INVALID, "round_prepare_resident: queued_off and queued_jobs must be NULL (the lists are derived from the resident job order; round_prepare takes explicit ones)");
+  if (!h->nodesSet || !h->jobsSet) return fail(h, ASCHED_ERR_INVALID, "round_prepare_resident: nodes_upsert and jobs_set first");
+  if (in->q < 0) return fail(h, ASCHED_ERR_INVALID, "round_prepare_resident: q < 0");
+  if (in->q > 4096) return fail(h, ASCHED_ERR_UNSUPPORTED, "more than 4096 queues");
+  if (h->mkJobsBuilt) return fail(h, ASCHED_ERR_UNSUPPORTED, "round_prepare_resident: the job set carries the market order (uploaded with bid prices or after asched_set_market), which is another order than the resident one the lists are derived from: give round_prepare the lists in that order");
+  if (nHeld < 0 || (nHeld > 0 && !held)) return fail(h, ASCHED_ERR_INVALID, "round_prepare_resident: n_held < 0, or n_held > 0 without held");
+  for (int32_t i = 0; i < nHeld; i++) if (held[i] < 0 || held[i] >= h->M) {
+    char buf[128]; snprintf(buf, sizeof buf, "round_prepare_resident: held[%d] = %d is outside [0, %d)", i, held[i], h->M);
+    return fail(h, ASCHED_ERR_INVALID, buf);
+  }
+  h->haveRoundResult = false; h->stateEpoch++;
+  return roundPrepareBody(h, in, true, nHeld, held);
+}
+// the queued lists the last prepare (either form) left on the device
+int32_t asched_round_queued(asched_t* h, int32_t* off, int32_t* jobs, int32_t cap) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
+  if (!h->queuedValid) return fail(h, ASCHED_ERR_INVALID, "round_queued: no round_prepare / round_prepare_resident since the handle was created");
+  if (!off) return fail(h, ASCHED_ERR_INVALID, "round_queued: off missing");
+  const int total = h->queuedTotal;
+  plat_d2h(off, h->dev.queuedOff, sizeof(int32_t) * ((size_t)h->Q + 1));
+  if (jobs && cap >= total && total > 0) plat_d2h(jobs, h->dev.queuedJobs, sizeof(int32_t) * (size_t)total);
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  return total;
 }
 
 static int downloadResult(asched* h, asched_round_result* out, const int32_t* io) {

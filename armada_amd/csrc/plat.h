@@ -119,6 +119,12 @@ static void plat_nodes_delete_ms(double* out /*[7]*/);   // measurement hook: de
 struct NaArgs;
 static int plat_nodes_append(Dev& d, NaArgs& a);
 static void plat_nodes_append_ms(double* out /*[4]*/);   // measurement hook: device ms of planes / narrow arrays / index order / mask rows of the last call (events around them when ASCHED_NA_TIMES=1, else zeros)
+// the queued lists of a round from the resident job order (kernels_queued_lists.h): mark (a flag byte per row of a.flag), hold (the rows of a.held cleared), then
+// plat_compact of dev.ordAll[0, ordTotal) by the flags with dev.ordAllOff as segment offsets: list [total], prefix [ordTotal] scratch, off [a.Q + 1], all platform memory.
+// *total is on the host on return.  The CPU build's definition sits in kernels_queued_lists.h.
+struct QlArgs;
+static int plat_queued_lists(Dev& d, const QlArgs& a, int ordTotal, int32_t* list, uint32_t* prefix, int32_t* off, int* total);
+static void plat_queued_lists_ms(double* out /*[3]*/);   // measurement hook: device ms of mark / hold / compact of the last call (events around them when ASCHED_QL_TIMES=1, else zeros)
 static int plat_run_fit_capacity(Dev& d, const std::vector<int32_t>& shapes, std::vector<int32_t>& firstNode, std::vector<long long>& capacity, const int32_t* nodeByRankHost);
 static int plat_run_submit_gangs(Dev& d, const std::vector<int32_t>& off, const std::vector<int32_t>& jobs, std::vector<int32_t>& out);
 static double plat_last_fit_ms();

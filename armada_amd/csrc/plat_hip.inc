@@ -38,6 +38,7 @@ struct PlatCtx {
   hipEvent_t naEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool naTimed = false;   // ASCHED_NA_TIMES=1: around the passes of the node-table append
   hipEvent_t jdEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool jdTimed = false;   // ASCHED_JD_TIMES=1: around the passes of the job-table delete
   hipEvent_t npEv[3] = {nullptr, nullptr, nullptr}; bool npTimed = false;   // ASCHED_NP_TIMES=1: around the passes of the node-table patch
+  hipEvent_t qlEv[4] = {nullptr, nullptr, nullptr, nullptr}; bool qlTimed = false;   // ASCHED_QL_TIMES=1: around the passes that derive the queued lists
   float roundTotalMs = 0.f, roundControlMs = 0.f; int roundLaunches = 0;
   int32_t* cmpScratch = nullptr; size_t cmpScratchInts = 0;   // block counts + total of the grid-wide compaction
   int optIndexN = -1, optIndexM = -1;   // sizes the optimiser's node -> jobs index in the scratch was built for (asched_host.inc decides when it may be reused)
@@ -260,6 +261,7 @@ static void plat_close(PlatCtx* c) {
   for (hipEvent_t e : c->jdEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ndEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->naEv) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->qlEv) if (e) (void)hipEventDestroy(e);
   if (c->helpBox) (void)hipFree(c->helpBox);
   if (c->cmpScratch) (void)hipFree(c->cmpScratch);
   if (c->optScratch) (void)hipFree(c->optScratch);
@@ -1137,6 +1139,37 @@ static int plat_nodes_append(Dev& d, NaArgs& a) {
 static void plat_nodes_append_ms(double* out) {
   hipEvent_t* ev = naEvents();
   for (int k = 0; k < 4; k++) { float ms = 0.f; if (ev && t_ctx->naTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
+}
+// the queued lists of a round from the resident job order (kernels_queued_lists.h; k_ql_mark / k_ql_hold in armada_sched_mgpu.hip, the compaction is plat_compact,
+// which brings the total back to the host).  ASCHED_QL_TIMES=1 puts events around the three passes (tools/probe_round_prepare_resident.py).
+#include "kernels_queued_lists.h"
+extern "C" int asched_internal_ql_mark(const QlArgs* a, hipStream_t s);
+extern "C" int asched_internal_ql_hold(const QlArgs* a, hipStream_t s);
+static hipEvent_t* qlEvents() {
+  static const bool on = [] { const char* e = getenv("ASCHED_QL_TIMES"); return e && e[0] == '1'; }();
+  PlatCtx* c = t_ctx;
+  if (!on) return nullptr;
+  if (!c->qlEv[3]) for (int i = 0; i < 4; i++) if (!c->qlEv[i] && hipEventCreate(&c->qlEv[i]) != hipSuccess) { c->qlEv[i] = nullptr; return nullptr; }
+  return c->qlEv;
+}
+static int plat_queued_lists(Dev& d, const QlArgs& a, int ordTotal, int32_t* list, uint32_t* prefix, int32_t* off, int* total) {
+  PlatCtx* c = t_ctx;
+  hipStream_t st = c->stream;
+  hipEvent_t* ev = qlEvents();
+  c->qlTimed = false;
+  if (ev) (void)hipEventRecord(ev[0], st);
+  if (asched_internal_ql_mark(&a, st)) { c->err = "k_ql_mark launch failed"; return -1; }
+  if (ev) (void)hipEventRecord(ev[1], st);
+  if (asched_internal_ql_hold(&a, st)) { c->err = "k_ql_hold launch failed"; return -1; }
+  if (ev) (void)hipEventRecord(ev[2], st);
+  if (plat_compact(d, d.ordAll, ordTotal, a.flag, list, prefix, d.ordAllOff, a.Q, off, total)) return -1;
+  if (ev) { (void)hipEventRecord(ev[3], st); if (!hipOk(hipEventSynchronize(ev[3]), "queued-list events")) return -1; }
+  c->qlTimed = ev != nullptr;
+  return 0;
+}
+static void plat_queued_lists_ms(double* out) {
+  hipEvent_t* ev = qlEvents();
+  for (int k = 0; k < 3; k++) { float ms = 0.f; if (ev && t_ctx->qlTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
 }
 // a caller-side buffer may be memory of this handle's GPU (a tensor the collective reduces in place: used directly) or host memory (staged)
 static bool plat_is_device_ptr(const void* p) {

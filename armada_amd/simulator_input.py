@@ -375,7 +375,7 @@ def run_cycles_arriving_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[in
     return _run_cycles_arriving(lib, sim, per_cycle, max_cycles, False)
 
 
-def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, every, deleted):
+def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, every, deleted, resident=None):
     from .binding import Scheduler
     wl = sim.workload
     m = wl.num_jobs
@@ -411,7 +411,7 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
             break
         upto = int(np.searchsorted(arrive, cycle, side="right"))
         new = np.arange(have, upto)
-        compact = cycle > 0 and cycle % max(1, int(every)) == 0
+        compact = cycle > 0 and cycle % max(1, int(every)) == 0 and resident != "held"
         if deleted:
             if cycle == 0:                            # the first cycle: jobs_set
                 s.jobs_set(wl.job_req[new], **table_args(new))
@@ -437,10 +437,14 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
             s.jobs_set(wl.job_req[job_of_row], **table_args(job_of_row))
         changed[:] = False
         have = upto
-        queued = [np.array([row_of_job[j] for j in q if j < have and not done[j] and node[j] < 0], dtype=np.int32) for q in wl.queued]
         nq = wl.num_queues
-        s.round_prepare(wl.queue_weight, queued, global_tokens=float(wl.global_burst), global_burst=wl.global_burst, global_rate_inf=wl.rate_inf,
-                        queue_tokens=[float(wl.queue_burst)] * nq, queue_burst=[wl.queue_burst] * nq, queue_rate_inf=[wl.rate_inf] * nq)
+        limits = dict(global_tokens=float(wl.global_burst), global_burst=wl.global_burst, global_rate_inf=wl.rate_inf,
+                      queue_tokens=[float(wl.queue_burst)] * nq, queue_burst=[wl.queue_burst] * nq, queue_rate_inf=[wl.rate_inf] * nq)
+        if resident:                                  # no per-cycle list: the library derives the queued lists; the finished rows still in the table are held
+            s.round_prepare_resident(wl.queue_weight, held=np.nonzero(done[job_of_row])[0].astype(np.int32), **limits)
+        else:
+            queued = [np.array([row_of_job[j] for j in q if j < have and not done[j] and node[j] < 0], dtype=np.int32) for q in wl.queued]
+            s.round_prepare(wl.queue_weight, queued, **limits)
         r = s.schedule_round()
         sched = {int(job_of_row[j]): int(n) for j, n in r.scheduled.items()}              # by job, not by row: rows are renumbered
         pre = {int(job_of_row[j]): int(n) for j, n in r.preempted.items()}
@@ -464,6 +468,14 @@ def run_cycles_compacting(lib, sim: SimulatorInput, per_cycle: Optional[int] = N
     terminal state are deleted on the device (Scheduler.jobs_delete: syncState's delete, scheduler.go:539-549) and the driver's own row <-> job map follows the id map the
     call returns.  Records as run_cycles_arriving, with "scheduled" / "preempted" keyed by JOB (the workload's row) and "rows" the table's row count."""
     return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, every, True)
+
+
+def run_cycles_resident(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000, hold_finished: bool = False):
+    """run_cycles_compacting with NO per-cycle queued list: the table is kept by jobs_append, jobs_patch and jobs_delete and every round is prepared with
+    Scheduler.round_prepare_resident, which derives the queued lists from the resident order on the device (NewQueuedJobsIterator over repo.QueuedJobs,
+    jobiteration.go:144-160).  The finished rows are deleted every cycle (the one row jobs_delete has to leave in a table of finished rows only is held); with
+    hold_finished they stay in the table and are named in `held` every cycle instead, which costs O(finished rows) per cycle.  Records as run_cycles_compacting."""
+    return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, 1, True, resident="held" if hold_finished else "delete")
 
 
 def run_cycles_compacting_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000, every: int = 1):

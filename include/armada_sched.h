@@ -742,6 +742,21 @@ int32_t ASCHED_FN(market_multi_iterate)(asched_t*, int32_t n1, const asched_mark
 /* Builds round state: ConstructNodeDb/populateNodeDb (bind every running job, scheduling_algo.go:738-781,
    1019-1098) + constructSchedulingContext + UpdateFairShares (:783-867).  Untimed "input build". */
 int32_t ASCHED_FN(round_prepare)(asched_t*, const asched_queues* queues);
+/* round_prepare with the queued lists derived on the device from the resident job order — what NewQueuedJobsIterator does when it reads
+   repo.QueuedJobs(queue, pool, sortOrder), a view of the resident jobDb and not a list handed in per cycle (scheduling/jobiteration.go:144-160; the host-side walk it
+   replaces is queuedJobs of integration/gpu_round.go Schedule).  queues->queued_off and queues->queued_jobs must be NULL; every other field means what it means to
+   round_prepare.  The list of queue q < queues->q is every row with queue == q that has no run and is not named in `held`, in the resident order (per queue the
+   SchedulingOrderCompare order jobs_set built and jobs_patch / jobs_append / jobs_delete keep exact); rows of queues >= queues->q take no part.  `held` is per call and
+   nothing of it is stored: it carries what the reference's per-pool queued view leaves out (a queued job whose pools exclude this pool, a row the host keeps but does
+   not want scheduled this cycle).  Duplicates are allowed; a held row that has a run has no effect.  Costs O(n_held) per call on top of one pass over the job table.
+   Refused before anything on the handle changes — ASCHED_ERR_INVALID: non-NULL queued_off or queued_jobs, n_held < 0, n_held > 0 without held, a held id outside
+   [0, M), nodes or jobs not set; ASCHED_ERR_UNSUPPORTED: more than 4096 queues, a job set that carries the market order (uploaded with bid prices or after
+   asched_set_market — the market order is another order than the resident one: give round_prepare the lists in that order). */
+int32_t ASCHED_FN(round_prepare_resident)(asched_t*, const asched_queues* queues,
+                                          int32_t n_held, const int32_t* held /*[n_held] rows left out of this round's queued lists, or NULL*/);
+/* The queued lists the last round_prepare or round_prepare_resident left on the device, i.e. what the round walks (the jobs NewQueuedJobsIterator yields per queue,
+   jobiteration.go:162-176).  Writes off[0..Q]; writes jobs[0..total) only if cap >= total.  Returns the total length, or ASCHED_ERR_INVALID before any prepare. */
+int32_t ASCHED_FN(round_queued)(asched_t*, int32_t* off /*[Q+1]*/, int32_t* jobs /*[cap]*/, int32_t cap);
 /* PreemptingQueueScheduler.Schedule (preempting_queue_scheduler.go:86-289) — what the metric times.
    Result buffers are owned by the handle until the next round_prepare/destroy. */
 int32_t ASCHED_FN(schedule_round)(asched_t*, asched_round_result* out);

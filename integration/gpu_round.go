@@ -1105,6 +1105,24 @@ func (g *GpuRound) uploadLabelValueInts() error {
 func (g *GpuRound) Schedule(ctx *armadacontext.Context, sctx *schedulercontext.SchedulingContext, cordoned map[string]bool,
 	perQueuePcLimitFraction map[string]map[string]map[string]float64, queuedJobs map[string][]int32,
 ) (*SchedulingResult, error) {
+	return g.schedule(ctx, sctx, cordoned, perQueuePcLimitFraction, queuedJobs, nil, false)
+}
+
+// ScheduleResident == Schedule without the per-cycle walk of the jobDb: the queued lists are derived by the library from the resident job table (UploadJobs once,
+// then AppendJobs / PatchJobs / DeleteJobs), the way NewQueuedJobsIterator reads repo.QueuedJobs(queue, pool, sortOrder) — a view of the jobDb, not a list built per
+// cycle (jobiteration.go:144-160).  held: the rows of the table that have no run and are NOT in this pool's queued view this cycle (a queued job whose pools exclude
+// the pool, a job in a terminal state that DeleteJobs has not removed yet); nothing of it is stored.  Not for a market-driven pool (the library refuses: its queued
+// jobs come in jobdb.PriceOrder, Schedule takes them).  The queue indices of the table are those of the sorted queue names of sctx, as for Schedule.
+func (g *GpuRound) ScheduleResident(ctx *armadacontext.Context, sctx *schedulercontext.SchedulingContext, cordoned map[string]bool,
+	perQueuePcLimitFraction map[string]map[string]map[string]float64, held []int32,
+) (*SchedulingResult, error) {
+	return g.schedule(ctx, sctx, cordoned, perQueuePcLimitFraction, nil, held, true)
+}
+
+// what Schedule and ScheduleResident share: everything but where the queued lists come from
+func (g *GpuRound) schedule(ctx *armadacontext.Context, sctx *schedulercontext.SchedulingContext, cordoned map[string]bool,
+	perQueuePcLimitFraction map[string]map[string]map[string]float64, queuedJobs map[string][]int32, held []int32, resident bool,
+) (*SchedulingResult, error) {
 	names := make([]string, 0, len(sctx.QueueSchedulingContexts))
 	for name := range sctx.QueueSchedulingContexts {
 		names = append(names, name)
@@ -1144,8 +1162,10 @@ func (g *GpuRound) Schedule(ctx *armadacontext.Context, sctx *schedulercontext.S
 				}
 			}
 		}
-		flat = append(flat, queuedJobs[name]...)
-		off[q+1] = int32(len(flat))
+		if !resident {
+			flat = append(flat, queuedJobs[name]...)
+			off[q+1] = int32(len(flat))
+		}
 	}
 	var pins runtime.Pinner
 	defer pins.Unpin()
@@ -1158,12 +1178,16 @@ func (g *GpuRound) Schedule(ctx *armadacontext.Context, sctx *schedulercontext.S
 		in.name_rank, in.weight = i32p(nameRank), f64p(weight)
 		in.short_job_penalty, in.cordoned, in.pc_resource_limit_fraction = i64p(penalty), u8p(cord), f64p(limits)
 		in.queue_tokens, in.queue_burst, in.queue_rate_inf = f64p(qTokens), i64p(qBurst), u8p(qInf)
-		in.queued_off = i32p(off)
+		if !resident {
+			in.queued_off = i32p(off)
+		}
 	}
 	if len(flat) > 0 {
 		pins.Pin(&flat[0])
 	}
-	in.queued_jobs = i32p(flat)
+	if !resident {
+		in.queued_jobs = i32p(flat)
+	}
 	in.global_tokens = C.double(sctx.Limiter.TokensAt(sctx.Started))
 	in.global_burst = C.int64_t(sctx.Limiter.Burst())
 	if math.IsInf(float64(sctx.Limiter.Limit()), 1) {
@@ -1183,7 +1207,14 @@ func (g *GpuRound) Schedule(ctx *armadacontext.Context, sctx *schedulercontext.S
 			return nil, err
 		}
 	}
-	if err := g.check(C.asched_round_prepare(g.h, &in)); err != nil {
+	if resident { // queued_off / queued_jobs stay NULL: asched_round_prepare_resident derives them on the device
+		if len(held) > 0 {
+			pins.Pin(&held[0])
+		}
+		if err := g.check(C.asched_round_prepare_resident(g.h, &in, C.int32_t(len(held)), i32p(held))); err != nil {
+			return nil, err
+		}
+	} else if err := g.check(C.asched_round_prepare(g.h, &in)); err != nil {
 		return nil, err
 	}
 	// hard timeout + cancellation: the library polls a host-mapped word from inside the round kernel
