@@ -264,6 +264,7 @@ ALL_SYMBOLS = [
     "round_preemption_causes", "preemption_join",
     "set_evictor_report", "round_evictor_report",
     "jobs_patch", "jobs_append", "jobs_append_stats", "jobs_delete", "jobs_delete_stats",
+    "set_append_in_place", "jobs_append_shape_stats",
     "nodes_patch", "nodes_patch_stats", "nodes_delete", "nodes_delete_stats", "nodes_append", "nodes_append_stats",
     "round_prepare_resident", "round_queued",
 ]
@@ -274,6 +275,7 @@ OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_d
                     "set_evictor_report", "round_evictor_report",   # (recorded by passes between the launches of the split round: tests/test_z_evictor_report.py restates it)
                     "jobs_patch", "jobs_append", "jobs_append_stats",   # (an incremental jobs_set: the oracle is given the whole table; tests/test_z_jobs_patch.py, test_z_jobs_append.py)
                     "jobs_delete", "jobs_delete_stats",                 # (likewise: tests/test_z_jobs_delete.py)
+                    "set_append_in_place", "jobs_append_shape_stats",   # (how jobs_append treats new shapes, not what it leaves: tests/test_z_jobs_append_shapes.py)
                     "nodes_patch", "nodes_patch_stats",                 # (an incremental nodes_upsert, likewise: tests/test_z_nodes_patch.py)
                     "nodes_delete", "nodes_delete_stats",               # (likewise: tests/test_z_nodes_delete.py)
                     "nodes_append", "nodes_append_stats",               # (likewise: tests/test_z_nodes_append.py)
@@ -474,6 +476,8 @@ class Library:
         f("jobs_patch", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _i64p])
         f("jobs_append", C.c_int32, [C.c_void_p, C.POINTER(CJobs)])
         f("jobs_append_stats", C.c_int32, [C.c_void_p, _i32p])
+        f("set_append_in_place", C.c_int32, [C.c_void_p, C.c_int32])
+        f("jobs_append_shape_stats", C.c_int32, [C.c_void_p, _i32p])
         f("jobs_delete", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p])
         f("jobs_delete_stats", C.c_int32, [C.c_void_p, _i32p])
         f("nodes_patch", C.c_int32, [C.c_void_p, C.POINTER(CNodesPatch)])
@@ -787,11 +791,26 @@ class Scheduler:
         self.num_jobs += m
 
     def jobs_append_stats(self):
-        """how the last jobs_append ran: rows, rows that entered the order, new shapes, new gangs, re-allocated, masks and fast structure rebuilt, capacity"""
+        """how the last jobs_append ran: rows, rows that entered the order, new shapes, new gangs, re-allocated, masks and fast structure rebuilt, capacity, shapes
+        served in place (set_append_in_place)"""
         fn = self._preemption_fn("jobs_append_stats")
         out = np.zeros(8, np.int32)
         self._check(fn(self.h, _ptr(out, C.c_int32)))
-        return dict(rows=int(out[0]), in_order=int(out[1]), new_shapes=int(out[2]), new_gangs=int(out[3]), reallocated=int(out[4]), rebuilt=int(out[5]), capacity=int(out[6]))
+        return dict(rows=int(out[0]), in_order=int(out[1]), new_shapes=int(out[2]), new_gangs=int(out[3]), reallocated=int(out[4]), rebuilt=int(out[5]), capacity=int(out[6]),
+                    in_place=int(out[7]))
+
+    def set_append_in_place(self, on: bool = True) -> None:
+        """jobs_append serves new (and revived) scheduling-key shapes by growing the shape-dependent tables instead of rebuilding them, where it can (same result either
+        way; jobs_append_shape_stats says which).  A property of the handle: off by default, survives jobs_set and nodes_upsert."""
+        self._check(self._preemption_fn("set_append_in_place")(self.h, 1 if on else 0))
+
+    def jobs_append_shape_stats(self):
+        """how the last jobs_append treated new shapes; reason: why the rebuild was taken although the switch is on (0 not taken, 1 no node table / masks, 2 key layout
+        differs, 3 first away rows, 4 fit shapes > SMAX, 5 negative request, 6 empty table)"""
+        fn = self._preemption_fn("jobs_append_shape_stats")
+        out = np.zeros(8, np.int32)
+        self._check(fn(self.h, _ptr(out, C.c_int32)))
+        return dict(on=int(out[0]), added=int(out[1]), revived=int(out[2]), mask_rows=int(out[3]), derived_classes=int(out[4]), fit_shapes=int(out[5]), reason=int(out[6]))
 
     def jobs_delete(self, rows, want_map=False):
         """syncState's delete of the jobs in a terminal state: rows `rows` leave the resident job table; the others keep their order and are renumbered densely (new id =

@@ -470,6 +470,31 @@ extern "C" int asched_internal_ja_fill(const Dev* d, const JaArgs* a, hipStream_
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ------------------------------------------------------------------------------------------------ new scheduling-key shapes join the shape mask (kernels_shapes_append.h)
+// one wave per 64-node output word, the workgroup's four waves take four consecutive words.  w is wave-uniform, so every lane of a wave takes the same branches and
+// the ballot sees all 64 lanes; a lane's totals are loaded once and the new rows are looped inside
+#define SA_FN __device__ static inline
+#include "kernels_shapes_append.h"
+__global__ __launch_bounds__(MG_THREADS) void k_sa_mask(SaArgs a) {
+  const long long t = MG_IDX();
+  const int w = (int)(t >> 6), lane = (int)(threadIdx.x & 63);
+  if (w >= a.W) return;
+  const int n = 64 * w + lane;
+  const bool live = n < a.N;
+  int64_t tot[MAXR];
+  if (live) saLoad(a, n, tot);
+  for (int row = 0; row < a.rows; row++) {
+    const uint64_t cw = a.classMask[(size_t)a.rowClass[row] * a.W + w];
+    const bool b = live && saBit(a, row, cw, lane, tot);
+    const unsigned long long word = __ballot(b);
+    if (lane == 0) a.outMask[(size_t)a.rowOut[row] * a.W + w] = word;
+  }
+}
+extern "C" int asched_internal_sa_mask(const SaArgs* a, hipStream_t st) {
+  if (a->rows > 0 && a->W > 0) hipLaunchKernelGGL(k_sa_mask, dim3(mgBlocks((long long)a->W * 64)), dim3(MG_THREADS), 0, st, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ------------------------------------------------------------------------------------------------ rows leave the resident job table (kernels_jobs_delete.h)
 // mark / unmark, the three gathers (each reads the survivors' list once), the renumbering of a compacted list; the scans are plat_compact's kernels
 #define JD_FN __device__ static inline

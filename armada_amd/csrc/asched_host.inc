@@ -30,6 +30,7 @@
 #include "kernels_evict_report.h"   // EvrArgs and, in the CPU build of the tests, plat_evict_report
 #include "kernels_jobs_patch.h"     // JpArgs and, in the CPU build of the tests, plat_jobs_patch
 #include "kernels_jobs_append.h"    // JaArgs and, in the CPU build of the tests, plat_jobs_append
+#include "kernels_shapes_append.h"  // SaArgs and, in the CPU build of the tests, plat_shapes_append
 #include "kernels_jobs_delete.h"    // JdArgs and, in the CPU build of the tests, plat_jobs_delete
 #include "kernels_nodes_patch.h"    // NpArgs and, in the CPU build of the tests, plat_nodes_patch
 #include "kernels_nodes_delete.h"   // NdArgs and, in the CPU build of the tests, plat_nodes_delete
@@ -250,6 +251,15 @@ struct asched {
   std::vector<int32_t> shapeRow;     // [S] first row of each scheduling-key shape (a new row's JobRec is copied from it on the device)
   std::vector<int32_t> shapeTable; std::vector<uint64_t> shapeHash;   // open-addressing table over the shapes, built by the first append of a job table
   int32_t jaStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_append_stats
+  // ---- the in-place path of asched_jobs_append for new shapes (asched_set_append_in_place; kernels_shapes_append.h).  What buildFast derives per scheduling-key shape
+  // stays on the handle (host only), so that an append can extend it: key delta / smallest key fields / "fits nowhere" per shape, the fit-shape ids in order of first
+  // occurrence with their table, and the two minima before they are packed (INT64_MAX: no shape yet)
+  bool appendInPlace = false;        // the switch: a property of the handle, survives jobs_set and nodes_upsert
+  int32_t jasStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_append_shape_stats
+  double saMs[2] = {0, 0};           // device ms of the new mask rows / the row copies of the last in-place append (ASCHED_JA_TIMES=1)
+  std::vector<uint64_t> fsDelta, fsMin; std::vector<uint8_t> fsNever; std::vector<int32_t> fitOf; std::vector<ShapeReq> fitTab;
+  std::map<std::tuple<uint64_t, uint64_t, int64_t, int64_t, int32_t, int32_t>, int32_t> fitIds;
+  int64_t fsMinField[MAXK] = {0}, fsMinExtra[MAXE] = {0};
   double jaMs[3] = {0, 0, 0};        // device ms of row fill / sort / merge of the last append (ASCHED_JA_TIMES=1)
   DevBufs jpBufs; char* jpScratch = nullptr; size_t jpScratchBytes = 0;   // the entries, the sort array and the kept list of a patch: one block, kept between calls and only ever grown
   double jpMs[4] = {0, 0, 0, 0};     // device ms of the four passes of the last patch (ASCHED_JP_TIMES=1)
@@ -383,6 +393,7 @@ bool classMatchesType(asched* h, int cls, const HType& t) {
 
 int buildFast(asched* h, const std::vector<uint64_t>& classMask);
 int bitsFor(uint64_t range);
+int buildRowTables(asched* h, const std::vector<int32_t>& shapeClassExt, std::vector<int32_t>& rowTypeOff, std::vector<int32_t>& rowTypes);
 
 // ---- NumExcludedNodesByReason (asched_excluded_nodes).  The device records what depends on the round's state (dev.h ExclDev); the reasons that are functions of the inputs
 // alone are worked out here, when asked: the checks of classMatchesType / classMatchesNode above, returning WHAT failed (nodematching.go:199-267).  Where the reference is
@@ -533,13 +544,11 @@ int layoutKeys(asched* h) {
   return 0;
 }
 
-// (re)build the per-shape node masks once both nodes and jobs are known
-int rebuildMasks(asched* h) {
-  if (!h->nodesSet || !h->jobsSet) return 0;
-  h->maskBufs.freeAll();
-  h->dClassMask = nullptr; h->dShapeClass = nullptr;
-  Dev& d = h->dev;
-  int W = d.cfg.W;
+// the per-row tables of the shape mask's rows (the S shape rows, then the away rows; shapeClassExt: the class of each): which rows take the literal iterator restatement
+// (h->rowLiteral) and the populated node types each row's class matches.  rebuildMasks, and the in-place path of asched_jobs_append over the grown shape table: an old
+// row's entries depend on its class, its shape and the node table only, so they come out as they were.
+int buildRowTables(asched* h, const std::vector<int32_t>& shapeClassExt, std::vector<int32_t>& rowTypeOff, std::vector<int32_t>& rowTypes) {
+  const int Sext = h->S + (int)h->awayRowClass.size();
   // Exactness of the packed-key argmin: (A) the request is a multiple of the index resolution on every indexed column (else the
   // skip-scan can jump over fitting nodes), (B) a requirement class that matches more than one populated node type needs
   // resolution-aligned allocatable and id order == index order (else the heap merge is not the key order; SURVEY hard part 2).
@@ -550,6 +559,31 @@ int rebuildMasks(asched* h) {
     for (size_t t = 0; t < h->types.size(); t++) if (h->types[t].numNodes > 0 && classMatchesType(h, c, h->types[t])) clsTypes[c].push_back((int32_t)t);
     if (clsTypes[c].size() > 1 && !(h->allocAligned && h->idRankMonotone)) clsLiteral[c] = 1;
   }
+  h->rowLiteral.assign(std::max(Sext, 1), 0);
+  rowTypeOff.assign(Sext + 1, 0); rowTypes.clear();
+  for (int row = 0; row < Sext; row++) {
+    int shape = row < h->S ? row : h->awayRowShape[row - h->S];
+    int cls = shapeClassExt[row];
+    rowTypeOff[row] = (int32_t)rowTypes.size();
+    rowTypes.insert(rowTypes.end(), clsTypes[cls].begin(), clsTypes[cls].end());
+    h->rowLiteral[row] = h->shapeUnaligned[shape] || clsLiteral[cls];
+#ifdef ASCHED_HOSTSIM
+    if (getenv("HOSTSIM_NO_LITERAL")) h->rowLiteral[row] = 0;  // negative control for the tests: the packed-key argmin is NOT exact for these rows
+#endif
+    if (h->rowLiteral[row] && clsTypes[cls].size() > LIT_TMAX)
+      return fail(h, ASCHED_ERR_UNSUPPORTED, "a requirement class on the literal iteration path matches more than LIT_TMAX node types");
+  }
+  rowTypeOff[Sext] = (int32_t)rowTypes.size();
+  return 0;
+}
+
+// (re)build the per-shape node masks once both nodes and jobs are known
+int rebuildMasks(asched* h) {
+  if (!h->nodesSet || !h->jobsSet) return 0;
+  h->maskBufs.freeAll();
+  h->dClassMask = nullptr; h->dShapeClass = nullptr;
+  Dev& d = h->dev;
+  int W = d.cfg.W;
   std::vector<uint64_t> classMask((size_t)h->Cext * W, 0);
   for (int c = 0; c < h->Cext; c++)
     for (int n = 0; n < h->N; n++)
@@ -567,21 +601,8 @@ int rebuildMasks(asched* h) {
   d.shapeReq = h->maskBufs.upload(shapeReqExt);
   d.awayRowOff = h->maskBufs.upload(h->awayRowOff);
   {
-    h->rowLiteral.assign(std::max(Sext, 1), 0);
-    std::vector<int32_t> rowTypeOff(Sext + 1, 0), rowTypes;
-    for (int row = 0; row < Sext; row++) {
-      int shape = row < h->S ? row : h->awayRowShape[row - h->S];
-      int cls = shapeClassExt[row];
-      rowTypeOff[row] = (int32_t)rowTypes.size();
-      rowTypes.insert(rowTypes.end(), clsTypes[cls].begin(), clsTypes[cls].end());
-      h->rowLiteral[row] = h->shapeUnaligned[shape] || clsLiteral[cls];
-#ifdef ASCHED_HOSTSIM
-      if (getenv("HOSTSIM_NO_LITERAL")) h->rowLiteral[row] = 0;  // negative control for the tests: the packed-key argmin is NOT exact for these rows
-#endif
-      if (h->rowLiteral[row] && clsTypes[cls].size() > LIT_TMAX)
-        return fail(h, ASCHED_ERR_UNSUPPORTED, "a requirement class on the literal iteration path matches more than LIT_TMAX node types");
-    }
-    rowTypeOff[Sext] = (int32_t)rowTypes.size();
+    std::vector<int32_t> rowTypeOff, rowTypes;
+    if (int rc = buildRowTables(h, shapeClassExt, rowTypeOff, rowTypes)) return rc;
     std::vector<uint64_t> typeMask(std::max<size_t>(h->types.size(), 1) * W, 0);
     for (int n = 0; n < h->N; n++) typeMask[(size_t)h->nodeType[n] * W + (n >> 6)] |= 1ull << (n & 63);
     d.rowLiteral = h->maskBufs.upload(h->rowLiteral);
@@ -609,6 +630,60 @@ int rebuildMasks(asched* h) {
   { Dev dm = d; dm.cfg.S = Sext; rc = plat_run_shape_mask(dm, dClassMask, dShapeClass); }  // all rows, away rows included
   if (rc) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
   return buildFast(h, classMask);
+}
+
+// What the fast structure holds per scheduling-key shape `s` (the next one: s == h->fsDelta.size()), from the handle's key layout, f.E / f.extraCol and h->rowLiteral:
+// the key delta of a bind, the smallest key fields the shape fits on, "fits nowhere" (a quotient the field cannot hold), its fit shape — scheduling-key shapes that
+// agree in everything a fit at priority -2 looks at (key fields, extras, requirement class, "never") share one, and ids are given in order of first occurrence, so a
+// shape added later never renumbers an earlier one — and its part in the two minima.  buildFast over all shapes; asched_jobs_append's in-place path for the new ones.
+static void fastShapeAdd(asched* h, int s) {
+  Dev& d = h->dev; FastCfg& f = d.f;
+  const int R = h->R, K = h->K;
+  const bool twoWords = d.cfg.keyWords == 2;
+  uint64_t delta = 0, mn = 0; uint8_t never = 0;
+  if (!twoWords) {
+    for (int c = 0; c < K; c++) {
+      int64_t q = h->shapeReq[(size_t)s * R + h->indexedCol[c]] / d.cfg.indexedRes[c];   // (the key's divisor: the index resolution, or layoutKeys' coarser one)
+      int64_t fm = q - d.cfg.keyLo[c];
+      int w = d.cfg.keyWidth[c];
+      if (w < 63 && (fm >= ((int64_t)1 << w) || q >= ((int64_t)1 << w))) { never = 1; continue; }
+      delta |= (uint64_t)q << d.cfg.keyShift[c];
+      mn |= (uint64_t)fm << d.cfg.keyShift[c];
+    }
+    if (!never) {
+      for (int c = 0; c < K; c++) h->fsMinField[c] = std::min(h->fsMinField[c], h->shapeReq[(size_t)s * R + h->indexedCol[c]] / d.cfg.indexedRes[c] - d.cfg.keyLo[c]);
+      for (int e = 0; e < f.E; e++) h->fsMinExtra[e] = std::min(h->fsMinExtra[e], h->shapeReq[(size_t)s * R + f.extraCol[e]]);
+    }
+  }
+  h->fsDelta.push_back(delta); h->fsMin.push_back(mn); h->fsNever.push_back(never);
+  ShapeReq q; q.fieldMin = mn; q.ex0 = f.E > 0 ? h->shapeReq[(size_t)s * R + f.extraCol[0]] : 0; q.ex1 = f.E > 1 ? h->shapeReq[(size_t)s * R + f.extraCol[1]] : 0;
+  q.cls = h->shapeClass[s]; q.never = (never || h->rowLiteral[s]) ? 1 : 0;
+  auto key = std::make_tuple(q.fieldMin, delta, q.ex0, q.ex1, q.cls, q.never);   // (the key delta is what a bind subtracts: same key fields => same delta)
+  auto it = h->fitIds.find(key);
+  if (it == h->fitIds.end()) { it = h->fitIds.emplace(key, (int32_t)h->fitTab.size()).first; h->fitTab.push_back(q); }
+  h->fitOf.push_back(it->second);
+  f.F = (int)h->fitTab.size();
+}
+// f.minFieldMin / f.minExtra from the handle's running minima
+static void fastMinimaPack(asched* h) {
+  Dev& d = h->dev; FastCfg& f = d.f;
+  f.minFieldMin = 0;
+  for (int c = 0; c < h->K && d.cfg.keyWords != 2; c++) if (h->fsMinField[c] != INT64_MAX) f.minFieldMin |= (uint64_t)h->fsMinField[c] << d.cfg.keyShift[c];
+  for (int e = 0; e < MAXE; e++) f.minExtra[e] = h->fsMinExtra[e] == INT64_MAX ? 0 : h->fsMinExtra[e];
+}
+// the JobRec of a row of scheduling-key shape s (buildFast's fill of every row; one template per shape in asched_jobs_append's in-place path)
+static void fastRecFill(asched* h, JobRec& r, int s, const int64_t* req, int32_t pc, int32_t gang, int32_t node0, int32_t runPrio) {
+  const FastCfg& f = h->dev.f;
+  memset(&r, 0, sizeof r);
+  for (int x = 0; x < h->R; x++) r.req[x] = req[x];
+  // literal rows: the generic path decides.  bit 1: some indexed request is not a multiple of its resolution — keyDelta (its quotients) is then NOT what a
+  // bind takes off a node's key fields, so no fast path may bind / unbind such a job by key arithmetic (the evicted job returning to its node included)
+  r.keyDelta = h->fsDelta[s]; r.fieldMin = h->fsMin[s]; r.never = ((h->fsNever[s] || h->rowLiteral[s]) ? 1 : 0) | (h->shapeUnaligned[s] ? 2 : 0);
+  r.pc = pc; r.shape = h->fitOf[s]; r.gang = gang; r.node0 = node0; r.runPrio = runPrio; r.cls = h->shapeClass[s];
+  r.pcPrio = h->pcPriority[r.pc]; r.preemptible = h->pcPreemptible[r.pc] ? 1 : 0;
+  auto levels = [&](int32_t cutoff) { int nl = 0; while (nl < h->P && h->prios[nl] <= cutoff) nl++; return (uint8_t)nl; };
+  r.nlPc = levels(r.preemptible ? r.pcPrio : INT32_MAX); r.nlRun = levels(r.preemptible ? r.runPrio : INT32_MAX);
+  r.ex0 = f.E > 0 ? r.req[f.extraCol[0]] : 0; r.ex1 = f.E > 1 ? r.req[f.extraCol[1]] : 0;
 }
 
 // Fast path tables (round_fast.h): exactness conditions, per-shape packed key deltas, JobRec array, node class bits, base buffers.
@@ -647,37 +722,13 @@ int buildFast(asched* h, const std::vector<uint64_t>& classMask) {
     f.fieldMask[c] = (w >= 64 ? ~0ull : ((1ull << w) - 1)) << d.cfg.keyShift[c];
     if (d.cfg.keyGuard) f.guardMask |= 1ull << (d.cfg.keyShift[c] + w);
   }
-  // per shape: key delta of a bind and the smallest key fields it fits on
-  std::vector<uint64_t> sDelta(S, 0), sMin(S, 0); std::vector<uint8_t> sNever(S, 0);
-  std::vector<int64_t> minField(K, INT64_MAX);
-  for (int e = 0; e < MAXE; e++) f.minExtra[e] = INT64_MAX;
-  for (int s = 0; s < S && !twoWords; s++) {
-    for (int c = 0; c < K; c++) {
-      int64_t q = h->shapeReq[(size_t)s * R + h->indexedCol[c]] / d.cfg.indexedRes[c];   // (the key's divisor: the index resolution, or layoutKeys' coarser one)
-      int64_t fm = q - d.cfg.keyLo[c];
-      int w = d.cfg.keyWidth[c];
-      if (w < 63 && (fm >= ((int64_t)1 << w) || q >= ((int64_t)1 << w))) { sNever[s] = 1; continue; }
-      sDelta[s] |= (uint64_t)q << d.cfg.keyShift[c];
-      sMin[s] |= (uint64_t)fm << d.cfg.keyShift[c];
-    }
-    if (sNever[s]) continue;
-    for (int c = 0; c < K; c++) minField[c] = std::min(minField[c], h->shapeReq[(size_t)s * R + h->indexedCol[c]] / d.cfg.indexedRes[c] - d.cfg.keyLo[c]);
-    for (int e = 0; e < f.E; e++) f.minExtra[e] = std::min(f.minExtra[e], h->shapeReq[(size_t)s * R + f.extraCol[e]]);
-  }
-  for (int c = 0; c < K && !twoWords; c++) if (minField[c] != INT64_MAX) f.minFieldMin |= (uint64_t)minField[c] << d.cfg.keyShift[c];
-  for (int e = 0; e < MAXE; e++) if (f.minExtra[e] == INT64_MAX) f.minExtra[e] = 0;
-  // fit shapes: scheduling-key shapes that agree in everything a fit at priority -2 looks at (key fields, extras, requirement class, "never")
-  std::vector<int32_t> fitOf(S, 0); std::vector<ShapeReq> fitTab;
-  { std::map<std::tuple<uint64_t, uint64_t, int64_t, int64_t, int32_t, int32_t>, int32_t> ids;
-    for (int s = 0; s < S; s++) {
-      ShapeReq q; q.fieldMin = sMin[s]; q.ex0 = f.E > 0 ? h->shapeReq[(size_t)s * R + f.extraCol[0]] : 0; q.ex1 = f.E > 1 ? h->shapeReq[(size_t)s * R + f.extraCol[1]] : 0;
-      q.cls = h->shapeClass[s]; q.never = (sNever[s] || h->rowLiteral[s]) ? 1 : 0;
-      auto key = std::make_tuple(q.fieldMin, sDelta[s], q.ex0, q.ex1, q.cls, q.never);   // (the key delta is what a bind subtracts: same key fields => same delta)
-      auto it = ids.find(key);
-      if (it == ids.end()) { it = ids.emplace(key, (int32_t)fitTab.size()).first; fitTab.push_back(q); }
-      fitOf[s] = it->second;
-    }
-    f.F = (int)fitTab.size(); }
+  // per shape: key delta of a bind and the smallest key fields it fits on; fit shapes: scheduling-key shapes that agree in everything a fit at priority -2 looks
+  // at (fastShapeAdd).  Kept on the handle: the in-place path of asched_jobs_append goes on from here
+  h->fsDelta.clear(); h->fsMin.clear(); h->fsNever.clear(); h->fitOf.clear(); h->fitTab.clear(); h->fitIds.clear();
+  for (int c = 0; c < MAXK; c++) h->fsMinField[c] = INT64_MAX;
+  for (int e = 0; e < MAXE; e++) h->fsMinExtra[e] = INT64_MAX;
+  for (int s = 0; s < S; s++) fastShapeAdd(h, s);
+  fastMinimaPack(h);
   if (f.F > SMAX) ok = false;   // more fit shapes than candidate slots: the generic scan serves the round
   if (!ok) return 0;
   static_assert(sizeof(JobRec) == 128, "JobRec is one 128-byte burst");
@@ -686,27 +737,14 @@ int buildFast(asched* h, const std::vector<uint64_t>& classMask) {
   if (h->stageRecsBytes < recBytes) { h->stageRecs.reset(new unsigned char[recBytes]); h->stageRecsBytes = recBytes; }   // not value-initialised: every record is written below
   JobRec* recs = (JobRec*)h->stageRecs.get();
   parallelChunks((size_t)M, 64, [&](size_t lo, size_t hi) {
-    for (size_t j = lo; j < hi; j++) {
-      JobRec& r = recs[j];
-      memset(&r, 0, sizeof r);
-      int s = h->jShape[j];
-      for (int x = 0; x < R; x++) r.req[x] = h->jReq[j * R + x];
-      // literal rows: the generic path decides.  bit 1: some indexed request is not a multiple of its resolution — keyDelta (its quotients) is then NOT what a
-      // bind takes off a node's key fields, so no fast path may bind / unbind such a job by key arithmetic (the evicted job returning to its node included)
-      r.keyDelta = sDelta[s]; r.fieldMin = sMin[s]; r.never = ((sNever[s] || h->rowLiteral[s]) ? 1 : 0) | (h->shapeUnaligned[s] ? 2 : 0);
-      r.pc = h->jPc[j]; r.shape = fitOf[s]; r.gang = h->jGangDense[j]; r.node0 = h->jNode[j]; r.runPrio = h->jRunPrio[j]; r.cls = h->shapeClass[s];
-      r.pcPrio = h->pcPriority[r.pc]; r.preemptible = h->pcPreemptible[r.pc] ? 1 : 0;
-      auto levels = [&](int32_t cutoff) { int nl = 0; while (nl < h->P && h->prios[nl] <= cutoff) nl++; return (uint8_t)nl; };
-      r.nlPc = levels(r.preemptible ? r.pcPrio : INT32_MAX); r.nlRun = levels(r.preemptible ? r.runPrio : INT32_MAX);
-      r.ex0 = f.E > 0 ? r.req[f.extraCol[0]] : 0; r.ex1 = f.E > 1 ? r.req[f.extraCol[1]] : 0;
-    }
+    for (size_t j = lo; j < hi; j++) fastRecFill(h, recs[j], h->jShape[j], &h->jReq[j * R], h->jPc[j], h->jGangDense[j], h->jNode[j], h->jRunPrio[j]);
   });
   prof.lap("JobRec fill");
   const size_t jcap = std::max((size_t)M, h->jobCap);   // (the job table's capacity: asched_jobs_append writes the records of new rows behind the M uploaded here)
   d.jrec = (JobRec*)h->fastBufs.alloc<unsigned char>(sizeof(JobRec) * std::max<size_t>(jcap, 1));
   if (M) plat_h2d(d.jrec, recs, sizeof(JobRec) * (size_t)M);
   prof.lap("JobRec upload");
-  d.shapeTab = h->fastBufs.upload(fitTab);
+  d.shapeTab = h->fastBufs.upload(h->fitTab);
   f.maskMode = 0;   // decided below, once the fit bitmaps exist
   std::vector<uint64_t> nodeCls(N, 0);
   for (int c = 0; c < h->C; c++) for (int n = 0; n < N; n++) if ((classMask[(size_t)c * W + (n >> 6)] >> (n & 63)) & 1) nodeCls[n] |= 1ull << c;
@@ -1430,7 +1468,7 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
   d.unfeasible = h->jobBufs.alloc<uint8_t>(std::max(h->S, 1)); d.unfeasibleReason = h->jobBufs.alloc<int32_t>(std::max(h->S, 1));
   h->jobCap = M; h->gangCap = h->G; h->gangArrCap = (size_t)gangOff[h->G + 1]; h->gangJobsCap = gangJobs.size(); h->gangOffCap = gangOff.size();
   h->ordCap = ord.size(); h->ordSpareCap = 0; h->ordOffCap = h->ordOffHost.size(); h->gangOffHost = gangOff;
-  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jdStats, 0, sizeof h->jdStats);
+  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats);
   h->jobsSet = true; h->prepared = false;
   h->jQPrioHost.swap(qprio); h->jSubmitHost.swap(submit); h->jRunTsHost.swap(runTs);   // (asched_jobs_patch uploads them when it is first called; nothing is copied here)
   prof.lap("uploads + per-job state allocation");
@@ -1541,6 +1579,9 @@ int32_t asched_jobs_patch(asched_t* h, int32_t n, const int32_t* job, const int3
 // per-queue sorted set at :691-700).  Rows M .. M+m-1 behind the resident ones, on the device; the handle is left as asched_jobs_set of the concatenated table would
 // leave it.  Two paths, chosen per call: every row's scheduling-key shape is already in the table — nothing jobs_set derives per shape changes, so no mask is rebuilt and
 // the fast structure stays; or some row brings a new shape — the per-row work is the same and the shape-dependent tables are re-derived by the code jobs_set ends with.
+// With asched_set_append_in_place on, the second case takes a third path where its conditions hold (DESIGN 3.16): nothing a new shape adds depends on the old rows — mask
+// rows (kernels_shapes_append.h), perhaps a derived away class and a fit shape, two minima, its own rows' records — so the tables GROW, the records of the resident rows
+// stay where they are, and the call ends like the first case.  Exact provided the key layout of the grown table is the one in force, which is checked first.
 static uint64_t jaShapeHash(int32_t cls, int32_t pc, const int64_t* req, int R) {   // (jobs_set's hash over (requirement class, priority class, requests))
   uint64_t x = 0x9e3779b97f4a7c15ull ^ ((uint64_t)(uint32_t)cls << 32 | (uint32_t)pc);
   for (int r = 0; r < R; r++) { x ^= (uint64_t)req[r]; x *= 0xff51afd7ed558ccdull; x ^= x >> 29; }
@@ -1641,9 +1682,18 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
   const int S1 = (int)h->shapeClass.size();
   const bool newShapes = S1 > S0 || !revived.empty();   // (a revived shape takes the path of a new one: the records are rebuilt from the mirrors, DESIGN 3.12)
   const DevCfg cfgSaved = d.cfg; const bool keyWideSaved = h->keyWide, keyCoarseSaved = h->keyCoarse;
+  const int Cext0 = h->Cext, A0 = (int)h->awayRowClass.size();   // derived classes and away rows before the call
   bool mirrorsGrown = false;
+  // the in-place path extends what buildFast left on the handle before it knows that every block can be had: `undo` takes it back
+  bool fastGrown = false; const int F0 = d.f.F; std::vector<uint8_t> rowLiteralSaved; int64_t minFieldSaved[MAXK], minExtraSaved[MAXE];
   auto undo = [&]() {   // a refusal after the shape lookup: the handle exactly as it was
     if (!newShapes) return;
+    if (fastGrown) {
+      h->fsDelta.resize(S0); h->fsMin.resize(S0); h->fsNever.resize(S0); h->fitOf.resize(S0); h->fitTab.resize(F0);
+      for (auto it = h->fitIds.begin(); it != h->fitIds.end();) it = it->second >= F0 ? h->fitIds.erase(it) : std::next(it);
+      memcpy(h->fsMinField, minFieldSaved, sizeof minFieldSaved); memcpy(h->fsMinExtra, minExtraSaved, sizeof minExtraSaved);
+      d.f.F = F0; h->rowLiteral = rowLiteralSaved;
+    }
     if (!revived.empty()) h->shapeRow = shapeRowSaved;
     h->shapeClass.resize(S0); h->shapePc.resize(S0); h->shapeReq.resize((size_t)S0 * R); h->shapeRow.resize(S0); h->shapeUnaligned.resize(S0);
     h->shapeTable.clear(); h->shapeHash.clear();
@@ -1671,6 +1721,55 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
       }
     }
   }
+  // ---- the in-place path for new shapes (asched_set_append_in_place): decided here, before anything changes.  inWhy: why the rebuild is taken although the switch is on
+  bool inPlace = false; int inWhy = 0;
+  const int A1 = (int)h->awayRowClass.size(), Sext0 = S0 + A0, Sext1 = S1 + A1, Wm = d.cfg.W;
+  std::vector<int32_t> shapeClassExt1, rowTypeOff1, rowTypes1, tplShape, aTpl; std::vector<int64_t> shapeReqExt1; std::vector<uint64_t> classRows1;
+  if (newShapes && h->appendInPlace) {
+    bool negNew = false;
+    for (size_t k = 0; k < (size_t)m * R && !negNew; k++) negNew = rows->req[k] < 0;
+    bool layoutSame = h->keyWide == keyWideSaved && h->keyCoarse == keyCoarseSaved && d.cfg.keyClamp == cfgSaved.keyClamp && d.cfg.idxBits == cfgSaved.idxBits &&
+                      d.cfg.keyGuard == cfgSaved.keyGuard && d.cfg.keyWords == cfgSaved.keyWords;
+    for (int c = 0; c < h->K; c++) layoutSame = layoutSame && d.cfg.keyLo[c] == cfgSaved.keyLo[c] && d.cfg.keyWidth[c] == cfgSaved.keyWidth[c] && d.cfg.keyShift[c] == cfgSaved.keyShift[c] &&
+                                                d.cfg.indexedRes[c] == cfgSaved.indexedRes[c];
+    if (M <= 0 || S0 <= 0) inWhy = 6;   // (buildFast's predicate can turn true)
+    else if (!h->nodesSet || !h->dClassMask || !h->dShapeClass || !d.shapeMask || h->fitOf.size() != (size_t)S0 || h->fsDelta.size() != (size_t)S0) inWhy = 1;
+    else if (!layoutSame) inWhy = 2;
+    else if (anyAway && !cfgSaved.hasAway) inWhy = 3;
+    else if (negNew && (d.f.structOk || d.f.cascadeFuse)) inWhy = 5;   // (buildFast's reqNonNeg: the structure and the fused pass go with the first negative request)
+    else {
+      // the row tables of the grown shape table, then per new shape what buildFast derives (it reads h->rowLiteral)
+      shapeClassExt1 = h->shapeClass; shapeReqExt1 = h->shapeReq;
+      for (int k = 0; k < A1; k++) {
+        shapeClassExt1.push_back(h->awayRowClass[k]);
+        for (int r = 0; r < R; r++) shapeReqExt1.push_back(h->shapeReq[(size_t)h->awayRowShape[k] * R + r]);
+      }
+      rowLiteralSaved = h->rowLiteral; memcpy(minFieldSaved, h->fsMinField, sizeof minFieldSaved); memcpy(minExtraSaved, h->fsMinExtra, sizeof minExtraSaved);
+      fastGrown = true;
+      if (int rrc = buildRowTables(h, shapeClassExt1, rowTypeOff1, rowTypes1)) { std::string why = h->err; undo(); return fail(h, rrc, "jobs_append: " + why); }
+      for (int s = S0; s < S1; s++) fastShapeAdd(h, s);
+      if (d.f.structOk && d.f.F > SMAX) inWhy = 4;   // (the rebuild that follows derives all of it again)
+      else inPlace = true;
+    }
+  }
+  if (inPlace) {
+    // the rows of the derived away classes this call adds: ids behind the old ones (deriveAwayRows numbers them in shape order)
+    classRows1.assign((size_t)(h->Cext - Cext0) * Wm, 0);
+    for (int c = Cext0; c < h->Cext; c++)
+      for (int n = 0; n < h->N; n++) if (classMatchesNode(h, c, n)) classRows1[(size_t)(c - Cext0) * Wm + (n >> 6)] |= 1ull << (n & 63);
+    // one template record per shape without a resident row below M (new or revived): every row of such a shape has aSrc < 0
+    if (d.f.structOk && d.jrec) {
+      std::unordered_map<int32_t, int32_t> tplOf;
+      aTpl.assign(m, -1);
+      for (int i = 0; i < m; i++) if (aSrc[i] < 0) {
+        auto it = tplOf.find(aShape[i]);
+        if (it == tplOf.end()) { it = tplOf.emplace(aShape[i], (int32_t)tplShape.size()).first; tplShape.push_back(aShape[i]); }
+        aTpl[i] = it->second;
+      }
+    }
+  }
+  const size_t nTpl = tplShape.size();
+  const int nNewRows = inPlace ? (S1 - S0) + (A1 - A0) : 0;
   // ---- sizes, and every new device block before anything changes: running out of device memory here is a refusal too
   const int total = h->ordOffHost.empty() ? 0 : h->ordOffHost[std::min<size_t>((size_t)h->ordQueues, h->ordOffHost.size() - 1)];
   const int total1 = total + nT;
@@ -1695,7 +1794,8 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
   }
   auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t o64 = up(sizeof(int32_t) * 8 * (size_t)m), oReq = o64 + up(sizeof(int64_t) * (size_t)m), oAl = oReq + up(sizeof(int64_t) * (size_t)m * R), oKeys = oAl + up((size_t)m),
-               need = oKeys + (nT > 0 ? up(sizeof(JpKey) * (size_t)nb2) : 0);
+               oTplIdx = oKeys + (nT > 0 ? up(sizeof(JpKey) * (size_t)nb2) : 0), oTpl = oTplIdx + (nTpl ? up(sizeof(int32_t) * (size_t)m) : 0),
+               oSa = oTpl + up(sizeof(JobRec) * nTpl), need = oSa + up((size_t)nNewRows * (8 + 8 * (size_t)R));   // (the in-place path for new shapes: each row's template, the template records, and request / class / output row of the new mask rows)
   char* scratchNew = nullptr;
   if (m > 0 && h->jpScratchBytes < need) {
     scratchNew = (char*)plat_malloc(need + need / 4);
@@ -1708,7 +1808,7 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
   const bool buildJp = m > 0 && !h->jp.built;
   const size_t gangOffCap1 = (size_t)G1 + 2 > h->gangOffCap ? std::max<size_t>((size_t)G1 + 2, h->gangOffCap + h->gangOffCap / 4) : h->gangOffCap;
   const size_t ordOffCap1 = std::max(h->ordOffCap, (size_t)std::max(Qj1, 1) + 4096 + 2);   // (the queue count outgrew the 4 096 padding)
-  const bool growRec = grow && d.f.structOk && d.jrec && !newShapes;   // (a new shape: rebuildMasks -> buildFast allocates the fast structure at the new capacity)
+  const bool growRec = grow && d.f.structOk && d.jrec && (!newShapes || inPlace);   // (a new shape off the in-place path: rebuildMasks -> buildFast allocates the fast structure at the new capacity)
   int32_t* ordTarget = nullptr; int32_t* ordNext = nullptr;
   if (m > 0) {
     if (grow) {
@@ -1747,6 +1847,23 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
     stage(&h->jobBufs, &d.gangTotal, (gangCap1 + 1) * (size_t)R * 8, 0, nullptr, 0); stage(&h->jobBufs, &d.gangAllEvicted, gangCap1 + 1, 0, nullptr, 0);
   }
   if (newShapes) { stage(&h->jobBufs, &d.unfeasible, (size_t)S1, 0, nullptr, 0); stage(&h->jobBufs, &d.unfeasibleReason, (size_t)S1 * 4, 0, nullptr, 0); }
+  uint64_t* shapeMask1 = nullptr;   // the grown shape mask [old shape rows | new shape rows | old away rows | new away rows]: filled by plat_shapes_append below
+  if (inPlace) {
+    if (Sext1 > Sext0) {
+      stage(&h->maskBufs, &shapeMask1, 8 * (size_t)Sext1 * Wm, 0, nullptr, -1, true);
+      stage(&h->maskBufs, &h->dShapeClass, 4 * shapeClassExt1.size(), 4 * shapeClassExt1.size(), shapeClassExt1.data(), 0);
+      stage(&h->maskBufs, &d.shapeReq, 8 * shapeReqExt1.size(), 8 * shapeReqExt1.size(), shapeReqExt1.data(), 0);
+      stage(&h->maskBufs, &d.awayRowOff, 4 * h->awayRowOff.size(), 4 * h->awayRowOff.size(), h->awayRowOff.data(), 0);
+      stage(&h->maskBufs, &d.rowLiteral, h->rowLiteral.size(), h->rowLiteral.size(), h->rowLiteral.data(), 0);
+      stage(&h->maskBufs, &d.rowTypeOff, 4 * rowTypeOff1.size(), 4 * rowTypeOff1.size(), rowTypeOff1.data(), 0);
+      stage(&h->maskBufs, &d.rowTypes, 4 * rowTypes1.size(), 4 * rowTypes1.size(), rowTypes1.data(), 0);
+    }
+    if (h->Cext > Cext0) stage(&h->maskBufs, &h->dClassMask, 8 * (size_t)h->Cext * Wm, 8 * (size_t)Cext0 * Wm, nullptr, -1);   // (the old rows device to device; the new ones are uploaded below)
+    if (d.f.structOk && d.f.F > F0) {
+      stage(&h->fastBufs, &d.shapeTab, sizeof(ShapeReq) * h->fitTab.size(), sizeof(ShapeReq) * h->fitTab.size(), h->fitTab.data(), 0);
+      if (d.fitBits) stage(&h->fastBufs, &d.fitBits, 8 * ((size_t)d.f.F * d.fitW + 64), 0, nullptr, 0);   // (scratch the next base build fills, as in asched_nodes_append)
+    }
+  }
   if (grow) {
     const size_t c = cap1;
     void* s32[] = {&d.schedAtPrio, &d.jobNode, &d.jobCutoff, &d.optGhost, &d.jcAssigned, &d.jcReason, &d.pcNode, &d.pcSap, &d.pcPap, &d.pcMethod, &d.jcGangCard, &d.jcUniValue, &d.jcStagedBy, &d.jcPreSib,
@@ -1768,13 +1885,14 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
   }
   // ---- what jobs_set resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the job table half appended: asched_jobs_set before anything else)
   h->haveRoundResult = false; h->stateEpoch++;
-  if (newShapes) fastInvalidate(h);
+  if (newShapes && !inPlace) fastInvalidate(h);
   else { h->dev.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
     int32_t zero = 0;
     plat_h2d(&h->dev.rs->fastActive, &zero, sizeof zero);
     plat_h2d(&h->dev.rs->l0SaveCount, &zero, sizeof zero); }
   h->prepared = false; h->evrSized = false;
   for (int k = 0; k < 3; k++) h->jaMs[k] = 0;
+  h->saMs[0] = h->saMs[1] = 0;
   if (scratchNew) { h->jpBufs.freeAll(); h->jpScratch = scratchNew; h->jpScratchBytes = need + need / 4; h->jpBufs.ptrs.push_back({scratchNew, need + need / 4}); }
   if (m > 0) {
     // the blocks: copies and fills queued on the handle's stream, the old blocks released once they are through
@@ -1814,8 +1932,41 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
     for (int k = 0; k < 7; k++) plat_h2d(e32 + k * mm, cols[k]->data(), mm * 4);
     plat_h2d(e32 + 7 * mm, aQPrio.data(), mm * 4);
     plat_h2d(h->jpScratch + o64, aSubmit.data(), mm * 8); plat_h2d(h->jpScratch + oReq, rows->req, mm * 8 * R); plat_h2d(h->jpScratch + oAl, aAligned.data(), mm);
+    if (inPlace) {
+      fastMinimaPack(h);
+      if (const char* ms = getenv("ASCHED_SHAPE_MASK")) if (d.fitBits && ms[0] == '1') d.f.maskMode = d.f.F <= 64 ? 1 : d.f.F <= 128 ? 2 : 0;   // (buildFast's rule, for the grown F)
+      if (h->Cext > Cext0) plat_h2d(h->dClassMask + (size_t)Cext0 * Wm, classRows1.data(), classRows1.size() * 8);
+      if (shapeMask1) {
+        const int nNew = nNewRows;
+        std::vector<int32_t> rowCls(nNew), rowOut(nNew); std::vector<int64_t> rowReq((size_t)nNew * R);
+        for (int k = 0; k < nNew; k++) {
+          const int row = k < S1 - S0 ? S0 + k : S1 + A0 + (k - (S1 - S0));
+          rowOut[k] = row; rowCls[k] = shapeClassExt1[row];
+          for (int r = 0; r < R; r++) rowReq[(size_t)k * R + r] = shapeReqExt1[(size_t)row * R + r];
+        }
+        int64_t* dReq = (int64_t*)(h->jpScratch + oSa); int32_t* dCls = (int32_t*)(dReq + (size_t)nNew * R);
+        plat_h2d(dReq, rowReq.data(), rowReq.size() * 8); plat_h2d(dCls, rowCls.data(), (size_t)nNew * 4); plat_h2d(dCls + nNew, rowOut.data(), (size_t)nNew * 4);
+        SaArgs sa; memset(&sa, 0, sizeof sa);
+        sa.N = h->N; sa.Npad = d.cfg.Npad; sa.W = Wm; sa.R = R; sa.rows = nNew;
+        sa.totalRes = d.totalRes; sa.classMask = h->dClassMask;
+        sa.rowClass = dCls; sa.rowOut = dCls + nNew; sa.rowReq = dReq;
+        sa.outMask = shapeMask1; sa.inMask = d.shapeMask;
+        sa.copy0 = (long long)S0 * Wm; sa.src1 = (long long)S0 * Wm; sa.dst1 = (long long)S1 * Wm; sa.copy1 = (long long)A0 * Wm;
+        int src = plat_take_failure() ? -1 : plat_shapes_append(d, sa);
+        if (src) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+        plat_shapes_append_ms(h->saMs);
+        release(&h->maskBufs, d.shapeMask);
+        d.shapeMask = shapeMask1;
+      }
+    }
     JaArgs a; memset(&a, 0, sizeof a);
-    a.M = M; a.m = m; a.nb2 = nb2; a.R = R; a.writeRec = (!newShapes && d.f.structOk && d.jrec) ? 1 : 0;
+    a.M = M; a.m = m; a.nb2 = nb2; a.R = R; a.writeRec = ((!newShapes || inPlace) && d.f.structOk && d.jrec) ? 1 : 0;
+    if (inPlace && nTpl) {
+      std::vector<JobRec> tpl(nTpl);
+      for (size_t t = 0; t < nTpl; t++) fastRecFill(h, tpl[t], tplShape[t], &h->shapeReq[(size_t)tplShape[t] * R], h->shapePc[tplShape[t]], -1, -1, 0);
+      plat_h2d(h->jpScratch + oTplIdx, aTpl.data(), (size_t)m * 4); plat_h2d(h->jpScratch + oTpl, tpl.data(), sizeof(JobRec) * nTpl);
+      a.tpl = (const JobRec*)(h->jpScratch + oTpl); a.aTpl = (const int32_t*)(h->jpScratch + oTplIdx);
+    }
     a.aQueue = e32; a.aPc = e32 + mm; a.aShape = e32 + 2 * mm; a.aGang = e32 + 3 * mm; a.aGangCard = e32 + 4 * mm; a.aGangUni = e32 + 5 * mm; a.aSrc = e32 + 6 * mm;
     a.aQPrio = (const uint32_t*)(e32 + 7 * mm); a.aSubmit = (const int64_t*)(h->jpScratch + o64); a.aReq = (const int64_t*)(h->jpScratch + oReq); a.aAligned = (const uint8_t*)(h->jpScratch + oAl);
     a.jQPrio = h->jp.qprio; a.jSubmit = h->jp.submit;
@@ -1849,14 +2000,19 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
       plat_h2d(d.ordAllOff, off.data(), off.size() * 4);
       h->ordOffHost.swap(off); h->ordQueues = Qj1; }
     if (const char* e = getenv("ASCHED_JA_TIMES")) if (e[0] == '1')
-      fprintf(stderr, "[asched jobs_append] jobs %d rows %d in the order %d: fill %.4f ms, sort %.4f ms, merge %.4f ms\n", M, m, nT, h->jaMs[0], h->jaMs[1], h->jaMs[2]);
+      fprintf(stderr, "[asched jobs_append] jobs %d rows %d in the order %d: fill %.4f ms, sort %.4f ms, merge %.4f ms; shapes in place %d: mask rows %.4f ms, row copies %.4f ms\n", M, m, nT,
+              h->jaMs[0], h->jaMs[1], h->jaMs[2], inPlace ? (S1 - S0) + (int)revived.size() : 0, h->saMs[0], h->saMs[1]);
   }
-  h->jaStats[0] = m; h->jaStats[1] = nT; h->jaStats[2] = S1 - S0; h->jaStats[3] = G1 - G0; h->jaStats[4] = (m > 0 && grow) ? 1 : 0; h->jaStats[5] = newShapes ? 1 : 0;
-  h->jaStats[6] = (int32_t)h->jobCap; h->jaStats[7] = 0;
+  h->jaStats[0] = m; h->jaStats[1] = nT; h->jaStats[2] = S1 - S0; h->jaStats[3] = G1 - G0; h->jaStats[4] = (m > 0 && grow) ? 1 : 0; h->jaStats[5] = (newShapes && !inPlace) ? 1 : 0;
+  h->jaStats[6] = (int32_t)h->jobCap; h->jaStats[7] = inPlace ? (S1 - S0) + (int32_t)revived.size() : 0;
+  { int32_t* t = h->jasStats;
+    t[0] = h->appendInPlace ? 1 : 0; t[1] = inPlace ? S1 - S0 : 0; t[2] = inPlace ? (int32_t)revived.size() : 0; t[3] = inPlace ? Sext1 - Sext0 : 0;
+    t[4] = inPlace ? h->Cext - Cext0 : 0; t[5] = d.f.F; t[6] = inWhy; t[7] = 0; }
   if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
   d.cfg.Q = 0;
-  if (newShapes) {   // the shape-dependent tables, by the code jobs_set ends with (the key layout was decided above)
+  if (newShapes && !inPlace) {   // the shape-dependent tables, by the code jobs_set ends with (the key layout was decided above)
     int rc = rebuildMasks(h);
+    h->jasStats[5] = d.f.F;   // (F after the call: the rebuild derived the fit shapes again)
     if (rc) return rc;
     rc = runControl(h, CMD_UPSERT_RESET);
     if (rc) return rc;
@@ -1873,6 +2029,17 @@ int32_t asched_jobs_append_stats(asched_t* h, int32_t* out) {
   if (!h || !out) return ASCHED_ERR_INVALID;
   plat_enter(h->plat);
   for (int k = 0; k < 8; k++) out[k] = h->jaStats[k];
+  return 0;
+}
+int32_t asched_set_append_in_place(asched_t* h, int32_t on) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
+  h->appendInPlace = on != 0;
+  return 0;
+}
+int32_t asched_jobs_append_shape_stats(asched_t* h, int32_t* out) {
+  if (!h || !out) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  for (int k = 0; k < 8; k++) out[k] = h->jasStats[k];
+  out[0] = h->appendInPlace ? 1 : 0;
   return 0;
 }
 

@@ -6,6 +6,8 @@
 // WHAT A NEW ROW NEEDS: its slots of the per-job static arrays, the order-key inputs of the patch (kernels_jobs_patch.h), its JobRec where the fast structure has one, and
 // its place in the pre-sorted order ordAll.  A new row is queued (no run) and its scheduling-key shape decides everything of its JobRec but the gang: the record of a
 // RESIDENT row of the same shape (a.aSrc, a row < M: no thread reads what another writes) is copied and the four own fields put in — no JobRec crosses PCIe.
+// A row whose shape has NO resident row — a new shape, or one asched_jobs_delete emptied — on the in-place path (asched_set_append_in_place, kernels_shapes_append.h)
+// copies the template record the host built for its shape instead (a.tpl / a.aTpl: 128 bytes a shape, not a row); a.tpl == NULL is the function without that path.
 //
 // THE PASSES (asched_host.inc asched_jobs_append queues them):
 //   row fill + keys, over the m rows padded to a power of two: slot i writes row M+i and leaves the row's order key in the sort array.  A row of no queue is in no order:
@@ -18,12 +20,14 @@
 
 struct JaArgs {   // everything in platform memory
   int32_t M, m, nb2, R;       // M: rows before the call; nb2: m padded to a power of two >= JP_TILE (m when no new row is in a queue)
-  int32_t writeRec, pad0_;    // writeRec: d.jrec has room for the new rows and every new row's shape has a resident row (no rebuild follows)
+  int32_t writeRec, pad0_;    // writeRec: d.jrec has room for the new rows and every new row's shape has a resident row or a template (no rebuild follows)
   const int32_t *aQueue, *aPc, *aShape, *aGang, *aGangCard, *aGangUni, *aSrc;   // [m] the new rows; aSrc: a resident row of the same scheduling-key shape, -1 = none
   const uint32_t* aQPrio;     // [m]
   const int64_t* aSubmit;     // [m]
   const int64_t* aReq;        // [m][R]
   const uint8_t* aAligned;    // [m]
+  const JobRec* tpl;          // the in-place path for new shapes (asched_set_append_in_place): one template record per shape without a resident row below M, or NULL
+  const int32_t* aTpl;        // [m] the template of a row with aSrc < 0, -1 = none
   uint32_t* jQPrio;           // the patch's order-key inputs, writable: room for M + m rows (p.jQPrio / p.jSubmit are the same arrays)
   int64_t* jSubmit;
   JpArgs p;                   // the order-key inputs (keep / jQPrio / jSubmit / jRunTs, with room for M + m rows), the sort array p.keys [nb2], and the merge: p.kept = the old ordAll,
@@ -42,8 +46,9 @@ JP_FN void jaFill(const Dev& d, const JaArgs& a, int i) {
     d.jAligned[j] = a.aAligned[i];
     for (int r = 0; r < a.R; r++) d.jReq[(size_t)j * a.R + r] = a.aReq[(size_t)i * a.R + r];
     a.p.keep[j] = 1; a.jQPrio[j] = a.aQPrio[i]; a.jSubmit[j] = a.aSubmit[i]; a.p.jRunTs[j] = 0;
-    if (a.writeRec && d.jrec && a.aSrc[i] >= 0) {
-      JobRec r = d.jrec[a.aSrc[i]];   // everything the shape fixes: req, keyDelta, fieldMin, never, fit shape, cls, pc, pcPrio, preemptible, nlPc, ex0, ex1
+    const bool fromTpl = a.tpl && a.aSrc[i] < 0 && a.aTpl[i] >= 0;   // a shape this call brings or revives: the host built its record once (128 B a shape)
+    if (a.writeRec && d.jrec && (a.aSrc[i] >= 0 || fromTpl)) {
+      JobRec r = fromTpl ? a.tpl[a.aTpl[i]] : d.jrec[a.aSrc[i]];   // everything the shape fixes: req, keyDelta, fieldMin, never, fit shape, cls, pc, pcPrio, preemptible, nlPc, ex0, ex1
       r.gang = a.aGang[i]; r.node0 = -1; r.runPrio = 0; r.nlRun = (uint8_t)jpLevels(d.cfg, r.preemptible ? 0 : INT32_MAX);
       d.jrec[j] = r;
     }

@@ -95,6 +95,12 @@ static void plat_jobs_patch_ms(double* out /*[4]*/);   // measurement hook: devi
 struct JaArgs;
 static int plat_jobs_append(Dev& d, JaArgs& a);
 static void plat_jobs_append_ms(double* out /*[3]*/);   // measurement hook: device ms of row fill / sort / merge of the last call (events around them when ASCHED_JA_TIMES=1, else zeros)
+// new scheduling-key shapes join the shape mask (kernels_shapes_append.h): the resident rows copied device to device into the fresh block a.outMask, then the new rows,
+// one wave per 64-node word.  Synchronous: the fresh block is complete on return; nothing the handle points to is written.  The CPU build's definition sits in
+// kernels_shapes_append.h.
+struct SaArgs;
+static int plat_shapes_append(Dev& d, SaArgs& a);
+static void plat_shapes_append_ms(double* out /*[2]*/);   // measurement hook: device ms of the new mask rows / the row copies of the last call (events around them when ASCHED_JA_TIMES=1, else zeros)
 // rows leave the resident job table (kernels_jobs_delete.h): mark, scan (plat_compact over the keep flags into a.src / a.newId; its count must be a.M1), the gather of the
 // static per-job arrays into the blocks of a.out*, the compaction and renumbering of the order (a.ordOut) and of the gang lists (a.gangOut), unmark.  Synchronous: everything
 // is complete on return.  The CPU build's definition sits in kernels_jobs_delete.h.

@@ -33,7 +33,8 @@ struct PlatCtx {
   hipEvent_t rEv0 = nullptr, rEv1 = nullptr;
   hipEvent_t evrEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool evrTimed[3] = {false, false, false};   // ASCHED_EVR_TIMES=1: around the passes of the evictor report
   hipEvent_t jaEv[4] = {nullptr, nullptr, nullptr, nullptr}; bool jaTimed = false;   // ASCHED_JA_TIMES=1: around the passes of the job-table append
-  hipEvent_t jpEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool jpTimed = false;   // ASCHED_JP_TIMES=1: around the passes of the job-table patch
+  hipEvent_t saEv[3] = {nullptr, nullptr, nullptr}; bool saTimed = false;   // ASCHED_JA_TIMES=1: around the row copies and the mask rows of an in-place append of new shapes
+  hipEvent_t jpEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool jpTimed = false;  // ASCHED_JP_TIMES=1: around the passes of the job-table patch
   hipEvent_t ndEv[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool ndTimed = false;   // ASCHED_ND_TIMES=1: around the passes of the node-table delete
   hipEvent_t naEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool naTimed = false;   // ASCHED_NA_TIMES=1: around the passes of the node-table append
   hipEvent_t jdEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool jdTimed = false;   // ASCHED_JD_TIMES=1: around the passes of the job-table delete
@@ -257,6 +258,7 @@ static void plat_close(PlatCtx* c) {
   for (hipEvent_t e : c->evrEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->jpEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->jaEv) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->saEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->npEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->jdEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ndEv) if (e) (void)hipEventDestroy(e);
@@ -950,6 +952,38 @@ static int plat_jobs_append(Dev& d, JaArgs& a) {
 static void plat_jobs_append_ms(double* out) {
   hipEvent_t* ev = jaEvents();
   for (int k = 0; k < 3; k++) { float ms = 0.f; if (ev && t_ctx->jaTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
+}
+// new scheduling-key shapes join the shape mask (kernels_shapes_append.h; k_sa_mask in armada_sched_mgpu.hip).  ASCHED_JA_TIMES=1 puts events around the row copies
+// and the mask rows (tools/probe_jobs_append_shapes.py).
+#include "kernels_shapes_append.h"
+extern "C" int asched_internal_sa_mask(const SaArgs* a, hipStream_t s);
+static hipEvent_t* saEvents() {
+  static const bool on = [] { const char* e = getenv("ASCHED_JA_TIMES"); return e && e[0] == '1'; }();
+  PlatCtx* c = t_ctx;
+  if (!on) return nullptr;
+  if (!c->saEv[2]) for (int i = 0; i < 3; i++) if (!c->saEv[i] && hipEventCreate(&c->saEv[i]) != hipSuccess) { c->saEv[i] = nullptr; return nullptr; }
+  return c->saEv;
+}
+static int plat_shapes_append(Dev& d, SaArgs& a) {
+  (void)d;
+  PlatCtx* c = t_ctx;
+  hipStream_t st = c->stream;
+  hipEvent_t* ev = saEvents();
+  c->saTimed = false;
+  if (ev) (void)hipEventRecord(ev[0], st);
+  if (a.copy0 > 0) plat_d2d(a.outMask, a.inMask, (size_t)a.copy0 * 8);
+  if (a.copy1 > 0) plat_d2d(a.outMask + a.dst1, a.inMask + a.src1, (size_t)a.copy1 * 8);
+  if (ev) (void)hipEventRecord(ev[1], st);
+  bool ok = asched_internal_sa_mask(&a, st) == 0;
+  if (ev) (void)hipEventRecord(ev[2], st);
+  ok = ok && hipOk(hipGetLastError(), "k_sa launch") && hipOk(hipStreamSynchronize(st), "k_sa");
+  if (!ok) { if (c->err.empty()) c->err = "k_sa_mask launch failed"; return -1; }
+  c->saTimed = ev != nullptr;
+  return 0;
+}
+static void plat_shapes_append_ms(double* out) {   // out[0]: the mask rows, out[1]: the copies
+  hipEvent_t* ev = saEvents();
+  for (int k = 0; k < 2; k++) { float ms = 0.f; if (ev && t_ctx->saTimed && hipEventElapsedTime(&ms, ev[1 - k], ev[2 - k]) != hipSuccess) ms = 0.f; out[k] = ms; }
 }
 // rows leave the resident job table (kernels_jobs_delete.h; k_jd_* in armada_sched_mgpu.hip, the scans are plat_compact's).  Each compaction brings its count back to the
 // host, which checks it against what the host counted before the next pass is sized by it.  ASCHED_JD_TIMES=1 puts events around the five passes (tools/probe_jobs_delete.py).

@@ -285,7 +285,7 @@ def arrival_cycles(sim: SimulatorInput, per_cycle: Optional[int] = None) -> np.n
     return np.maximum.accumulate(np.maximum(c, 0))   # (row = arrival order: a row never arrives before the one in front of it)
 
 
-def _run_cycles_arriving(lib, sim: SimulatorInput, per_cycle, max_cycles, appended, node_events=(), nodes_patched=True):
+def _run_cycles_arriving(lib, sim: SimulatorInput, per_cycle, max_cycles, appended, node_events=(), nodes_patched=True, in_place=False):
     from .binding import Scheduler
     wl = sim.workload
     m = wl.num_jobs
@@ -301,6 +301,7 @@ def _run_cycles_arriving(lib, sim: SimulatorInput, per_cycle, max_cycles, append
     allocatable = np.array(wl.node_total, dtype=np.int64)            # the node state the events of run_cycles_cordoning move
     unschedulable = np.zeros(wl.num_nodes, np.uint8)
     have = 0                                          # rows in the handle's table: the jobs that have arrived, in arrival order, finished ones included
+    shapes_in_place = appends_rebuilt = 0
     t = 0.0
     for cycle in range(max_cycles):
         finished = (node >= 0) & (started >= 0) & (started + sim.job_runtime_s <= t)
@@ -314,8 +315,13 @@ def _run_cycles_arriving(lib, sim: SimulatorInput, per_cycle, max_cycles, append
             if cycle == 0:                            # the first cycle: jobs_set
                 s.jobs_set(wl.job_req[:upto], queue=wl.job_queue[:upto], pc=wl.job_pc[:upto], submit_time=wl.job_submit[:upto], node=node[:upto],
                            scheduled_at_priority=run_prio[:upto], run_timestamp=np.zeros(upto, np.int64))
+                if in_place:                          # once: new shapes of later cycles grow the shape tables instead of rebuilding them
+                    s.set_append_in_place(True)
             elif upto > have:                         # the submissions since the last cycle
                 s.jobs_append(wl.job_req[have:upto], queue=wl.job_queue[have:upto], pc=wl.job_pc[have:upto], submit_time=wl.job_submit[have:upto])
+                if in_place:
+                    st = s.jobs_append_stats()
+                    shapes_in_place += st["in_place"]; appends_rebuilt += st["rebuilt"]
             rows = np.nonzero(changed)[0].astype(np.int32)
             if len(rows):                             # then the run state of the rows that changed
                 running = node[rows] >= 0
@@ -355,6 +361,9 @@ def _run_cycles_arriving(lib, sim: SimulatorInput, per_cycle, max_cycles, append
             node[j], started[j] = -1, -1.0
             changed[j] = True
         out.append({"time_s": t, "scheduled": sched, "preempted": pre, "termination_reason": r.termination_reason, "rows": have})
+        if in_place:
+            out[-1]["shapes_in_place"] = shapes_in_place      # new and revived shapes the appends so far served without a rebuild
+            out[-1]["appends_rebuilt"] = appends_rebuilt      # appends so far that took the rebuild of masks and fast structure
         if have == m and not sched and not pre and not (node >= 0).any():
             break   # everything has arrived, nothing runs and nothing can be placed: the rest never will
         t += sim.cycle_period_s
@@ -362,11 +371,12 @@ def _run_cycles_arriving(lib, sim: SimulatorInput, per_cycle, max_cycles, append
     return out
 
 
-def run_cycles_arriving(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000):
+def run_cycles_arriving(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000, in_place: bool = False):
     """run_cycles_patched with the workload's jobs ENTERING the table as they are submitted instead of all at once: the first cycle's arrivals by jobs_set, every later
     cycle's by Scheduler.jobs_append (syncState's upsert of the new jobs), then the run-state patch, round_prepare and the round.  Row = arrival order (the workload's
-    rows are in submission order); arrival_cycles says which cycle a row arrives in.  Records as run_cycles, plus the table's row count."""
-    return _run_cycles_arriving(lib, sim, per_cycle, max_cycles, True)
+    rows are in submission order); arrival_cycles says which cycle a row arrives in.  Records as run_cycles, plus the table's row count.  in_place: Scheduler.set_append_in_place once after
+    the first jobs_set — an append that brings new scheduling-key shapes grows the shape tables instead of rebuilding them (same records; "shapes_in_place" counts them)."""
+    return _run_cycles_arriving(lib, sim, per_cycle, max_cycles, True, in_place=in_place)
 
 
 def run_cycles_arriving_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000):
@@ -375,7 +385,7 @@ def run_cycles_arriving_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[in
     return _run_cycles_arriving(lib, sim, per_cycle, max_cycles, False)
 
 
-def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, every, deleted, resident=None):
+def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, every, deleted, resident=None, in_place=False):
     from .binding import Scheduler
     wl = sim.workload
     m = wl.num_jobs
@@ -391,6 +401,7 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
     s = Scheduler(lib, wl.config)
     s.nodes_upsert(wl.node_total, id_rank=wl.node_id_rank)
     have = 0                                          # jobs that have arrived
+    shapes_in_place = appends_rebuilt = 0
     t = 0.0
 
     def table_args(jobs):
@@ -415,8 +426,13 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
         if deleted:
             if cycle == 0:                            # the first cycle: jobs_set
                 s.jobs_set(wl.job_req[new], **table_args(new))
+                if in_place:
+                    s.set_append_in_place(True)
             elif len(new):                            # syncState: the upserts — the submissions since the last cycle, the run state of the rows that changed
                 s.jobs_append(wl.job_req[new], queue=wl.job_queue[new], pc=wl.job_pc[new], submit_time=wl.job_submit[new])
+                if in_place:
+                    st = s.jobs_append_stats()
+                    shapes_in_place += st["in_place"]; appends_rebuilt += st["rebuilt"]
             row_of_job[new] = len(job_of_row) + np.arange(len(new))
             job_of_row = np.concatenate([job_of_row, new])
             jobs = np.nonzero(changed & (row_of_job >= 0))[0]
@@ -456,6 +472,8 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
             node[k], started[k] = -1, -1.0
             changed[k] = True
         out.append({"time_s": t, "scheduled": sched, "preempted": pre, "termination_reason": r.termination_reason, "rows": len(job_of_row)})
+        if in_place:                                  # as in run_cycles_arriving: shapes served without a rebuild (new ones and ones the deletes had emptied), appends that rebuilt
+            out[-1]["shapes_in_place"], out[-1]["appends_rebuilt"] = shapes_in_place, appends_rebuilt
         if have == m and not sched and not pre and not (node >= 0).any():
             break   # everything has arrived, nothing runs and nothing can be placed: the rest never will
         t += sim.cycle_period_s
@@ -470,12 +488,13 @@ def run_cycles_compacting(lib, sim: SimulatorInput, per_cycle: Optional[int] = N
     return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, every, True)
 
 
-def run_cycles_resident(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000, hold_finished: bool = False):
+def run_cycles_resident(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000, hold_finished: bool = False, in_place: bool = False):
     """run_cycles_compacting with NO per-cycle queued list: the table is kept by jobs_append, jobs_patch and jobs_delete and every round is prepared with
     Scheduler.round_prepare_resident, which derives the queued lists from the resident order on the device (NewQueuedJobsIterator over repo.QueuedJobs,
     jobiteration.go:144-160).  The finished rows are deleted every cycle (the one row jobs_delete has to leave in a table of finished rows only is held); with
-    hold_finished they stay in the table and are named in `held` every cycle instead, which costs O(finished rows) per cycle.  Records as run_cycles_compacting."""
-    return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, 1, True, resident="held" if hold_finished else "delete")
+    hold_finished they stay in the table and are named in `held` every cycle instead, which costs O(finished rows) per cycle.  in_place: as for run_cycles_arriving
+    (shapes that the deletes emptied come back in place as well).  Records as run_cycles_compacting."""
+    return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, 1, True, resident="held" if hold_finished else "delete", in_place=in_place)
 
 
 def run_cycles_compacting_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000, every: int = 1):

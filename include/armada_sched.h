@@ -408,8 +408,25 @@ int32_t ASCHED_FN(jobs_patch)(asched_t*, int32_t n, const int32_t* job, const in
    then needs asched_jobs_set, as documented for jobs_patch. */
 int32_t ASCHED_FN(jobs_append)(asched_t*, const asched_jobs* rows);
 /* how the last jobs_append ran: out[0] rows of the call, [1] rows that entered the order (queue >= 0), [2] new shapes, [3] new gangs, [4] 1 = the per-job arrays were
-   re-allocated, [5] 1 = masks and fast structure were rebuilt, [6] capacity (rows) after the call, [7] 0 (reserved).  Zeros after jobs_set. */
+   re-allocated, [5] 1 = masks and fast structure were rebuilt (0 after an in-place append of new shapes), [6] capacity (rows) after the call, [7] shapes served in
+   place, new plus revived (asched_set_append_in_place).  Zeros after jobs_set. */
 int32_t ASCHED_FN(jobs_append_stats)(asched_t*, int32_t* out /*[8]*/);
+/* New shapes without a rebuild.  A scheduling-key shape is the whole request vector, so most cycles of a production pool bring one; with the switch on, a
+   jobs_append whose rows bring new shapes — or shapes asched_jobs_delete left without a resident row — grows the shape-dependent tables by what those shapes add
+   instead of re-deriving them for every shape: the new rows of the shape mask on the device (one wave per 64-node word), the rows of a newly derived away class,
+   the new fit shapes, the two minima of the fast structure, and one record template per shape from which the device fills the new rows' records.  No resident row's
+   record, no resident mask row and no class is recomputed or uploaded.  The handle is left as jobs_set of the concatenated table would leave it, as for every
+   jobs_append; the result is the same with the switch on or off.  The path is taken where (a) the handle has a node table and masks, (b) the key layout layoutKeys
+   chooses for the grown table is the one in force, (c) the batch does not bring the first away rows of the table, (d) the fit shapes still number at most SMAX,
+   (e) no request of the batch is negative on a handle with the fast structure or the fused level pass, (f) the table had rows and shapes before the call; otherwise
+   the rebuild of jobs_append runs and asched_jobs_append_shape_stats says why.  A handle without the fast structure (two-word keys, alloc_by_prio, ...) takes the
+   mask part only.  A property of the handle like asched_set_evictor_report: off by default, survives jobs_set and nodes_upsert.  Off, jobs_append is unchanged. */
+int32_t ASCHED_FN(set_append_in_place)(asched_t*, int32_t on);
+/* how the last jobs_append treated new shapes: out[0] the switch, [1] shapes added in place, [2] shapes revived in place, [3] mask rows added (shape rows + away
+   rows), [4] derived away classes added, [5] fit shapes F after the call, [6] why the rebuild was taken although the switch is on — 0 not taken, 1 no node table or no
+   masks yet, 2 the key layout of the grown table differs, 3 the batch turns away rows on for a table that had none, 4 more than SMAX fit shapes, 5 a negative
+   request on a handle with the fast structure, 6 the table had no rows or shapes — [7] 0 (reserved).  [1..7] are zero after jobs_set; [0] is always the switch. */
+int32_t ASCHED_FN(jobs_append_shape_stats)(asched_t*, int32_t* out /*[8]*/);
 /* syncState's delete of the jobs in a terminal state from the jobDb, after the upserts of the same cycle (scheduler.go:539-549; Txn.BatchDelete / delete,
    jobdb/jobdb.go:941-990): the n rows job[0..n) leave the table.  The remaining rows keep their order and are renumbered densely: new id = old id - number of
    deleted rows below it.  new_id, when not NULL, receives that map for the M rows the table had before the call, -1 for a deleted row.

@@ -359,6 +359,12 @@ func NewGpuRound(cfg configuration.SchedulingConfig, rlf *internaltypes.Resource
 		g.Close()
 		return nil, err
 	}
+	// AppendJobs: a submission with a request vector the table has not seen (a new scheduling-key shape, most cycles of a production pool bring one) grows the
+	// shape-dependent tables instead of rebuilding masks and job records (asched_set_append_in_place; same result either way)
+	if err := g.check(C.asched_set_append_in_place(g.h, 1)); err != nil {
+		g.Close()
+		return nil, err
+	}
 	return g, nil
 }
 
