@@ -265,6 +265,7 @@ ALL_SYMBOLS = [
     "set_evictor_report", "round_evictor_report",
     "jobs_patch", "jobs_append", "jobs_append_stats", "jobs_delete", "jobs_delete_stats",
     "set_append_in_place", "jobs_append_shape_stats",
+    "req_classes_append", "req_classes_append_stats",
     "nodes_patch", "nodes_patch_stats", "nodes_delete", "nodes_delete_stats", "nodes_append", "nodes_append_stats",
     "round_prepare_resident", "round_queued",
 ]
@@ -276,6 +277,7 @@ OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_d
                     "jobs_patch", "jobs_append", "jobs_append_stats",   # (an incremental jobs_set: the oracle is given the whole table; tests/test_z_jobs_patch.py, test_z_jobs_append.py)
                     "jobs_delete", "jobs_delete_stats",                 # (likewise: tests/test_z_jobs_delete.py)
                     "set_append_in_place", "jobs_append_shape_stats",   # (how jobs_append treats new shapes, not what it leaves: tests/test_z_jobs_append_shapes.py)
+                    "req_classes_append", "req_classes_append_stats",   # (an incremental jobs_set: the oracle is given the whole class list; tests/test_z_req_classes_append.py)
                     "nodes_patch", "nodes_patch_stats",                 # (an incremental nodes_upsert, likewise: tests/test_z_nodes_patch.py)
                     "nodes_delete", "nodes_delete_stats",               # (likewise: tests/test_z_nodes_delete.py)
                     "nodes_append", "nodes_append_stats",               # (likewise: tests/test_z_nodes_append.py)
@@ -478,6 +480,8 @@ class Library:
         f("jobs_append_stats", C.c_int32, [C.c_void_p, _i32p])
         f("set_append_in_place", C.c_int32, [C.c_void_p, C.c_int32])
         f("jobs_append_shape_stats", C.c_int32, [C.c_void_p, _i32p])
+        f("req_classes_append", C.c_int32, [C.c_void_p, C.POINTER(CReqClasses)])
+        f("req_classes_append_stats", C.c_int32, [C.c_void_p, _i32p])
         f("jobs_delete", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p])
         f("jobs_delete_stats", C.c_int32, [C.c_void_p, _i32p])
         f("nodes_patch", C.c_int32, [C.c_void_p, C.POINTER(CNodesPatch)])
@@ -541,6 +545,36 @@ class Config:
 
 
 AWAY_COND_OPS = {">": 0, "<": 1, "==": 2}
+
+
+def _req_classes(tolerations, selectors, affinities, keep):
+    """an asched_req_classes of these classes (jobs_set, req_classes_append); the arrays it points to are appended to `keep`"""
+    cls = CReqClasses()
+    tols = tolerations if tolerations is not None else [[]]
+    sels = selectors if selectors is not None else [[] for _ in tols]
+    assert len(tols) == len(sels)
+    cls.n = len(tols)
+    off, (tk, to, tv, te) = _csr(tols, 4)
+    keep += [off, tk, to, tv, te]
+    cls.tol_off, cls.tol_key, cls.tol_op, cls.tol_value, cls.tol_effect = (_ptr(x, C.c_int32) for x in (off, tk, to, tv, te))
+    off2, (sk, sv) = _csr(sels, 2)
+    keep += [off2, sk, sv]
+    cls.sel_off, cls.sel_key, cls.sel_value = (_ptr(x, C.c_int32) for x in (off2, sk, sv))
+    if affinities is not None and any(a is not None for a in affinities):
+        assert len(affinities) == len(tols)
+        has, term_off, expr_off, ekey, eop, val_off, vals = [], [0], [0], [], [], [0], []
+        for a in affinities:
+            has.append(0 if a is None else 1)
+            for term in (a or []):
+                for key, op, values in term:
+                    ekey.append(key); eop.append(op); vals.extend(values); val_off.append(len(vals))
+                expr_off.append(len(ekey))
+            term_off.append(len(expr_off) - 1)
+        arrs = [_arr(has, np.uint8)] + [_arr(x or [0], np.int32) for x in (term_off, expr_off, ekey, eop, val_off, vals)]
+        keep += arrs
+        cls.has_affinity = _ptr(arrs[0], C.c_uint8)
+        (cls.aff_term_off, cls.aff_expr_off, cls.aff_expr_key, cls.aff_expr_op, cls.aff_value_off, cls.aff_values) = (_ptr(x, C.c_int32) for x in arrs[1:])
+    return cls
 
 
 class Scheduler:
@@ -722,31 +756,7 @@ class Scheduler:
         put("scheduled_at_priority", scheduled_at_priority, np.int32, C.c_int32)
         put("run_timestamp", run_timestamp, np.int64, C.c_int64)
         put("away", away, np.uint8, C.c_uint8)   # cross-pool away jobs (context.IsHomeJob false)
-        cls = CReqClasses()
-        tols = class_tolerations if class_tolerations is not None else [[]]
-        sels = class_selectors if class_selectors is not None else [[] for _ in tols]
-        assert len(tols) == len(sels)
-        cls.n = len(tols)
-        off, (tk, to, tv, te) = _csr(tols, 4)
-        keep += [off, tk, to, tv, te]
-        cls.tol_off, cls.tol_key, cls.tol_op, cls.tol_value, cls.tol_effect = (_ptr(x, C.c_int32) for x in (off, tk, to, tv, te))
-        off2, (sk, sv) = _csr(sels, 2)
-        keep += [off2, sk, sv]
-        cls.sel_off, cls.sel_key, cls.sel_value = (_ptr(x, C.c_int32) for x in (off2, sk, sv))
-        if class_affinities is not None and any(a is not None for a in class_affinities):
-            assert len(class_affinities) == len(tols)
-            has, term_off, expr_off, ekey, eop, val_off, vals = [], [0], [0], [], [], [0], []
-            for a in class_affinities:
-                has.append(0 if a is None else 1)
-                for term in (a or []):
-                    for key, op, values in term:
-                        ekey.append(key); eop.append(op); vals.extend(values); val_off.append(len(vals))
-                    expr_off.append(len(ekey))
-                term_off.append(len(expr_off) - 1)
-            arrs = [_arr(has, np.uint8)] + [_arr(x or [0], np.int32) for x in (term_off, expr_off, ekey, eop, val_off, vals)]
-            keep += arrs
-            cls.has_affinity = _ptr(arrs[0], C.c_uint8)
-            (cls.aff_term_off, cls.aff_expr_off, cls.aff_expr_key, cls.aff_expr_op, cls.aff_value_off, cls.aff_values) = (_ptr(x, C.c_int32) for x in arrs[1:])
+        cls = _req_classes(class_tolerations, class_selectors, class_affinities, keep)
         self._check(self.lib.jobs_set(self.h, C.byref(s), C.byref(cls)))
         self.num_jobs = m
 
@@ -811,6 +821,25 @@ class Scheduler:
         out = np.zeros(8, np.int32)
         self._check(fn(self.h, _ptr(out, C.c_int32)))
         return dict(on=int(out[0]), added=int(out[1]), revived=int(out[2]), mask_rows=int(out[3]), derived_classes=int(out[4]), fit_shapes=int(out[5]), reason=int(out[6]))
+
+    def req_classes_append(self, tolerations, selectors=None, affinities=None):
+        """new requirement classes behind the resident ones, without jobs_set: per class its tolerations, node selector and (optional) required node affinity, as for
+        jobs_set's class_* keywords.  Returns the id of the first new class (the others follow in order).  Leaves the handle as jobs_set of the same job table with
+        the concatenated class list would; go on with jobs_append of the rows that name the new classes, or with round_prepare."""
+        fn = self._preemption_fn("req_classes_append")
+        keep = []
+        cls = _req_classes(list(tolerations), selectors, affinities, keep)
+        self._check(fn(self.h, C.byref(cls)))
+        return self.req_classes_append_stats()["classes"] - cls.n
+
+    def req_classes_append_stats(self):
+        """how the last req_classes_append ran; reason: why masks and fast structure were rebuilt (0 not rebuilt, 1 no node table / masks yet, 2 C crosses 64 on a handle
+        with the fast structure)"""
+        fn = self._preemption_fn("req_classes_append_stats")
+        out = np.zeros(8, np.int32)
+        self._check(fn(self.h, _ptr(out, C.c_int32)))
+        return dict(added=int(out[0]), by_type=int(out[1]), on_host=int(out[2]), moved=int(out[3]), rebuilt=int(out[4]), reason=int(out[5]), classes=int(out[6]),
+                    classes_ext=int(out[7]))
 
     def jobs_delete(self, rows, want_map=False):
         """syncState's delete of the jobs in a terminal state: rows `rows` leave the resident job table; the others keep their order and are renumbered densely (new id =

@@ -495,6 +495,29 @@ extern "C" int asched_internal_sa_mask(const SaArgs* a, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ------------------------------------------------------------------------------------------------ new requirement classes join the class mask (kernels_req_classes_append.h)
+// one wave per 64-node word, the workgroup's four waves take four consecutive words.  w is wave-uniform, so the loop over the new classes and the loop over a class's
+// node types are uniform and their loads are the same address in every lane; a lane keeps only its own bit of each word
+#define CA_FN __device__ static inline
+#include "kernels_req_classes_append.h"
+__global__ __launch_bounds__(MG_THREADS) void k_ca_rows(CaArgs a) {
+  const long long t = MG_IDX();
+  const int w = (int)(t >> 6), lane = (int)(threadIdx.x & 63);
+  if (w >= a.W) return;
+  const int n = 64 * w + lane;
+  uint64_t acc = 0;
+  for (int c = 0; c < a.dC; c++) {
+    const uint64_t word = caWord(a, c, w);
+    if (lane == 0) a.outMask[(size_t)(a.C0 + c) * a.W + w] = word;
+    acc |= caBit(a, c, word, lane);
+  }
+  if (a.nodeCls && n < a.N) a.nodeCls[n] |= acc;
+}
+extern "C" int asched_internal_ca_rows(const CaArgs* a, hipStream_t st) {
+  if (a->dC > 0 && a->W > 0) hipLaunchKernelGGL(k_ca_rows, dim3(mgBlocks((long long)a->W * 64)), dim3(MG_THREADS), 0, st, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ------------------------------------------------------------------------------------------------ rows leave the resident job table (kernels_jobs_delete.h)
 // mark / unmark, the three gathers (each reads the survivors' list once), the renumbering of a compacted list; the scans are plat_compact's kernels
 #define JD_FN __device__ static inline

@@ -31,6 +31,7 @@
 #include "kernels_jobs_patch.h"     // JpArgs and, in the CPU build of the tests, plat_jobs_patch
 #include "kernels_jobs_append.h"    // JaArgs and, in the CPU build of the tests, plat_jobs_append
 #include "kernels_shapes_append.h"  // SaArgs and, in the CPU build of the tests, plat_shapes_append
+#include "kernels_req_classes_append.h"   // CaArgs and, in the CPU build of the tests, plat_req_classes_append
 #include "kernels_jobs_delete.h"    // JdArgs and, in the CPU build of the tests, plat_jobs_delete
 #include "kernels_nodes_patch.h"    // NpArgs and, in the CPU build of the tests, plat_nodes_patch
 #include "kernels_nodes_delete.h"   // NdArgs and, in the CPU build of the tests, plat_nodes_delete
@@ -260,6 +261,9 @@ struct asched {
   std::vector<uint64_t> fsDelta, fsMin; std::vector<uint8_t> fsNever; std::vector<int32_t> fitOf; std::vector<ShapeReq> fitTab;
   std::map<std::tuple<uint64_t, uint64_t, int64_t, int64_t, int32_t, int32_t>, int32_t> fitIds;
   int64_t fsMinField[MAXK] = {0}, fsMinExtra[MAXE] = {0};
+  // ---- asched_req_classes_append (kernels_req_classes_append.h): new requirement classes behind the C resident ones
+  int32_t caStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_req_classes_append_stats
+  double caMs[2] = {0, 0}, caHostMs[2] = {0, 0};   // device ms of the new rows / the row copies; host ms of the taint scan / the tier-2 rows of the last call (ASCHED_CA_TIMES=1)
   double jaMs[3] = {0, 0, 0};        // device ms of row fill / sort / merge of the last append (ASCHED_JA_TIMES=1)
   DevBufs jpBufs; char* jpScratch = nullptr; size_t jpScratchBytes = 0;   // the entries, the sort array and the kept list of a patch: one block, kept between calls and only ever grown
   double jpMs[4] = {0, 0, 0, 0};     // device ms of the four passes of the last patch (ASCHED_JP_TIMES=1)
@@ -1232,6 +1236,25 @@ int32_t asched_set_label_value_ints(asched_t* h, int32_t n, const int32_t* ids, 
   for (int i = 0; i < n; i++) h->valueInts[ids[i]] = ints[i];
   return 0;
 }
+// class i of an asched_req_classes: its tolerations, node selector and required node affinity (asched_jobs_set, asched_req_classes_append)
+static int reqClassParse(asched* h, const asched_req_classes* c, int i, std::vector<HTol>& tol, std::vector<HSel>& sel, HAffinity& aff) {
+  if (c->tol_off) for (int k = c->tol_off[i]; k < c->tol_off[i + 1]; k++) tol.push_back({c->tol_key[k], c->tol_op[k], c->tol_value[k], c->tol_effect[k]});
+  if (c->sel_off) for (int k = c->sel_off[i]; k < c->sel_off[i + 1]; k++) sel.push_back({c->sel_key[k], c->sel_value[k]});
+  if (c->has_affinity && c->has_affinity[i]) {
+    aff.present = true;
+    for (int t = c->aff_term_off[i]; t < c->aff_term_off[i + 1]; t++) {
+      std::vector<HAffExpr> term;
+      for (int x = c->aff_expr_off[t]; x < c->aff_expr_off[t + 1]; x++) {
+        HAffExpr ex; ex.key = c->aff_expr_key[x]; ex.op = c->aff_expr_op[x];
+        if (ex.op < ASCHED_AFFINITY_OP_IN || ex.op > ASCHED_AFFINITY_OP_LT) return fail(h, ASCHED_ERR_UNSUPPORTED, "unknown node affinity operator");
+        ex.values.assign(c->aff_values + c->aff_value_off[x], c->aff_values + c->aff_value_off[x + 1]);
+        term.push_back(ex);
+      }
+      aff.terms.push_back(term);
+    }
+  }
+  return 0;
+}
 int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_classes* c) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat);
   if (h) { h->haveRoundResult = false; h->stateEpoch++; }
   fastInvalidate(h);
@@ -1257,21 +1280,9 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
   h->clsTol.assign(h->C, {}); h->clsSel.assign(h->C, {}); h->clsAff.clear();
   if (c && c->has_affinity) h->clsAff.assign(h->C, {});
   for (int i = 0; i < nc; i++) {
-    if (c->tol_off) for (int k = c->tol_off[i]; k < c->tol_off[i + 1]; k++) h->clsTol[i].push_back({c->tol_key[k], c->tol_op[k], c->tol_value[k], c->tol_effect[k]});
-    if (c->sel_off) for (int k = c->sel_off[i]; k < c->sel_off[i + 1]; k++) h->clsSel[i].push_back({c->sel_key[k], c->sel_value[k]});
-    if (c->has_affinity && c->has_affinity[i]) {
-      h->clsAff[i].present = true;
-      for (int t = c->aff_term_off[i]; t < c->aff_term_off[i + 1]; t++) {
-        std::vector<HAffExpr> term;
-        for (int x = c->aff_expr_off[t]; x < c->aff_expr_off[t + 1]; x++) {
-          HAffExpr ex; ex.key = c->aff_expr_key[x]; ex.op = c->aff_expr_op[x];
-          if (ex.op < ASCHED_AFFINITY_OP_IN || ex.op > ASCHED_AFFINITY_OP_LT) return fail(h, ASCHED_ERR_UNSUPPORTED, "unknown node affinity operator");
-          ex.values.assign(c->aff_values + c->aff_value_off[x], c->aff_values + c->aff_value_off[x + 1]);
-          term.push_back(ex);
-        }
-        h->clsAff[i].terms.push_back(term);
-      }
-    }
+    HAffinity aff;
+    if (int prc = reqClassParse(h, c, i, h->clsTol[i], h->clsSel[i], aff)) return prc;
+    if (aff.present) h->clsAff[i] = aff;
   }
   d.cfg.C = h->C;
   prof.lap("copy-in + classes");
@@ -1468,7 +1479,7 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
   d.unfeasible = h->jobBufs.alloc<uint8_t>(std::max(h->S, 1)); d.unfeasibleReason = h->jobBufs.alloc<int32_t>(std::max(h->S, 1));
   h->jobCap = M; h->gangCap = h->G; h->gangArrCap = (size_t)gangOff[h->G + 1]; h->gangJobsCap = gangJobs.size(); h->gangOffCap = gangOff.size();
   h->ordCap = ord.size(); h->ordSpareCap = 0; h->ordOffCap = h->ordOffHost.size(); h->gangOffHost = gangOff;
-  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats);
+  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->caStats, 0, sizeof h->caStats);
   h->jobsSet = true; h->prepared = false;
   h->jQPrioHost.swap(qprio); h->jSubmitHost.swap(submit); h->jRunTsHost.swap(runTs);   // (asched_jobs_patch uploads them when it is first called; nothing is copied here)
   prof.lap("uploads + per-job state allocation");
@@ -2040,6 +2051,191 @@ int32_t asched_jobs_append_shape_stats(asched_t* h, int32_t* out) {
   plat_enter(h->plat);
   for (int k = 0; k < 8; k++) out[k] = h->jasStats[k];
   out[0] = h->appendInPlace ? 1 : 0;
+  return 0;
+}
+
+// ---- asched_req_classes_append (kernels_req_classes_append.h): a submission whose (tolerations, node selector, required node affinity) set the table has not seen —
+// the requirement-class part of the scheduling key (internaltypes/podutils.go:52-72) in syncState's upsert.  The n classes get ids C .. C + n - 1 behind the C resident
+// real ones; the handle is left as asched_jobs_set of the same job table with the concatenated class list would leave it (DESIGN 3.17).  No resident row names a new
+// class, so shapes, shape mask, fit shapes, minima, key layout and job records stay; the class mask grows by n rows in a fresh block, the derived away classes (numbered
+// behind C by deriveAwayRows, in shape order) move up by n, and where the fast structure exists every node gains the bits of the new classes that match it.  Where that
+// cannot be exact the tail of jobs_set runs on the grown class list (the rebuild path of asched_jobs_append) and the statistics give the reason.
+int32_t asched_req_classes_append(asched_t* h, const asched_req_classes* more) {
+  if (!h) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  Dev& d = h->dev;
+  const int M = h->M;
+  // ---- every refusal before anything changes
+  if (!h->jobsSet) return fail(h, ASCHED_ERR_INVALID, "req_classes_append: no job table on this handle (jobs_set first)");
+  if (!more || more->n < 0) return fail(h, ASCHED_ERR_INVALID, "req_classes_append: bad arguments");
+  if (h->mkJobsBuilt) return fail(h, ASCHED_ERR_UNSUPPORTED, "req_classes_append: the job set carries the market order (jobs_set instead)");
+  const int n = more->n, C0 = h->C, Cext0 = h->Cext;
+  if ((long long)Cext0 + n > (1ll << 24)) return fail(h, ASCHED_ERR_UNSUPPORTED, "req_classes_append: more than 2^24 requirement classes");
+  const int C1 = C0 + n, W = d.cfg.W;
+  if (n > 0) {
+    auto ascending = [&](const int32_t* off, int len) { if (off[0] < 0) return false; for (int i = 0; i < len; i++) if (off[i] > off[i + 1]) return false; return true; };
+    if (!more->tol_off && (more->tol_key || more->tol_op || more->tol_value || more->tol_effect)) return fail(h, ASCHED_ERR_INVALID, "req_classes_append: toleration values without tol_off");
+    if (!more->sel_off && (more->sel_key || more->sel_value)) return fail(h, ASCHED_ERR_INVALID, "req_classes_append: selector values without sel_off");
+    if (more->tol_off && !ascending(more->tol_off, n)) return fail(h, ASCHED_ERR_INVALID, "req_classes_append: tol_off is not ascending");
+    if (more->sel_off && !ascending(more->sel_off, n)) return fail(h, ASCHED_ERR_INVALID, "req_classes_append: sel_off is not ascending");
+    if (more->tol_off && more->tol_off[n] > 0 && !(more->tol_key && more->tol_op && more->tol_value && more->tol_effect)) return fail(h, ASCHED_ERR_INVALID, "req_classes_append: tol_off without the toleration arrays");
+    if (more->sel_off && more->sel_off[n] > 0 && !(more->sel_key && more->sel_value)) return fail(h, ASCHED_ERR_INVALID, "req_classes_append: sel_off without the selector arrays");
+    if (more->has_affinity) {
+      bool any = false;
+      for (int i = 0; i < n; i++) any = any || more->has_affinity[i];
+      if (any) {
+        if (!more->aff_term_off || !more->aff_expr_off) return fail(h, ASCHED_ERR_INVALID, "req_classes_append: has_affinity without the term arrays");
+        if (!ascending(more->aff_term_off, n) || !ascending(more->aff_expr_off, more->aff_term_off[n])) return fail(h, ASCHED_ERR_INVALID, "req_classes_append: an affinity offset array is not ascending");
+        const int nx = more->aff_expr_off[more->aff_term_off[n]];
+        if (nx > 0 && !(more->aff_expr_key && more->aff_expr_op && more->aff_value_off)) return fail(h, ASCHED_ERR_INVALID, "req_classes_append: has_affinity without the expression arrays");
+        if (nx > 0 && (!ascending(more->aff_value_off, nx) || (more->aff_value_off[nx] > 0 && !more->aff_values))) return fail(h, ASCHED_ERR_INVALID, "req_classes_append: aff_value_off is not ascending or has no values");
+      }
+    }
+  }
+  std::vector<std::vector<HTol>> newTol(n); std::vector<std::vector<HSel>> newSel(n); std::vector<HAffinity> newAff(n);
+  bool anyAff = false;
+  for (int i = 0; i < n; i++) {
+    if (int prc = reqClassParse(h, more, i, newTol[i], newSel[i], newAff[i])) return prc;   // (an unknown affinity operator: jobs_set's own refusal)
+    anyAff = anyAff || newAff[i].present;
+  }
+  // (the rebuild path can refuse nothing here: layoutKeys reads no class, and LIT_TMAX is a property of a mask row — no row names a new class)
+  const bool haveMasks = h->nodesSet && h->dClassMask && h->dShapeClass && d.typeMask;
+  const bool haveFast = d.f.structOk && d.nodeCls;
+  int why = 0;
+  if (n > 0 && !haveMasks) why = 1;
+  else if (n > 0 && haveFast && C0 <= 64 && C1 > 64) why = 2;   // (buildFast requires C <= 64: the rebuild gives the structure up as jobs_set would)
+  const bool inPlace = n > 0 && !why;
+  // ---- the host mirrors with the grown class list (saved: a refusal for memory puts them back)
+  const auto tolSaved = h->clsTol; const auto selSaved = h->clsSel; const auto affSaved = h->clsAff;
+  const auto awayOffSaved = h->awayRowOff, awayClassSaved = h->awayRowClass, awayShapeSaved = h->awayRowShape;
+  auto undo = [&]() {
+    h->clsTol = tolSaved; h->clsSel = selSaved; h->clsAff = affSaved; h->awayRowOff = awayOffSaved; h->awayRowClass = awayClassSaved; h->awayRowShape = awayShapeSaved;
+    h->C = C0; d.cfg.C = C0; h->Cext = Cext0;
+  };
+  if (n > 0) {
+    h->clsTol.resize(C0); h->clsSel.resize(C0);
+    if (!h->clsAff.empty()) h->clsAff.resize(C0);
+    else if (anyAff) h->clsAff.assign(C0, {});   // (the first class with an affinity: every resident class has none)
+    for (int i = 0; i < n; i++) { h->clsTol.push_back(newTol[i]); h->clsSel.push_back(newSel[i]); if (!h->clsAff.empty()) h->clsAff.push_back(newAff[i]); }
+    h->C = C1; d.cfg.C = C1;
+    deriveAwayRows(h, d.cfg.hasAway != 0);   // (the same derived classes over the unchanged shape table, each id larger by n)
+  }
+  const int A = (int)h->awayRowClass.size(), Sext = h->S + A;
+  // ---- the rows of the new classes: decided per class.  Tier 1: by node type, on the device; tier 2: matched node by node here
+  std::vector<int32_t> typeOff(n + 1, 0), typeList, hostRow(n, -1); std::vector<uint64_t> hostRows;
+  int nT1 = 0, nT2 = 0;
+  h->caHostMs[0] = h->caHostMs[1] = 0;
+  if (inPlace) {
+    if (h->Cext != Cext0 + n || (int)awayClassSaved.size() != A) { undo(); return fail(h, ASCHED_ERR_INVALID, "req_classes_append: the derived classes of the handle do not follow from its shape table (jobs_set)"); }
+    int taintsIndexed = -1;   // every taint a resident node carries is in its node type: decided once, when the call has a candidate
+    for (int i = 0; i < n; i++) {
+      const int c = C0 + i;
+      bool byType = !newAff[i].present && !h->hasTypeOverride;
+      for (auto& sl : newSel[i]) byType = byType && h->indexedLabels.count(sl.key);
+      if (byType && taintsIndexed < 0) {
+        auto t0 = std::chrono::steady_clock::now();
+        taintsIndexed = 1;
+        if (!h->indexAllTaints) for (int v = 0; v < h->N && taintsIndexed; v++) for (auto& x : h->nodeTaints[v]) if (!h->indexedTaints.count(x.key)) { taintsIndexed = 0; break; }
+        h->caHostMs[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      }
+      byType = byType && taintsIndexed == 1;
+      typeOff[i] = (int32_t)typeList.size();
+      if (byType) {
+        for (size_t t = 0; t < h->types.size(); t++) if (h->types[t].numNodes > 0 && classMatchesType(h, c, h->types[t])) typeList.push_back((int32_t)t);
+        nT1++;
+      } else {
+        auto t0 = std::chrono::steady_clock::now();
+        hostRow[i] = nT2++;
+        hostRows.resize((size_t)nT2 * W, 0);
+        uint64_t* row = hostRows.data() + (size_t)hostRow[i] * W;
+        for (int v = 0; v < h->N; v++) if (classMatchesNode(h, c, v)) row[v >> 6] |= 1ull << (v & 63);
+        h->caHostMs[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      }
+    }
+    typeOff[n] = (int32_t)typeList.size();
+  }
+  // ---- every new device block before anything changes on the device
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t oTypes = up(4 * (size_t)(n + 1)), oHostRow = oTypes + up(4 * std::max<size_t>(typeList.size(), 1)), oRows = oHostRow + up(4 * (size_t)std::max(n, 1)),
+               scratchBytes = oRows + up(8 * std::max<size_t>(hostRows.size(), 1));
+  uint64_t* mask1 = nullptr; char* scratch = nullptr;
+  if (inPlace) {
+    mask1 = (uint64_t*)plat_malloc(8 * (size_t)std::max(h->Cext, 1) * W);
+    scratch = mask1 ? (char*)plat_malloc(scratchBytes) : nullptr;
+    if (!mask1 || !scratch) {
+      (void)plat_take_failure();
+      if (mask1) plat_free(mask1);
+      undo();
+      return fail(h, ASCHED_ERR_DEVICE, "req_classes_append: out of device memory for the grown class mask; the handle is as it was");
+    }
+  }
+  // ---- what jobs_set resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the class tables half grown: asched_jobs_set before anything else)
+  h->haveRoundResult = false; h->stateEpoch++;
+  if (why) fastInvalidate(h);
+  else { d.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
+    int32_t zero = 0;
+    plat_h2d(&d.rs->fastActive, &zero, sizeof zero);
+    plat_h2d(&d.rs->l0SaveCount, &zero, sizeof zero); }
+  h->prepared = false; h->evrSized = false;
+  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats);
+  h->caMs[0] = h->caMs[1] = 0;
+  { int32_t* t = h->caStats;
+    t[0] = n; t[1] = nT1; t[2] = nT2; t[3] = inPlace ? Cext0 - C0 : 0; t[4] = why ? 1 : 0; t[5] = why; t[6] = h->C; t[7] = h->Cext; }
+  if (inPlace) {
+    plat_h2d(scratch, typeOff.data(), 4 * typeOff.size());
+    if (!typeList.empty()) plat_h2d(scratch + oTypes, typeList.data(), 4 * typeList.size());
+    plat_h2d(scratch + oHostRow, hostRow.data(), 4 * hostRow.size());
+    if (!hostRows.empty()) plat_h2d(scratch + oRows, hostRows.data(), 8 * hostRows.size());
+    CaArgs a; memset(&a, 0, sizeof a);
+    a.N = h->N; a.W = W; a.C0 = C0; a.dC = n;
+    a.typeMask = d.typeMask; a.typeOff = (const int32_t*)scratch; a.types = (const int32_t*)(scratch + oTypes);
+    a.hostRow = (const int32_t*)(scratch + oHostRow); a.hostRows = (const uint64_t*)(scratch + oRows);
+    a.outMask = mask1; a.nodeCls = haveFast && C1 <= 64 ? d.nodeCls : nullptr;
+    a.inMask = h->dClassMask; a.copy0 = (long long)C0 * W; a.src1 = (long long)C0 * W; a.dst1 = (long long)C1 * W; a.copy1 = (long long)(Cext0 - C0) * W;
+    const int src = plat_take_failure() ? -1 : plat_req_classes_append(d, a);
+    if (src) { plat_free(scratch); plat_free(mask1); return fail(h, ASCHED_ERR_DEVICE, plat_last_error()); }
+    plat_req_classes_append_ms(h->caMs);
+#ifdef ASCHED_HOSTSIM
+    { // the CPU build: every row decided by node type against the node-by-node match
+      std::vector<uint64_t> got((size_t)n * W);
+      plat_d2h(got.data(), mask1 + (size_t)C0 * W, got.size() * 8);
+      for (int i = 0; i < n; i++) if (hostRow[i] < 0)
+        for (int v = 0; v < h->N; v++)
+          if ((int)((got[(size_t)i * W + (v >> 6)] >> (v & 63)) & 1) != (classMatchesNode(h, C0 + i, v) ? 1 : 0)) {
+            fprintf(stderr, "hostsim: req_classes_append: class %d decided by node type differs from classMatchesNode on node %d\n", C0 + i, v); abort(); }
+    }
+#endif
+    for (size_t k = 0; k < h->maskBufs.ptrs.size(); k++) if (h->maskBufs.ptrs[k].first == h->dClassMask) { h->maskBufs.ptrs.erase(h->maskBufs.ptrs.begin() + k); break; }
+    plat_free(h->dClassMask);
+    h->dClassMask = mask1; h->maskBufs.ptrs.push_back({mask1, 8 * (size_t)std::max(h->Cext, 1) * W});
+    plat_free(scratch);
+    if (Cext0 > C0 && Sext > 0) {   // the class of every mask row: the away rows name derived classes, whose ids moved
+      std::vector<int32_t> shapeClassExt = h->shapeClass;
+      shapeClassExt.insert(shapeClassExt.end(), h->awayRowClass.begin(), h->awayRowClass.end());
+      plat_h2d(h->dShapeClass, shapeClassExt.data(), 4 * shapeClassExt.size());
+    }
+    if (const char* e = getenv("ASCHED_CA_TIMES")) if (e[0] == '1')
+      fprintf(stderr, "[asched req_classes_append] nodes %d classes %d (by node type %d, on the host %d), derived rows moved %d: new rows %.4f ms, row copies %.4f ms; host: taint scan %.4f ms, host rows %.4f ms\n",
+              h->N, n, nT1, nT2, Cext0 - C0, h->caMs[0], h->caMs[1], h->caHostMs[0], h->caHostMs[1]);
+  }
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  d.cfg.Q = 0;
+  if (why) {   // the tail of jobs_set on the grown class list
+    int rc = rebuildMasks(h);
+    if (rc) return rc;
+    rc = runControl(h, CMD_UPSERT_RESET);
+    if (rc) return rc;
+    rc = runControl(h, CMD_RESET_JOBS);
+    h->allocPristine = h->nodesSet;
+    h->evictedDirty = false;
+    return rc;
+  }
+  return resetDynamicState(h, M);
+}
+int32_t asched_req_classes_append_stats(asched_t* h, int32_t* out) {
+  if (!h || !out) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  for (int k = 0; k < 8; k++) out[k] = h->caStats[k];
   return 0;
 }
 

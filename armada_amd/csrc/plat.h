@@ -101,6 +101,12 @@ static void plat_jobs_append_ms(double* out /*[3]*/);   // measurement hook: dev
 struct SaArgs;
 static int plat_shapes_append(Dev& d, SaArgs& a);
 static void plat_shapes_append_ms(double* out /*[2]*/);   // measurement hook: device ms of the new mask rows / the row copies of the last call (events around them when ASCHED_JA_TIMES=1, else zeros)
+// new requirement classes join the class mask (kernels_req_classes_append.h): the resident rows copied device to device into the fresh block a.outMask (the derived
+// classes' rows dC rows further up), then the new rows and, where a.nodeCls is given, the new bits of every node, one wave per 64-node word.  Synchronous: the fresh
+// block is complete on return; of what the handle points to only a.nodeCls is written.  The CPU build's definition sits in kernels_req_classes_append.h.
+struct CaArgs;
+static int plat_req_classes_append(Dev& d, CaArgs& a);
+static void plat_req_classes_append_ms(double* out /*[2]*/);   // measurement hook: device ms of the new rows / the row copies of the last call (events around them when ASCHED_CA_TIMES=1, else zeros)
 // rows leave the resident job table (kernels_jobs_delete.h): mark, scan (plat_compact over the keep flags into a.src / a.newId; its count must be a.M1), the gather of the
 // static per-job arrays into the blocks of a.out*, the compaction and renumbering of the order (a.ordOut) and of the gang lists (a.gangOut), unmark.  Synchronous: everything
 // is complete on return.  The CPU build's definition sits in kernels_jobs_delete.h.

@@ -34,6 +34,7 @@ struct PlatCtx {
   hipEvent_t evrEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool evrTimed[3] = {false, false, false};   // ASCHED_EVR_TIMES=1: around the passes of the evictor report
   hipEvent_t jaEv[4] = {nullptr, nullptr, nullptr, nullptr}; bool jaTimed = false;   // ASCHED_JA_TIMES=1: around the passes of the job-table append
   hipEvent_t saEv[3] = {nullptr, nullptr, nullptr}; bool saTimed = false;   // ASCHED_JA_TIMES=1: around the row copies and the mask rows of an in-place append of new shapes
+  hipEvent_t caEv[3] = {nullptr, nullptr, nullptr}; bool caTimed = false;   // ASCHED_CA_TIMES=1: around the row copies and the new rows of asched_req_classes_append
   hipEvent_t jpEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool jpTimed = false;  // ASCHED_JP_TIMES=1: around the passes of the job-table patch
   hipEvent_t ndEv[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool ndTimed = false;   // ASCHED_ND_TIMES=1: around the passes of the node-table delete
   hipEvent_t naEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool naTimed = false;   // ASCHED_NA_TIMES=1: around the passes of the node-table append
@@ -259,6 +260,7 @@ static void plat_close(PlatCtx* c) {
   for (hipEvent_t e : c->jpEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->jaEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->saEv) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->caEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->npEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->jdEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ndEv) if (e) (void)hipEventDestroy(e);
@@ -984,6 +986,38 @@ static int plat_shapes_append(Dev& d, SaArgs& a) {
 static void plat_shapes_append_ms(double* out) {   // out[0]: the mask rows, out[1]: the copies
   hipEvent_t* ev = saEvents();
   for (int k = 0; k < 2; k++) { float ms = 0.f; if (ev && t_ctx->saTimed && hipEventElapsedTime(&ms, ev[1 - k], ev[2 - k]) != hipSuccess) ms = 0.f; out[k] = ms; }
+}
+// new requirement classes join the class mask (kernels_req_classes_append.h; k_ca_rows in armada_sched_mgpu.hip).  ASCHED_CA_TIMES=1 puts events around the row copies
+// and the new rows (tools/probe_req_classes_append.py).
+#include "kernels_req_classes_append.h"
+extern "C" int asched_internal_ca_rows(const CaArgs* a, hipStream_t s);
+static hipEvent_t* caEvents() {
+  static const bool on = [] { const char* e = getenv("ASCHED_CA_TIMES"); return e && e[0] == '1'; }();
+  PlatCtx* c = t_ctx;
+  if (!on) return nullptr;
+  if (!c->caEv[2]) for (int i = 0; i < 3; i++) if (!c->caEv[i] && hipEventCreate(&c->caEv[i]) != hipSuccess) { c->caEv[i] = nullptr; return nullptr; }
+  return c->caEv;
+}
+static int plat_req_classes_append(Dev& d, CaArgs& a) {
+  (void)d;
+  PlatCtx* c = t_ctx;
+  hipStream_t st = c->stream;
+  hipEvent_t* ev = caEvents();
+  c->caTimed = false;
+  if (ev) (void)hipEventRecord(ev[0], st);
+  if (a.copy0 > 0) plat_d2d(a.outMask, a.inMask, (size_t)a.copy0 * 8);
+  if (a.copy1 > 0) plat_d2d(a.outMask + a.dst1, a.inMask + a.src1, (size_t)a.copy1 * 8);
+  if (ev) (void)hipEventRecord(ev[1], st);
+  bool ok = asched_internal_ca_rows(&a, st) == 0;
+  if (ev) (void)hipEventRecord(ev[2], st);
+  ok = ok && hipOk(hipGetLastError(), "k_ca launch") && hipOk(hipStreamSynchronize(st), "k_ca");
+  if (!ok) { if (c->err.empty()) c->err = "k_ca_rows launch failed"; return -1; }
+  c->caTimed = ev != nullptr;
+  return 0;
+}
+static void plat_req_classes_append_ms(double* out) {   // out[0]: the new rows, out[1]: the copies
+  hipEvent_t* ev = caEvents();
+  for (int k = 0; k < 2; k++) { float ms = 0.f; if (ev && t_ctx->caTimed && hipEventElapsedTime(&ms, ev[1 - k], ev[2 - k]) != hipSuccess) ms = 0.f; out[k] = ms; }
 }
 // rows leave the resident job table (kernels_jobs_delete.h; k_jd_* in armada_sched_mgpu.hip, the scans are plat_compact's).  Each compaction brings its count back to the
 // host, which checks it against what the host counted before the next pass is sized by it.  ASCHED_JD_TIMES=1 puts events around the five passes (tools/probe_jobs_delete.py).

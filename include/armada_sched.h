@@ -427,6 +427,28 @@ int32_t ASCHED_FN(set_append_in_place)(asched_t*, int32_t on);
    masks yet, 2 the key layout of the grown table differs, 3 the batch turns away rows on for a table that had none, 4 more than SMAX fit shapes, 5 a negative
    request on a handle with the fast structure, 6 the table had no rows or shapes — [7] 0 (reserved).  [1..7] are zero after jobs_set; [0] is always the switch. */
 int32_t ASCHED_FN(jobs_append_shape_stats)(asched_t*, int32_t* out /*[8]*/);
+/* New requirement classes without jobs_set.  A submission whose (tolerations, node selector, required node affinity) set the table has not seen — a new node
+   selector, a pin to a hostname, a new toleration — brings a requirement class: the selector / toleration / affinity part of the scheduling key
+   (internaltypes/podutils.go:52-72), which syncState's upsert of the new jobs (scheduler.go:539-549) carries into the jobDb.  `more` has the layout jobs_set takes;
+   its more->n classes get the ids C .. C + n - 1 behind the C resident real classes (C >= 1: a jobs_set without classes has the empty class 0), in their order.
+   Returns 0.  The handle is left as jobs_set of the same job table with the concatenated class list would leave it, including everything jobs_set resets (what
+   jobs_append resets for no rows; n == 0 performs the resets only); go on with jobs_append of the rows that name the new classes, or round_prepare.
+   No resident row names a new class, so shapes, shape mask, fit shapes, key layout and job records stay.  The class mask grows by n rows in a fresh block: the
+   resident rows are copied device to device, the derived away classes behind C move up by n, and a new row is decided by node type on the device (the OR of the
+   node-type mask rows of the types the class matches) where the class has no required affinity, every selector key is an indexed label key, every taint a
+   resident node carries is indexed and the node table came without node_type_override; otherwise the host matches it node by node and uploads the row.  Where
+   the fast structure exists every node gains the bits of the new classes that match it.  Where that cannot be exact the tail of jobs_set runs on the grown class
+   list and asched_req_classes_append_stats gives the reason; the result is the same.  A handle without the fast structure takes the mask part only.
+   Refused before anything changes: no job table, more == NULL, n < 0, a CSR offset array that is missing where its values are given or that is not ascending,
+   has_affinity without the term arrays (ASCHED_ERR_INVALID); an unknown affinity operator, a job set that carries the market order (ASCHED_ERR_UNSUPPORTED); no
+   device memory for the fresh class mask (ASCHED_ERR_DEVICE, the handle is as it was).  A launch or copy that fails later is ASCHED_ERR_DEVICE and the handle
+   then needs asched_jobs_set, as documented for jobs_patch. */
+int32_t ASCHED_FN(req_classes_append)(asched_t*, const asched_req_classes* more);
+/* how the last req_classes_append ran: out[0] classes added, [1] rows decided by node type on the device, [2] rows matched on the host, [3] derived rows moved,
+   [4] 1 = masks and fast structure were rebuilt, [5] why — 0 not rebuilt, 1 no node table or no masks yet (the classes are kept on the host and the next
+   nodes_upsert builds everything), 2 the call takes C from at most 64 to more than 64 on a handle with the fast structure — [6] C after the call, [7] C plus the
+   derived away classes after the call.  Zeros after jobs_set. */
+int32_t ASCHED_FN(req_classes_append_stats)(asched_t*, int32_t* out /*[8]*/);
 /* syncState's delete of the jobs in a terminal state from the jobDb, after the upserts of the same cycle (scheduler.go:539-549; Txn.BatchDelete / delete,
    jobdb/jobdb.go:941-990): the n rows job[0..n) leave the table.  The remaining rows keep their order and are renumbered densely: new id = old id - number of
    deleted rows below it.  new_id, when not NULL, receives that map for the M rows the table had before the call, -1 for a deleted row.

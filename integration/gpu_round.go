@@ -614,7 +614,55 @@ func (g *GpuRound) UploadJobs(jobs []*jobdb.Job, queueIndex map[string]int32) er
 			}
 		}
 	}
-	// requirement classes as CSR
+	csr := marshalClasses(classes) // requirement classes as CSR
+	var pins runtime.Pinner
+	defer pins.Unpin()
+	pin32 := func(s []int32) *C.int32_t {
+		if len(s) > 0 {
+			pins.Pin(&s[0])
+		}
+		return i32p(s)
+	}
+	var cls C.asched_req_classes
+	csr.set(&cls, &pins)
+	var in C.asched_jobs
+	in.m = C.int32_t(m)
+	if m > 0 {
+		pins.Pin(&qprio[0]); pins.Pin(&submit[0]); pins.Pin(&runTs[0]); pins.Pin(&req[0])
+		in.queue, in.pc, in.req_class = pin32(queue), pin32(pc), pin32(reqClassIdx)
+		in.queue_priority = (*C.uint32_t)(unsafe.Pointer(&qprio[0]))
+		in.submit_time, in.run_timestamp, in.req = i64p(submit), i64p(runTs), i64p(req)
+		in.gang_id, in.gang_cardinality, in.gang_uniformity_label = pin32(gangId), pin32(gangCard), pin32(gangUni)
+		in.node, in.scheduled_at_priority = pin32(node), pin32(runPrio)
+		if anyAway {
+			pins.Pin(&away[0])
+			in.away = (*C.uint8_t)(unsafe.Pointer(&away[0]))
+		}
+		if g.market != nil && g.market.Enabled { // job.GetBidPrice(pool) as the job stands now (jobdb/job.go:459-481): queued / running / non-preemptible-running bid
+			bid := make([]float64, m)
+			for i, job := range jobs {
+				bid[i] = job.GetBidPrice(g.pool)
+			}
+			pins.Pin(&bid[0])
+			in.bid_price = f64p(bid)
+		}
+	}
+	if err := g.uploadLabelValueInts(); err != nil { // Gt / Lt compare integers: every interned string that parses, before the masks are built
+		return err
+	}
+	return g.check(C.asched_jobs_set(g.h, &in, &cls))
+}
+
+// classCSR is a list of requirement classes in the layout of asched_req_classes (UploadJobs: the whole list; AppendJobs: the classes a batch brings)
+type classCSR struct {
+	n                                                                 int
+	tolOff, tolKey, tolOp, tolVal, tolEff, selOff, selKey, selVal     []int32
+	affTermOff, exprOff, exprKey, exprOp, valueOff, values            []int32
+	hasAff                                                            []uint8
+	anyAff                                                            bool
+}
+
+func marshalClasses(classes []reqClass) *classCSR {
 	nc := len(classes)
 	tolOff, selOff, affTermOff := make([]int32, 1, nc+1), make([]int32, 1, nc+1), make([]int32, 1, nc+1)
 	var tolKey, tolOp, tolVal, tolEff, selKey, selVal, exprKey, exprOp, values []int32
@@ -649,50 +697,27 @@ func (g *GpuRound) UploadJobs(jobs []*jobdb.Job, queueIndex map[string]int32) er
 		}
 		affTermOff = append(affTermOff, int32(len(exprOff)-1))
 	}
-	var pins runtime.Pinner
-	defer pins.Unpin()
+	return &classCSR{n: nc, tolOff: tolOff, tolKey: tolKey, tolOp: tolOp, tolVal: tolVal, tolEff: tolEff, selOff: selOff, selKey: selKey, selVal: selVal,
+		affTermOff: affTermOff, exprOff: exprOff, exprKey: exprKey, exprOp: exprOp, valueOff: valueOff, values: values, hasAff: hasAff, anyAff: anyAff}
+}
+
+// set points cls at the arrays, pinned for the duration of the call
+func (c *classCSR) set(cls *C.asched_req_classes, pins *runtime.Pinner) {
 	pin32 := func(s []int32) *C.int32_t {
 		if len(s) > 0 {
 			pins.Pin(&s[0])
 		}
 		return i32p(s)
 	}
-	var cls C.asched_req_classes
-	cls.n = C.int32_t(nc)
-	cls.tol_off, cls.tol_key, cls.tol_op, cls.tol_value, cls.tol_effect = pin32(tolOff), pin32(tolKey), pin32(tolOp), pin32(tolVal), pin32(tolEff)
-	cls.sel_off, cls.sel_key, cls.sel_value = pin32(selOff), pin32(selKey), pin32(selVal)
-	if anyAff {
-		pins.Pin(&hasAff[0])
-		cls.has_affinity = u8p(hasAff)
-		cls.aff_term_off, cls.aff_expr_off, cls.aff_expr_key, cls.aff_expr_op = pin32(affTermOff), pin32(exprOff), pin32(exprKey), pin32(exprOp)
-		cls.aff_value_off, cls.aff_values = pin32(valueOff), pin32(values)
+	cls.n = C.int32_t(c.n)
+	cls.tol_off, cls.tol_key, cls.tol_op, cls.tol_value, cls.tol_effect = pin32(c.tolOff), pin32(c.tolKey), pin32(c.tolOp), pin32(c.tolVal), pin32(c.tolEff)
+	cls.sel_off, cls.sel_key, cls.sel_value = pin32(c.selOff), pin32(c.selKey), pin32(c.selVal)
+	if c.anyAff {
+		pins.Pin(&c.hasAff[0])
+		cls.has_affinity = u8p(c.hasAff)
+		cls.aff_term_off, cls.aff_expr_off, cls.aff_expr_key, cls.aff_expr_op = pin32(c.affTermOff), pin32(c.exprOff), pin32(c.exprKey), pin32(c.exprOp)
+		cls.aff_value_off, cls.aff_values = pin32(c.valueOff), pin32(c.values)
 	}
-	var in C.asched_jobs
-	in.m = C.int32_t(m)
-	if m > 0 {
-		pins.Pin(&qprio[0]); pins.Pin(&submit[0]); pins.Pin(&runTs[0]); pins.Pin(&req[0])
-		in.queue, in.pc, in.req_class = pin32(queue), pin32(pc), pin32(reqClassIdx)
-		in.queue_priority = (*C.uint32_t)(unsafe.Pointer(&qprio[0]))
-		in.submit_time, in.run_timestamp, in.req = i64p(submit), i64p(runTs), i64p(req)
-		in.gang_id, in.gang_cardinality, in.gang_uniformity_label = pin32(gangId), pin32(gangCard), pin32(gangUni)
-		in.node, in.scheduled_at_priority = pin32(node), pin32(runPrio)
-		if anyAway {
-			pins.Pin(&away[0])
-			in.away = (*C.uint8_t)(unsafe.Pointer(&away[0]))
-		}
-		if g.market != nil && g.market.Enabled { // job.GetBidPrice(pool) as the job stands now (jobdb/job.go:459-481): queued / running / non-preemptible-running bid
-			bid := make([]float64, m)
-			for i, job := range jobs {
-				bid[i] = job.GetBidPrice(g.pool)
-			}
-			pins.Pin(&bid[0])
-			in.bid_price = f64p(bid)
-		}
-	}
-	if err := g.uploadLabelValueInts(); err != nil { // Gt / Lt compare integers: every interned string that parses, before the masks are built
-		return err
-	}
-	return g.check(C.asched_jobs_set(g.h, &in, &cls))
 }
 
 // ErrNeedsUpload is what AppendJobs answers for a batch the resident job table cannot take: the caller falls back to UploadJobs of the whole job set.
@@ -702,9 +727,10 @@ var ErrNeedsUpload = fmt.Errorf("the job table has to be uploaded again")
 // jobDb (scheduler.go:478-535; jobdb/jobdb.go:572-700).  The shim's cycle is AppendJobs(new submissions), PatchJobs(run-state changes), Schedule.  jobs: queued jobs
 // only, none of them uploaded before; sorted here by id — newly submitted ULIDs sort after the resident ones, and the batch's rows follow the table's.  A finished
 // job stays as a row without a run (it is in no queued list and takes no part in a round).  ErrNeedsUpload — UploadJobs instead — where the library would refuse or
-// the shim cannot know the row: the first cycle (no table), a market-driven pool, a job with a run, a job whose requirement class the last UploadJobs did not see
-// (the classes are those of the last asched_jobs_set), a job that joins a gang already in the table (a gang is submitted in one piece), an id that sorts in front
-// of a resident one.  Now and then the caller uploads anyway, to drop the rows of finished jobs.
+// the shim cannot know the row: the first cycle (no table), a market-driven pool, a job with a run, a job that joins a gang already in the table (a gang is submitted in one piece), an id that sorts in front
+// of a resident one.  A job whose requirement class the table has not seen — a new node selector, a hostname pin, a new toleration — brings the class first
+// (asched_req_classes_append: the selector / toleration / affinity part of the scheduling key, internaltypes/podutils.go:52-72), then joins like any other row.
+// Now and then the caller uploads anyway, to drop the rows of finished jobs.
 func (g *GpuRound) AppendJobs(jobs []*jobdb.Job, queueIndex map[string]int32) error {
 	if g.jobs == nil || g.gangIds == nil || (g.market != nil && g.market.Enabled) {
 		return ErrNeedsUpload
@@ -725,6 +751,8 @@ func (g *GpuRound) AppendJobs(jobs []*jobdb.Job, queueIndex map[string]int32) er
 	req := make([]int64, m*R)
 	gangId, gangCard, gangUni := make([]int32, m), make([]int32, m), make([]int32, m)
 	newGangs := map[string]int32{}
+	newClassIdx := map[string]int32{}
+	var newClasses []reqClass
 	for i, j := range jobs {
 		if !j.Queued() {
 			return ErrNeedsUpload
@@ -738,10 +766,14 @@ func (g *GpuRound) AppendJobs(jobs []*jobdb.Job, queueIndex map[string]int32) er
 		qprio[i] = j.Priority()
 		submit[i] = j.SubmitTime().UnixNano()
 		copy(req[i*R:], g.vec(j.AllResourceRequirements()))
-		key, _ := g.classKey(j)
+		key, rc := g.classKey(j)
 		ci, ok := g.classes[key]
-		if !ok {
-			return ErrNeedsUpload
+		if !ok { // a requirement class the table has not seen: it joins behind the resident ones (asched_req_classes_append below), in order of first occurrence
+			if ci, ok = newClassIdx[key]; !ok {
+				ci = int32(len(g.classes) + len(newClasses))
+				newClassIdx[key] = ci
+				newClasses = append(newClasses, rc)
+			}
 		}
 		reqClassIdx[i] = ci
 		gangId[i], gangCard[i], gangUni[i] = -1, 1, -1
@@ -766,6 +798,21 @@ func (g *GpuRound) AppendJobs(jobs []*jobdb.Job, queueIndex map[string]int32) er
 	pin32 := func(s []int32) *C.int32_t {
 		pins.Pin(&s[0])
 		return i32p(s)
+	}
+	if len(newClasses) > 0 {
+		// the new classes first, then the rows that name them: asched_req_classes_append gives them the ids len(g.classes) .. in this order, without the jobs_set of
+		// the whole table this batch used to cost (ErrNeedsUpload).  Both calls leave the handle as jobs_set would; a refusal of the second leaves classes without rows
+		if err := g.uploadLabelValueInts(); err != nil { // (an affinity of a new class may compare a label value interned since the last upload)
+			return err
+		}
+		var cls C.asched_req_classes
+		marshalClasses(newClasses).set(&cls, &pins)
+		if err := g.check(C.asched_req_classes_append(g.h, &cls)); err != nil {
+			return err
+		}
+		for k, id := range newClassIdx {
+			g.classes[k] = id
+		}
 	}
 	in.m = C.int32_t(m)
 	pins.Pin(&qprio[0]); pins.Pin(&submit[0]); pins.Pin(&req[0])
