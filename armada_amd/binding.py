@@ -264,6 +264,7 @@ ALL_SYMBOLS = [
     "round_preemption_causes", "preemption_join",
     "set_evictor_report", "round_evictor_report",
     "jobs_patch", "jobs_append", "jobs_append_stats", "jobs_delete", "jobs_delete_stats",
+    "jobs_reprioritise", "jobs_reprioritise_stats",
     "set_append_in_place", "jobs_append_shape_stats",
     "req_classes_append", "req_classes_append_stats",
     "nodes_patch", "nodes_patch_stats", "nodes_delete", "nodes_delete_stats", "nodes_append", "nodes_append_stats",
@@ -276,6 +277,7 @@ OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_d
                     "set_evictor_report", "round_evictor_report",   # (recorded by passes between the launches of the split round: tests/test_z_evictor_report.py restates it)
                     "jobs_patch", "jobs_append", "jobs_append_stats",   # (an incremental jobs_set: the oracle is given the whole table; tests/test_z_jobs_patch.py, test_z_jobs_append.py)
                     "jobs_delete", "jobs_delete_stats",                 # (likewise: tests/test_z_jobs_delete.py)
+                    "jobs_reprioritise", "jobs_reprioritise_stats",     # (likewise: tests/test_z_jobs_reprioritise.py)
                     "set_append_in_place", "jobs_append_shape_stats",   # (how jobs_append treats new shapes, not what it leaves: tests/test_z_jobs_append_shapes.py)
                     "req_classes_append", "req_classes_append_stats",   # (an incremental jobs_set: the oracle is given the whole class list; tests/test_z_req_classes_append.py)
                     "nodes_patch", "nodes_patch_stats",                 # (an incremental nodes_upsert, likewise: tests/test_z_nodes_patch.py)
@@ -476,6 +478,8 @@ class Library:
         f("set_evictor_report", C.c_int32, [C.c_void_p, C.c_int32])
         f("round_evictor_report", C.c_int32, [C.c_void_p, C.POINTER(CEvictorReport)])
         f("jobs_patch", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _i64p])
+        f("jobs_reprioritise", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _u32p])
+        f("jobs_reprioritise_stats", C.c_int32, [C.c_void_p, _i32p])
         f("jobs_append", C.c_int32, [C.c_void_p, C.POINTER(CJobs)])
         f("jobs_append_stats", C.c_int32, [C.c_void_p, _i32p])
         f("set_append_in_place", C.c_int32, [C.c_void_p, C.c_int32])
@@ -770,6 +774,23 @@ class Scheduler:
         sp = None if scheduled_at_priority is None else _arr(np.broadcast_to(np.asarray(scheduled_at_priority, dtype=np.int32), (n,)), np.int32)
         ts = None if run_timestamp is None else _arr(np.broadcast_to(np.asarray(run_timestamp, dtype=np.int64), (n,)), np.int64)
         self._check(fn(self.h, n, _ptr(jb, C.c_int32), _ptr(nd, C.c_int32), _ptr(sp, C.c_int32), _ptr(ts, C.c_int64)))
+
+    def jobs_reprioritise(self, jobs, queue_priority):
+        """`armadactl reprioritize` for resident jobs: rows `jobs` of the job table get the priority `queue_priority` within their queue (uint32; a scalar is given to
+        every row).  Leaves the handle as jobs_set of the edited table would; go on with round_prepare."""
+        fn = self._preemption_fn("jobs_reprioritise")
+        jb = _arr(jobs, np.int32).reshape(-1)
+        n = len(jb)
+        qp = _arr(np.broadcast_to(np.asarray(queue_priority, dtype=np.uint32), (n,)), np.uint32)
+        self._check(fn(self.h, n, _ptr(jb, C.c_int32), _ptr(qp, C.c_uint32)))
+
+    def jobs_reprioritise_stats(self):
+        """how the last jobs_reprioritise ran: entries, entries that name a row in the order, entries whose priority did not change, whether the call made the order-key
+        inputs resident (the first incremental call on the table), device ms of scatter / remove / sort / merge (measured with ASCHED_JP_TIMES=1, else zeros)"""
+        fn = self._preemption_fn("jobs_reprioritise_stats")
+        out = np.zeros(8, np.int32)
+        self._check(fn(self.h, _ptr(out, C.c_int32)))
+        return dict(entries=int(out[0]), in_order=int(out[1]), unchanged=int(out[2]), made_resident=int(out[3]), device_ms=[int(x) / 1000.0 for x in out[4:8]])
 
     def jobs_append(self, req, *, queue=None, pc=None, queue_priority=None, submit_time=None, req_class=None, gang_id=None, gang_cardinality=None,
                     gang_uniformity_label=None, node=None, scheduled_at_priority=None, run_timestamp=None, away=None, bid_price=None):

@@ -458,6 +458,18 @@ extern "C" int asched_internal_jp_merge(const Dev* d, const JpArgs* a, hipStream
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ------------------------------------------------------------------------------------------------ queue priorities of resident jobs change (kernels_jobs_reprioritise.h)
+// scatter + keys: one thread per entry, plain stores; the remove, the sort and the merge by rank are the patch's (plat_compact, asched_internal_jp_sort / _jp_merge on JrArgs::p)
+#include "kernels_jobs_reprioritise.h"
+__global__ __launch_bounds__(MG_THREADS) void k_jr_scatter(Dev d, JrArgs a) {
+  long long i = MG_IDX();
+  if (i < a.p.nb2) jrScatter(d, a, (int)i);
+}
+extern "C" int asched_internal_jr_scatter(const Dev* d, const JrArgs* a, hipStream_t st) {
+  if (a->p.nb2 > 0) hipLaunchKernelGGL(k_jr_scatter, dim3(mgBlocks(a->p.nb2)), dim3(MG_THREADS), 0, st, *d, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ------------------------------------------------------------------------------------------------ newly submitted jobs behind the resident job table (kernels_jobs_append.h)
 // row fill + keys; the sort and the merge by rank are the patch's (asched_internal_jp_sort / _jp_merge on JaArgs::p)
 #include "kernels_jobs_append.h"

@@ -29,6 +29,7 @@
 #include "kernels_preempt_join.h"   // PjArgs and, in the CPU build of the tests, plat_preempt_join
 #include "kernels_evict_report.h"   // EvrArgs and, in the CPU build of the tests, plat_evict_report
 #include "kernels_jobs_patch.h"     // JpArgs and, in the CPU build of the tests, plat_jobs_patch
+#include "kernels_jobs_reprioritise.h"   // JrArgs and, in the CPU build of the tests, plat_jobs_reprioritise
 #include "kernels_jobs_append.h"    // JaArgs and, in the CPU build of the tests, plat_jobs_append
 #include "kernels_shapes_append.h"  // SaArgs and, in the CPU build of the tests, plat_shapes_append
 #include "kernels_req_classes_append.h"   // CaArgs and, in the CPU build of the tests, plat_req_classes_append
@@ -267,6 +268,7 @@ struct asched {
   double jaMs[3] = {0, 0, 0};        // device ms of row fill / sort / merge of the last append (ASCHED_JA_TIMES=1)
   DevBufs jpBufs; char* jpScratch = nullptr; size_t jpScratchBytes = 0;   // the entries, the sort array and the kept list of a patch: one block, kept between calls and only ever grown
   double jpMs[4] = {0, 0, 0, 0};     // device ms of the four passes of the last patch (ASCHED_JP_TIMES=1)
+  int32_t jrStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_reprioritise_stats (kernels_jobs_reprioritise.h)
   // ---- asched_jobs_delete (kernels_jobs_delete.h).  A scheduling-key shape that lost its last row keeps its id with shapeRow[s] == -1 (an append that uses it goes
   // through the rebuild path); a gang that lost its last row keeps its dense id with no members and leaves gangMap
   int32_t jdStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_delete_stats
@@ -1479,7 +1481,7 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
   d.unfeasible = h->jobBufs.alloc<uint8_t>(std::max(h->S, 1)); d.unfeasibleReason = h->jobBufs.alloc<int32_t>(std::max(h->S, 1));
   h->jobCap = M; h->gangCap = h->G; h->gangArrCap = (size_t)gangOff[h->G + 1]; h->gangJobsCap = gangJobs.size(); h->gangOffCap = gangOff.size();
   h->ordCap = ord.size(); h->ordSpareCap = 0; h->ordOffCap = h->ordOffHost.size(); h->gangOffHost = gangOff;
-  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->caStats, 0, sizeof h->caStats);
+  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->caStats, 0, sizeof h->caStats);
   h->jobsSet = true; h->prepared = false;
   h->jQPrioHost.swap(qprio); h->jSubmitHost.swap(submit); h->jRunTsHost.swap(runTs);   // (asched_jobs_patch uploads them when it is first called; nothing is copied here)
   prof.lap("uploads + per-job state allocation");
@@ -1497,6 +1499,16 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
   h->evictedDirty = false;
   prof.lap("state reset launches");
   return rc;
+}
+
+// the first incremental call on a job table that is a patch or a reprioritise: the order-key inputs become resident as the host mirrors hold them, with the keep flags
+// and the second order buffer (all in jobBufs: gone with the job table).  total: length of ordAll
+static void jpMakeResident(asched* h, int total) {
+  const size_t M = (size_t)h->M;
+  h->jp.qprio = h->jobBufs.upload(h->jQPrioHost); h->jp.submit = h->jobBufs.upload(h->jSubmitHost); h->jp.runTs = h->jobBufs.upload(h->jRunTsHost);
+  h->jp.keep = h->jobBufs.allocRaw<uint8_t>(h->jobCap); plat_memset(h->jp.keep, 1, M);
+  h->jp.ordSpare = h->jobBufs.allocRaw<int32_t>(std::max<size_t>((size_t)total, h->ordCap)); h->ordSpareCap = std::max<size_t>((size_t)total, h->ordCap);   // (as long as the order: the two swap)
+  h->jp.built = true;
 }
 
 // jobdb.Txn.Upsert for run-state changes (scheduling/scheduling_algo.go:280-283 with the jobs of :956-981; jobdb/jobdb.go:572-700): the named rows get a new active run
@@ -1556,12 +1568,7 @@ int32_t asched_jobs_patch(asched_t* h, int32_t n, const int32_t* job, const int3
       const int j = job[i];
       h->jNode[j] = node[i]; h->jRunPrio[j] = scheduled_at_priority ? scheduled_at_priority[i] : 0; h->jRunTsHost[j] = run_timestamp ? run_timestamp[i] : 0;
     }
-    if (!h->jp.built) {   // first patch of this job table: the order-key inputs become resident (the run timestamps as patched above)
-      h->jp.qprio = h->jobBufs.upload(h->jQPrioHost); h->jp.submit = h->jobBufs.upload(h->jSubmitHost); h->jp.runTs = h->jobBufs.upload(h->jRunTsHost);
-      h->jp.keep = h->jobBufs.allocRaw<uint8_t>(h->jobCap); plat_memset(h->jp.keep, 1, (size_t)M);
-      h->jp.ordSpare = h->jobBufs.allocRaw<int32_t>(std::max<size_t>((size_t)total, h->ordCap)); h->ordSpareCap = std::max<size_t>((size_t)total, h->ordCap);   // (as long as the order: the two swap)
-      h->jp.built = true;
-    }
+    if (!h->jp.built) jpMakeResident(h, total);   // first patch of this job table: the order-key inputs become resident (the run timestamps as patched above)
     JpArgs a; memset(&a, 0, sizeof a);
     a.M = M; a.n = n; a.nT = nT; a.total = total; a.nb2 = nb2;
     std::vector<int32_t> prioZero; std::vector<int64_t> tsZero;
@@ -1584,6 +1591,89 @@ int32_t asched_jobs_patch(asched_t* h, int32_t n, const int32_t* job, const int3
   // job dynamic state: everything unbound until round_prepare, as at the end of jobs_set
   d.cfg.Q = 0;
   return resetDynamicState(h, M);
+}
+
+// `armadactl reprioritize` for resident jobs (jobdb/reconciliation.go:198-200 records the requested priority, scheduler.go:1198-1199 applies it with job.WithPriority,
+// jobdb/job.go:523; Txn.Upsert re-seats the job in its queue's sorted set, jobdb/jobdb.go:583-587 and :695-699): the named rows get a new queue priority, the second word
+// of the order key (jobdb/comparison.go:70-79), on the device (kernels_jobs_reprioritise.h).  Leaves the handle as asched_jobs_set would have, given the table with
+// queue_priority replaced in those rows.  Only ordAll depends on it: the scatter of this call, then the remove / sort / merge passes of the patch.
+int32_t asched_jobs_reprioritise(asched_t* h, int32_t n, const int32_t* job, const uint32_t* queue_priority) {
+  if (!h) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  const int M = h->M;
+  // ---- every refusal before anything changes
+  if (!h->jobsSet || h->jQPrioHost.size() != (size_t)M || h->jSubmitHost.size() != (size_t)M || h->jRunTsHost.size() != (size_t)M || h->jNode.size() != (size_t)M)
+    return fail(h, ASCHED_ERR_INVALID, "jobs_reprioritise: no job table on this handle (jobs_set first)");
+  if (n < 0 || (n > 0 && (!job || !queue_priority))) return fail(h, ASCHED_ERR_INVALID, "jobs_reprioritise: bad arguments");
+  if (h->mkJobsBuilt) return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_reprioritise: the job set carries the market order (jobs_set instead)");
+  if (n > (1 << 29)) return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_reprioritise: more than 2^29 entries");
+  if (h->jpSeen.size() != (size_t)M) h->jpSeen.assign(M, 0);
+  int seen = 0, nT = 0, nSame = 0;
+  const char* why = nullptr;
+  for (int i = 0; i < n; i++) {
+    const int j = job[i];
+    if (j < 0 || j >= M) { why = "jobs_reprioritise: a row outside the job table"; break; }
+    if (h->jpSeen[j]) { why = "jobs_reprioritise: a row named twice"; break; }
+    h->jpSeen[j] = 1; seen = i + 1;
+    if (h->jQueue[j] >= 0) nT++;
+    if (h->jQPrioHost[j] == queue_priority[i]) nSame++;
+  }
+  for (int i = 0; i < seen; i++) h->jpSeen[job[i]] = 0;
+  if (why) return fail(h, ASCHED_ERR_INVALID, why);
+  // the patch's scratch block, kept and only ever grown: the entries | the sort array | the kept rows.  Sized before anything changes: running out of device memory here is a refusal too
+  const int total = h->ordOffHost.empty() ? 0 : h->ordOffHost[std::min<size_t>((size_t)h->ordQueues, h->ordOffHost.size() - 1)];
+  int nb2 = n;
+  if (nT > 0) { nb2 = JP_TILE; while (nb2 < n) nb2 <<= 1; }
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t oKeys = up(sizeof(int32_t) * 2 * (size_t)n), oKept = oKeys + (nT > 0 ? up(sizeof(JpKey) * (size_t)nb2) : 0), need = oKept + (nT > 0 ? up(sizeof(int32_t) * (size_t)total) : 0);
+  if (n > 0 && h->jpScratchBytes < need) {
+    char* fresh = (char*)plat_malloc(need + need / 4);
+    if (!fresh) { (void)plat_take_failure(); return fail(h, ASCHED_ERR_DEVICE, "jobs_reprioritise: out of device memory for the scratch; the handle is as it was"); }
+    h->jpBufs.freeAll(); h->jpScratch = fresh; h->jpScratchBytes = need + need / 4;
+    h->jpBufs.ptrs.push_back({fresh, need + need / 4});
+  }
+  // ---- what jobs_set resets, as asched_jobs_patch.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the order half built: asched_jobs_set before anything else)
+  h->haveRoundResult = false; h->stateEpoch++;
+  { h->dev.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
+    int32_t zero = 0;
+    plat_h2d(&h->dev.rs->fastActive, &zero, sizeof zero);
+    plat_h2d(&h->dev.rs->l0SaveCount, &zero, sizeof zero); }
+  h->prepared = false;
+  Dev& d = h->dev;
+  for (int k = 0; k < 4; k++) h->jpMs[k] = 0;
+  const bool madeResident = n > 0 && !h->jp.built;
+  if (n > 0) {
+    // the host mirror: jobs_append and jobs_delete stage and squeeze it, and a later first build uploads it
+    for (int i = 0; i < n; i++) h->jQPrioHost[job[i]] = queue_priority[i];
+    if (!h->jp.built) jpMakeResident(h, total);   // first incremental call on this job table: the order-key inputs become resident (the priorities as replaced above)
+    JrArgs a; memset(&a, 0, sizeof a);
+    a.p.M = M; a.p.n = n; a.p.nT = nT; a.p.total = total; a.p.nb2 = nb2;
+    int32_t* e32 = (int32_t*)h->jpScratch;
+    plat_h2d(e32, job, sizeof(int32_t) * (size_t)n); plat_h2d(e32 + n, queue_priority, sizeof(uint32_t) * (size_t)n);
+    a.p.pJob = e32; a.pQPrio = (const uint32_t*)(e32 + n);
+    a.jQPrio = h->jp.qprio;
+    a.p.keep = h->jp.keep; a.p.jQPrio = h->jp.qprio; a.p.jSubmit = h->jp.submit; a.p.jRunTs = h->jp.runTs;
+    int32_t* keptBuf = nullptr;
+    if (nT > 0) { a.p.keys = (JpKey*)(h->jpScratch + oKeys); keptBuf = (int32_t*)(h->jpScratch + oKept); a.p.out = h->jp.ordSpare; }
+    int prc = plat_take_failure() ? -1 : plat_jobs_reprioritise(d, a, keptBuf);
+    if (prc) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+    if (nT > 0) { std::swap(d.ordAll, h->jp.ordSpare); std::swap(h->ordCap, h->ordSpareCap); }
+    plat_jobs_patch_ms(h->jpMs);
+    if (const char* e = getenv("ASCHED_JP_TIMES")) if (e[0] == '1')
+      fprintf(stderr, "[asched jobs_reprioritise] jobs %d entries %d in the order %d: scatter %.4f ms, remove %.4f ms, sort %.4f ms, merge %.4f ms\n", M, n, nT, h->jpMs[0], h->jpMs[1], h->jpMs[2], h->jpMs[3]);
+  }
+  { int32_t* t = h->jrStats;
+    t[0] = n; t[1] = nT; t[2] = nSame; t[3] = madeResident ? 1 : 0;
+    for (int k = 0; k < 4; k++) t[4 + k] = (int32_t)(h->jpMs[k] * 1000.0 + 0.5); }
+  // job dynamic state: everything unbound until round_prepare, as at the end of jobs_set
+  d.cfg.Q = 0;
+  return resetDynamicState(h, M);
+}
+int32_t asched_jobs_reprioritise_stats(asched_t* h, int32_t* out) {
+  if (!h || !out) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  for (int k = 0; k < 8; k++) out[k] = h->jrStats[k];
+  return 0;
 }
 
 // ---- asched_jobs_append (kernels_jobs_append.h): syncState's upsert of the newly submitted jobs (scheduler.go:478-535; jobdb/jobdb.go:572-700, the insertion into the
@@ -2177,7 +2267,7 @@ int32_t asched_req_classes_append(asched_t* h, const asched_req_classes* more) {
     plat_h2d(&d.rs->fastActive, &zero, sizeof zero);
     plat_h2d(&d.rs->l0SaveCount, &zero, sizeof zero); }
   h->prepared = false; h->evrSized = false;
-  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats);
+  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats);
   h->caMs[0] = h->caMs[1] = 0;
   { int32_t* t = h->caStats;
     t[0] = n; t[1] = nT1; t[2] = nT2; t[3] = inPlace ? Cext0 - C0 : 0; t[4] = why ? 1 : 0; t[5] = why; t[6] = h->C; t[7] = h->Cext; }

@@ -117,8 +117,8 @@ JP_FN void jpMerge(const Dev& d, const JpArgs& a, long long i) {
 #ifdef ASCHED_HOSTSIM
 // ---- the CPU build's plat_jobs_patch (plat.h): the same per-element functions, one element after the other; the sort is the standard library's
 // a.nT == 0 (no entry names a row of a queue): a.keys == nullptr, a.nb2 == a.n, and the order is left alone
-static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf) {
-  for (int i = 0; i < a.nb2; i++) jpScatter(d, a, i);
+// plat_jobs_reseat: everything behind the scatter — remove, sort, merge by rank (asched_jobs_reprioritise, kernels_jobs_reprioritise.h, ends with the same passes)
+static int plat_jobs_reseat(Dev& d, JpArgs& a, int32_t* keptBuf) {
   a.kept = keptBuf; a.nKept = 0;
   if (a.nT > 0) {
     int nk = 0;
@@ -130,6 +130,10 @@ static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf) {
   const long long work = (long long)a.nT + a.nKept + a.n;
   for (long long i = 0; i < work; i++) jpMerge(d, a, i);
   return 0;
+}
+static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf) {
+  for (int i = 0; i < a.nb2; i++) jpScatter(d, a, i);
+  return plat_jobs_reseat(d, a, keptBuf);
 }
 static void plat_jobs_patch_ms(double* out) { out[0] = out[1] = out[2] = out[3] = 0; }
 #endif

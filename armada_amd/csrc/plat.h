@@ -90,6 +90,10 @@ static void plat_evict_report_ms(double* out /*[3]*/);   // measurement hook: de
 struct JpArgs;
 static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf);
 static void plat_jobs_patch_ms(double* out /*[4]*/);   // measurement hook: device ms of scatter / remove / sort / merge of the last call (events around them when ASCHED_JP_TIMES=1, else zeros)
+// queue priorities of resident jobs change (kernels_jobs_reprioritise.h): its scatter + keys, then the patch's remove, sort and merge by rank into a.p.out; fills
+// a.p.kept / a.p.nKept.  Synchronous: the new order is complete on return; plat_jobs_patch_ms reports its passes.  The CPU build's definition sits in kernels_jobs_reprioritise.h.
+struct JrArgs;
+static int plat_jobs_reprioritise(Dev& d, JrArgs& a, int32_t* keptBuf);
 // newly submitted jobs behind the resident job table (kernels_jobs_append.h): row fill + keys, the patch's sort, the patch's merge by rank of the old order (a.p.kept) and the
 // sorted new keys into a.p.out.  Synchronous: rows and order are complete on return.  The CPU build's definition sits in kernels_jobs_append.h.
 struct JaArgs;

@@ -894,13 +894,14 @@ static hipEvent_t* jpEvents() {
   if (!c->jpEv[4]) for (int i = 0; i < 5; i++) if (!c->jpEv[i] && hipEventCreate(&c->jpEv[i]) != hipSuccess) { c->jpEv[i] = nullptr; return nullptr; }
   return c->jpEv;
 }
-static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf) {
+// the four passes behind one another; scatter: the launch of the caller's scatter (the patch's or the reprioritise's), launched between the first two events
+template <class Scatter> static int jpPasses(Dev& d, JpArgs& a, int32_t* keptBuf, Scatter scatter) {
   PlatCtx* c = t_ctx;
   hipStream_t st = c->stream;
   hipEvent_t* ev = jpEvents();
   c->jpTimed = false;
   if (ev) (void)hipEventRecord(ev[0], st);
-  bool ok = asched_internal_jp_scatter(&d, &a, st) == 0;
+  bool ok = scatter(st) == 0;
   if (ev) (void)hipEventRecord(ev[1], st);
   a.kept = keptBuf; a.nKept = 0;
   if (ok && a.nT > 0) {
@@ -919,9 +920,19 @@ static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf) {
   c->jpTimed = ev != nullptr;
   return 0;
 }
+static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf) {
+  return jpPasses(d, a, keptBuf, [&](hipStream_t st) { return asched_internal_jp_scatter(&d, &a, st); });
+}
 static void plat_jobs_patch_ms(double* out) {
   hipEvent_t* ev = jpEvents();
   for (int k = 0; k < 4; k++) { float ms = 0.f; if (ev && t_ctx->jpTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
+}
+// queue priorities of resident jobs change (kernels_jobs_reprioritise.h; k_jr_scatter in armada_sched_mgpu.hip): its own scatter, then the patch's remove, sort and
+// merge.  The events and plat_jobs_patch_ms are the patch's (ASCHED_JP_TIMES=1; tools/probe_jobs_reprioritise.py).
+#include "kernels_jobs_reprioritise.h"
+extern "C" int asched_internal_jr_scatter(const Dev* d, const JrArgs* a, hipStream_t s);
+static int plat_jobs_reprioritise(Dev& d, JrArgs& a, int32_t* keptBuf) {
+  return jpPasses(d, a.p, keptBuf, [&](hipStream_t st) { return asched_internal_jr_scatter(&d, &a, st); });
 }
 // newly submitted jobs behind the resident job table (kernels_jobs_append.h; k_ja_fill in armada_sched_mgpu.hip, the sort and the merge are the patch's kernels).
 // ASCHED_JA_TIMES=1 puts events around the three passes (tools/probe_jobs_append.py).

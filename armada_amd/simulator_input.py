@@ -385,7 +385,7 @@ def run_cycles_arriving_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[in
     return _run_cycles_arriving(lib, sim, per_cycle, max_cycles, False)
 
 
-def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, every, deleted, resident=None, in_place=False):
+def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, every, deleted, resident=None, in_place=False, reprio=None):
     from .binding import Scheduler
     wl = sim.workload
     m = wl.num_jobs
@@ -395,6 +395,7 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
     started = np.full(m, -1.0)
     done = np.zeros(m, bool)
     changed = np.zeros(m, bool)
+    qprio = np.zeros(m, np.uint32)                    # per JOB: the priority within its queue, which the events of run_cycles_reprioritising move
     job_of_row = np.zeros(0, np.int64)                # the driver's own row <-> job map: the table's rows are the jobs that arrived and were not deleted, in job order
     row_of_job = np.full(m, -1, np.int64)
     out = []
@@ -406,8 +407,11 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
 
     def table_args(jobs):
         running = node[jobs] >= 0
-        return dict(queue=wl.job_queue[jobs], pc=wl.job_pc[jobs], submit_time=wl.job_submit[jobs], node=node[jobs], scheduled_at_priority=np.where(running, run_prio[jobs], 0),
-                    run_timestamp=np.where(running, np.maximum(started[jobs], 0) * 1e9, 0).astype(np.int64))
+        a = dict(queue=wl.job_queue[jobs], pc=wl.job_pc[jobs], submit_time=wl.job_submit[jobs], node=node[jobs], scheduled_at_priority=np.where(running, run_prio[jobs], 0),
+                 run_timestamp=np.where(running, np.maximum(started[jobs], 0) * 1e9, 0).astype(np.int64))
+        if reprio is not None:
+            a["queue_priority"] = qprio[jobs]
+        return a
 
     def terminal(jobs):
         rows = np.nonzero(done[jobs])[0]
@@ -423,6 +427,11 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
         upto = int(np.searchsorted(arrive, cycle, side="right"))
         new = np.arange(have, upto)
         compact = cycle > 0 and cycle % max(1, int(every)) == 0 and resident != "held"
+        moved = []                                    # this cycle's reprioritise events, in the schedule's order: (jobs that have arrived, priority)
+        for ev in reprio or ():
+            if ev[0] == cycle:
+                jobs = np.asarray(ev[1], dtype=np.int64).reshape(-1)
+                moved.append((jobs[jobs < upto], int(ev[2])))
         if deleted:
             if cycle == 0:                            # the first cycle: jobs_set
                 s.jobs_set(wl.job_req[new], **table_args(new))
@@ -439,12 +448,19 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
             if len(jobs):
                 a = table_args(jobs)
                 s.jobs_patch(row_of_job[jobs].astype(np.int32), a["node"], a["scheduled_at_priority"], a["run_timestamp"])
+            for jobs, p in moved:                     # then the priorities requested since the last cycle (the rows still in the table)
+                qprio[jobs] = p
+                jobs = jobs[row_of_job[jobs] >= 0]
+                if len(jobs):
+                    s.jobs_reprioritise(row_of_job[jobs].astype(np.int32), p)
             gone = terminal(job_of_row) if compact else np.zeros(0, np.int64)
             if len(gone):                             # then the delete of the jobs in a terminal state, with the id map applied to the driver's table
                 new_id = s.jobs_delete(gone.astype(np.int32), want_map=True)
                 row_of_job[job_of_row] = new_id
                 job_of_row = job_of_row[new_id >= 0]
         else:
+            for jobs, p in moved:
+                qprio[jobs] = p
             job_of_row = np.concatenate([job_of_row, new])
             if compact:
                 job_of_row = np.delete(job_of_row, terminal(job_of_row))
@@ -495,6 +511,20 @@ def run_cycles_resident(lib, sim: SimulatorInput, per_cycle: Optional[int] = Non
     hold_finished they stay in the table and are named in `held` every cycle instead, which costs O(finished rows) per cycle.  in_place: as for run_cycles_arriving
     (shapes that the deletes emptied come back in place as well).  Records as run_cycles_compacting."""
     return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, 1, True, resident="held" if hold_finished else "delete", in_place=in_place)
+
+
+def run_cycles_reprioritising(lib, sim: SimulatorInput, events, per_cycle: Optional[int] = None, max_cycles: int = 1000):
+    """run_cycles_resident plus a schedule of `armadactl reprioritize` requests: events is a list of (cycle, jobs, priority) — the workload's rows `jobs` get the
+    priority `priority` within their queue (every job starts at 0).  A cycle's events are applied after its upserts (jobs_append, jobs_patch) and before its delete,
+    each with ONE Scheduler.jobs_reprioritise of the named jobs that are in the table; a job that has not arrived yet is not touched (the reference has no such job
+    to reprioritise).  Records as run_cycles_resident."""
+    return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, 1, True, resident="delete", reprio=list(events))
+
+
+def run_cycles_reprioritising_rebuilt(lib, sim: SimulatorInput, events, per_cycle: Optional[int] = None, max_cycles: int = 1000):
+    """the rebuilt counterpart of run_cycles_reprioritising: jobs_set of the live rows with their edited queue priorities in every cycle, then the same
+    round_prepare_resident.  Same rows, same records."""
+    return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, 1, False, resident="delete", reprio=list(events))
 
 
 def run_cycles_compacting_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000, every: int = 1):

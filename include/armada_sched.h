@@ -388,6 +388,26 @@ int32_t ASCHED_FN(jobs_set)(asched_t*, const asched_jobs* jobs, const asched_req
    No other field changes (a finished job stays as a row without a run until asched_jobs_delete removes it); newly submitted rows are appended with
    asched_jobs_append. */
 int32_t ASCHED_FN(jobs_patch)(asched_t*, int32_t n, const int32_t* job, const int32_t* node, const int32_t* scheduled_at_priority, const int64_t* run_timestamp);
+/* `armadactl reprioritize` for resident jobs, one job or a whole job set: jobdb/reconciliation.go:198-200 records the requested priority, scheduler.go:1198-1199
+   applies it (job.WithPriority(job.RequestedPriority()), jobdb/job.go:523), and Txn.Upsert takes the job out of its queue's sorted set and puts it back under the new
+   key (jobdb/jobdb.go:583-587, :695-699); the queue priority is the second word of that key (SchedulingOrderCompare, jobdb/comparison.go:70-79).
+   entry i: job[i] (row of the job table) now has queue_priority[i]; any uint32 value, 0 and 0xFFFFFFFF included.  Any row may be named: queued or running (the active
+   group of a queue is ordered by priority class, queue priority, run timestamp), a gang member, a cross-pool away row, a row of queue -1 (its stored priority changes
+   and it stays in no order).  An entry that repeats the row's current priority is legal and leaves the row where it is.
+   After a successful call the handle is in the state asched_jobs_set would have left, given the same job table with queue_priority replaced in the named rows and the
+   same requirement classes — for every entry point (rounds after either form of round_prepare, scheduling_order, round_queued, the NodeDb-level calls, the submit
+   check, the optimiser, a later jobs_patch / jobs_append / jobs_delete / nodes_* / req_classes_append in any order), including everything jobs_set and jobs_patch
+   reset; the caller goes on with round_prepare.  n == 0 performs the resets only.  Only the pre-sorted order depends on the queue priority: the work is on the device
+   and proportional to the job order — no static masks, no job-record upload, no sort of all jobs, no segment offset changes; the fast structure stays.
+   Refused before anything changes — ASCHED_ERR_INVALID: no job table, n < 0, n > 0 without job or queue_priority, a row outside [0, M), a row named twice;
+   ASCHED_ERR_UNSUPPORTED: the job set carries the market order, more than 2^29 entries; ASCHED_ERR_DEVICE with "the handle is as it was" in last_error: out of device
+   memory for the scratch.  Any other ASCHED_ERR_DEVICE (a failed launch or copy) is NOT such a refusal: the handle then needs asched_jobs_set, as documented for
+   jobs_patch.  No other field changes: queue, priority class, submit time, request and gang of a row are fixed for as long as it is in the table. */
+int32_t ASCHED_FN(jobs_reprioritise)(asched_t*, int32_t n, const int32_t* job, const uint32_t* queue_priority);
+/* how the last jobs_reprioritise ran: out[0] entries, [1] entries that name a row in the order (queue >= 0), [2] entries whose priority did not change, [3] 1 = this
+   call made the order-key inputs resident (the first incremental call on the job table), [4..7] device microseconds of scatter / remove / sort / merge (measured only
+   with ASCHED_JP_TIMES=1, else 0).  Zeros after jobs_set. */
+int32_t ASCHED_FN(jobs_reprioritise_stats)(asched_t*, int32_t* out /*[8]*/);
 /* syncState's upsert of the newly submitted jobs into the jobDb at the start of a cycle (scheduler.go:478-535; jobdb/jobdb.go:572-700, the insertion into the per-queue
    sorted set at :691-700): rows->m rows are added behind the M rows the handle holds; the new job ids are M .. M+m-1.  Rows must stay in ascending job-id order, as for
    jobs_set (newly submitted ULIDs sort after the resident ones; the caller sorts the batch).  The requirement classes are those of the last jobs_set.

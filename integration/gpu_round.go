@@ -891,6 +891,42 @@ func (g *GpuRound) PatchJobs(scheduled, preempted []*schedulercontext.JobSchedul
 	return g.check(C.asched_jobs_patch(g.h, C.int32_t(n), i32p(job), i32p(node), i32p(prio), i64p(ts)))
 }
 
+// ReprioritiseJobs tells the library the queue priorities `armadactl reprioritize` changed since the last cycle, for one job or a whole job set, without re-describing the
+// job set (asched_jobs_reprioritise): jobdb/reconciliation.go:198-200 records the requested priority and the scheduler applies it with
+// job.WithPriority(job.RequestedPriority()) (scheduler.go:1198-1199, jobdb/job.go:523); the caller passes the jobs it called WithPriority on, as they are after the call.
+// The library re-seats those rows in the per-queue order as Txn.Upsert does in the jobDb (jobdb/jobdb.go:583-587, :695-699); nothing else UploadJobs derived depends on
+// the queue priority.  Every job must be one of the last UploadJobs or of an AppendJobs since, each at most once; queued and running jobs alike.  ErrNeedsUpload on the
+// first cycle and on a market-driven pool (the library refuses a job set in market order).  In the sync step it stands beside PatchJobs, in either order, before
+// DeleteJobs.  Not compiled: there is no Go toolchain where the library is built.
+func (g *GpuRound) ReprioritiseJobs(jobs []*jobdb.Job) error {
+	if g.jobs == nil || (g.market != nil && g.market.Enabled) {
+		return ErrNeedsUpload
+	}
+	if g.jobRow == nil {
+		g.jobRow = make(map[string]int32, len(g.jobs))
+		for i, j := range g.jobs {
+			g.jobRow[j.Id()] = int32(i)
+		}
+	}
+	n := len(jobs)
+	if n == 0 {
+		return g.check(C.asched_jobs_reprioritise(g.h, 0, nil, nil))
+	}
+	row, prio := make([]int32, n), make([]uint32, n)
+	for i, j := range jobs {
+		r, ok := g.jobRow[j.Id()]
+		if !ok {
+			return fmt.Errorf("ReprioritiseJobs: job %s is not one of the uploaded jobs", j.Id())
+		}
+		row[i], prio[i] = r, j.Priority()
+		g.jobs[r] = j // (the object with the new priority: what a later UploadJobs of g.jobs would describe)
+	}
+	var pins runtime.Pinner
+	defer pins.Unpin()
+	pins.Pin(&row[0]); pins.Pin(&prio[0])
+	return g.check(C.asched_jobs_reprioritise(g.h, C.int32_t(n), i32p(row), (*C.uint32_t)(unsafe.Pointer(&prio[0]))))
+}
+
 // DeleteJobs drops the rows of jobs in a terminal state from the uploaded job table (asched_jobs_delete): what syncState does after its upserts, every cycle
 // (scheduler.go:539-549; Txn.BatchDelete / delete, jobdb/jobdb.go:941-990).  The shim's sync step is AppendJobs(new submissions), PatchJobs(run-state changes),
 // DeleteJobs(terminal jobs), then Schedule.  ids: each one of the last UploadJobs or of an AppendJobs since, at most once.  The library renumbers the remaining rows
