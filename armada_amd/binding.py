@@ -267,6 +267,7 @@ ALL_SYMBOLS = [
     "jobs_reprioritise", "jobs_reprioritise_stats",
     "set_append_in_place", "jobs_append_shape_stats",
     "req_classes_append", "req_classes_append_stats",
+    "shapes_compact", "shapes_compact_stats",
     "nodes_patch", "nodes_patch_stats", "nodes_delete", "nodes_delete_stats", "nodes_append", "nodes_append_stats",
     "round_prepare_resident", "round_queued",
 ]
@@ -280,10 +281,12 @@ OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_d
                     "jobs_reprioritise", "jobs_reprioritise_stats",     # (likewise: tests/test_z_jobs_reprioritise.py)
                     "set_append_in_place", "jobs_append_shape_stats",   # (how jobs_append treats new shapes, not what it leaves: tests/test_z_jobs_append_shapes.py)
                     "req_classes_append", "req_classes_append_stats",   # (an incremental jobs_set: the oracle is given the whole class list; tests/test_z_req_classes_append.py)
+                    "shapes_compact", "shapes_compact_stats",           # (the oracle is given the job table afresh and never holds a dead shape: tests/test_z_shapes_compact.py)
                     "nodes_patch", "nodes_patch_stats",                 # (an incremental nodes_upsert, likewise: tests/test_z_nodes_patch.py)
                     "nodes_delete", "nodes_delete_stats",               # (likewise: tests/test_z_nodes_delete.py)
                     "nodes_append", "nodes_append_stats",               # (likewise: tests/test_z_nodes_append.py)
                     "round_prepare_resident", "round_queued"}           # (the oracle has no resident table and is always given explicit lists: tests/test_z_round_prepare_resident.py)
+COMPACT_CLASSES, COMPACT_COUNT_ONLY = 1, 2   # ASCHED_COMPACT_* (asched_shapes_compact)
 PREEMPTION_UNKNOWN, PREEMPTION_UNKNOWN_GANG, PREEMPTION_FAIRSHARE, PREEMPTION_URGENCY, PREEMPTION_OPTIMISER = 1, 2, 3, 4, 5   # ASCHED_PREEMPTION_* (context.PreemptionType)
 # ASCHED_EVR_* bits of asched_evictor_report.node_reasons, in bit order: the reference's reason strings in alphabetical order (makeNodePreemptiblityStats sorts them)
 EVICTOR_REASONS = ("all_jobs_preemptible", "below_protected_fair_share", "invalid_queue", "job_not_preemptible", "node_empty", "node_unschedulable")
@@ -486,6 +489,8 @@ class Library:
         f("jobs_append_shape_stats", C.c_int32, [C.c_void_p, _i32p])
         f("req_classes_append", C.c_int32, [C.c_void_p, C.POINTER(CReqClasses)])
         f("req_classes_append_stats", C.c_int32, [C.c_void_p, _i32p])
+        f("shapes_compact", C.c_int32, [C.c_void_p, C.c_int32, _i32p])
+        f("shapes_compact_stats", C.c_int32, [C.c_void_p, _i32p])
         f("jobs_delete", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p])
         f("jobs_delete_stats", C.c_int32, [C.c_void_p, _i32p])
         f("nodes_patch", C.c_int32, [C.c_void_p, C.POINTER(CNodesPatch)])
@@ -665,6 +670,7 @@ class Scheduler:
         self.K = len(cfg.indexed_col)
         self.num_nodes = 0
         self.num_jobs = 0
+        self.num_classes = 0
         self.num_queues = 0
         self._keep = []
 
@@ -763,6 +769,7 @@ class Scheduler:
         cls = _req_classes(class_tolerations, class_selectors, class_affinities, keep)
         self._check(self.lib.jobs_set(self.h, C.byref(s), C.byref(cls)))
         self.num_jobs = m
+        self.num_classes = max(int(cls.n), 1)   # (a jobs_set without classes has the empty class 0)
 
     def jobs_patch(self, jobs, node, scheduled_at_priority=None, run_timestamp=None):
         """jobdb.Txn.Upsert for run-state changes: rows `jobs` of the resident job table now run on `node` (-1: no active run any more) at `scheduled_at_priority`,
@@ -851,7 +858,8 @@ class Scheduler:
         keep = []
         cls = _req_classes(list(tolerations), selectors, affinities, keep)
         self._check(fn(self.h, C.byref(cls)))
-        return self.req_classes_append_stats()["classes"] - cls.n
+        self.num_classes = self.req_classes_append_stats()["classes"]
+        return self.num_classes - cls.n
 
     def req_classes_append_stats(self):
         """how the last req_classes_append ran; reason: why masks and fast structure were rebuilt (0 not rebuilt, 1 no node table / masks yet, 2 C crosses 64 on a handle
@@ -861,6 +869,29 @@ class Scheduler:
         self._check(fn(self.h, _ptr(out, C.c_int32)))
         return dict(added=int(out[0]), by_type=int(out[1]), on_host=int(out[2]), moved=int(out[3]), rebuilt=int(out[4]), reason=int(out[5]), classes=int(out[6]),
                     classes_ext=int(out[7]))
+
+    def shapes_compact(self, classes=False, count_only=False, want_map=False):
+        """retire the scheduling-key shapes no resident row names (jobs_delete emptied them) with the fit shapes only they mapped to and, with classes=True, the
+        requirement classes only they named; the live ones keep their order and get dense ids.  Leaves the handle as jobs_set of the same job table (with the
+        reduced class list) would; go on with round_prepare or any resident call.  count_only: changes nothing, shapes_compact_stats then says what a call would
+        retire.  want_map (with classes): returns the old -> new class id map (int32 [classes before the call], -1 for a retired class), which the caller applies
+        to the class ids it passes to later jobs_append / req_classes_append calls."""
+        fn = self._preemption_fn("shapes_compact")
+        flags = (COMPACT_CLASSES if classes else 0) | (COMPACT_COUNT_ONLY if count_only else 0)
+        buf = np.full(max(int(getattr(self, "num_classes", 0)), 1), -2, np.int32) if (want_map and classes and not count_only) else None
+        self._check(fn(self.h, flags, _ptr(buf, C.c_int32)))
+        if classes and not count_only:
+            self.num_classes = getattr(self, "num_classes", 0) - self.shapes_compact_stats()["classes_retired"]
+        return buf
+
+    def shapes_compact_stats(self):
+        """how the last shapes_compact ran; reason: why masks and fast structure were rebuilt (0 not rebuilt, 1 no node table / masks yet, 2 the fit shapes came back
+        under SMAX, 3 the classes came back under 65).  After count_only: what a call would retire, and the current shapes / fit_shapes."""
+        fn = self._preemption_fn("shapes_compact_stats")
+        out = np.zeros(8, np.int32)
+        self._check(fn(self.h, _ptr(out, C.c_int32)))
+        return dict(shapes_retired=int(out[0]), fit_retired=int(out[1]), classes_retired=int(out[2]), derived_classes=int(out[3]), rebuilt=int(out[4]), reason=int(out[5]),
+                    shapes=int(out[6]), fit_shapes=int(out[7]))
 
     def jobs_delete(self, rows, want_map=False):
         """syncState's delete of the jobs in a terminal state: rows `rows` leave the resident job table; the others keep their order and are renumbered densely (new id =

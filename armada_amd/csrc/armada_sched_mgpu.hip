@@ -530,6 +530,53 @@ extern "C" int asched_internal_ca_rows(const CaArgs* a, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ------------------------------------------------------------------------------------------------ dead shapes and classes leave the resident tables (kernels_shapes_compact.h)
+// k_sc_rows: SC_RPB rows to a workgroup, thread t takes rows base + t, base + t + 256, ... (coalesced); the three maps from LDS where the launcher found that they fit
+// (a.staged: uniform over the grid, so every thread of a workgroup reaches the barrier or none does), else from global memory.  k_sc_gather: one thread per output
+// word.  k_sc_clsbits: one thread per node
+#define SC_FN __device__ static inline
+#include "kernels_shapes_compact.h"
+__global__ __launch_bounds__(MG_THREADS) void k_sc_rows(ScArgs a) {
+  __shared__ int32_t sS[SC_LDS_CAP], sF[SC_LDS_CAP], sC[SC_LDS_CAP];
+  const int32_t* mS = a.shapeNew; const int32_t* mF = a.fitNew; const int32_t* mC = a.clsNew;
+  if (a.staged) {
+    for (int i = threadIdx.x; i < a.S0 && i < SC_LDS_CAP; i += MG_THREADS) sS[i] = a.shapeNew[i];
+    if (a.fitNew) for (int i = threadIdx.x; i < a.F0 && i < SC_LDS_CAP; i += MG_THREADS) sF[i] = a.fitNew[i];
+    if (a.clsNew) for (int i = threadIdx.x; i < a.C0 && i < SC_LDS_CAP; i += MG_THREADS) sC[i] = a.clsNew[i];
+    __syncthreads();
+    mS = sS; if (a.fitNew) mF = sF; if (a.clsNew) mC = sC;
+  }
+  const long long base = (long long)blockIdx.x * SC_RPB;
+  for (int k = threadIdx.x; k < SC_RPB; k += MG_THREADS) {
+    const long long j = base + k;
+    if (j < a.M) scRow(a, (int)j, mS, mF, mC);
+  }
+}
+__global__ __launch_bounds__(MG_THREADS) void k_sc_gather(const uint64_t* in, uint64_t* out, const int32_t* src, int W, long long words) {
+  const long long i = MG_IDX();
+  if (i < words) scGather(in, out, src, W, i);
+}
+__global__ __launch_bounds__(MG_THREADS) void k_sc_clsbits(ScArgs a) {
+  const long long n = MG_IDX();
+  if (n < a.N) { const uint64_t in = a.nodeCls[n], v = scClsBits(in, a.liveCls); if (v != in) a.nodeCls[n] = v; }
+}
+extern "C" int asched_internal_sc_rows(const ScArgs* a, hipStream_t st) {
+  ScArgs x = *a; x.staged = scFits(x);
+  if (x.M > 0 && x.S0 > 0) hipLaunchKernelGGL(k_sc_rows, dim3((unsigned)(((long long)x.M + SC_RPB - 1) / SC_RPB)), dim3(MG_THREADS), 0, st, x);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_sc_gather(const ScArgs* a, hipStream_t st) {
+  if (a->shapeOut && a->shapeRows > 0 && a->W > 0)
+    hipLaunchKernelGGL(k_sc_gather, dim3(mgBlocks((long long)a->shapeRows * a->W)), dim3(MG_THREADS), 0, st, a->shapeIn, a->shapeOut, a->shapeSrc, a->W, (long long)a->shapeRows * a->W);
+  if (a->clsOut && a->clsRows > 0 && a->W > 0)
+    hipLaunchKernelGGL(k_sc_gather, dim3(mgBlocks((long long)a->clsRows * a->W)), dim3(MG_THREADS), 0, st, a->clsIn, a->clsOut, a->clsSrc, a->W, (long long)a->clsRows * a->W);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+extern "C" int asched_internal_sc_clsbits(const ScArgs* a, hipStream_t st) {
+  if (a->nodeCls && a->N > 0) hipLaunchKernelGGL(k_sc_clsbits, dim3(mgBlocks(a->N)), dim3(MG_THREADS), 0, st, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ------------------------------------------------------------------------------------------------ rows leave the resident job table (kernels_jobs_delete.h)
 // mark / unmark, the three gathers (each reads the survivors' list once), the renumbering of a compacted list; the scans are plat_compact's kernels
 #define JD_FN __device__ static inline

@@ -33,6 +33,7 @@
 #include "kernels_jobs_append.h"    // JaArgs and, in the CPU build of the tests, plat_jobs_append
 #include "kernels_shapes_append.h"  // SaArgs and, in the CPU build of the tests, plat_shapes_append
 #include "kernels_req_classes_append.h"   // CaArgs and, in the CPU build of the tests, plat_req_classes_append
+#include "kernels_shapes_compact.h"   // ScArgs and, in the CPU build of the tests, plat_shapes_compact
 #include "kernels_jobs_delete.h"    // JdArgs and, in the CPU build of the tests, plat_jobs_delete
 #include "kernels_nodes_patch.h"    // NpArgs and, in the CPU build of the tests, plat_nodes_patch
 #include "kernels_nodes_delete.h"   // NdArgs and, in the CPU build of the tests, plat_nodes_delete
@@ -265,6 +266,9 @@ struct asched {
   // ---- asched_req_classes_append (kernels_req_classes_append.h): new requirement classes behind the C resident ones
   int32_t caStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_req_classes_append_stats
   double caMs[2] = {0, 0}, caHostMs[2] = {0, 0};   // device ms of the new rows / the row copies; host ms of the taint scan / the tier-2 rows of the last call (ASCHED_CA_TIMES=1)
+  // ---- asched_shapes_compact (kernels_shapes_compact.h): dead shapes, fit shapes and requirement classes leave the resident tables
+  int32_t scStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_shapes_compact_stats
+  double scMs[3] = {0, 0, 0}, scHostMs = 0;        // device ms of rows / gathers / class bits, host ms of the mirror remap of the last call (ASCHED_SC_TIMES=1)
   double jaMs[3] = {0, 0, 0};        // device ms of row fill / sort / merge of the last append (ASCHED_JA_TIMES=1)
   DevBufs jpBufs; char* jpScratch = nullptr; size_t jpScratchBytes = 0;   // the entries, the sort array and the kept list of a patch: one block, kept between calls and only ever grown
   double jpMs[4] = {0, 0, 0, 0};     // device ms of the four passes of the last patch (ASCHED_JP_TIMES=1)
@@ -1482,6 +1486,7 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
   h->jobCap = M; h->gangCap = h->G; h->gangArrCap = (size_t)gangOff[h->G + 1]; h->gangJobsCap = gangJobs.size(); h->gangOffCap = gangOff.size();
   h->ordCap = ord.size(); h->ordSpareCap = 0; h->ordOffCap = h->ordOffHost.size(); h->gangOffHost = gangOff;
   memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->caStats, 0, sizeof h->caStats);
+  memset(h->scStats, 0, sizeof h->scStats);
   h->jobsSet = true; h->prepared = false;
   h->jQPrioHost.swap(qprio); h->jSubmitHost.swap(submit); h->jRunTsHost.swap(runTs);   // (asched_jobs_patch uploads them when it is first called; nothing is copied here)
   prof.lap("uploads + per-job state allocation");
@@ -2326,6 +2331,240 @@ int32_t asched_req_classes_append_stats(asched_t* h, int32_t* out) {
   if (!h || !out) return ASCHED_ERR_INVALID;
   plat_enter(h->plat);
   for (int k = 0; k < 8; k++) out[k] = h->caStats[k];
+  return 0;
+}
+
+// ---- asched_shapes_compact (kernels_shapes_compact.h): the shape and requirement-class tables of a resident handle only grow — asched_jobs_delete keeps an emptied
+// shape's id, mask rows and fit shape, the in-place append adds shapes, classes are append-only — while buildFast gives the fast structure up above SMAX fit shapes or 64
+// real classes.  This call retires what no resident row names: a shape with shapeRow[s] < 0, a fit shape no live shape maps to and, with ASCHED_COMPACT_CLASSES, a real
+// class no live shape names.  The live ones keep their relative order and get dense ids; the handle is left as asched_jobs_set of the same job table (with the reduced
+// class list) would leave it (DESIGN 3.19).  What is a bound or a union over rows and shapes stays: the key layout, the two minima, hasAway, the gang tables, the
+// capacities — removing shapes can only make the true value tighter, and every consumer reads them as bounds (DESIGN 3.12).
+//
+// buildFast's predicate without its two counts (F <= SMAX, C <= 64): asked only where one of the counts comes back under its limit on a handle without the structure
+static bool scQualifiesButCounts(asched* h) {
+  const Dev& d = h->dev;
+  int extra = 0;
+  for (int r = 0; r < h->R; r++) { bool idx = false; for (int c = 0; c < h->K; c++) idx = idx || h->indexedCol[c] == r; if (!idx) extra++; }
+  std::set<int32_t> distinctIdx(h->indexedCol.begin(), h->indexedCol.end());
+  if (!(h->N > 0 && h->M > 0 && !h->hasAllocByPrio && h->allocLeTotal && extra <= MAXE && (int)distinctIdx.size() == h->K && d.cfg.keyWords != 2)) return false;
+  for (int64_t v : h->jReq) if (v < 0) return false;
+  return true;
+}
+int32_t asched_shapes_compact(asched_t* h, int32_t flags, int32_t* class_new_id) {
+  if (!h) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  Dev& d = h->dev;
+  const int M = h->M, R = h->R, W = d.cfg.W;
+  // ---- every refusal before anything changes
+  if (!h->jobsSet || h->jShape.size() != (size_t)M || h->shapeRow.size() != (size_t)h->S || h->shapeClass.size() != (size_t)h->S || h->awayRowOff.size() != (size_t)h->S + 1)
+    return fail(h, ASCHED_ERR_INVALID, "shapes_compact: no job table on this handle (jobs_set first)");
+  if (flags & ~(ASCHED_COMPACT_CLASSES | ASCHED_COMPACT_COUNT_ONLY)) return fail(h, ASCHED_ERR_INVALID, "shapes_compact: unknown flag bits");
+  if (h->mkJobsBuilt) return fail(h, ASCHED_ERR_UNSUPPORTED, "shapes_compact: the job set carries the market order (jobs_set instead)");
+  if (M <= 0) return fail(h, ASCHED_ERR_UNSUPPORTED, "shapes_compact: the table has no rows, so every shape is dead (a handle holds at least one job: jobs_set of the next table instead)");
+  const bool withCls = (flags & ASCHED_COMPACT_CLASSES) != 0, countOnly = (flags & ASCHED_COMPACT_COUNT_ONLY) != 0;
+  const int S0 = h->S, C0 = h->C, Cext0 = h->Cext, A0 = (int)h->awayRowClass.size();
+  const bool haveMasks = h->nodesSet && h->dClassMask && h->dShapeClass && d.shapeMask && h->fitOf.size() == (size_t)S0 && h->fsDelta.size() == (size_t)S0 &&
+                         h->fsMin.size() == (size_t)S0 && h->fsNever.size() == (size_t)S0 && h->awayRowOff.size() == (size_t)S0 + 1;
+  const int F0 = haveMasks ? (int)h->fitTab.size() : 0;
+  // ---- liveness and the three maps: O(S) on the host, no device pass (jobs_delete and jobs_append maintain shapeRow)
+  std::vector<int32_t> shapeNew(S0, -1), fitNew(F0, -1), clsNew(C0, -1), oldShape, oldFit, oldCls;
+  std::vector<uint8_t> fitLive(F0, 0), clsLive(C0, withCls ? 0 : 1);
+  for (int s = 0; s < S0; s++) if (h->shapeRow[s] >= 0) {
+    if (h->shapeClass[s] < 0 || h->shapeClass[s] >= C0 || (haveMasks && (h->fitOf[s] < 0 || h->fitOf[s] >= F0))) return fail(h, ASCHED_ERR_INVALID, "shapes_compact: the shape table of the handle is inconsistent (jobs_set)");
+    shapeNew[s] = (int32_t)oldShape.size(); oldShape.push_back(s);
+    clsLive[h->shapeClass[s]] = 1;
+    if (haveMasks) fitLive[h->fitOf[s]] = 1;
+  }
+  for (int f = 0; f < F0; f++) if (fitLive[f]) { fitNew[f] = (int32_t)oldFit.size(); oldFit.push_back(f); }
+  for (int c = 0; c < C0; c++) if (clsLive[c]) { clsNew[c] = (int32_t)oldCls.size(); oldCls.push_back(c); }
+  const int S1 = (int)oldShape.size(), F1 = (int)oldFit.size(), C1 = (int)oldCls.size();
+  if (S1 <= 0) return fail(h, ASCHED_ERR_INVALID, "shapes_compact: no resident row names a shape (jobs_set)");
+  if (countOnly) {
+    int32_t* t = h->scStats;
+    t[0] = S0 - S1; t[1] = F0 - F1; t[2] = C0 - C1; t[3] = Cext0 - C0; t[4] = 0; t[5] = 0; t[6] = S0; t[7] = F0;
+    return 0;
+  }
+  const bool anyDead = S1 < S0 || C1 < C0;
+  int why = 0;
+  if (anyDead && !haveMasks) why = 1;
+  else if (anyDead && !d.f.structOk && F1 <= SMAX && C1 <= 64 && (F0 > SMAX || C0 > 64) && scQualifiesButCounts(h)) why = F0 > SMAX ? 2 : 3;   // buildFast's predicate turns true
+  const bool inPlace = anyDead && !why;
+  const bool haveRec = inPlace && d.f.structOk && d.jrec;
+  // ---- the compacted host mirrors (the old ones saved: a refusal below puts them back)
+  struct Saved {
+    std::vector<int32_t> shapeClass, shapePc, shapeRow, fitOf, awayRowOff, awayRowClass, awayRowShape; std::vector<int64_t> shapeReq; std::vector<uint8_t> shapeUnaligned, fsNever, rowLiteral;
+    std::vector<uint64_t> fsDelta, fsMin; std::vector<ShapeReq> fitTab; decltype(asched::fitIds) fitIds;
+    std::vector<std::vector<HTol>> clsTol; std::vector<std::vector<HSel>> clsSel; std::vector<HAffinity> clsAff;
+  } sv;
+  auto undo = [&]() {
+    h->shapeClass.swap(sv.shapeClass); h->shapePc.swap(sv.shapePc); h->shapeRow.swap(sv.shapeRow); h->shapeReq.swap(sv.shapeReq); h->shapeUnaligned.swap(sv.shapeUnaligned);
+    h->awayRowOff.swap(sv.awayRowOff); h->awayRowClass.swap(sv.awayRowClass); h->awayRowShape.swap(sv.awayRowShape); h->rowLiteral.swap(sv.rowLiteral);
+    if (haveMasks) { h->fitOf.swap(sv.fitOf); h->fsNever.swap(sv.fsNever); h->fsDelta.swap(sv.fsDelta); h->fsMin.swap(sv.fsMin); h->fitTab.swap(sv.fitTab); h->fitIds.swap(sv.fitIds); }
+    h->clsTol.swap(sv.clsTol); h->clsSel.swap(sv.clsSel); h->clsAff.swap(sv.clsAff);
+    h->S = S0; h->C = C0; h->Cext = Cext0;
+  };
+  std::vector<int32_t> shapeSrc, clsSrc, shapeClassExt1, rowTypeOff1, rowTypes1; std::vector<int64_t> shapeReqExt1;
+  bool clsMoves = false;
+  if (anyDead) {
+    sv.shapeClass = h->shapeClass; sv.shapePc = h->shapePc; sv.shapeRow = h->shapeRow; sv.shapeReq = h->shapeReq; sv.shapeUnaligned = h->shapeUnaligned;
+    sv.awayRowOff = h->awayRowOff; sv.awayRowClass = h->awayRowClass; sv.awayRowShape = h->awayRowShape; sv.rowLiteral = h->rowLiteral;
+    if (haveMasks) { sv.fitOf = h->fitOf; sv.fsNever = h->fsNever; sv.fsDelta = h->fsDelta; sv.fsMin = h->fsMin; sv.fitTab = h->fitTab; sv.fitIds = h->fitIds; }
+    sv.clsTol = h->clsTol; sv.clsSel = h->clsSel; sv.clsAff = h->clsAff;
+    for (int s1 = 0; s1 < S1; s1++) {
+      const int s = oldShape[s1];
+      h->shapeClass[s1] = clsNew[sv.shapeClass[s]]; h->shapePc[s1] = sv.shapePc[s]; h->shapeRow[s1] = sv.shapeRow[s]; h->shapeUnaligned[s1] = sv.shapeUnaligned[s];
+      for (int r = 0; r < R; r++) h->shapeReq[(size_t)s1 * R + r] = sv.shapeReq[(size_t)s * R + r];
+      if (haveMasks) { h->fitOf[s1] = fitNew[sv.fitOf[s]]; h->fsNever[s1] = sv.fsNever[s]; h->fsDelta[s1] = sv.fsDelta[s]; h->fsMin[s1] = sv.fsMin[s]; }
+    }
+    h->shapeClass.resize(S1); h->shapePc.resize(S1); h->shapeRow.resize(S1); h->shapeUnaligned.resize(S1); h->shapeReq.resize((size_t)S1 * R);
+    if (haveMasks) {
+      h->fitOf.resize(S1); h->fsNever.resize(S1); h->fsDelta.resize(S1); h->fsMin.resize(S1);
+      h->fitTab.resize(F1); h->fitIds.clear();
+      for (int f1 = 0; f1 < F1; f1++) { h->fitTab[f1] = sv.fitTab[oldFit[f1]]; h->fitTab[f1].cls = clsNew[h->fitTab[f1].cls]; }
+      for (int s1 = 0; s1 < S1; s1++) { const ShapeReq& q = h->fitTab[h->fitOf[s1]]; h->fitIds.emplace(std::make_tuple(q.fieldMin, h->fsDelta[s1], q.ex0, q.ex1, q.cls, q.never), h->fitOf[s1]); }   // (fastShapeAdd's key)
+    }
+    if (C1 < C0) {   // the real classes, compacted; deriveAwayRows cuts the derived ones off and derives them again
+      for (int c1 = 0; c1 < C1; c1++) { h->clsTol[c1] = sv.clsTol[oldCls[c1]]; h->clsSel[c1] = sv.clsSel[oldCls[c1]]; if (!h->clsAff.empty()) h->clsAff[c1] = sv.clsAff[oldCls[c1]]; }
+    }
+    h->S = S1; h->C = C1;
+    deriveAwayRows(h, d.cfg.hasAway != 0);
+    // the source of every mask row and class row of the compacted tables: away rows of a live shape keep their order within the shape (one per away entry of its
+    // priority class), derived classes are re-numbered by first occurrence — gathered through these tables, never assumed to be in the old order
+    const int A1 = (int)h->awayRowClass.size();
+    shapeSrc.assign((size_t)S1 + A1, -1); clsSrc.assign(h->Cext, -1);
+    for (int s1 = 0; s1 < S1; s1++) shapeSrc[s1] = oldShape[s1];
+    for (int c1 = 0; c1 < C1; c1++) clsSrc[c1] = oldCls[c1];
+    bool okRows = true;
+    for (int k1 = 0; k1 < A1 && okRows; k1++) {
+      const int s1 = h->awayRowShape[k1], s = oldShape[s1], kOld = sv.awayRowOff[s] + (k1 - h->awayRowOff[s1]);
+      if (kOld >= sv.awayRowOff[s + 1] || kOld >= A0) { okRows = false; break; }
+      shapeSrc[(size_t)S1 + k1] = S0 + kOld;
+      int32_t& src = clsSrc[h->awayRowClass[k1]];
+      if (src >= 0 && src != sv.awayRowClass[kOld]) okRows = false;
+      src = sv.awayRowClass[kOld];
+    }
+    for (int32_t v : clsSrc) okRows = okRows && v >= 0 && v < Cext0;
+    if (!okRows) { undo(); return fail(h, ASCHED_ERR_INVALID, "shapes_compact: the derived classes of the handle do not follow from its shape table (jobs_set)"); }
+    clsMoves = h->Cext != Cext0;
+    for (int c = 0; c < h->Cext && !clsMoves; c++) clsMoves = clsSrc[c] != c;
+    if (inPlace) {
+      shapeClassExt1 = h->shapeClass; shapeReqExt1 = h->shapeReq;
+      for (int k = 0; k < A1; k++) {
+        shapeClassExt1.push_back(h->awayRowClass[k]);
+        for (int r = 0; r < R; r++) shapeReqExt1.push_back(h->shapeReq[(size_t)h->awayRowShape[k] * R + r]);
+      }
+      if (int rrc = buildRowTables(h, shapeClassExt1, rowTypeOff1, rowTypes1)) { std::string msg = h->err; undo(); return fail(h, rrc, "shapes_compact: " + msg); }   // (cannot happen: every row was a row before)
+    }
+  }
+  const int A1 = (int)h->awayRowClass.size(), Sext1 = S1 + A1, Cext1 = h->Cext;
+  // ---- the scratch (the maps and the source tables) and the fresh mask blocks before anything changes on the device: running out of memory is a refusal too
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t oFit = up(4 * (size_t)S0), oCls = oFit + up(4 * (size_t)std::max(F0, 1)), oSSrc = oCls + up(4 * (size_t)C0), oCSrc = oSSrc + up(4 * (size_t)std::max(Sext1, 1)),
+               scratchBytes = oCSrc + up(4 * (size_t)std::max(Cext1, 1));
+  char* scratch = nullptr; uint64_t* shapeMask1 = nullptr; uint64_t* classMask1 = nullptr;
+  if (anyDead) {
+    bool ok = (scratch = (char*)plat_malloc(scratchBytes)) != nullptr;
+    if (ok && inPlace) ok = (shapeMask1 = (uint64_t*)plat_malloc(8 * (size_t)std::max(Sext1, 1) * W)) != nullptr;
+    if (ok && inPlace && clsMoves) ok = (classMask1 = (uint64_t*)plat_malloc(8 * (size_t)std::max(Cext1, 1) * W)) != nullptr;
+    if (!ok) {
+      (void)plat_take_failure();
+      if (scratch) plat_free(scratch);
+      if (shapeMask1) plat_free(shapeMask1);
+      if (classMask1) plat_free(classMask1);
+      undo();
+      return fail(h, ASCHED_ERR_DEVICE, "shapes_compact: out of device memory for the compacted mask blocks; the handle is as it was");
+    }
+  }
+  // ---- what jobs_set resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the tables half compacted: asched_jobs_set before anything else)
+  h->haveRoundResult = false; h->stateEpoch++;
+  if (why) fastInvalidate(h);
+  else { d.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
+    int32_t zero = 0;
+    plat_h2d(&d.rs->fastActive, &zero, sizeof zero);
+    plat_h2d(&d.rs->l0SaveCount, &zero, sizeof zero); }
+  h->prepared = false; h->evrSized = false;
+  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->caStats, 0, sizeof h->caStats);
+  h->scMs[0] = h->scMs[1] = h->scMs[2] = 0; h->scHostMs = 0;
+  if (anyDead) {
+    plat_h2d(scratch, shapeNew.data(), 4 * (size_t)S0);
+    if (F0 > 0) plat_h2d(scratch + oFit, fitNew.data(), 4 * (size_t)F0);
+    plat_h2d(scratch + oCls, clsNew.data(), 4 * (size_t)C0);
+    if (Sext1 > 0) plat_h2d(scratch + oSSrc, shapeSrc.data(), 4 * (size_t)Sext1);
+    if (Cext1 > 0) plat_h2d(scratch + oCSrc, clsSrc.data(), 4 * (size_t)Cext1);
+    ScArgs a; memset(&a, 0, sizeof a);
+    a.M = M; a.S0 = S0; a.F0 = F0; a.C0 = C0; a.W = W; a.N = h->N;
+    a.shapeNew = (const int32_t*)scratch; a.jShape = d.jShape;
+    if (haveRec) { a.jrec = d.jrec; a.fitNew = (const int32_t*)(scratch + oFit); if (C1 < C0) a.clsNew = (const int32_t*)(scratch + oCls); }
+    if (inPlace) {
+      a.shapeIn = d.shapeMask; a.shapeOut = shapeMask1; a.shapeSrc = (const int32_t*)(scratch + oSSrc); a.shapeRows = Sext1;
+      if (classMask1) { a.clsIn = h->dClassMask; a.clsOut = classMask1; a.clsSrc = (const int32_t*)(scratch + oCSrc); a.clsRows = Cext1; }
+      if (C1 < C0 && d.f.structOk && d.nodeCls && C0 <= 64) { a.nodeCls = d.nodeCls; for (int c = 0; c < C0; c++) if (clsLive[c]) a.liveCls |= 1ull << c; }
+    }
+    const int src = plat_take_failure() ? -1 : plat_shapes_compact(d, a);
+    if (src) { plat_free(scratch); if (shapeMask1) plat_free(shapeMask1); if (classMask1) plat_free(classMask1); return fail(h, ASCHED_ERR_DEVICE, plat_last_error()); }
+    plat_shapes_compact_ms(h->scMs);
+    plat_free(scratch);
+    auto swapIn = [&](void* oldp, void* fresh, size_t bytes) {
+      for (size_t k = 0; k < h->maskBufs.ptrs.size(); k++) if (h->maskBufs.ptrs[k].first == oldp) { h->maskBufs.ptrs.erase(h->maskBufs.ptrs.begin() + k); break; }
+      plat_free(oldp);
+      h->maskBufs.ptrs.push_back({fresh, bytes});
+    };
+    if (inPlace) {
+      swapIn(d.shapeMask, shapeMask1, 8 * (size_t)std::max(Sext1, 1) * W); d.shapeMask = shapeMask1;
+      if (classMask1) { swapIn(h->dClassMask, classMask1, 8 * (size_t)std::max(Cext1, 1) * W); h->dClassMask = classMask1; }
+      // the small tables from the compacted host vectors: each is no longer than the block that holds it
+      plat_h2d(h->dShapeClass, shapeClassExt1.data(), 4 * shapeClassExt1.size());
+      plat_h2d(d.shapeReq, shapeReqExt1.data(), 8 * shapeReqExt1.size());
+      plat_h2d(d.awayRowOff, h->awayRowOff.data(), 4 * h->awayRowOff.size());
+      plat_h2d(d.rowLiteral, h->rowLiteral.data(), h->rowLiteral.size());
+      plat_h2d(d.rowTypeOff, rowTypeOff1.data(), 4 * rowTypeOff1.size());
+      if (!rowTypes1.empty()) plat_h2d(d.rowTypes, rowTypes1.data(), 4 * rowTypes1.size());
+      d.f.F = F1;
+      if (d.f.structOk && d.shapeTab) {
+        plat_h2d(d.shapeTab, h->fitTab.data(), sizeof(ShapeReq) * h->fitTab.size());
+        // (d.fitBits [F][fitW] is scratch the next base build fills for the F it finds: the block of the larger F holds it)
+        if (const char* ms = getenv("ASCHED_SHAPE_MASK")) if (d.fitBits && ms[0] == '1') d.f.maskMode = F1 <= 64 ? 1 : F1 <= 128 ? 2 : 0;   // (buildFast's rule, for the smaller F)
+      }
+    }
+    // the per-shape results of a round: fresh (zero) for the new shape ids, as jobs_set allocates them
+    if (d.unfeasible) plat_memset(d.unfeasible, 0, (size_t)S0);
+    if (d.unfeasibleReason) plat_memset(d.unfeasibleReason, 0, 4 * (size_t)S0);
+    d.cfg.S = S1; d.cfg.C = C1;
+    h->shapeTable.clear(); h->shapeHash.clear();   // (the next append builds them over the compacted shapes)
+    // ---- the O(M) host step: the shape (and class) of every row in the mirrors, on the host threads
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool remapCls = C1 < C0 && h->jReqClass.size() == (size_t)M;
+    parallelChunks((size_t)M, 64, [&](size_t lo, size_t hi) {
+      for (size_t j = lo; j < hi; j++) { h->jShape[j] = shapeNew[h->jShape[j]]; if (remapCls) h->jReqClass[j] = clsNew[h->jReqClass[j]]; }
+    });
+    h->scHostMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (const char* e = getenv("ASCHED_SC_TIMES")) if (e[0] == '1')
+      fprintf(stderr, "[asched shapes_compact] jobs %d shapes %d -> %d fit %d -> %d classes %d -> %d (ext %d -> %d) %s: rows %.4f ms, gathers %.4f ms, class bits %.4f ms; host mirrors %.4f ms\n",
+              M, S0, S1, F0, F1, C0, C1, Cext0, Cext1, why ? "rebuild" : "in place", h->scMs[0], h->scMs[1], h->scMs[2], h->scHostMs);
+  }
+  if (withCls && class_new_id) for (int c = 0; c < C0; c++) class_new_id[c] = clsNew[c];
+  { int32_t* t = h->scStats;
+    t[0] = S0 - S1; t[1] = F0 - F1; t[2] = C0 - C1; t[3] = Cext1 - C1; t[4] = why ? 1 : 0; t[5] = why; t[6] = S1; t[7] = haveMasks ? F1 : 0; }
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  d.cfg.Q = 0;
+  if (why) {   // the tail of jobs_set on the compacted mirrors
+    int rc = rebuildMasks(h);
+    if (h->nodesSet) h->scStats[7] = d.f.F;
+    if (rc) return rc;
+    rc = runControl(h, CMD_UPSERT_RESET);
+    if (rc) return rc;
+    rc = runControl(h, CMD_RESET_JOBS);
+    h->allocPristine = h->nodesSet;
+    h->evictedDirty = false;
+    return rc;
+  }
+  return resetDynamicState(h, M);
+}
+int32_t asched_shapes_compact_stats(asched_t* h, int32_t* out) {
+  if (!h || !out) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  for (int k = 0; k < 8; k++) out[k] = h->scStats[k];
   return 0;
 }
 

@@ -111,6 +111,12 @@ static void plat_shapes_append_ms(double* out /*[2]*/);   // measurement hook: d
 struct CaArgs;
 static int plat_req_classes_append(Dev& d, CaArgs& a);
 static void plat_req_classes_append_ms(double* out /*[2]*/);   // measurement hook: device ms of the new rows / the row copies of the last call (events around them when ASCHED_CA_TIMES=1, else zeros)
+// dead shapes and classes leave the resident tables (kernels_shapes_compact.h): the remap of a.jShape and the job records in place, the gathers of the mask rows into
+// the fresh blocks a.shapeOut / a.clsOut, the bit compaction of a.nodeCls in place.  Synchronous: everything is complete on return.  The CPU build's definition sits
+// in kernels_shapes_compact.h.
+struct ScArgs;
+static int plat_shapes_compact(Dev& d, ScArgs& a);
+static void plat_shapes_compact_ms(double* out /*[3]*/);   // measurement hook: device ms of rows / gathers / class bits of the last call (events around them when ASCHED_SC_TIMES=1, else zeros)
 // rows leave the resident job table (kernels_jobs_delete.h): mark, scan (plat_compact over the keep flags into a.src / a.newId; its count must be a.M1), the gather of the
 // static per-job arrays into the blocks of a.out*, the compaction and renumbering of the order (a.ordOut) and of the gang lists (a.gangOut), unmark.  Synchronous: everything
 // is complete on return.  The CPU build's definition sits in kernels_jobs_delete.h.

@@ -35,6 +35,7 @@ struct PlatCtx {
   hipEvent_t jaEv[4] = {nullptr, nullptr, nullptr, nullptr}; bool jaTimed = false;   // ASCHED_JA_TIMES=1: around the passes of the job-table append
   hipEvent_t saEv[3] = {nullptr, nullptr, nullptr}; bool saTimed = false;   // ASCHED_JA_TIMES=1: around the row copies and the mask rows of an in-place append of new shapes
   hipEvent_t caEv[3] = {nullptr, nullptr, nullptr}; bool caTimed = false;   // ASCHED_CA_TIMES=1: around the row copies and the new rows of asched_req_classes_append
+  hipEvent_t scEv[4] = {nullptr, nullptr, nullptr, nullptr}; bool scTimed = false;   // ASCHED_SC_TIMES=1: around the passes of asched_shapes_compact
   hipEvent_t jpEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool jpTimed = false;  // ASCHED_JP_TIMES=1: around the passes of the job-table patch
   hipEvent_t ndEv[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool ndTimed = false;   // ASCHED_ND_TIMES=1: around the passes of the node-table delete
   hipEvent_t naEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool naTimed = false;   // ASCHED_NA_TIMES=1: around the passes of the node-table append
@@ -261,6 +262,7 @@ static void plat_close(PlatCtx* c) {
   for (hipEvent_t e : c->jaEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->saEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->caEv) if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : c->scEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->npEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->jdEv) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : c->ndEv) if (e) (void)hipEventDestroy(e);
@@ -1029,6 +1031,41 @@ static int plat_req_classes_append(Dev& d, CaArgs& a) {
 static void plat_req_classes_append_ms(double* out) {   // out[0]: the new rows, out[1]: the copies
   hipEvent_t* ev = caEvents();
   for (int k = 0; k < 2; k++) { float ms = 0.f; if (ev && t_ctx->caTimed && hipEventElapsedTime(&ms, ev[1 - k], ev[2 - k]) != hipSuccess) ms = 0.f; out[k] = ms; }
+}
+// dead shapes and classes leave the resident tables (kernels_shapes_compact.h; k_sc_* in armada_sched_mgpu.hip).  ASCHED_SC_TIMES=1 puts events around the three
+// passes (tools/probe_shapes_compact.py).
+#include "kernels_shapes_compact.h"
+extern "C" int asched_internal_sc_rows(const ScArgs* a, hipStream_t s);
+extern "C" int asched_internal_sc_gather(const ScArgs* a, hipStream_t s);
+extern "C" int asched_internal_sc_clsbits(const ScArgs* a, hipStream_t s);
+static hipEvent_t* scEvents() {
+  static const bool on = [] { const char* e = getenv("ASCHED_SC_TIMES"); return e && e[0] == '1'; }();
+  PlatCtx* c = t_ctx;
+  if (!on) return nullptr;
+  if (!c->scEv[3]) for (int i = 0; i < 4; i++) if (!c->scEv[i] && hipEventCreate(&c->scEv[i]) != hipSuccess) { c->scEv[i] = nullptr; return nullptr; }
+  return c->scEv;
+}
+static int plat_shapes_compact(Dev& d, ScArgs& a) {
+  (void)d;
+  PlatCtx* c = t_ctx;
+  hipStream_t st = c->stream;
+  hipEvent_t* ev = scEvents();
+  c->scTimed = false;
+  if (ev) (void)hipEventRecord(ev[0], st);
+  bool ok = asched_internal_sc_rows(&a, st) == 0;
+  if (ev) (void)hipEventRecord(ev[1], st);
+  ok = ok && asched_internal_sc_gather(&a, st) == 0;
+  if (ev) (void)hipEventRecord(ev[2], st);
+  ok = ok && asched_internal_sc_clsbits(&a, st) == 0;
+  if (ev) (void)hipEventRecord(ev[3], st);
+  ok = ok && hipOk(hipGetLastError(), "k_sc launch") && hipOk(hipStreamSynchronize(st), "k_sc");
+  if (!ok) { if (c->err.empty()) c->err = "k_sc launch failed"; return -1; }
+  c->scTimed = ev != nullptr;
+  return 0;
+}
+static void plat_shapes_compact_ms(double* out) {   // rows / gathers / class bits
+  hipEvent_t* ev = scEvents();
+  for (int k = 0; k < 3; k++) { float ms = 0.f; if (ev && t_ctx->scTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
 }
 // rows leave the resident job table (kernels_jobs_delete.h; k_jd_* in armada_sched_mgpu.hip, the scans are plat_compact's).  Each compaction brings its count back to the
 // host, which checks it against what the host counted before the next pass is sized by it.  ASCHED_JD_TIMES=1 puts events around the five passes (tools/probe_jobs_delete.py).

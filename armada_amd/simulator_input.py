@@ -385,11 +385,16 @@ def run_cycles_arriving_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[in
     return _run_cycles_arriving(lib, sim, per_cycle, max_cycles, False)
 
 
-def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, every, deleted, resident=None, in_place=False, reprio=None):
+def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, every, deleted, resident=None, in_place=False, reprio=None, retire=0, classes=False):
     from .binding import Scheduler
     wl = sim.workload
     m = wl.num_jobs
     arrive = arrival_cycles(sim, per_cycle)
+    # run_cycles_retiring: with `classes` the jobs of arrival cycle c name a requirement class of their own (no tolerations, no selector: every class matches what the
+    # others match, but each is a class, so its jobs' shapes are theirs alone).  cls_id: the id the handle knows the class of a cycle by — it moves when classes retire
+    jcls = arrive.astype(np.int32) if classes else None
+    cls_id = {}
+    compacts = shapes_retired = classes_retired = 0
     node = np.full(m, -1, np.int32)                   # per JOB (the workload's row), as in _run_cycles_arriving
     run_prio = np.zeros(m, np.int32)
     started = np.full(m, -1.0)
@@ -413,6 +418,13 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
             a["queue_priority"] = qprio[jobs]
         return a
 
+    def class_ids(jobs):
+        """the handle's ids of the classes the jobs name; a class the handle does not hold (new, or retired since) is appended first"""
+        for c in sorted(set(int(x) for x in jcls[jobs])):
+            if cls_id.get(c, -1) < 0:
+                cls_id[c] = s.req_classes_append([[]])
+        return np.array([cls_id[int(x)] for x in jcls[jobs]], dtype=np.int32)
+
     def terminal(jobs):
         rows = np.nonzero(done[jobs])[0]
         return rows[:-1] if len(rows) == len(jobs) else rows         # (a table keeps at least one row: jobs_delete refuses to empty it)
@@ -434,11 +446,16 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
                 moved.append((jobs[jobs < upto], int(ev[2])))
         if deleted:
             if cycle == 0:                            # the first cycle: jobs_set
-                s.jobs_set(wl.job_req[new], **table_args(new))
+                if classes:                           # (with the classes of the first arrivals, numbered densely in cycle order)
+                    first = sorted(set(int(x) for x in jcls[new]))
+                    cls_id.update({c: i for i, c in enumerate(first)})
+                    s.jobs_set(wl.job_req[new], req_class=np.array([cls_id[int(x)] for x in jcls[new]], dtype=np.int32), class_tolerations=[[] for _ in first], **table_args(new))
+                else:
+                    s.jobs_set(wl.job_req[new], **table_args(new))
                 if in_place:
                     s.set_append_in_place(True)
             elif len(new):                            # syncState: the upserts — the submissions since the last cycle, the run state of the rows that changed
-                s.jobs_append(wl.job_req[new], queue=wl.job_queue[new], pc=wl.job_pc[new], submit_time=wl.job_submit[new])
+                s.jobs_append(wl.job_req[new], queue=wl.job_queue[new], pc=wl.job_pc[new], submit_time=wl.job_submit[new], req_class=class_ids(new) if classes else None)
                 if in_place:
                     st = s.jobs_append_stats()
                     shapes_in_place += st["in_place"]; appends_rebuilt += st["rebuilt"]
@@ -458,6 +475,13 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
                 new_id = s.jobs_delete(gone.astype(np.int32), want_map=True)
                 row_of_job[job_of_row] = new_id
                 job_of_row = job_of_row[new_id >= 0]
+            if retire and cycle > 0 and cycle % retire == 0:      # then the shapes (and classes) the deletes left without a row; the class map applied to the driver's ids
+                cmap = s.shapes_compact(classes=classes, want_map=classes)
+                st = s.shapes_compact_stats()
+                compacts += 1; shapes_retired += st["shapes_retired"]; classes_retired += st["classes_retired"]
+                if classes:
+                    for c, i in cls_id.items():
+                        cls_id[c] = int(cmap[i]) if i >= 0 else -1
         else:
             for jobs, p in moved:
                 qprio[jobs] = p
@@ -466,7 +490,10 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
                 job_of_row = np.delete(job_of_row, terminal(job_of_row))
             row_of_job[:] = -1
             row_of_job[job_of_row] = np.arange(len(job_of_row))
-            s.jobs_set(wl.job_req[job_of_row], **table_args(job_of_row))
+            if classes:                               # (every class any job so far has named, under the id the driver gave it: retired ones simply have no rows)
+                s.jobs_set(wl.job_req[job_of_row], req_class=jcls[job_of_row], class_tolerations=[[] for _ in range(int(jcls[:upto].max()) + 1)], **table_args(job_of_row))
+            else:
+                s.jobs_set(wl.job_req[job_of_row], **table_args(job_of_row))
         changed[:] = False
         have = upto
         nq = wl.num_queues
@@ -490,11 +517,28 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
         out.append({"time_s": t, "scheduled": sched, "preempted": pre, "termination_reason": r.termination_reason, "rows": len(job_of_row)})
         if in_place:                                  # as in run_cycles_arriving: shapes served without a rebuild (new ones and ones the deletes had emptied), appends that rebuilt
             out[-1]["shapes_in_place"], out[-1]["appends_rebuilt"] = shapes_in_place, appends_rebuilt
+        if retire:                                    # run_cycles_retiring: compacts so far and what they retired
+            out[-1]["compacts"], out[-1]["shapes_retired"], out[-1]["classes_retired"] = compacts, shapes_retired, classes_retired
         if have == m and not sched and not pre and not (node >= 0).any():
             break   # everything has arrived, nothing runs and nothing can be placed: the rest never will
         t += sim.cycle_period_s
     s.close()
     return out
+
+
+def run_cycles_retiring(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, every: int = 1, classes: bool = False, max_cycles: int = 1000):
+    """run_cycles_compacting (in place: new shapes grow the shape tables) with the DEAD shapes leaving as well: the finished rows are deleted every cycle and every
+    `every` cycles Scheduler.shapes_compact retires the scheduling-key shapes the deletes left without a row.  classes: the jobs of every arrival cycle name a
+    requirement class of their own (appended with Scheduler.req_classes_append when its first job arrives); the compact retires the classes without rows too, and the
+    driver applies the class map it returns to the ids it passes later — a class that comes back after it was retired is appended again.  Records as
+    run_cycles_compacting, plus the compacts so far and the shapes and classes they retired."""
+    return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, 1, True, in_place=True, retire=max(1, int(every)), classes=classes)
+
+
+def run_cycles_retiring_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, every: int = 1, classes: bool = False, max_cycles: int = 1000):
+    """the rebuilt counterpart of run_cycles_retiring: jobs_set of the live rows in every cycle, with every class any job has named so far — what any library, the
+    oracle included, can run.  Same rows, same records (`every` changes nothing here: a fresh table has no dead shape)."""
+    return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, 1, False, classes=classes)
 
 
 def run_cycles_compacting(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000, every: int = 1):

@@ -469,6 +469,32 @@ int32_t ASCHED_FN(req_classes_append)(asched_t*, const asched_req_classes* more)
    nodes_upsert builds everything), 2 the call takes C from at most 64 to more than 64 on a handle with the fast structure — [6] C after the call, [7] C plus the
    derived away classes after the call.  Zeros after jobs_set. */
 int32_t ASCHED_FN(req_classes_append_stats)(asched_t*, int32_t* out /*[8]*/);
+/* Retire the scheduling-key shapes and requirement classes no resident row names.  jobs_delete keeps an emptied shape's id, mask rows and fit shape, the in-place
+   append only adds shapes and classes are append-only, while the fast structure needs at most SMAX (256) fit shapes and 64 real classes and the split node engine at
+   most 128 fit shapes: on a handle that stays resident the dead ones alone reach those limits.  A shape is dead when no resident row has it, a fit shape when no
+   live shape maps to it, a real class (only with ASCHED_COMPACT_CLASSES) when no live shape names it.  The live ones keep their relative order and get dense ids:
+   new id = old id - number of dead ones below it.  With ASCHED_COMPACT_CLASSES class_new_id, when not NULL, receives that map for the C classes the handle had
+   before the call, -1 for a retired class: rows of a later jobs_append and the classes of a later req_classes_append use the new ids.  Without the flag classes and
+   their ids stay and class_new_id is ignored.
+   Returns 0.  The handle is left as jobs_set of the same job table (with the class list reduced to the live classes and req_class renumbered, where classes were
+   retired) would leave it, for every entry point and including everything jobs_set resets; go on with round_prepare or any other resident call.  Results equal the
+   fresh handle's; internal shape ids need not.  The key layout, the two minima, hasAway, the gang tables and the capacities stay: bounds and unions over rows and
+   shapes, which fewer shapes can only make tighter.  Nothing dead performs the resets only.
+   In place where the handle has masks: the rows' shape ids and job records are remapped on the device, the mask rows gathered into fresh blocks, the class bits
+   of every node compacted; no mask is matched again and no job record uploaded.  Where the compaction makes the fast structure possible again (F from above SMAX
+   to at most SMAX, or C from above 64 to at most 64, on a handle that otherwise qualifies), and where there are no masks yet, the tail of jobs_set runs on the
+   compacted tables; asched_shapes_compact_stats says which.
+   Refused before anything changes: no job table, unknown flag bits (ASCHED_ERR_INVALID); a job set that carries the market order, a table with no rows
+   (ASCHED_ERR_UNSUPPORTED); no device memory for the fresh blocks (ASCHED_ERR_DEVICE, the handle is as it was).  A launch or copy that fails later is
+   ASCHED_ERR_DEVICE and the handle then needs asched_jobs_set, as documented for jobs_patch. */
+#define ASCHED_COMPACT_CLASSES    1   /* also retire requirement classes that no remaining shape names */
+#define ASCHED_COMPACT_COUNT_ONLY 2   /* change nothing: fill the statistics only (O(S) on the host) */
+int32_t ASCHED_FN(shapes_compact)(asched_t*, int32_t flags, int32_t* class_new_id /* [C before the call] or NULL */);
+/* how the last shapes_compact ran: out[0] shapes retired, [1] fit shapes retired, [2] real classes retired, [3] derived away classes after the call, [4] 1 = masks
+   and fast structure were rebuilt, [5] why — 0 not rebuilt, 1 no node table or no masks yet, 2 F came back under SMAX, 3 C came back under 65 — [6] shapes S after
+   the call, [7] fit shapes F after the call.  After ASCHED_COMPACT_COUNT_ONLY: [0..2] what a call with the same flags would retire, [6..7] the current values.
+   Zeros after jobs_set. */
+int32_t ASCHED_FN(shapes_compact_stats)(asched_t*, int32_t* out /*[8]*/);
 /* syncState's delete of the jobs in a terminal state from the jobDb, after the upserts of the same cycle (scheduler.go:539-549; Txn.BatchDelete / delete,
    jobdb/jobdb.go:941-990): the n rows job[0..n) leave the table.  The remaining rows keep their order and are renumbered densely: new id = old id - number of
    deleted rows below it.  new_id, when not NULL, receives that map for the M rows the table had before the call, -1 for a deleted row.

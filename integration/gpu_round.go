@@ -982,6 +982,53 @@ func (g *GpuRound) DeleteJobs(ids []string) error {
 	return nil
 }
 
+// CompactShapes retires the scheduling-key shapes (and, with retireClasses, the requirement classes) that DeleteJobs left without a row (asched_shapes_compact).  The
+// library keeps an emptied shape's id, mask rows and fit shape, and its fast path needs at most 256 fit shapes and 64 classes — the split node engine at most 128 fit
+// shapes — so on a handle that stays resident the dead ones alone reach those limits.  Called from the sync step after DeleteJobs, every cycle: a COUNT_ONLY query
+// (O(shapes) on the host, nothing changes) says what a call would retire, and the call is made only where the dead fit shapes take F over 128 or the dead classes
+// take C over 64.  With retireClasses the class map the library returns is applied to g.classes, the shim's class-interning table: a retired class leaves it and is
+// appended again by AppendJobs when a job names it once more.  ErrNeedsUpload on the first cycle and on a market-driven pool.  -> whether the library was called.
+func (g *GpuRound) CompactShapes(retireClasses bool) (bool, error) {
+	if g.jobs == nil || (g.market != nil && g.market.Enabled) {
+		return false, ErrNeedsUpload
+	}
+	flags := C.int32_t(0)
+	if retireClasses {
+		flags |= C.ASCHED_COMPACT_CLASSES
+	}
+	var st [8]C.int32_t
+	if err := g.check(C.asched_shapes_compact(g.h, flags|C.ASCHED_COMPACT_COUNT_ONLY, nil)); err != nil {
+		return false, err
+	}
+	if err := g.check(C.asched_shapes_compact_stats(g.h, &st[0])); err != nil {
+		return false, err
+	}
+	deadFit, deadCls, fit, cls := int(st[1]), int(st[2]), int(st[7]), len(g.classes)
+	if cls == 0 {
+		cls = 1 // (a table without classes has the empty class 0)
+	}
+	if !((deadFit > 0 && fit > 128) || (deadCls > 0 && cls > 64)) {
+		return false, nil
+	}
+	newId := make([]int32, cls)
+	var pins runtime.Pinner
+	defer pins.Unpin()
+	pins.Pin(&newId[0])
+	if err := g.check(C.asched_shapes_compact(g.h, flags, i32p(newId))); err != nil {
+		return false, err
+	}
+	if retireClasses {
+		for k, id := range g.classes {
+			if int(id) < len(newId) && newId[id] >= 0 {
+				g.classes[k] = newId[id]
+			} else {
+				delete(g.classes, k)
+			}
+		}
+	}
+	return true, nil
+}
+
 // ErrNeedsNodeUpload is what PatchNodes answers for a change the resident node table cannot take: the caller falls back to UploadNodes of the whole pool.
 var ErrNeedsNodeUpload = fmt.Errorf("the node table has to be uploaded again")
 
