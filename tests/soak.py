@@ -12,6 +12,7 @@
     python tests/soak.py hcedges 250        # tests/test_z_hc_engine_edges.py's recipe at random: 30 ... 1100 live dirty nodes, fragments used up and reopened, 1-8 queues, 0 / 1 / 2 non-indexed columns; bulk merge from 64 entries
     python tests/soak.py features 400      # tests/test_z_feature_mix.py rounds (affinity, conditional away, extra column, limits ...)
     python tests/soak.py ops 3000           # tests/test_z_nodedb_op_sequences.py NodeDb-level operation sequences
+    python tests/soak.py resident 3000      # tests/test_z_resident_sequences.py sequences of the resident table calls (jobs_* / nodes_* / req_classes_append / shapes_compact), a full check after every operation
     python tests/soak.py submitcheck 400    # batched SubmitChecker vs the literal sequential restatement (and 3-entry cache)
     python tests/soak.py fit 600            # fit_select_batch at every priority on occupied NodeDbs
     python tests/soak.py sharded 1000       # ONE pool's round on 2-3 replicas with its wide passes split and all-reduced (asched_shard_round; SOAK_SHARD=direct on a GPU box: asched_shard_peers)
@@ -227,6 +228,9 @@ def main():
             elif kind == "ops":
                 import test_z_nodedb_op_sequences as T
                 assert T.run_ops(orc, seed) == T.run_ops(hs, seed), "operation traces differ"
+            elif kind == "resident":   # seeded interleavings of the resident table calls (tests/resident_sequences.py): the handle against a fresh handle of the model and the oracle's round after every operation
+                import resident_sequences as T
+                T.run_sequence(hs, orc, seed)
             elif kind == "submitcheck":
                 import submitcheck_harness as H
                 import test_zzz_submitcheck as T
@@ -279,7 +283,7 @@ def main():
             else:
                 refused += 1
         except AssertionError as e:
-            bad += 1; print("seed", seed, str(e)[:300])
+            bad += 1; print("seed", seed, str(e)[:300 if kind != "resident" else 6000])
     print(f"{kind}: {n} seeds, {bad} divergences, {refused} refused (ASCHED_ERR_UNSUPPORTED), {time.time() - t0:.0f} s")
     sys.exit(1 if bad else 0)
 
