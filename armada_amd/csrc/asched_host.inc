@@ -40,6 +40,12 @@
 #include "kernels_nodes_append.h"   // NaArgs and, in the CPU build of the tests, plat_nodes_append
 #include "kernels_queued_lists.h"   // QlArgs and, in the CPU build of the tests, plat_queued_lists
 
+// plat_try_malloc (plat.h) for a platform layer that defines none of its own (PLAT_TRY_MALLOC_OWN: the CPU build of the tests, which can fail any one of them): what a
+// resident call did by hand, plat_malloc with the failure it latches taken back
+#ifndef PLAT_TRY_MALLOC_OWN
+static void* plat_try_malloc(size_t n) { void* p = plat_malloc(n); if (!p) (void)plat_take_failure(); return p; }
+#endif
+
 namespace {
 
 // The input build touches every job a few times (scheduling-key shapes, SchedulingOrderCompare order, one JobRec per job): the loops
@@ -134,6 +140,68 @@ struct DevBufs {
     ptrs.clear();
   }
   void freeAll() { for (auto& b : ptrs) plat_free(b.first); ptrs.clear(); for (auto& c : cache) plat_free(c.second); cache.clear(); cacheBytes = 0; }
+  void release(void* p) {   // one block back to the driver
+    for (size_t k = 0; k < ptrs.size(); k++) if (ptrs[k].first == p) { ptrs.erase(ptrs.begin() + k); break; }
+    plat_free(p);
+  }
+};
+
+static size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }   // the parts of a scratch block start at multiples of 256 bytes
+
+// The device blocks a resident table call (asched_jobs_patch ... asched_nodes_append) replaces.  The rule they enforce: every device block the call needs is obtained
+// before the first byte of the handle changes, so a call that cannot get one is refused with the handle as it was.  stage() names a block: the DevBufs that will own it,
+// the pointer it replaces (a member of the handle, or a local variable of the call with keepOld), its size, the bytes to copy into it from the old block or from
+// `host`, a fill byte (-1: none).  allocate() gets all of them or none.  fill() queues the fills and copies; commit() releases each old block that is not kept, swaps the
+// fresh one in and registers it with its owner — the call decides when the device has been waited for; drop() is for a refusal or failure after allocate().
+struct StagedBlocks {
+  struct Entry { DevBufs* owner; void** slot; size_t bytes, copyBytes; const void* host; int fill; bool keepOld; void* fresh; };
+  std::vector<Entry> blocks;
+  void stage(DevBufs* owner, void* slot, size_t bytes, size_t copyBytes, const void* host, int fill, bool keepOld = false) {
+    blocks.push_back({owner, (void**)slot, std::max<size_t>(bytes, 1), copyBytes, host, fill, keepOld, nullptr});
+  }
+  void stage(DevBufs* owner, void* slot, size_t bytes, int fill = 0) { stage(owner, slot, bytes, 0, nullptr, fill); }
+  bool allocate() {
+    for (auto& b : blocks) if (!(b.fresh = plat_try_malloc(b.bytes))) { drop(); return false; }
+    return true;
+  }
+  void drop() { for (auto& b : blocks) { plat_free(b.fresh); b.fresh = nullptr; } }
+  void* fresh(void* slot) const { for (auto& b : blocks) if ((void*)b.slot == slot) return b.fresh; return nullptr; }
+  void fill() const {
+    for (auto& b : blocks) {
+      if (b.fill >= 0) plat_memset(b.fresh, b.fill, b.bytes);
+      if (b.host) { if (b.copyBytes) plat_h2d(b.fresh, b.host, b.copyBytes); }
+      else if (b.copyBytes && *b.slot) plat_d2d(b.fresh, *b.slot, b.copyBytes);
+    }
+  }
+  void commit() {
+    for (auto& b : blocks) {
+      if (!b.keepOld && *b.slot) b.owner->release(*b.slot);
+      *b.slot = b.fresh;
+      b.owner->ptrs.push_back({b.fresh, b.bytes});
+    }
+  }
+};
+
+// A device block a call keeps between calls and only ever grows: its entry scratch (a quarter larger than asked for), asched_nodes_delete's keep flags (exact).
+// tryGrow() asks for the larger block and changes nothing, for a call that must first know every other block can be had; adopt() releases the old block and takes the
+// new one.  grow() is both, for a call with nothing else to ask for.
+template <class T> struct KeptBlock {
+  DevBufs& owner; T*& p; size_t& bytes;
+  void* fresh = nullptr; size_t freshBytes = 0;
+  bool tryGrow(size_t need, bool slack = true) {
+    if (bytes >= need) return true;
+    freshBytes = slack ? need + need / 4 : need;
+    return (fresh = plat_try_malloc(freshBytes)) != nullptr;
+  }
+  void drop() { plat_free(fresh); fresh = nullptr; }
+  bool adopt() {
+    if (!fresh) return false;
+    if (p) owner.release(p);
+    p = (T*)fresh; bytes = freshBytes; owner.ptrs.push_back({fresh, freshBytes});
+    fresh = nullptr;
+    return true;
+  }
+  bool grow(size_t need) { return tryGrow(need) && (adopt(), true); }
 };
 
 }  // namespace
@@ -926,11 +994,29 @@ void asched_destroy(asched_t* h) {
 const char* asched_last_error(asched_t* h) { plat_enter(h ? h->plat : nullptr); return h ? h->err.c_str() : "null handle"; }
 int32_t asched_priorities(asched_t* h, int32_t* out) { if (!h) return ASCHED_ERR_INVALID; plat_enter(h->plat); for (int i = 0; i < h->P; i++) out[i] = h->prios[i]; return h->P; }
 
-static void fastInvalidate(asched* h) {  // inputs are being replaced: the level-0 fast structure no longer describes them
-  h->dev.f.structOk = h->dev.f.iterOk = 0;
+static void fastDeactivate(asched* h) {  // the fast structure stays (structOk) and is not in use: round_prepare decides iterOk again
+  h->dev.f.iterOk = 0;
   int32_t zero = 0;
   plat_h2d(&h->dev.rs->fastActive, &zero, sizeof zero);
   plat_h2d(&h->dev.rs->l0SaveCount, &zero, sizeof zero);
+}
+static void fastInvalidate(asched* h) {  // inputs are being replaced: the level-0 fast structure no longer describes them
+  h->dev.f.structOk = 0;
+  fastDeactivate(h);
+}
+// What jobs_set resets, for a resident call on the job table, from its point of no return on (a device failure after it leaves the table half changed: asched_jobs_set
+// before anything else).  fastGoes: the call ends with the tail of jobs_set (rebuildMasks), which builds the fast structure anew.  sizesStay: M and the capacities are
+// what they were, so the evictor report's buffers still fit (asched_jobs_patch, asched_jobs_reprioritise)
+static void residentTouchJobs(asched* h, bool fastGoes = false, bool sizesStay = false) {
+  h->haveRoundResult = false; h->stateEpoch++;
+  if (fastGoes) fastInvalidate(h); else fastDeactivate(h);
+  h->prepared = false;
+  if (!sizesStay) h->evrSized = false;
+}
+// What nodes_upsert resets, for a resident call on the node table: the above, and every priority level's planes are equal again
+static void residentTouchNodes(asched* h) {
+  residentTouchJobs(h);
+  h->equalLevels = h->P;
 }
 
 }  // extern "C"
@@ -1548,23 +1634,12 @@ int32_t asched_jobs_patch(asched_t* h, int32_t n, const int32_t* job, const int3
   const int total = h->ordOffHost.empty() ? 0 : h->ordOffHost[std::min<size_t>((size_t)h->ordQueues, h->ordOffHost.size() - 1)];
   int nb2 = n;
   if (nT > 0) { nb2 = JP_TILE; while (nb2 < n) nb2 <<= 1; }
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t oTs = up(sizeof(int32_t) * 3 * (size_t)n), oKeys = oTs + up(sizeof(int64_t) * (size_t)n), oKept = oKeys + (nT > 0 ? up(sizeof(JpKey) * (size_t)nb2) : 0),
-               need = oKept + (nT > 0 ? up(sizeof(int32_t) * (size_t)total) : 0);
-  if (n > 0 && h->jpScratchBytes < need) {
-    h->jpBufs.freeAll(); h->jpScratch = nullptr; h->jpScratchBytes = 0;
-    h->jpScratch = (char*)plat_malloc(need + need / 4);
-    if (!h->jpScratch) { (void)plat_take_failure(); return fail(h, ASCHED_ERR_DEVICE, "jobs_patch: out of device memory for the patch scratch; the handle is as it was"); }
-    h->jpBufs.ptrs.push_back({h->jpScratch, need + need / 4});
-    h->jpScratchBytes = need + need / 4;
-  }
-  // ---- what jobs_set resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the job table half patched: asched_jobs_set before anything else)
-  h->haveRoundResult = false; h->stateEpoch++;
-  { h->dev.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
-    int32_t zero = 0;
-    plat_h2d(&h->dev.rs->fastActive, &zero, sizeof zero);
-    plat_h2d(&h->dev.rs->l0SaveCount, &zero, sizeof zero); }
-  h->prepared = false;
+  const size_t oTs = up256(sizeof(int32_t) * 3 * (size_t)n), oKeys = oTs + up256(sizeof(int64_t) * (size_t)n), oKept = oKeys + (nT > 0 ? up256(sizeof(JpKey) * (size_t)nb2) : 0),
+               need = oKept + (nT > 0 ? up256(sizeof(int32_t) * (size_t)total) : 0);
+  KeptBlock<char> scratch{h->jpBufs, h->jpScratch, h->jpScratchBytes};
+  if (n > 0 && !scratch.grow(need)) return fail(h, ASCHED_ERR_DEVICE, "jobs_patch: out of device memory for the patch scratch; the handle is as it was");
+  // ---- what jobs_set resets (the job table half patched).  evrSized stays, on purpose: a patch changes no size
+  residentTouchJobs(h, false, true);
   Dev& d = h->dev;
   for (int k = 0; k < 4; k++) h->jpMs[k] = 0;
   if (n > 0) {
@@ -1629,21 +1704,11 @@ int32_t asched_jobs_reprioritise(asched_t* h, int32_t n, const int32_t* job, con
   const int total = h->ordOffHost.empty() ? 0 : h->ordOffHost[std::min<size_t>((size_t)h->ordQueues, h->ordOffHost.size() - 1)];
   int nb2 = n;
   if (nT > 0) { nb2 = JP_TILE; while (nb2 < n) nb2 <<= 1; }
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t oKeys = up(sizeof(int32_t) * 2 * (size_t)n), oKept = oKeys + (nT > 0 ? up(sizeof(JpKey) * (size_t)nb2) : 0), need = oKept + (nT > 0 ? up(sizeof(int32_t) * (size_t)total) : 0);
-  if (n > 0 && h->jpScratchBytes < need) {
-    char* fresh = (char*)plat_malloc(need + need / 4);
-    if (!fresh) { (void)plat_take_failure(); return fail(h, ASCHED_ERR_DEVICE, "jobs_reprioritise: out of device memory for the scratch; the handle is as it was"); }
-    h->jpBufs.freeAll(); h->jpScratch = fresh; h->jpScratchBytes = need + need / 4;
-    h->jpBufs.ptrs.push_back({fresh, need + need / 4});
-  }
-  // ---- what jobs_set resets, as asched_jobs_patch.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the order half built: asched_jobs_set before anything else)
-  h->haveRoundResult = false; h->stateEpoch++;
-  { h->dev.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
-    int32_t zero = 0;
-    plat_h2d(&h->dev.rs->fastActive, &zero, sizeof zero);
-    plat_h2d(&h->dev.rs->l0SaveCount, &zero, sizeof zero); }
-  h->prepared = false;
+  const size_t oKeys = up256(sizeof(int32_t) * 2 * (size_t)n), oKept = oKeys + (nT > 0 ? up256(sizeof(JpKey) * (size_t)nb2) : 0), need = oKept + (nT > 0 ? up256(sizeof(int32_t) * (size_t)total) : 0);
+  KeptBlock<char> scratch{h->jpBufs, h->jpScratch, h->jpScratchBytes};
+  if (n > 0 && !scratch.grow(need)) return fail(h, ASCHED_ERR_DEVICE, "jobs_reprioritise: out of device memory for the scratch; the handle is as it was");
+  // ---- what jobs_set resets (the order half built).  evrSized stays, as in asched_jobs_patch and for its reason
+  residentTouchJobs(h, false, true);
   Dev& d = h->dev;
   for (int k = 0; k < 4; k++) h->jpMs[k] = 0;
   const bool madeResident = n > 0 && !h->jp.built;
@@ -1704,9 +1769,6 @@ static void jaShapeTableBuild(asched* h, size_t room) {   // over the shapes the
     h->shapeTable[pos] = (int32_t)s;
   }
 }
-// one device array of the job table that moves into a larger (or first) block: allocated before anything changes, filled and swapped in afterwards
-struct JaBlock { DevBufs* owner; void** slot; size_t bytes, copyBytes; const void* host; int fill; bool keepOld; void* fresh; };
-
 int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
   if (!h) return ASCHED_ERR_INVALID;
   plat_enter(h->plat);
@@ -1898,19 +1960,13 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
       for (int i = 0; i < m; i++) if (aGang[i] >= 0) gangTail[(size_t)(fill2[aGang[i] - G0]++ - gangOff1[G0])] = M + i; }
     gangOff1[G1 + 1] = gangOff1[G1] + std::max(M1, 1);   // scratch gang slot for schedule_many
   }
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t o64 = up(sizeof(int32_t) * 8 * (size_t)m), oReq = o64 + up(sizeof(int64_t) * (size_t)m), oAl = oReq + up(sizeof(int64_t) * (size_t)m * R), oKeys = oAl + up((size_t)m),
-               oTplIdx = oKeys + (nT > 0 ? up(sizeof(JpKey) * (size_t)nb2) : 0), oTpl = oTplIdx + (nTpl ? up(sizeof(int32_t) * (size_t)m) : 0),
-               oSa = oTpl + up(sizeof(JobRec) * nTpl), need = oSa + up((size_t)nNewRows * (8 + 8 * (size_t)R));   // (the in-place path for new shapes: each row's template, the template records, and request / class / output row of the new mask rows)
-  char* scratchNew = nullptr;
-  if (m > 0 && h->jpScratchBytes < need) {
-    scratchNew = (char*)plat_malloc(need + need / 4);
-    if (!scratchNew) { (void)plat_take_failure(); undo(); return fail(h, ASCHED_ERR_DEVICE, "jobs_append: out of device memory for the append scratch; the handle is as it was"); }
-  }
-  std::vector<JaBlock> blocks;
-  auto stage = [&](DevBufs* owner, void* slot, size_t bytes, size_t copyBytes, const void* host, int fill, bool keepOld = false) {
-    blocks.push_back({owner, (void**)slot, std::max<size_t>(bytes, 1), copyBytes, host, fill, keepOld, nullptr});
-  };
+  const size_t o64 = up256(sizeof(int32_t) * 8 * (size_t)m), oReq = o64 + up256(sizeof(int64_t) * (size_t)m), oAl = oReq + up256(sizeof(int64_t) * (size_t)m * R), oKeys = oAl + up256((size_t)m),
+               oTplIdx = oKeys + (nT > 0 ? up256(sizeof(JpKey) * (size_t)nb2) : 0), oTpl = oTplIdx + (nTpl ? up256(sizeof(int32_t) * (size_t)m) : 0),
+               oSa = oTpl + up256(sizeof(JobRec) * nTpl), need = oSa + up256((size_t)nNewRows * (8 + 8 * (size_t)R));   // (the in-place path for new shapes: each row's template, the template records, and request / class / output row of the new mask rows)
+  KeptBlock<char> scratch{h->jpBufs, h->jpScratch, h->jpScratchBytes};
+  if (m > 0 && !scratch.tryGrow(need)) { undo(); return fail(h, ASCHED_ERR_DEVICE, "jobs_append: out of device memory for the append scratch; the handle is as it was"); }
+  // each staged block is one device array of the job table that moves into a larger (or first) block: allocated before anything changes, filled and swapped in afterwards
+  StagedBlocks sb;
   const bool buildJp = m > 0 && !h->jp.built;
   const size_t gangOffCap1 = (size_t)G1 + 2 > h->gangOffCap ? std::max<size_t>((size_t)G1 + 2, h->gangOffCap + h->gangOffCap / 4) : h->gangOffCap;
   const size_t ordOffCap1 = std::max(h->ordOffCap, (size_t)std::max(Qj1, 1) + 4096 + 2);   // (the queue count outgrew the 4 096 padding)
@@ -1919,29 +1975,29 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
   if (m > 0) {
     if (grow) {
       const size_t c = cap1, o = (size_t)M;
-      stage(&h->jobBufs, &d.jQueue, c * 4, o * 4, nullptr, -1); stage(&h->jobBufs, &d.jPc, c * 4, o * 4, nullptr, -1); stage(&h->jobBufs, &d.jShape, c * 4, o * 4, nullptr, -1);
-      stage(&h->jobBufs, &d.jGang, c * 4, o * 4, nullptr, -1); stage(&h->jobBufs, &d.jGangCard, c * 4, o * 4, nullptr, -1); stage(&h->jobBufs, &d.jGangUni, c * 4, o * 4, nullptr, -1);
-      stage(&h->jobBufs, &d.jNode0, c * 4, o * 4, nullptr, -1); stage(&h->jobBufs, &d.jRunPrio, c * 4, o * 4, nullptr, -1);
-      if (d.jAway) stage(&h->jobBufs, &d.jAway, c, o, nullptr, -1);
-      stage(&h->jobBufs, &d.jReq, c * 8 * R, o * 8 * R, nullptr, -1); stage(&h->jobBufs, &d.jAligned, c, o, nullptr, -1); stage(&h->jobBufs, &d.jLeaseMs, c * 8, o * 8, nullptr, -1);
+      sb.stage(&h->jobBufs, &d.jQueue, c * 4, o * 4, nullptr, -1); sb.stage(&h->jobBufs, &d.jPc, c * 4, o * 4, nullptr, -1); sb.stage(&h->jobBufs, &d.jShape, c * 4, o * 4, nullptr, -1);
+      sb.stage(&h->jobBufs, &d.jGang, c * 4, o * 4, nullptr, -1); sb.stage(&h->jobBufs, &d.jGangCard, c * 4, o * 4, nullptr, -1); sb.stage(&h->jobBufs, &d.jGangUni, c * 4, o * 4, nullptr, -1);
+      sb.stage(&h->jobBufs, &d.jNode0, c * 4, o * 4, nullptr, -1); sb.stage(&h->jobBufs, &d.jRunPrio, c * 4, o * 4, nullptr, -1);
+      if (d.jAway) sb.stage(&h->jobBufs, &d.jAway, c, o, nullptr, -1);
+      sb.stage(&h->jobBufs, &d.jReq, c * 8 * R, o * 8 * R, nullptr, -1); sb.stage(&h->jobBufs, &d.jAligned, c, o, nullptr, -1); sb.stage(&h->jobBufs, &d.jLeaseMs, c * 8, o * 8, nullptr, -1);
       if (growRec) {
-        stage(&h->fastBufs, &d.jrec, sizeof(JobRec) * c, sizeof(JobRec) * o, nullptr, -1);
-        stage(&h->fastBufs, &d.evIdxByPos, c * 4, 0, nullptr, 0); stage(&h->fastBufs, &d.evKey, sizeof(EvKey) * c, 0, nullptr, 0); stage(&h->fastBufs, &d.evCheap, 4104 + c + 8, 0, nullptr, 0);
+        sb.stage(&h->fastBufs, &d.jrec, sizeof(JobRec) * c, sizeof(JobRec) * o, nullptr, -1);
+        sb.stage(&h->fastBufs, &d.evIdxByPos, c * 4, 0, nullptr, 0); sb.stage(&h->fastBufs, &d.evKey, sizeof(EvKey) * c, 0, nullptr, 0); sb.stage(&h->fastBufs, &d.evCheap, 4104 + c + 8, 0, nullptr, 0);
       }
     }
     if (buildJp) {   // first append or patch of this job table: the order-key inputs become resident
-      stage(&h->jobBufs, &h->jp.qprio, cap1 * 4, (size_t)M * 4, h->jQPrioHost.data(), -1); stage(&h->jobBufs, &h->jp.submit, cap1 * 8, (size_t)M * 8, h->jSubmitHost.data(), -1);
-      stage(&h->jobBufs, &h->jp.runTs, cap1 * 8, (size_t)M * 8, h->jRunTsHost.data(), -1); stage(&h->jobBufs, &h->jp.keep, cap1, 0, nullptr, 1);
+      sb.stage(&h->jobBufs, &h->jp.qprio, cap1 * 4, (size_t)M * 4, h->jQPrioHost.data(), -1); sb.stage(&h->jobBufs, &h->jp.submit, cap1 * 8, (size_t)M * 8, h->jSubmitHost.data(), -1);
+      sb.stage(&h->jobBufs, &h->jp.runTs, cap1 * 8, (size_t)M * 8, h->jRunTsHost.data(), -1); sb.stage(&h->jobBufs, &h->jp.keep, cap1, 0, nullptr, 1);
     } else if (grow) {
-      stage(&h->jobBufs, &h->jp.qprio, cap1 * 4, (size_t)M * 4, nullptr, -1); stage(&h->jobBufs, &h->jp.submit, cap1 * 8, (size_t)M * 8, nullptr, -1);
-      stage(&h->jobBufs, &h->jp.runTs, cap1 * 8, (size_t)M * 8, nullptr, -1); stage(&h->jobBufs, &h->jp.keep, cap1, 0, nullptr, 1);
+      sb.stage(&h->jobBufs, &h->jp.qprio, cap1 * 4, (size_t)M * 4, nullptr, -1); sb.stage(&h->jobBufs, &h->jp.submit, cap1 * 8, (size_t)M * 8, nullptr, -1);
+      sb.stage(&h->jobBufs, &h->jp.runTs, cap1 * 8, (size_t)M * 8, nullptr, -1); sb.stage(&h->jobBufs, &h->jp.keep, cap1, 0, nullptr, 1);
     }
     // the two order buffers (they swap): the merge's target and the spare it leaves must both hold the grown order
-    if (h->ordSpareCap < (size_t)total1 || !h->jp.ordSpare) stage(&h->jobBufs, &ordTarget, cap1 * 4, 0, nullptr, -1, true);
-    if (h->ordCap < (size_t)total1) stage(&h->jobBufs, &ordNext, cap1 * 4, 0, nullptr, -1, true);
-    if ((size_t)gangOff1[G1] > h->gangJobsCap) stage(&h->jobBufs, &d.gangJobs, std::max<size_t>((size_t)gangOff1[G1], h->gangJobsCap + h->gangJobsCap / 4) * 4, (size_t)gangOff1[G0] * 4, nullptr, -1);
-    if (gangOffCap1 > h->gangOffCap) stage(&h->jobBufs, &d.gangOff, gangOffCap1 * 4, 0, nullptr, -1);
-    if (ordOffCap1 > h->ordOffCap) stage(&h->jobBufs, &d.ordAllOff, ordOffCap1 * 4, 0, nullptr, -1);
+    if (h->ordSpareCap < (size_t)total1 || !h->jp.ordSpare) sb.stage(&h->jobBufs, &ordTarget, cap1 * 4, 0, nullptr, -1, true);
+    if (h->ordCap < (size_t)total1) sb.stage(&h->jobBufs, &ordNext, cap1 * 4, 0, nullptr, -1, true);
+    if ((size_t)gangOff1[G1] > h->gangJobsCap) sb.stage(&h->jobBufs, &d.gangJobs, std::max<size_t>((size_t)gangOff1[G1], h->gangJobsCap + h->gangJobsCap / 4) * 4, (size_t)gangOff1[G0] * 4, nullptr, -1);
+    if (gangOffCap1 > h->gangOffCap) sb.stage(&h->jobBufs, &d.gangOff, gangOffCap1 * 4, 0, nullptr, -1);
+    if (ordOffCap1 > h->ordOffCap) sb.stage(&h->jobBufs, &d.ordAllOff, ordOffCap1 * 4, 0, nullptr, -1);
   }
   // the per-job and per-gang state of a round: allocated fresh (zeroed) where the capacity grows, as jobs_set allocates it
   const size_t gangJobsCap1 = m > 0 && (size_t)gangOff1[G1] > h->gangJobsCap ? std::max<size_t>((size_t)gangOff1[G1], h->gangJobsCap + h->gangJobsCap / 4) : h->gangJobsCap;
@@ -1949,25 +2005,25 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
   const size_t gangCap1 = growGang ? std::max<size_t>((size_t)G1, h->gangCap + (h->gangCap + 3) / 4) : h->gangCap;
   const size_t gangArrCap1 = growGang ? std::max<size_t>(gangJobsCap1 + std::max<size_t>(cap1, 1), (size_t)gangOff1[G1] + (size_t)std::max(M1, 1)) : h->gangArrCap;
   if (growGang) {
-    stage(&h->jobBufs, &d.gangSeen, (gangCap1 + 1) * 4, 0, nullptr, 0); stage(&h->jobBufs, &d.gangArr, gangArrCap1 * 4, 0, nullptr, 0);
-    stage(&h->jobBufs, &d.gangTotal, (gangCap1 + 1) * (size_t)R * 8, 0, nullptr, 0); stage(&h->jobBufs, &d.gangAllEvicted, gangCap1 + 1, 0, nullptr, 0);
+    sb.stage(&h->jobBufs, &d.gangSeen, (gangCap1 + 1) * 4, 0, nullptr, 0); sb.stage(&h->jobBufs, &d.gangArr, gangArrCap1 * 4, 0, nullptr, 0);
+    sb.stage(&h->jobBufs, &d.gangTotal, (gangCap1 + 1) * (size_t)R * 8, 0, nullptr, 0); sb.stage(&h->jobBufs, &d.gangAllEvicted, gangCap1 + 1, 0, nullptr, 0);
   }
-  if (newShapes) { stage(&h->jobBufs, &d.unfeasible, (size_t)S1, 0, nullptr, 0); stage(&h->jobBufs, &d.unfeasibleReason, (size_t)S1 * 4, 0, nullptr, 0); }
+  if (newShapes) { sb.stage(&h->jobBufs, &d.unfeasible, (size_t)S1, 0, nullptr, 0); sb.stage(&h->jobBufs, &d.unfeasibleReason, (size_t)S1 * 4, 0, nullptr, 0); }
   uint64_t* shapeMask1 = nullptr;   // the grown shape mask [old shape rows | new shape rows | old away rows | new away rows]: filled by plat_shapes_append below
   if (inPlace) {
     if (Sext1 > Sext0) {
-      stage(&h->maskBufs, &shapeMask1, 8 * (size_t)Sext1 * Wm, 0, nullptr, -1, true);
-      stage(&h->maskBufs, &h->dShapeClass, 4 * shapeClassExt1.size(), 4 * shapeClassExt1.size(), shapeClassExt1.data(), 0);
-      stage(&h->maskBufs, &d.shapeReq, 8 * shapeReqExt1.size(), 8 * shapeReqExt1.size(), shapeReqExt1.data(), 0);
-      stage(&h->maskBufs, &d.awayRowOff, 4 * h->awayRowOff.size(), 4 * h->awayRowOff.size(), h->awayRowOff.data(), 0);
-      stage(&h->maskBufs, &d.rowLiteral, h->rowLiteral.size(), h->rowLiteral.size(), h->rowLiteral.data(), 0);
-      stage(&h->maskBufs, &d.rowTypeOff, 4 * rowTypeOff1.size(), 4 * rowTypeOff1.size(), rowTypeOff1.data(), 0);
-      stage(&h->maskBufs, &d.rowTypes, 4 * rowTypes1.size(), 4 * rowTypes1.size(), rowTypes1.data(), 0);
+      sb.stage(&h->maskBufs, &shapeMask1, 8 * (size_t)Sext1 * Wm, 0, nullptr, -1, true);
+      sb.stage(&h->maskBufs, &h->dShapeClass, 4 * shapeClassExt1.size(), 4 * shapeClassExt1.size(), shapeClassExt1.data(), 0);
+      sb.stage(&h->maskBufs, &d.shapeReq, 8 * shapeReqExt1.size(), 8 * shapeReqExt1.size(), shapeReqExt1.data(), 0);
+      sb.stage(&h->maskBufs, &d.awayRowOff, 4 * h->awayRowOff.size(), 4 * h->awayRowOff.size(), h->awayRowOff.data(), 0);
+      sb.stage(&h->maskBufs, &d.rowLiteral, h->rowLiteral.size(), h->rowLiteral.size(), h->rowLiteral.data(), 0);
+      sb.stage(&h->maskBufs, &d.rowTypeOff, 4 * rowTypeOff1.size(), 4 * rowTypeOff1.size(), rowTypeOff1.data(), 0);
+      sb.stage(&h->maskBufs, &d.rowTypes, 4 * rowTypes1.size(), 4 * rowTypes1.size(), rowTypes1.data(), 0);
     }
-    if (h->Cext > Cext0) stage(&h->maskBufs, &h->dClassMask, 8 * (size_t)h->Cext * Wm, 8 * (size_t)Cext0 * Wm, nullptr, -1);   // (the old rows device to device; the new ones are uploaded below)
+    if (h->Cext > Cext0) sb.stage(&h->maskBufs, &h->dClassMask, 8 * (size_t)h->Cext * Wm, 8 * (size_t)Cext0 * Wm, nullptr, -1);   // (the old rows device to device; the new ones are uploaded below)
     if (d.f.structOk && d.f.F > F0) {
-      stage(&h->fastBufs, &d.shapeTab, sizeof(ShapeReq) * h->fitTab.size(), sizeof(ShapeReq) * h->fitTab.size(), h->fitTab.data(), 0);
-      if (d.fitBits) stage(&h->fastBufs, &d.fitBits, 8 * ((size_t)d.f.F * d.fitW + 64), 0, nullptr, 0);   // (scratch the next base build fills, as in asched_nodes_append)
+      sb.stage(&h->fastBufs, &d.shapeTab, sizeof(ShapeReq) * h->fitTab.size(), sizeof(ShapeReq) * h->fitTab.size(), h->fitTab.data(), 0);
+      if (d.fitBits) sb.stage(&h->fastBufs, &d.fitBits, 8 * ((size_t)d.f.F * d.fitW + 64), 0, nullptr, 0);   // (scratch the next base build fills, as in asched_nodes_append)
     }
   }
   if (grow) {
@@ -1975,48 +2031,25 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
     void* s32[] = {&d.schedAtPrio, &d.jobNode, &d.jobCutoff, &d.optGhost, &d.jcAssigned, &d.jcReason, &d.pcNode, &d.pcSap, &d.pcPap, &d.pcMethod, &d.jcGangCard, &d.jcUniValue, &d.jcStagedBy, &d.jcPreSib,
                    &d.preemptedNode, &d.evList, &d.evTabJob, &d.evIndexOfJob, &d.fairEnt, &d.fairEntJob, &d.preList, &d.resJob, &d.resNode, &d.resPrio, &d.resMethod, &d.resPreJob, &d.resPreNode};
     void* s8[] = {&d.jobEvictedOnNode, &d.jobFlags, &d.optSched, &d.optPre, &d.jcEvicted, &d.jcHasPctx, &d.jcPreempted, &d.inPreempted, &d.inScheduled, &d.inSchedAndEvicted, &d.evTabAlive, &d.evFlag};
-    for (void* sl : s32) stage(&h->jobBufs, sl, c * 4, 0, nullptr, 0);
-    for (void* sl : s8) stage(&h->jobBufs, sl, c, 0, nullptr, 0);
-    stage(&h->jobBufs, &d.evSortKey, (c + 1) * 4, 0, nullptr, 0);
+    for (void* sl : s32) sb.stage(&h->jobBufs, sl, c * 4, 0, nullptr, 0);
+    for (void* sl : s8) sb.stage(&h->jobBufs, sl, c, 0, nullptr, 0);
+    sb.stage(&h->jobBufs, &d.evSortKey, (c + 1) * 4, 0, nullptr, 0);
   }
-  for (auto& b : blocks) {
-    b.fresh = plat_malloc(b.bytes);
-    if (!b.fresh) {
-      (void)plat_take_failure();
-      for (auto& x : blocks) if (x.fresh) plat_free(x.fresh);
-      if (scratchNew) plat_free(scratchNew);
-      undo();
-      return fail(h, ASCHED_ERR_DEVICE, "jobs_append: out of device memory for the grown job table; the handle is as it was");
-    }
+  if (!sb.allocate()) {
+    scratch.drop();
+    undo();
+    return fail(h, ASCHED_ERR_DEVICE, "jobs_append: out of device memory for the grown job table; the handle is as it was");
   }
-  // ---- what jobs_set resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the job table half appended: asched_jobs_set before anything else)
-  h->haveRoundResult = false; h->stateEpoch++;
-  if (newShapes && !inPlace) fastInvalidate(h);
-  else { h->dev.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
-    int32_t zero = 0;
-    plat_h2d(&h->dev.rs->fastActive, &zero, sizeof zero);
-    plat_h2d(&h->dev.rs->l0SaveCount, &zero, sizeof zero); }
-  h->prepared = false; h->evrSized = false;
+  // ---- what jobs_set resets (the job table half appended).  A new shape off the in-place path ends with rebuildMasks: the fast structure goes
+  residentTouchJobs(h, newShapes && !inPlace);
   for (int k = 0; k < 3; k++) h->jaMs[k] = 0;
   h->saMs[0] = h->saMs[1] = 0;
-  if (scratchNew) { h->jpBufs.freeAll(); h->jpScratch = scratchNew; h->jpScratchBytes = need + need / 4; h->jpBufs.ptrs.push_back({scratchNew, need + need / 4}); }
+  scratch.adopt();
   if (m > 0) {
     // the blocks: copies and fills queued on the handle's stream, the old blocks released once they are through
-    std::vector<std::pair<DevBufs*, void*>> old;
-    for (auto& b : blocks) {
-      if (b.fill >= 0) plat_memset(b.fresh, b.fill, b.bytes);
-      if (b.host) { if (b.copyBytes) plat_h2d(b.fresh, b.host, b.copyBytes); }
-      else if (b.copyBytes && *b.slot) plat_d2d(b.fresh, *b.slot, b.copyBytes);
-      if (!b.keepOld && *b.slot) old.push_back({b.owner, *b.slot});
-      *b.slot = b.fresh;
-      b.owner->ptrs.push_back({b.fresh, b.bytes});
-    }
-    auto release = [&](DevBufs* owner, void* p) {
-      for (size_t k = 0; k < owner->ptrs.size(); k++) if (owner->ptrs[k].first == p) { owner->ptrs.erase(owner->ptrs.begin() + k); break; }
-      plat_free(p);
-    };
+    sb.fill();
     plat_sync();
-    for (auto& o : old) release(o.first, o.second);
+    sb.commit();
     h->jp.built = true;
     h->jobCap = cap1; h->gangCap = gangCap1; h->gangArrCap = gangArrCap1; h->gangJobsCap = gangJobsCap1;
     h->gangOffCap = gangOffCap1; h->ordOffCap = ordOffCap1;
@@ -2061,7 +2094,7 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
         int src = plat_take_failure() ? -1 : plat_shapes_append(d, sa);
         if (src) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
         plat_shapes_append_ms(h->saMs);
-        release(&h->maskBufs, d.shapeMask);
+        h->maskBufs.release(d.shapeMask);
         d.shapeMask = shapeMask1;
       }
     }
@@ -2088,12 +2121,12 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
       const size_t oldAllCap = h->ordCap, oldSpareCap = h->ordSpareCap;
       if (nT > 0) {
         d.ordAll = target; h->ordCap = ordTarget ? cap1 : oldSpareCap;
-        if (ordTarget && oldSpare) release(&h->jobBufs, oldSpare);
-        if (ordNext) { h->jp.ordSpare = ordNext; h->ordSpareCap = cap1; release(&h->jobBufs, oldAll); }
+        if (ordTarget && oldSpare) h->jobBufs.release(oldSpare);
+        if (ordNext) { h->jp.ordSpare = ordNext; h->ordSpareCap = cap1; h->jobBufs.release(oldAll); }
         else { h->jp.ordSpare = oldAll; h->ordSpareCap = oldAllCap; }
       } else {   // the order stays; the spare is whatever is long enough
-        if (ordTarget) { if (oldSpare) release(&h->jobBufs, oldSpare); h->jp.ordSpare = ordTarget; h->ordSpareCap = cap1; }
-        if (ordNext) { release(&h->jobBufs, ordNext); }
+        if (ordTarget) { if (oldSpare) h->jobBufs.release(oldSpare); h->jp.ordSpare = ordTarget; h->ordSpareCap = cap1; }
+        if (ordNext) { h->jobBufs.release(ordNext); }
       } }
     if (gangTail.size()) plat_h2d(d.gangJobs + gangOff1[G0], gangTail.data(), gangTail.size() * 4);
     plat_h2d(d.gangOff, gangOff1.data(), gangOff1.size() * 4);
@@ -2250,28 +2283,20 @@ int32_t asched_req_classes_append(asched_t* h, const asched_req_classes* more) {
     typeOff[n] = (int32_t)typeList.size();
   }
   // ---- every new device block before anything changes on the device
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t oTypes = up(4 * (size_t)(n + 1)), oHostRow = oTypes + up(4 * std::max<size_t>(typeList.size(), 1)), oRows = oHostRow + up(4 * (size_t)std::max(n, 1)),
-               scratchBytes = oRows + up(8 * std::max<size_t>(hostRows.size(), 1));
-  uint64_t* mask1 = nullptr; char* scratch = nullptr;
+  const size_t oTypes = up256(4 * (size_t)(n + 1)), oHostRow = oTypes + up256(4 * std::max<size_t>(typeList.size(), 1)), oRows = oHostRow + up256(4 * (size_t)std::max(n, 1)),
+               scratchBytes = oRows + up256(8 * std::max<size_t>(hostRows.size(), 1));
+  StagedBlocks sb; char* scratch = nullptr;   // the grown class mask; the scratch is this call's alone and freed at its end
   if (inPlace) {
-    mask1 = (uint64_t*)plat_malloc(8 * (size_t)std::max(h->Cext, 1) * W);
-    scratch = mask1 ? (char*)plat_malloc(scratchBytes) : nullptr;
-    if (!mask1 || !scratch) {
-      (void)plat_take_failure();
-      if (mask1) plat_free(mask1);
+    sb.stage(&h->maskBufs, &h->dClassMask, 8 * (size_t)std::max(h->Cext, 1) * W, -1);
+    if (!(sb.allocate() && (scratch = (char*)plat_try_malloc(scratchBytes)))) {
+      sb.drop();
       undo();
       return fail(h, ASCHED_ERR_DEVICE, "req_classes_append: out of device memory for the grown class mask; the handle is as it was");
     }
   }
-  // ---- what jobs_set resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the class tables half grown: asched_jobs_set before anything else)
-  h->haveRoundResult = false; h->stateEpoch++;
-  if (why) fastInvalidate(h);
-  else { d.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
-    int32_t zero = 0;
-    plat_h2d(&d.rs->fastActive, &zero, sizeof zero);
-    plat_h2d(&d.rs->l0SaveCount, &zero, sizeof zero); }
-  h->prepared = false; h->evrSized = false;
+  uint64_t* mask1 = (uint64_t*)sb.fresh(&h->dClassMask);
+  // ---- what jobs_set resets (the class tables half grown).  Off the in-place path the call ends with rebuildMasks: the fast structure goes
+  residentTouchJobs(h, why != 0);
   memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats);
   h->caMs[0] = h->caMs[1] = 0;
   { int32_t* t = h->caStats;
@@ -2288,7 +2313,7 @@ int32_t asched_req_classes_append(asched_t* h, const asched_req_classes* more) {
     a.outMask = mask1; a.nodeCls = haveFast && C1 <= 64 ? d.nodeCls : nullptr;
     a.inMask = h->dClassMask; a.copy0 = (long long)C0 * W; a.src1 = (long long)C0 * W; a.dst1 = (long long)C1 * W; a.copy1 = (long long)(Cext0 - C0) * W;
     const int src = plat_take_failure() ? -1 : plat_req_classes_append(d, a);
-    if (src) { plat_free(scratch); plat_free(mask1); return fail(h, ASCHED_ERR_DEVICE, plat_last_error()); }
+    if (src) { plat_free(scratch); sb.drop(); return fail(h, ASCHED_ERR_DEVICE, plat_last_error()); }
     plat_req_classes_append_ms(h->caMs);
 #ifdef ASCHED_HOSTSIM
     { // the CPU build: every row decided by node type against the node-by-node match
@@ -2300,9 +2325,7 @@ int32_t asched_req_classes_append(asched_t* h, const asched_req_classes* more) {
             fprintf(stderr, "hostsim: req_classes_append: class %d decided by node type differs from classMatchesNode on node %d\n", C0 + i, v); abort(); }
     }
 #endif
-    for (size_t k = 0; k < h->maskBufs.ptrs.size(); k++) if (h->maskBufs.ptrs[k].first == h->dClassMask) { h->maskBufs.ptrs.erase(h->maskBufs.ptrs.begin() + k); break; }
-    plat_free(h->dClassMask);
-    h->dClassMask = mask1; h->maskBufs.ptrs.push_back({mask1, 8 * (size_t)std::max(h->Cext, 1) * W});
+    sb.commit();
     plat_free(scratch);
     if (Cext0 > C0 && Sext > 0) {   // the class of every mask row: the away rows name derived classes, whose ids moved
       std::vector<int32_t> shapeClassExt = h->shapeClass;
@@ -2459,31 +2482,21 @@ int32_t asched_shapes_compact(asched_t* h, int32_t flags, int32_t* class_new_id)
   }
   const int A1 = (int)h->awayRowClass.size(), Sext1 = S1 + A1, Cext1 = h->Cext;
   // ---- the scratch (the maps and the source tables) and the fresh mask blocks before anything changes on the device: running out of memory is a refusal too
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t oFit = up(4 * (size_t)S0), oCls = oFit + up(4 * (size_t)std::max(F0, 1)), oSSrc = oCls + up(4 * (size_t)C0), oCSrc = oSSrc + up(4 * (size_t)std::max(Sext1, 1)),
-               scratchBytes = oCSrc + up(4 * (size_t)std::max(Cext1, 1));
-  char* scratch = nullptr; uint64_t* shapeMask1 = nullptr; uint64_t* classMask1 = nullptr;
+  const size_t oFit = up256(4 * (size_t)S0), oCls = oFit + up256(4 * (size_t)std::max(F0, 1)), oSSrc = oCls + up256(4 * (size_t)C0), oCSrc = oSSrc + up256(4 * (size_t)std::max(Sext1, 1)),
+               scratchBytes = oCSrc + up256(4 * (size_t)std::max(Cext1, 1));
+  StagedBlocks sb; char* scratch = nullptr;   // the compacted masks; the scratch is this call's alone and freed before they are swapped in
   if (anyDead) {
-    bool ok = (scratch = (char*)plat_malloc(scratchBytes)) != nullptr;
-    if (ok && inPlace) ok = (shapeMask1 = (uint64_t*)plat_malloc(8 * (size_t)std::max(Sext1, 1) * W)) != nullptr;
-    if (ok && inPlace && clsMoves) ok = (classMask1 = (uint64_t*)plat_malloc(8 * (size_t)std::max(Cext1, 1) * W)) != nullptr;
-    if (!ok) {
-      (void)plat_take_failure();
-      if (scratch) plat_free(scratch);
-      if (shapeMask1) plat_free(shapeMask1);
-      if (classMask1) plat_free(classMask1);
+    if (inPlace) sb.stage(&h->maskBufs, &d.shapeMask, 8 * (size_t)std::max(Sext1, 1) * W, -1);
+    if (inPlace && clsMoves) sb.stage(&h->maskBufs, &h->dClassMask, 8 * (size_t)std::max(Cext1, 1) * W, -1);
+    if (!((scratch = (char*)plat_try_malloc(scratchBytes)) && sb.allocate())) {
+      plat_free(scratch);
       undo();
       return fail(h, ASCHED_ERR_DEVICE, "shapes_compact: out of device memory for the compacted mask blocks; the handle is as it was");
     }
   }
-  // ---- what jobs_set resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the tables half compacted: asched_jobs_set before anything else)
-  h->haveRoundResult = false; h->stateEpoch++;
-  if (why) fastInvalidate(h);
-  else { d.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
-    int32_t zero = 0;
-    plat_h2d(&d.rs->fastActive, &zero, sizeof zero);
-    plat_h2d(&d.rs->l0SaveCount, &zero, sizeof zero); }
-  h->prepared = false; h->evrSized = false;
+  uint64_t* shapeMask1 = (uint64_t*)sb.fresh(&d.shapeMask); uint64_t* classMask1 = (uint64_t*)sb.fresh(&h->dClassMask);
+  // ---- what jobs_set resets (the tables half compacted).  Off the in-place path the call ends with rebuildMasks: the fast structure goes
+  residentTouchJobs(h, why != 0);
   memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->caStats, 0, sizeof h->caStats);
   h->scMs[0] = h->scMs[1] = h->scMs[2] = 0; h->scHostMs = 0;
   if (anyDead) {
@@ -2502,17 +2515,11 @@ int32_t asched_shapes_compact(asched_t* h, int32_t flags, int32_t* class_new_id)
       if (C1 < C0 && d.f.structOk && d.nodeCls && C0 <= 64) { a.nodeCls = d.nodeCls; for (int c = 0; c < C0; c++) if (clsLive[c]) a.liveCls |= 1ull << c; }
     }
     const int src = plat_take_failure() ? -1 : plat_shapes_compact(d, a);
-    if (src) { plat_free(scratch); if (shapeMask1) plat_free(shapeMask1); if (classMask1) plat_free(classMask1); return fail(h, ASCHED_ERR_DEVICE, plat_last_error()); }
+    if (src) { plat_free(scratch); sb.drop(); return fail(h, ASCHED_ERR_DEVICE, plat_last_error()); }
     plat_shapes_compact_ms(h->scMs);
     plat_free(scratch);
-    auto swapIn = [&](void* oldp, void* fresh, size_t bytes) {
-      for (size_t k = 0; k < h->maskBufs.ptrs.size(); k++) if (h->maskBufs.ptrs[k].first == oldp) { h->maskBufs.ptrs.erase(h->maskBufs.ptrs.begin() + k); break; }
-      plat_free(oldp);
-      h->maskBufs.ptrs.push_back({fresh, bytes});
-    };
     if (inPlace) {
-      swapIn(d.shapeMask, shapeMask1, 8 * (size_t)std::max(Sext1, 1) * W); d.shapeMask = shapeMask1;
-      if (classMask1) { swapIn(h->dClassMask, classMask1, 8 * (size_t)std::max(Cext1, 1) * W); h->dClassMask = classMask1; }
+      sb.commit();
       // the small tables from the compacted host vectors: each is no longer than the block that holds it
       plat_h2d(h->dShapeClass, shapeClassExt1.data(), 4 * shapeClassExt1.size());
       plat_h2d(d.shapeReq, shapeReqExt1.data(), 8 * shapeReqExt1.size());
@@ -2609,70 +2616,57 @@ int32_t asched_jobs_delete(asched_t* h, int32_t n, const int32_t* job, int32_t* 
   const bool haveRec = d.f.structOk && d.jrec;
   // ---- the scratch and every new block before anything changes: running out of device memory here is a refusal too.  The scratch: the entries | the survivors' list |
   // the new ids | the compacted gang lists.  The blocks: one per static per-job array, of the table's capacity (capacities do not shrink); the old ones are released at the end
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t oSrc = up(sizeof(int32_t) * (size_t)n), oNew = oSrc + up(sizeof(int32_t) * (size_t)M), oGang = oNew + up(sizeof(int32_t) * (size_t)M),
-               need = oGang + up(sizeof(int32_t) * (size_t)gangLen);
-  struct Block { DevBufs* owner; void** slot; size_t bytes; void* fresh; };
-  std::vector<Block> blocks;
-  char* scratchNew = nullptr;
+  const size_t oSrc = up256(sizeof(int32_t) * (size_t)n), oNew = oSrc + up256(sizeof(int32_t) * (size_t)M), oGang = oNew + up256(sizeof(int32_t) * (size_t)M),
+               need = oGang + up256(sizeof(int32_t) * (size_t)gangLen);
+  StagedBlocks sb;
+  KeptBlock<char> scratch{h->jpBufs, h->jpScratch, h->jpScratchBytes};
   const bool buildJp = n > 0 && !h->jp.built;
   const bool needSpare = n > 0 && (!h->jp.ordSpare || h->ordSpareCap < (size_t)total1);
-  int32_t* ordSpareNew = nullptr;   // (its block is the one whose slot is this variable)
+  int32_t* ordSpareNew = nullptr;   // (its block is the one whose slot is this variable: nothing to release in its place)
   if (n > 0) {
-    auto stage = [&](DevBufs* owner, void* slot, size_t bytes) { blocks.push_back({owner, (void**)slot, std::max<size_t>(bytes, 1), nullptr}); };
+    // (fill -1: none of these blocks is filled; the keep flags of a first incremental call are)
     void* s32[] = {&d.jQueue, &d.jPc, &d.jShape, &d.jGang, &d.jGangCard, &d.jGangUni, &d.jNode0, &d.jRunPrio, &h->jp.qprio};
-    for (void* sl : s32) stage(&h->jobBufs, sl, cap * 4);
-    if (d.jAway) stage(&h->jobBufs, &d.jAway, cap);
-    stage(&h->jobBufs, &d.jAligned, cap); stage(&h->jobBufs, &d.jLeaseMs, cap * 8); stage(&h->jobBufs, &h->jp.submit, cap * 8); stage(&h->jobBufs, &h->jp.runTs, cap * 8);
-    stage(&h->jobBufs, &d.jReq, cap * 8 * R);
-    if (haveRec) stage(&h->fastBufs, &d.jrec, sizeof(JobRec) * cap);
-    if (buildJp) stage(&h->jobBufs, &h->jp.keep, cap);
-    if (needSpare) stage(&h->jobBufs, &ordSpareNew, std::max<size_t>((size_t)total, h->ordCap) * 4);
-    bool ok = true;
-    if (h->jpScratchBytes < need) { scratchNew = (char*)plat_malloc(need + need / 4); ok = scratchNew != nullptr; }
-    for (auto& b : blocks) { if (!ok) break; b.fresh = plat_malloc(b.bytes); ok = b.fresh != nullptr; }
-    if (!ok) {
-      (void)plat_take_failure();
-      for (auto& b : blocks) if (b.fresh) plat_free(b.fresh);
-      if (scratchNew) plat_free(scratchNew);
+    for (void* sl : s32) sb.stage(&h->jobBufs, sl, cap * 4, -1);
+    if (d.jAway) sb.stage(&h->jobBufs, &d.jAway, cap, -1);
+    sb.stage(&h->jobBufs, &d.jAligned, cap, -1); sb.stage(&h->jobBufs, &d.jLeaseMs, cap * 8, -1); sb.stage(&h->jobBufs, &h->jp.submit, cap * 8, -1); sb.stage(&h->jobBufs, &h->jp.runTs, cap * 8, -1);
+    sb.stage(&h->jobBufs, &d.jReq, cap * 8 * R, -1);
+    if (haveRec) sb.stage(&h->fastBufs, &d.jrec, sizeof(JobRec) * cap, -1);
+    if (buildJp) sb.stage(&h->jobBufs, &h->jp.keep, cap, 1);   // first incremental call of this job table: the keep flags (the order-key inputs are uploaded below, compacted)
+    if (needSpare) sb.stage(&h->jobBufs, &ordSpareNew, std::max<size_t>((size_t)total, h->ordCap) * 4, 0, nullptr, -1, true);
+    if (!(scratch.tryGrow(need) && sb.allocate())) {
+      scratch.drop();
       for (int i = 0; i < n; i++) gone[job[i]] = 0;
       return fail(h, ASCHED_ERR_DEVICE, "jobs_delete: out of device memory for the scratch and the compacted job table; the handle is as it was");
     }
   }
-  // ---- what jobs_set resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the job table half compacted: asched_jobs_set before anything else)
-  h->haveRoundResult = false; h->stateEpoch++;
-  { h->dev.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
-    int32_t zero = 0;
-    plat_h2d(&h->dev.rs->fastActive, &zero, sizeof zero);
-    plat_h2d(&h->dev.rs->l0SaveCount, &zero, sizeof zero); }
-  h->prepared = false; h->evrSized = false;
+  // ---- what jobs_set resets (the job table half compacted)
+  residentTouchJobs(h);
   for (int k = 0; k < 5; k++) h->jdMs[k] = 0;
   h->jdHostMs = 0;
   int gangsEmptied = 0, shapesEmptied = 0;
   if (n > 0) {
-    if (scratchNew) { h->jpBufs.freeAll(); h->jpScratch = scratchNew; h->jpScratchBytes = need + need / 4; h->jpBufs.ptrs.push_back({scratchNew, need + need / 4}); }
-    auto fresh = [&](void* slot) -> void* { for (auto& b : blocks) if ((void*)b.slot == slot) return b.fresh; return nullptr; };
-    if (needSpare) ordSpareNew = (int32_t*)fresh(&ordSpareNew);
-    if (buildJp) plat_memset(fresh(&h->jp.keep), 1, cap);   // first incremental call of this job table: the keep flags (the order-key inputs are uploaded below, compacted)
+    scratch.adopt();
+    if (needSpare) ordSpareNew = (int32_t*)sb.fresh(&ordSpareNew);
+    sb.fill();
     JdArgs a; memset(&a, 0, sizeof a);
     a.M = M; a.M1 = M1; a.n = n; a.R = R; a.total = total; a.total1 = total1; a.gangLen = gangLen; a.gangLen1 = gangLen1;
     int32_t* e32 = (int32_t*)h->jpScratch;
     plat_h2d(e32, job, sizeof(int32_t) * (size_t)n);
-    a.job = e32; a.keep = buildJp ? (uint8_t*)fresh(&h->jp.keep) : h->jp.keep;
+    a.job = e32; a.keep = buildJp ? (uint8_t*)sb.fresh(&h->jp.keep) : h->jp.keep;
     a.src = (int32_t*)(h->jpScratch + oSrc); a.newId = (uint32_t*)(h->jpScratch + oNew);
     { const int32_t* in[JD_N32] = {d.jQueue, d.jPc, d.jShape, d.jGang, d.jGangCard, d.jGangUni, d.jNode0, d.jRunPrio, buildJp ? nullptr : (const int32_t*)h->jp.qprio};   // (the queue priorities move as the 4-byte words they are)
       void* sl[JD_N32] = {&d.jQueue, &d.jPc, &d.jShape, &d.jGang, &d.jGangCard, &d.jGangUni, &d.jNode0, &d.jRunPrio, &h->jp.qprio};
-      for (int k = 0; k < JD_N32; k++) { a.in32[k] = in[k]; a.out32[k] = (int32_t*)fresh(sl[k]); } }
-    a.inAway = d.jAway; a.outAway = (uint8_t*)fresh(&d.jAway); a.inAligned = d.jAligned; a.outAligned = (uint8_t*)fresh(&d.jAligned);
-    a.inLease = d.jLeaseMs; a.outLease = (int64_t*)fresh(&d.jLeaseMs);
-    a.inSubmit = buildJp ? nullptr : h->jp.submit; a.outSubmit = (int64_t*)fresh(&h->jp.submit); a.inRunTs = buildJp ? nullptr : h->jp.runTs; a.outRunTs = (int64_t*)fresh(&h->jp.runTs);
-    a.inReq = d.jReq; a.outReq = (int64_t*)fresh(&d.jReq);
-    if (haveRec) { a.inRec = d.jrec; a.outRec = (JobRec*)fresh(&d.jrec); }
+      for (int k = 0; k < JD_N32; k++) { a.in32[k] = in[k]; a.out32[k] = (int32_t*)sb.fresh(sl[k]); } }
+    a.inAway = d.jAway; a.outAway = (uint8_t*)sb.fresh(&d.jAway); a.inAligned = d.jAligned; a.outAligned = (uint8_t*)sb.fresh(&d.jAligned);
+    a.inLease = d.jLeaseMs; a.outLease = (int64_t*)sb.fresh(&d.jLeaseMs);
+    a.inSubmit = buildJp ? nullptr : h->jp.submit; a.outSubmit = (int64_t*)sb.fresh(&h->jp.submit); a.inRunTs = buildJp ? nullptr : h->jp.runTs; a.outRunTs = (int64_t*)sb.fresh(&h->jp.runTs);
+    a.inReq = d.jReq; a.outReq = (int64_t*)sb.fresh(&d.jReq);
+    if (haveRec) { a.inRec = d.jrec; a.outRec = (JobRec*)sb.fresh(&d.jrec); }
     a.ordIn = d.ordAll; a.ordOut = ordSpareNew ? ordSpareNew : h->jp.ordSpare;
     a.gangIn = d.gangJobs; a.gangOut = (int32_t*)(h->jpScratch + oGang);
     int prc = plat_take_failure() ? -1 : plat_jobs_delete(d, a);
     if (prc) {
-      for (auto& b : blocks) plat_free(b.fresh);
+      sb.drop();
       gone.assign(M, 0);
       return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
     }
@@ -2683,15 +2677,8 @@ int32_t asched_jobs_delete(asched_t* h, int32_t n, const int32_t* job, int32_t* 
       for (int i = 0; i < n; i++) new_id[job[i]] = -1;
     }
     // the blocks: swapped in, the old ones released (plat_jobs_delete has waited for the device)
-    auto release = [&](DevBufs* owner, void* p) {
-      for (size_t k = 0; k < owner->ptrs.size(); k++) if (owner->ptrs[k].first == p) { owner->ptrs.erase(owner->ptrs.begin() + k); break; }
-      plat_free(p);
-    };
-    if (ordSpareNew) { if (h->jp.ordSpare) release(&h->jobBufs, h->jp.ordSpare); h->jp.ordSpare = nullptr; }
-    for (auto& b : blocks) {
-      if ((void*)b.slot != (void*)&ordSpareNew) { if (*b.slot) release(b.owner, *b.slot); *b.slot = b.fresh; }
-      b.owner->ptrs.push_back({b.fresh, b.bytes});
-    }
+    if (ordSpareNew) { if (h->jp.ordSpare) h->jobBufs.release(h->jp.ordSpare); h->jp.ordSpare = nullptr; }
+    sb.commit();
     if (ordSpareNew) { h->jp.ordSpare = ordSpareNew; h->ordSpareCap = std::max<size_t>((size_t)total, h->ordCap); }
     if (total > 0) { std::swap(d.ordAll, h->jp.ordSpare); std::swap(h->ordCap, h->ordSpareCap); }
     // ---- the host mirrors, compacted in place (row order is kept: every element moves down or stays), one array per host thread; then what the host derives from them
@@ -2876,24 +2863,13 @@ int32_t asched_nodes_patch(asched_t* h, const asched_nodes_patch_rows* rows) {
   // ---- the device path.  One scratch block for the entries, kept and only ever grown, sized before anything changes: running out of device memory here is a refusal too
   const bool masks = h->jobsSet && h->dClassMask && h->dShapeClass;
   const int Cext = masks ? h->Cext : 0, CW = std::max(1, (Cext + 63) / 64);
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t oType = up(sizeof(int32_t) * (size_t)n), oWordOff = oType + up(sizeof(int32_t) * (size_t)n), oWordIdx = oWordOff + up(sizeof(int32_t) * ((size_t)n + 1)),
-               oFlags = oWordIdx + up(sizeof(int32_t) * (size_t)n), oAlloc = oFlags + up((size_t)n), oCls = oAlloc + up(sizeof(int64_t) * (size_t)n * R),
-               need = oCls + up(sizeof(uint64_t) * (size_t)n * CW);
-  if (n > 0 && h->npScratchBytes < need) {
-    char* p = (char*)plat_malloc(need + need / 4);
-    if (!p) { (void)plat_take_failure(); return fail(h, ASCHED_ERR_DEVICE, "nodes_patch: out of device memory for the patch entries; the handle is as it was"); }
-    h->npBufs.freeAll();
-    h->npScratch = p; h->npScratchBytes = need + need / 4;
-    h->npBufs.ptrs.push_back({p, need + need / 4});
-  }
-  // ---- what nodes_upsert resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the node table half patched: asched_nodes_upsert before anything else)
-  h->haveRoundResult = false; h->stateEpoch++;
-  { d.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
-    int32_t zero = 0;
-    plat_h2d(&d.rs->fastActive, &zero, sizeof zero);
-    plat_h2d(&d.rs->l0SaveCount, &zero, sizeof zero); }
-  h->prepared = false; h->evrSized = false; h->equalLevels = h->P;
+  const size_t oType = up256(sizeof(int32_t) * (size_t)n), oWordOff = oType + up256(sizeof(int32_t) * (size_t)n), oWordIdx = oWordOff + up256(sizeof(int32_t) * ((size_t)n + 1)),
+               oFlags = oWordIdx + up256(sizeof(int32_t) * (size_t)n), oAlloc = oFlags + up256((size_t)n), oCls = oAlloc + up256(sizeof(int64_t) * (size_t)n * R),
+               need = oCls + up256(sizeof(uint64_t) * (size_t)n * CW);
+  KeptBlock<char> scratch{h->npBufs, h->npScratch, h->npScratchBytes};
+  if (n > 0 && !scratch.grow(need)) return fail(h, ASCHED_ERR_DEVICE, "nodes_patch: out of device memory for the patch entries; the handle is as it was");
+  // ---- what nodes_upsert resets (the node table half patched: asched_nodes_upsert before anything else)
+  residentTouchNodes(h);
   memset(h->npStats, 0, sizeof h->npStats); h->npMs[0] = h->npMs[1] = 0;
   h->npStats[0] = n; h->npStats[1] = typeChanged;
   if (n > 0) {
@@ -3024,45 +3000,32 @@ int32_t asched_nodes_delete(asched_t* h, int32_t n, const int32_t* node, int32_t
   const bool masks = !why && h->jobsSet && h->dClassMask && h->dShapeClass;
   const bool haveFast = !why && h->jobsSet && d.f.structOk && d.nodeCls;
   const int Sext = masks ? h->S + (int)h->awayRowClass.size() : 0, labelRows = masks && !h->uniOffHost.empty() ? h->uniOffHost.back() : 0;
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t oSrc = up(sizeof(int32_t) * (size_t)n), oNew = oSrc + up(sizeof(int32_t) * (size_t)N), oBad = oNew + up(sizeof(int32_t) * (size_t)N), need = oBad + 256;
-  struct Block { DevBufs* owner; void** slot; size_t bytes; int fill; void* fresh; };
-  std::vector<Block> blocks;
-  char* scratchNew = nullptr; uint8_t* keepNew = nullptr;
+  const size_t oSrc = up256(sizeof(int32_t) * (size_t)n), oNew = oSrc + up256(sizeof(int32_t) * (size_t)N), oBad = oNew + up256(sizeof(int32_t) * (size_t)N), need = oBad + 256;
+  StagedBlocks sb;   // (every block starts as zeros; the keys as 0xff bytes)
+  KeptBlock<char> scratch{h->ndBufs, h->ndScratch, h->ndScratchBytes};
+  KeptBlock<uint8_t> keep{h->ndBufs, h->ndKeep, h->ndKeepCap};   // the keep flags: [N] exactly, all 1 between calls
   if (n > 0) {
-    auto stage = [&](DevBufs* owner, void* slot, size_t bytes, int fill = 0) { blocks.push_back({owner, (void**)slot, std::max<size_t>(bytes, 1), fill, nullptr}); };
     if (!why) {
       const size_t np = (size_t)Npad;
-      stage(&h->nodeBufs, &d.totalRes, 8 * R * np); stage(&h->nodeBufs, &d.allocatable, 8 * R * np); stage(&h->nodeBufs, &d.alloc, 8 * (size_t)P * R * np);
-      stage(&h->nodeBufs, &d.keys, 8 * 2 * (size_t)P * np, 0xff);
-      stage(&h->nodeBufs, &d.nodeFlags, (size_t)N); stage(&h->nodeBufs, &d.idxRank, 4 * (size_t)N); stage(&h->nodeBufs, &d.nodeByRank, 4 * (size_t)N); stage(&h->nodeBufs, &d.nodeIdRank, 4 * (size_t)N);
-      stage(&h->nodeBufs, &d.accAvail, 8 * np * R); stage(&h->nodeBufs, &d.accStamp, 4 * np); stage(&h->nodeBufs, &d.accStaticFailed, np);
-      stage(&h->nodeBufs, &d.fairOff, 4 * (np + 2)); stage(&h->nodeBufs, &d.nodeOver, 4 * np);
+      sb.stage(&h->nodeBufs, &d.totalRes, 8 * R * np); sb.stage(&h->nodeBufs, &d.allocatable, 8 * R * np); sb.stage(&h->nodeBufs, &d.alloc, 8 * (size_t)P * R * np);
+      sb.stage(&h->nodeBufs, &d.keys, 8 * 2 * (size_t)P * np, 0xff);
+      sb.stage(&h->nodeBufs, &d.nodeFlags, (size_t)N); sb.stage(&h->nodeBufs, &d.idxRank, 4 * (size_t)N); sb.stage(&h->nodeBufs, &d.nodeByRank, 4 * (size_t)N); sb.stage(&h->nodeBufs, &d.nodeIdRank, 4 * (size_t)N);
+      sb.stage(&h->nodeBufs, &d.accAvail, 8 * np * R); sb.stage(&h->nodeBufs, &d.accStamp, 4 * np); sb.stage(&h->nodeBufs, &d.accStaticFailed, np);
+      sb.stage(&h->nodeBufs, &d.fairOff, 4 * (np + 2)); sb.stage(&h->nodeBufs, &d.nodeOver, 4 * np);
       if (masks) {
-        stage(&h->maskBufs, &h->dClassMask, 8 * (size_t)h->Cext * W); stage(&h->maskBufs, &d.shapeMask, 8 * (size_t)std::max(Sext, 1) * W);
-        stage(&h->maskBufs, &d.typeMask, 8 * std::max<size_t>(h->types.size(), 1) * W); stage(&h->maskBufs, &d.labelMask, 8 * (size_t)std::max(labelRows, 1) * W);
-        stage(&h->maskBufs, &h->dNodeType, 4 * (size_t)N);
+        sb.stage(&h->maskBufs, &h->dClassMask, 8 * (size_t)h->Cext * W); sb.stage(&h->maskBufs, &d.shapeMask, 8 * (size_t)std::max(Sext, 1) * W);
+        sb.stage(&h->maskBufs, &d.typeMask, 8 * std::max<size_t>(h->types.size(), 1) * W); sb.stage(&h->maskBufs, &d.labelMask, 8 * (size_t)std::max(labelRows, 1) * W);
+        sb.stage(&h->maskBufs, &h->dNodeType, 4 * (size_t)N);
       }
-      if (haveFast) stage(&h->fastBufs, &d.nodeCls, 8 * (size_t)N);
+      if (haveFast) sb.stage(&h->fastBufs, &d.nodeCls, 8 * (size_t)N);
     }
-    bool ok = true;
-    if (h->ndScratchBytes < need) { scratchNew = (char*)plat_malloc(need + need / 4); ok = scratchNew != nullptr; }
-    if (ok && h->ndKeepCap < (size_t)N) { keepNew = (uint8_t*)plat_malloc((size_t)N); ok = keepNew != nullptr; }
-    for (auto& b : blocks) { if (!ok) break; b.fresh = plat_malloc(b.bytes); ok = b.fresh != nullptr; }
-    if (!ok) {
-      (void)plat_take_failure();
-      for (auto& b : blocks) if (b.fresh) plat_free(b.fresh);
-      if (scratchNew) plat_free(scratchNew);
-      if (keepNew) plat_free(keepNew);
+    if (!(scratch.tryGrow(need) && keep.tryGrow((size_t)N, false) && sb.allocate())) {
+      scratch.drop(); keep.drop();
       ungone(n);
       return fail(h, ASCHED_ERR_DEVICE, "nodes_delete: out of device memory for the scratch and the compacted node table; the handle is as it was");
     }
-    auto adopt = [&](void* fresh, size_t bytes, void* old) {
-      for (size_t k = 0; k < h->ndBufs.ptrs.size(); k++) if (old && h->ndBufs.ptrs[k].first == old) { h->ndBufs.ptrs.erase(h->ndBufs.ptrs.begin() + k); plat_free(old); break; }
-      h->ndBufs.ptrs.push_back({fresh, bytes});
-    };
-    if (scratchNew) { adopt(scratchNew, need + need / 4, h->ndScratch); h->ndScratch = scratchNew; h->ndScratchBytes = need + need / 4; }
-    if (keepNew) { adopt(keepNew, (size_t)N, h->ndKeep); h->ndKeep = keepNew; h->ndKeepCap = (size_t)N; plat_memset(keepNew, 1, (size_t)N); }
+    scratch.adopt();
+    if (keep.adopt()) plat_memset(h->ndKeep, 1, (size_t)N);
   }
   // ---- mark and check: a running job on a named row is the last refusal, read from the device before anything else is written
   NdArgs a; memset(&a, 0, sizeof a);
@@ -3075,41 +3038,35 @@ int32_t asched_nodes_delete(asched_t* h, int32_t n, const int32_t* node, int32_t
     int32_t bad = ND_NONE;
     const int crc = plat_take_failure() ? -1 : plat_nodes_delete_check(d, a, &bad);
     if (crc || bad != ND_NONE) {
-      for (auto& b : blocks) plat_free(b.fresh);
+      sb.drop();
       ungone(n);
       if (crc) { h->ndBufs.freeAll(); h->ndKeep = nullptr; h->ndKeepCap = 0; h->ndScratch = nullptr; h->ndScratchBytes = 0; return fail(h, ASCHED_ERR_DEVICE, plat_last_error()); }
       return fail(h, ASCHED_ERR_INVALID, "nodes_delete: job row " + std::to_string(bad) + " runs on a named node (say what became of the run first: jobs_patch with node -1, or jobs_delete)");
     }
   }
-  // ---- what nodes_upsert resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the tables half compacted: asched_nodes_upsert and asched_jobs_set before anything else)
-  h->haveRoundResult = false; h->stateEpoch++;
-  { d.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
-    int32_t zero = 0;
-    plat_h2d(&d.rs->fastActive, &zero, sizeof zero);
-    plat_h2d(&d.rs->l0SaveCount, &zero, sizeof zero); }
-  h->prepared = false; h->evrSized = false; h->equalLevels = P;
+  // ---- what nodes_upsert resets (the tables half compacted: asched_nodes_upsert and asched_jobs_set before anything else)
+  residentTouchNodes(h);
   memset(h->ndStats, 0, sizeof h->ndStats); for (int k = 0; k < 7; k++) h->ndMs[k] = 0;
   int renumbered = 0;
   if (n > 0) {
-    auto fresh = [&](void* slot) -> void* { for (auto& b : blocks) if ((void*)b.slot == slot) return b.fresh; return nullptr; };
-    for (auto& b : blocks) plat_memset(b.fresh, b.fill, b.bytes);
+    sb.fill();
     a.jobsOnly = why ? 1 : 0;
     if (!why) {
-      a.inTotal = d.totalRes; a.outTotal = (int64_t*)fresh(&d.totalRes); a.inAlloc = d.allocatable; a.outAlloc = (int64_t*)fresh(&d.allocatable);
-      a.inFlags = d.nodeFlags; a.outFlags = (uint8_t*)fresh(&d.nodeFlags); a.inIdRank = d.nodeIdRank; a.outIdRank = (int32_t*)fresh(&d.nodeIdRank);
-      a.rankIn = d.nodeByRank; a.rankOut = (int32_t*)fresh(&d.nodeByRank); a.idxRankOut = (int32_t*)fresh(&d.idxRank);
+      a.inTotal = d.totalRes; a.outTotal = (int64_t*)sb.fresh(&d.totalRes); a.inAlloc = d.allocatable; a.outAlloc = (int64_t*)sb.fresh(&d.allocatable);
+      a.inFlags = d.nodeFlags; a.outFlags = (uint8_t*)sb.fresh(&d.nodeFlags); a.inIdRank = d.nodeIdRank; a.outIdRank = (int32_t*)sb.fresh(&d.nodeIdRank);
+      a.rankIn = d.nodeByRank; a.rankOut = (int32_t*)sb.fresh(&d.nodeByRank); a.idxRankOut = (int32_t*)sb.fresh(&d.idxRank);
       if (masks) {
-        a.inType = h->dNodeType; a.outType = (int32_t*)fresh(&h->dNodeType);
+        a.inType = h->dNodeType; a.outType = (int32_t*)sb.fresh(&h->dNodeType);
         const uint64_t* in[ND_MASKS] = {h->dClassMask, d.shapeMask, d.typeMask, d.labelMask};
         void* sl[ND_MASKS] = {&h->dClassMask, &d.shapeMask, &d.typeMask, &d.labelMask};
         const int rows[ND_MASKS] = {h->Cext, Sext, (int)h->types.size(), labelRows};
-        for (int k = 0; k < ND_MASKS; k++) { a.inMask[k] = in[k]; a.outMask[k] = (uint64_t*)fresh(sl[k]); a.rows[k] = rows[k]; }
+        for (int k = 0; k < ND_MASKS; k++) { a.inMask[k] = in[k]; a.outMask[k] = (uint64_t*)sb.fresh(sl[k]); a.rows[k] = rows[k]; }
       }
-      if (haveFast) { a.inCls = d.nodeCls; a.outCls = (uint64_t*)fresh(&d.nodeCls); }
+      if (haveFast) { a.inCls = d.nodeCls; a.outCls = (uint64_t*)sb.fresh(&d.nodeCls); }
     }
     const int prc = plat_take_failure() ? -1 : plat_nodes_delete(d, a);
     if (prc) {
-      for (auto& b : blocks) plat_free(b.fresh);
+      sb.drop();
       gone.assign(N, 0);
       h->ndBufs.freeAll(); h->ndKeep = nullptr; h->ndKeepCap = 0; h->ndScratch = nullptr; h->ndScratchBytes = 0;
       return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
@@ -3142,11 +3099,7 @@ int32_t asched_nodes_delete(asched_t* h, int32_t n, const int32_t* node, int32_t
       if (rc) return rc;
     } else {
       // ---- the device path: the blocks swapped in, the old ones released (plat_nodes_delete has waited for the device)
-      auto release = [&](DevBufs* owner, void* p) {
-        for (size_t k = 0; k < owner->ptrs.size(); k++) if (owner->ptrs[k].first == p) { owner->ptrs.erase(owner->ptrs.begin() + k); break; }
-        plat_free(p);
-      };
-      for (auto& b : blocks) { if (*b.slot) release(b.owner, *b.slot); *b.slot = b.fresh; b.owner->ptrs.push_back({b.fresh, b.bytes}); }
+      sb.commit();
       // scratch indexed by node that lives in the fast structure: the start a fresh nodes_upsert + jobs_set gives it (zeros), over the whole block
       if (haveFast) {
         void* scr[] = {d.baseKey, d.baseNode, d.baseExtra, d.baseCls, d.baseRemoved, d.posOf, d.l0Slot, d.fitBits};
@@ -3365,59 +3318,46 @@ int32_t asched_nodes_append(asched_t* h, const asched_nodes_append_rows* rows) {
   const bool haveFast = h->jobsSet && d.f.structOk && d.nodeCls;
   const int Cext = masks ? h->Cext : 0, CW = std::max(1, (Cext + 63) / 64);
   const int Sext = masks ? h->S + (int)h->awayRowClass.size() : 0, T = masks ? (int)h->types.size() : 0, labelRows = masks && !h->uniOffHost.empty() ? h->uniOffHost.back() : 0;
-  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t mm = (size_t)m;
-  const size_t oAlloc = up(8 * mm * R), oIdRank = oAlloc + up(8 * mm * R), oType = oIdRank + up(4 * mm), oIns = oType + up(4 * mm), oInsRow = oIns + up(4 * mm),
-               oLab = oInsRow + up(4 * mm), oCls = oLab + up(4 * mm * std::max<size_t>(L, 1)), oFlags = oCls + up(8 * mm * CW), oAll = oFlags + up(mm),
-               need = oAll + (rows->id_rank_all ? up(4 * (size_t)N1) : 0) + 256;
-  struct Block { DevBufs* owner; void** slot; size_t bytes; int fill; void* fresh; };
-  std::vector<Block> blocks; std::vector<std::pair<void*, size_t>> zeroed;
-  char* scratchNew = nullptr;
+  const size_t oAlloc = up256(8 * mm * R), oIdRank = oAlloc + up256(8 * mm * R), oType = oIdRank + up256(4 * mm), oIns = oType + up256(4 * mm), oInsRow = oIns + up256(4 * mm),
+               oLab = oInsRow + up256(4 * mm), oCls = oLab + up256(4 * mm * std::max<size_t>(L, 1)), oFlags = oCls + up256(8 * mm * CW), oAll = oFlags + up256(mm),
+               need = oAll + (rows->id_rank_all ? up256(4 * (size_t)N1) : 0) + 256;
+  StagedBlocks sb; std::vector<std::pair<void*, size_t>> zeroed;   // (every block starts as zeros; the keys as 0xff bytes)
+  KeptBlock<char> entries{h->naBufs, h->naScratch, h->naScratchBytes};
   if (m > 0) {
-    auto stage = [&](DevBufs* owner, void* slot, size_t bytes, int fill = 0) { blocks.push_back({owner, (void**)slot, std::max<size_t>(bytes, 1), fill, nullptr}); };
     auto scratch = [&](DevBufs* owner, void* slot, size_t bytes) {   // node-indexed scratch: zeros of at least `bytes`
       void* p = *(void**)slot;
       for (auto& e : owner->ptrs) if (p && e.first == p && e.second >= bytes) { zeroed.push_back({p, e.second}); return; }
-      stage(owner, slot, bytes);
+      sb.stage(owner, slot, bytes);
     };
     const size_t np = (size_t)Npad1, n1 = (size_t)N1;
-    stage(&h->nodeBufs, &d.totalRes, 8 * R * np); stage(&h->nodeBufs, &d.allocatable, 8 * R * np); stage(&h->nodeBufs, &d.alloc, 8 * (size_t)P * R * np);
-    stage(&h->nodeBufs, &d.keys, 8 * 2 * (size_t)P * np, 0xff);
-    stage(&h->nodeBufs, &d.nodeFlags, n1); stage(&h->nodeBufs, &d.idxRank, 4 * n1); stage(&h->nodeBufs, &d.nodeByRank, 4 * n1); stage(&h->nodeBufs, &d.nodeIdRank, 4 * n1);
+    sb.stage(&h->nodeBufs, &d.totalRes, 8 * R * np); sb.stage(&h->nodeBufs, &d.allocatable, 8 * R * np); sb.stage(&h->nodeBufs, &d.alloc, 8 * (size_t)P * R * np);
+    sb.stage(&h->nodeBufs, &d.keys, 8 * 2 * (size_t)P * np, 0xff);
+    sb.stage(&h->nodeBufs, &d.nodeFlags, n1); sb.stage(&h->nodeBufs, &d.idxRank, 4 * n1); sb.stage(&h->nodeBufs, &d.nodeByRank, 4 * n1); sb.stage(&h->nodeBufs, &d.nodeIdRank, 4 * n1);
     scratch(&h->nodeBufs, &d.accAvail, 8 * np * R); scratch(&h->nodeBufs, &d.accStamp, 4 * np); scratch(&h->nodeBufs, &d.accStaticFailed, np);
     scratch(&h->nodeBufs, &d.fairOff, 4 * (np + 2)); scratch(&h->nodeBufs, &d.nodeOver, 4 * np);
     if (masks) {
-      stage(&h->maskBufs, &h->dClassMask, 8 * (size_t)std::max(Cext, 1) * W1); stage(&h->maskBufs, &d.shapeMask, 8 * (size_t)std::max(Sext, 1) * W1);
-      stage(&h->maskBufs, &d.typeMask, 8 * (size_t)std::max(T, 1) * W1); stage(&h->maskBufs, &d.labelMask, 8 * (size_t)std::max(labelRows, 1) * W1);
-      stage(&h->maskBufs, &h->dNodeType, 4 * n1);
+      sb.stage(&h->maskBufs, &h->dClassMask, 8 * (size_t)std::max(Cext, 1) * W1); sb.stage(&h->maskBufs, &d.shapeMask, 8 * (size_t)std::max(Sext, 1) * W1);
+      sb.stage(&h->maskBufs, &d.typeMask, 8 * (size_t)std::max(T, 1) * W1); sb.stage(&h->maskBufs, &d.labelMask, 8 * (size_t)std::max(labelRows, 1) * W1);
+      sb.stage(&h->maskBufs, &h->dNodeType, 4 * n1);
     }
     if (haveFast) {
       size_t Nb2 = 64;
       while (Nb2 < n1) Nb2 <<= 1;
-      stage(&h->fastBufs, &d.nodeCls, 8 * n1);
+      sb.stage(&h->fastBufs, &d.nodeCls, 8 * n1);
       scratch(&h->fastBufs, &d.baseKey, 8 * Nb2); scratch(&h->fastBufs, &d.baseNode, 4 * np); scratch(&h->fastBufs, &d.baseExtra, 8 * np * MAXE); scratch(&h->fastBufs, &d.baseCls, 8 * np);
       scratch(&h->fastBufs, &d.baseRemoved, np); scratch(&h->fastBufs, &d.posOf, 4 * np); scratch(&h->fastBufs, &d.l0Slot, 4 * np);
       if (d.fitBits) scratch(&h->fastBufs, &d.fitBits, 8 * ((size_t)d.f.F * ((n1 + 63) / 64) + 64));
     }
-    bool ok = true;
-    if (h->naScratchBytes < need) { scratchNew = (char*)plat_malloc(need + need / 4); ok = scratchNew != nullptr; }
-    for (auto& b : blocks) { if (!ok) break; b.fresh = plat_malloc(b.bytes); ok = b.fresh != nullptr; }
-    if (!ok) {
-      (void)plat_take_failure();
-      for (auto& b : blocks) if (b.fresh) plat_free(b.fresh);
-      if (scratchNew) plat_free(scratchNew);
+    if (!(entries.tryGrow(need) && sb.allocate())) {
+      entries.drop();
       return fail(h, ASCHED_ERR_DEVICE, "nodes_append: out of device memory for the scratch and the grown node table; the handle is as it was");
     }
-    if (scratchNew) { h->naBufs.freeAll(); h->naScratch = scratchNew; h->naScratchBytes = need + need / 4; h->naBufs.ptrs.push_back({scratchNew, need + need / 4}); }
+    entries.adopt();
   }
   prof.lap("allocations");
-  // ---- what nodes_upsert resets.  (A device failure from here on — ASCHED_ERR_DEVICE — leaves the handle between two tables: asched_nodes_upsert before anything else)
-  h->haveRoundResult = false; h->stateEpoch++;
-  { d.f.iterOk = 0;   // (the fast structure stays: structOk.  round_prepare decides iterOk again)
-    int32_t zero = 0;
-    plat_h2d(&d.rs->fastActive, &zero, sizeof zero);
-    plat_h2d(&d.rs->l0SaveCount, &zero, sizeof zero); }
-  h->prepared = false; h->evrSized = false; h->equalLevels = P;
+  // ---- what nodes_upsert resets (the handle between two tables: asched_nodes_upsert before anything else)
+  residentTouchNodes(h);
   memset(h->naStats, 0, sizeof h->naStats); for (int k = 0; k < 4; k++) h->naMs[k] = 0;
   memset(h->npStats, 0, sizeof h->npStats); memset(h->ndStats, 0, sizeof h->ndStats);
   if (m > 0) {
@@ -3463,34 +3403,29 @@ int32_t asched_nodes_append(asched_t* h, const asched_nodes_append_rows* rows) {
     if (rows->id_rank_all) { plat_h2d(s + oAll, rows->id_rank_all, 4 * (size_t)N1); a.idRankAll = (const int32_t*)(s + oAll); }
     a.pTotal = (const int64_t*)s; a.pAlloc = (const int64_t*)(s + oAlloc); a.pIdRank = (const int32_t*)(s + oIdRank); a.pType = (const int32_t*)(s + oType);
     a.ins = (const int32_t*)(s + oIns); a.insRow = (const int32_t*)(s + oInsRow); a.pLab = (const int32_t*)(s + oLab); a.pCls = (const uint64_t*)(s + oCls); a.pFlags = (const uint8_t*)(s + oFlags);
-    auto fresh = [&](void* slot) -> void* { for (auto& b : blocks) if ((void*)b.slot == slot) return b.fresh; return nullptr; };
     prof.lap("mirrors, class bits and the upload of the entries");
-    for (auto& b : blocks) plat_memset(b.fresh, b.fill, b.bytes);
-    a.inTotal = d.totalRes; a.outTotal = (int64_t*)fresh(&d.totalRes); a.inAlloc = d.allocatable; a.outAlloc = (int64_t*)fresh(&d.allocatable);
-    a.inFlags = d.nodeFlags; a.outFlags = (uint8_t*)fresh(&d.nodeFlags); a.inIdRank = d.nodeIdRank; a.outIdRank = (int32_t*)fresh(&d.nodeIdRank);
-    a.rankIn = d.nodeByRank; a.rankOut = (int32_t*)fresh(&d.nodeByRank); a.idxRankOut = (int32_t*)fresh(&d.idxRank);
+    sb.fill();
+    a.inTotal = d.totalRes; a.outTotal = (int64_t*)sb.fresh(&d.totalRes); a.inAlloc = d.allocatable; a.outAlloc = (int64_t*)sb.fresh(&d.allocatable);
+    a.inFlags = d.nodeFlags; a.outFlags = (uint8_t*)sb.fresh(&d.nodeFlags); a.inIdRank = d.nodeIdRank; a.outIdRank = (int32_t*)sb.fresh(&d.nodeIdRank);
+    a.rankIn = d.nodeByRank; a.rankOut = (int32_t*)sb.fresh(&d.nodeByRank); a.idxRankOut = (int32_t*)sb.fresh(&d.idxRank);
     if (masks) {
-      a.inType = h->dNodeType; a.outType = (int32_t*)fresh(&h->dNodeType);
+      a.inType = h->dNodeType; a.outType = (int32_t*)sb.fresh(&h->dNodeType);
       a.shapeClass = h->dShapeClass; a.shapeReq = d.shapeReq;
       const uint64_t* in[NA_MASKS] = {h->dClassMask, d.shapeMask, d.typeMask, d.labelMask};
       void* sl[NA_MASKS] = {&h->dClassMask, &d.shapeMask, &d.typeMask, &d.labelMask};
       const int nrows[NA_MASKS] = {Cext, Sext, T, labelRows};
-      for (int k = 0; k < NA_MASKS; k++) { a.inMask[k] = in[k]; a.outMask[k] = (uint64_t*)fresh(sl[k]); a.rows[k] = nrows[k]; }
+      for (int k = 0; k < NA_MASKS; k++) { a.inMask[k] = in[k]; a.outMask[k] = (uint64_t*)sb.fresh(sl[k]); a.rows[k] = nrows[k]; }
     }
-    if (haveFast) { a.inCls = d.nodeCls; a.outCls = (uint64_t*)fresh(&d.nodeCls); }
+    if (haveFast) { a.inCls = d.nodeCls; a.outCls = (uint64_t*)sb.fresh(&d.nodeCls); }
     const int prc = plat_take_failure() ? -1 : plat_nodes_append(d, a);
     if (prc) {
-      for (auto& b : blocks) plat_free(b.fresh);
+      sb.drop();
       return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
     }
     plat_nodes_append_ms(h->naMs);
     prof.lap("memsets and the passes");
     // the blocks swapped in, the old ones released (plat_nodes_append has waited for the device); the node-indexed scratch that stays gets the start a fresh upload gives it
-    auto release = [&](DevBufs* owner, void* p) {
-      for (size_t k = 0; k < owner->ptrs.size(); k++) if (owner->ptrs[k].first == p) { owner->ptrs.erase(owner->ptrs.begin() + k); break; }
-      plat_free(p);
-    };
-    for (auto& b : blocks) { if (*b.slot) release(b.owner, *b.slot); *b.slot = b.fresh; b.owner->ptrs.push_back({b.fresh, b.bytes}); }
+    sb.commit();
     for (auto& z : zeroed) plat_memset(z.first, 0, z.second);
     h->N = N1; d.cfg.N = N1; d.cfg.Npad = Npad1; d.cfg.W = W1;
     if (haveFast) d.fitW = (N1 + 63) / 64;
@@ -3498,7 +3433,7 @@ int32_t asched_nodes_append(asched_t* h, const asched_nodes_append_rows* rows) {
     prof.lap("releases and exclSetup");
     if (const char* e = getenv("ASCHED_NA_TIMES")) if (e[0] == '1')
       fprintf(stderr, "[asched nodes_append] nodes %d entries %d mask rows %d fresh blocks %zu: planes %.4f ms, narrow arrays %.4f ms, index order %.4f ms, mask rows %.4f ms\n",
-              N, m, a.rows[0] + a.rows[1] + a.rows[2] + a.rows[3], blocks.size(), h->naMs[0], h->naMs[1], h->naMs[2], h->naMs[3]);
+              N, m, a.rows[0] + a.rows[1] + a.rows[2] + a.rows[3], sb.blocks.size(), h->naMs[0], h->naMs[1], h->naMs[2], h->naMs[3]);
   }
   h->naStats[0] = m; h->naStats[1] = Npad1 != Npad ? 1 : 0; h->naStats[4] = h->N;
   if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());

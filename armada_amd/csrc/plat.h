@@ -25,6 +25,8 @@ static int plat_wall_clock_khz();
 // ---- memory and copies.  Device (plat_malloc) and pinned host (plat_pinned) memory; plat_malloc returns nullptr on failure.  Copies and memsets return
 // nothing: a failure latches in the context and is read (and cleared) with plat_take_failure.  plat_d2h_async completes at plat_sync.
 static void* plat_malloc(size_t n);
+static void* plat_try_malloc(size_t n);   // an allocation whose failure the caller handles by refusing the call: nullptr when there is no memory, and nothing latched in the context
+                                          // (asched_host.inc defines it over plat_malloc unless the platform layer says PLAT_TRY_MALLOC_OWN and brings its own)
 static void plat_free(void* p);
 static void plat_memset(void* p, int v, size_t n);
 static void plat_h2d(void* d, const void* s, size_t n);

@@ -6,6 +6,7 @@
 // by armada_amd (the product loads only armada_amd/csrc/libarmada_sched.so, built by hipcc for gfx950) and
 // it proves nothing about the kernels' parallel primitives — the `-m gpu` tests do that on the MI355X.
 #define ASCHED_HOSTSIM 1
+#define PLAT_TRY_MALLOC_OWN 1   // plat_try_malloc below, with the tests' hook, stands for asched_host.inc's
 #define ASCHED_PREFIX asched_
 #include <algorithm>
 #include <cstdlib>
@@ -142,6 +143,12 @@ static std::string g_err;
 struct PlatCtx { int32_t cancelWord = 0; double deadlineS = 0; bool inRound = false; int launches = 0; asched_allreduce_fn extFn = nullptr; void* extCtx = nullptr; int commRank = 0, commWorld = 1; };   // per handle, like the device build's (stream / events / mailbox there)
 static thread_local PlatCtx* t_ctx = nullptr;
 static void* plat_malloc(size_t n) { return malloc(n); }
+// the allocations a resident call may be refused for: malloc, plus a hook for the tests (tests/test_z_resident_out_of_memory.py).  hostsim_try_malloc_fail_at(k): the
+// k-th plat_try_malloc from now, counted from 0, returns nullptr once; k < 0 disarms.  hostsim_try_malloc_seen(): the plat_try_malloc calls since arming.  Per thread, as t_ctx
+static thread_local int g_tryFailAt = -1, g_trySeen = 0;
+extern "C" void hostsim_try_malloc_fail_at(int k) { g_tryFailAt = k < 0 ? -1 : k; g_trySeen = 0; }
+extern "C" int hostsim_try_malloc_seen() { return g_trySeen; }
+static void* plat_try_malloc(size_t n) { if (g_trySeen++ == g_tryFailAt) { g_tryFailAt = -1; return nullptr; } return malloc(n); }
 static void plat_free(void* p) { free(p); }
 static void plat_memset(void* p, int v, size_t n) { memset(p, v, n); }
 static void plat_h2d(void* d, const void* s, size_t n) { memcpy(d, s, n); }

@@ -6,6 +6,10 @@
 // After every step every row's first fit at every priority level and a round are compared with a second handle that is given the model's tables by
 // asched_nodes_upsert and asched_jobs_set.  In the CPU build the "device" arrays are heap blocks: a block sized by a stale capacity (jobCap, ordCap / ordSpareCap,
 // ndKeepCap ...) or a stale stride (Npad, W) shows up here as a heap overflow even where the answers stay right.
+// Every one of the nine calls is made under the sweep of tests/test_z_resident_out_of_memory.py first: the CPU build's hook refuses its k-th plat_try_malloc for
+// k = 0, 1, 2, ... until the hook no longer fires.  Each refused call must return ASCHED_ERR_DEVICE with "the handle is as it was" and leave the table sizes; the call
+// that goes through is then compared as above, so a refusal that changed the handle shows there, and a fresh block a refusal did not free is a leak at exit
+// (LeakSanitizer: ASAN_OPTIONS=detect_leaks=1, the default on Linux).
 // Test infrastructure; nothing here is linked into the product.  From the repository root:
 //   g++ -Itests/hostsim -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -ffp-contract=off -fno-strict-aliasing -Wno-unused-function -pthread \
 //       -o /tmp/resident_sequences_sanitize tools/resident_sequences_sanitize.cpp && /tmp/resident_sequences_sanitize [sequences [steps [first seed]]]
@@ -17,6 +21,23 @@
 static int failures = 0;
 #define CHECK(c) do { if (!(c)) { fprintf(stderr, "FAILED %s:%d: %s   [seed %d step %d %s]\n", __FILE__, __LINE__, #c, curSeed, curStep, curOp); failures++; } } while (0)
 static int curSeed = 0, curStep = 0; static const char* curOp = "";
+static int refusals[9] = {0};
+
+// `call` (the same arguments every time) armed at k = 0, 1, 2, ...: refused for memory while the hook fires -> the return code of the call that goes through
+template <class F> static int swept(asched_t* h, int op, F call) {
+  const int N = asched_num_nodes(h);
+  for (int k = 0;; k++) {
+    hostsim_try_malloc_fail_at(k);
+    const int rc = call();
+    const bool fired = hostsim_try_malloc_seen() > k;
+    hostsim_try_malloc_fail_at(-1);
+    if (!fired) return rc;
+    CHECK(rc == ASCHED_ERR_DEVICE && strstr(asched_last_error(h), "the handle is as it was") != nullptr);
+    CHECK(asched_num_nodes(h) == N);
+    if (rc != ASCHED_ERR_DEVICE) return rc;
+    refusals[op]++;
+  }
+}
 
 static const int R = 4, Q = 3;
 static const int32_t pcPrio[3] = {0, 1, 3};
@@ -221,7 +242,7 @@ static void sequence(const asched_config& c, int seed, int steps, int counts[16]
         i += cnt;
       }
       CHECK(asched_set_append_in_place(h, below(g, 10) < 6) == 0);
-      CHECK(t.append(h, m0) == 0);
+      CHECK(swept(h, 0, [&] { return t.append(h, m0); }) == 0);
       int32_t st[8]; CHECK(asched_jobs_append_stats(h, st) == 0 && st[0] == t.m() - m0);
       counts[9] += st[5]; counts[10] += st[4];
     } break;
@@ -239,7 +260,7 @@ static void sequence(const asched_config& c, int seed, int steps, int counts[16]
       while (extra > 0) { if (rows.insert(below(g, M)).second) extra--; }
       if ((int)rows.size() >= M) rows.erase(rows.begin());
       std::vector<int32_t> r(rows.begin(), rows.end()), map(M);
-      CHECK(asched_jobs_delete(h, (int32_t)r.size(), r.data(), map.data()) == 0);
+      CHECK(swept(h, 1, [&] { return asched_jobs_delete(h, (int32_t)r.size(), r.data(), map.data()); }) == 0);
       std::vector<uint8_t> keep(M, 1); for (int j : r) keep[j] = 0;
       int next = 0; for (int j = 0; j < M; j++) CHECK(map[j] == (keep[j] ? next++ : -1));
       t.keepRows(keep);
@@ -253,7 +274,7 @@ static void sequence(const asched_config& c, int seed, int steps, int counts[16]
       for (size_t i = 0; i < run.size() / 5; i++) { const int j = run[i]; t.node[j] = -1; t.prio[j] = 0; t.ts[j] = 0; t.held[j] = 1; rows.insert(j); }
       std::vector<int32_t> jb(rows.begin(), rows.end()), n2, p2; std::vector<int64_t> t2;
       for (int j : jb) { n2.push_back(t.node[j]); p2.push_back(t.prio[j]); t2.push_back(t.ts[j]); }
-      CHECK(asched_jobs_patch(h, (int32_t)jb.size(), jb.data(), n2.data(), p2.data(), t2.data()) == 0);
+      CHECK(swept(h, 2, [&] { return asched_jobs_patch(h, (int32_t)jb.size(), jb.data(), n2.data(), p2.data(), t2.data()); }) == 0);
     } break;
     case 3: { curOp = "jobs_reprioritise";
       std::set<int> rows; const int k = 1 + below(g, std::max(1, M / 3));
@@ -263,18 +284,18 @@ static void sequence(const asched_config& c, int seed, int steps, int counts[16]
         for (int j = 0; j < M; j++) if (t.gang[j] == t.gang[j0]) { rows.insert(j); np[j] = np[j0]; }
       std::vector<int32_t> jb(rows.begin(), rows.end()); std::vector<uint32_t> qp;
       for (int j : jb) { t.qprio[j] = np[j]; qp.push_back(np[j]); }
-      CHECK(asched_jobs_reprioritise(h, (int32_t)jb.size(), jb.data(), qp.data()) == 0);
+      CHECK(swept(h, 3, [&] { return asched_jobs_reprioritise(h, (int32_t)jb.size(), jb.data(), qp.data()); }) == 0);
     } break;
     case 4: { curOp = "req_classes_append";
       const Cls cl = {below(g, 2) == 0, below(g, 4) - 1};
       Table::CCls cc; Table::classesOf({cl}, cc);
-      CHECK(asched_req_classes_append(h, &cc.rc) == 0);
+      CHECK(swept(h, 4, [&] { return asched_req_classes_append(h, &cc.rc); }) == 0);
       t.classes.push_back(cl);
     } break;
     case 5: { curOp = "shapes_compact";
       const bool withClasses = below(g, 2) == 0;
       std::vector<int32_t> map(t.classes.size(), -2);
-      CHECK(asched_shapes_compact(h, withClasses ? ASCHED_COMPACT_CLASSES : 0, withClasses ? map.data() : nullptr) == 0);
+      CHECK(swept(h, 5, [&] { return asched_shapes_compact(h, withClasses ? ASCHED_COMPACT_CLASSES : 0, withClasses ? map.data() : nullptr); }) == 0);
       int32_t st[8]; CHECK(asched_shapes_compact_stats(h, st) == 0);
       counts[11] += st[0] > 0; counts[12] += st[2] > 0;
       if (withClasses) {   // the class map applied to the model
@@ -298,7 +319,7 @@ static void sequence(const asched_config& c, int seed, int steps, int counts[16]
         for (int i : r) { bool closed = false; for (int j = 0; j < M; j++) closed |= t.node[j] == i && !t.classes[t.cls[j]].tolerates; nd.tainted[i] = !(nd.tainted[i] || closed); }
         cs = nd.csr(std::vector<int>(r.begin(), r.end()));
         p.taint_off = cs.tOff.data(); p.taint_key = cs.tKey.data(); p.taint_value = cs.tVal.data(); p.taint_effect = cs.tEff.data(); }
-      CHECK(asched_nodes_patch(h, &p) == 0);
+      CHECK(swept(h, 6, [&] { return asched_nodes_patch(h, &p); }) == 0);
     } break;
     case 7: { curOp = "nodes_delete";
       std::vector<int> freeRows; for (int i = 0; i < N; i++) if (!used[i]) freeRows.push_back(i);
@@ -306,7 +327,7 @@ static void sequence(const asched_config& c, int seed, int steps, int counts[16]
       const int k = below(g, 4) == 0 ? most : 1 + below(g, most);
       std::shuffle(freeRows.begin(), freeRows.end(), g); freeRows.resize(k); std::sort(freeRows.begin(), freeRows.end());
       std::vector<int32_t> r(freeRows.begin(), freeRows.end()), map(N);
-      CHECK(asched_nodes_delete(h, k, r.data(), map.data()) == 0);
+      CHECK(swept(h, 7, [&] { return asched_nodes_delete(h, k, r.data(), map.data()); }) == 0);
       std::vector<uint8_t> keep(N, 1); for (int i : r) keep[i] = 0;
       for (int j = 0; j < M; j++) if (t.node[j] >= 0) { CHECK(map[t.node[j]] >= 0); t.node[j] = map[t.node[j]]; }
       nd.keepRows(keep);
@@ -315,7 +336,7 @@ static void sequence(const asched_config& c, int seed, int steps, int counts[16]
     default: { curOp = "nodes_append";
       const int k = 1 + below(g, 70);
       for (int e = 0; e < k; e++) { const int src = below(g, N); nd.push(nd.lVal[src], nd.tainted[src]); }
-      CHECK(nd.append(h, N) == 0);
+      CHECK(swept(h, 8, [&] { return nd.append(h, N); }) == 0);
       counts[14] += (N <= 64 && nd.n() > 64) + (N <= 128 && nd.n() > 128);
     } break;
     }
@@ -339,7 +360,8 @@ int main(int argc, char** argv) {
   int counts[16] = {0};
   for (int s = first; s < first + sequences && !failures; s++) sequence(c, s, steps, counts);
   static const char* names[9] = {"jobs_append", "jobs_delete", "jobs_patch", "jobs_reprioritise", "req_classes_append", "shapes_compact", "nodes_patch", "nodes_delete", "nodes_append"};
-  for (int i = 0; i < 9; i++) printf("%-20s %d\n", names[i], counts[i]);
+  for (int i = 0; i < 9; i++) printf("%-20s %d calls, %d refusals for memory\n", names[i], counts[i], refusals[i]);
+  for (int i = 0; i < 9; i++) if (sequences >= 20 && refusals[i] == 0) { fprintf(stderr, "%s was never refused for memory\n", names[i]); failures++; }
   printf("appends rebuilt %d, reallocated %d; compacts that retired a shape %d, a class %d; node deletes / appends across a word edge %d / %d; tables of one node %d\n",
          counts[9], counts[10], counts[11], counts[12], counts[13], counts[14], counts[15]);
   if (failures) { fprintf(stderr, "%d check(s) failed\n", failures); return 1; }
