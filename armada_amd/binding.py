@@ -265,6 +265,7 @@ ALL_SYMBOLS = [
     "set_evictor_report", "round_evictor_report",
     "jobs_patch", "jobs_append", "jobs_append_stats", "jobs_delete", "jobs_delete_stats",
     "jobs_reprioritise", "jobs_reprioritise_stats",
+    "jobs_respec", "jobs_respec_stats",
     "set_append_in_place", "jobs_append_shape_stats",
     "req_classes_append", "req_classes_append_stats",
     "shapes_compact", "shapes_compact_stats",
@@ -279,6 +280,7 @@ OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_d
                     "jobs_patch", "jobs_append", "jobs_append_stats",   # (an incremental jobs_set: the oracle is given the whole table; tests/test_z_jobs_patch.py, test_z_jobs_append.py)
                     "jobs_delete", "jobs_delete_stats",                 # (likewise: tests/test_z_jobs_delete.py)
                     "jobs_reprioritise", "jobs_reprioritise_stats",     # (likewise: tests/test_z_jobs_reprioritise.py)
+                    "jobs_respec", "jobs_respec_stats",                 # (likewise: tests/test_z_jobs_respec.py)
                     "set_append_in_place", "jobs_append_shape_stats",   # (how jobs_append treats new shapes, not what it leaves: tests/test_z_jobs_append_shapes.py)
                     "req_classes_append", "req_classes_append_stats",   # (an incremental jobs_set: the oracle is given the whole class list; tests/test_z_req_classes_append.py)
                     "shapes_compact", "shapes_compact_stats",           # (the oracle is given the job table afresh and never holds a dead shape: tests/test_z_shapes_compact.py)
@@ -483,6 +485,8 @@ class Library:
         f("jobs_patch", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _i64p])
         f("jobs_reprioritise", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _u32p])
         f("jobs_reprioritise_stats", C.c_int32, [C.c_void_p, _i32p])
+        f("jobs_respec", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i64p])
+        f("jobs_respec_stats", C.c_int32, [C.c_void_p, _i32p])
         f("jobs_append", C.c_int32, [C.c_void_p, C.POINTER(CJobs)])
         f("jobs_append_stats", C.c_int32, [C.c_void_p, _i32p])
         f("set_append_in_place", C.c_int32, [C.c_void_p, C.c_int32])
@@ -798,6 +802,26 @@ class Scheduler:
         out = np.zeros(8, np.int32)
         self._check(fn(self.h, _ptr(out, C.c_int32)))
         return dict(entries=int(out[0]), in_order=int(out[1]), unchanged=int(out[2]), made_resident=int(out[3]), device_ms=[int(x) / 1000.0 for x in out[4:8]])
+
+    def jobs_respec(self, jobs, req_class=None, req=None):
+        """a retry of resident jobs (scheduler.go:1342-1383): rows `jobs` of the job table, which have no run, get the requirement class `req_class` (None: unchanged;
+        a scalar is given to every row; a new class is brought first with req_classes_append) and the request `req` [n][R] (None: unchanged; one vector is given to
+        every row).  Leaves the handle as jobs_set of the edited table would; go on with round_prepare."""
+        fn = self._preemption_fn("jobs_respec")
+        jb = _arr(jobs, np.int32).reshape(-1)
+        n = len(jb)
+        rc = None if req_class is None else _arr(np.broadcast_to(np.asarray(req_class, dtype=np.int32), (n,)), np.int32)
+        rq = None if req is None else _arr(np.broadcast_to(np.asarray(req, dtype=np.int64).reshape(-1, self.R), (n, self.R)), np.int64)
+        self._check(fn(self.h, n, _ptr(jb, C.c_int32), _ptr(rc, C.c_int32), _ptr(rq, C.c_int64)))
+
+    def jobs_respec_stats(self):
+        """how the last jobs_respec ran: entries, entries that changed nothing, new shapes, revived shapes, shapes the call left without a row, whether masks and fast
+        structure were rebuilt, the reason code of jobs_append_shape_stats (0 = in place or nothing to grow), records written from templates"""
+        fn = self._preemption_fn("jobs_respec_stats")
+        out = np.zeros(8, np.int32)
+        self._check(fn(self.h, _ptr(out, C.c_int32)))
+        return dict(entries=int(out[0]), unchanged=int(out[1]), new_shapes=int(out[2]), revived=int(out[3]), emptied=int(out[4]), rebuilt=int(out[5]), reason=int(out[6]),
+                    from_templates=int(out[7]))
 
     def jobs_append(self, req, *, queue=None, pc=None, queue_priority=None, submit_time=None, req_class=None, gang_id=None, gang_cardinality=None,
                     gang_uniformity_label=None, node=None, scheduled_at_priority=None, run_timestamp=None, away=None, bid_price=None):

@@ -470,6 +470,18 @@ extern "C" int asched_internal_jr_scatter(const Dev* d, const JrArgs* a, hipStre
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ------------------------------------------------------------------------------------------------ retried jobs change class and request in place (kernels_jobs_respec.h)
+// one thread per entry, plain stores: every row is named at most once and a record's source row is named by no entry
+#include "kernels_jobs_respec.h"
+__global__ __launch_bounds__(MG_THREADS) void k_js_scatter(Dev d, JsArgs a) {
+  long long i = MG_IDX();
+  if (i < a.n) jsScatter(d, a, (int)i);
+}
+extern "C" int asched_internal_js_scatter(const Dev* d, const JsArgs* a, hipStream_t st) {
+  if (a->n > 0) hipLaunchKernelGGL(k_js_scatter, dim3(mgBlocks(a->n)), dim3(MG_THREADS), 0, st, *d, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ------------------------------------------------------------------------------------------------ newly submitted jobs behind the resident job table (kernels_jobs_append.h)
 // row fill + keys; the sort and the merge by rank are the patch's (asched_internal_jp_sort / _jp_merge on JaArgs::p)
 #include "kernels_jobs_append.h"

@@ -30,6 +30,7 @@
 #include "kernels_evict_report.h"   // EvrArgs and, in the CPU build of the tests, plat_evict_report
 #include "kernels_jobs_patch.h"     // JpArgs and, in the CPU build of the tests, plat_jobs_patch
 #include "kernels_jobs_reprioritise.h"   // JrArgs and, in the CPU build of the tests, plat_jobs_reprioritise
+#include "kernels_jobs_respec.h"         // JsArgs and, in the CPU build of the tests, plat_jobs_respec
 #include "kernels_jobs_append.h"    // JaArgs and, in the CPU build of the tests, plat_jobs_append
 #include "kernels_shapes_append.h"  // SaArgs and, in the CPU build of the tests, plat_shapes_append
 #include "kernels_req_classes_append.h"   // CaArgs and, in the CPU build of the tests, plat_req_classes_append
@@ -341,6 +342,7 @@ struct asched {
   DevBufs jpBufs; char* jpScratch = nullptr; size_t jpScratchBytes = 0;   // the entries, the sort array and the kept list of a patch: one block, kept between calls and only ever grown
   double jpMs[4] = {0, 0, 0, 0};     // device ms of the four passes of the last patch (ASCHED_JP_TIMES=1)
   int32_t jrStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_reprioritise_stats (kernels_jobs_reprioritise.h)
+  int32_t jsStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_respec_stats (kernels_jobs_respec.h)
   // ---- asched_jobs_delete (kernels_jobs_delete.h).  A scheduling-key shape that lost its last row keeps its id with shapeRow[s] == -1 (an append that uses it goes
   // through the rebuild path); a gang that lost its last row keeps its dense id with no members and leaves gangMap
   int32_t jdStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_delete_stats
@@ -1571,7 +1573,7 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
   d.unfeasible = h->jobBufs.alloc<uint8_t>(std::max(h->S, 1)); d.unfeasibleReason = h->jobBufs.alloc<int32_t>(std::max(h->S, 1));
   h->jobCap = M; h->gangCap = h->G; h->gangArrCap = (size_t)gangOff[h->G + 1]; h->gangJobsCap = gangJobs.size(); h->gangOffCap = gangOff.size();
   h->ordCap = ord.size(); h->ordSpareCap = 0; h->ordOffCap = h->ordOffHost.size(); h->gangOffHost = gangOff;
-  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->caStats, 0, sizeof h->caStats);
+  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->jsStats, 0, sizeof h->jsStats); memset(h->caStats, 0, sizeof h->caStats);
   memset(h->scStats, 0, sizeof h->scStats);
   h->jobsSet = true; h->prepared = false;
   h->jQPrioHost.swap(qprio); h->jSubmitHost.swap(submit); h->jRunTsHost.swap(runTs);   // (asched_jobs_patch uploads them when it is first called; nothing is copied here)
@@ -1769,6 +1771,186 @@ static void jaShapeTableBuild(asched* h, size_t room) {   // over the shapes the
     h->shapeTable[pos] = (int32_t)s;
   }
 }
+// ---- what asched_jobs_append and asched_jobs_respec (kernels_jobs_respec.h) share: a call whose rows bring new shapes, or shapes without a resident row.  The state of
+// one such call between its steps, then the steps in the order both calls take them: the shape lookup, what the rebuild would refuse, the in-place decision, the staged
+// shape-dependent blocks, what fills them, the template records, and `undo` for a refusal after the lookup.  M0 / S0 / A0 / Cext0 / F0: rows, shapes, away rows, classes
+// with the derived ones, and fit shapes before the call.
+struct JaShapes {
+  int M0 = 0, S0 = 0, A0 = 0, Cext0 = 0, F0 = 0;
+  DevCfg cfgSaved; bool keyWideSaved = false, keyCoarseSaved = false;
+  std::vector<int32_t> revived, shapeRowSaved;   // shapes without a resident row that this call gives one, and shapeRow as it was (for `undo`)
+  bool mirrorsGrown = false;
+  // the in-place path extends what buildFast left on the handle before it knows that every block can be had: `undo` takes it back
+  bool fastGrown = false; std::vector<uint8_t> rowLiteralSaved; int64_t minFieldSaved[MAXK], minExtraSaved[MAXE];
+  bool inPlace = false; int inWhy = 0;   // inWhy: why the rebuild is taken although the switch is on
+  std::vector<int32_t> shapeClassExt1, rowTypeOff1, rowTypes1; std::vector<int64_t> shapeReqExt1; std::vector<uint64_t> classRows1;
+  uint64_t* shapeMask1 = nullptr;   // the grown shape mask [old shape rows | new shape rows | old away rows | new away rows]: filled by plat_shapes_append
+  void begin(asched* h) {
+    M0 = h->M; S0 = h->S; A0 = (int)h->awayRowClass.size(); Cext0 = h->Cext; F0 = h->dev.f.F;
+    cfgSaved = h->dev.cfg; keyWideSaved = h->keyWide; keyCoarseSaved = h->keyCoarse;
+  }
+};
+// the shape (cls, pc, req) in the handle's shape table; one the table does not hold gets the next id, with firstRow as its first row
+static int32_t jaShapeFind(asched* h, int32_t cls, int32_t pc, const int64_t* req, int32_t firstRow) {
+  const int R = h->R;
+  const uint64_t hv = jaShapeHash(cls, pc, req, R);
+  size_t cap = h->shapeTable.size(), pos = hv & (cap - 1);
+  auto same = [&](int32_t s) {
+    if (h->shapeHash[s] != hv || h->shapeClass[s] != cls || h->shapePc[s] != pc) return false;
+    for (int r = 0; r < R; r++) if (h->shapeReq[(size_t)s * R + r] != req[r]) return false;
+    return true;
+  };
+  while (h->shapeTable[pos] >= 0 && !same(h->shapeTable[pos])) pos = (pos + 1) & (cap - 1);
+  if (h->shapeTable[pos] >= 0) return h->shapeTable[pos];
+  const int32_t s = (int32_t)h->shapeClass.size();
+  h->shapeTable[pos] = s; h->shapeHash.push_back(hv);
+  h->shapeClass.push_back(cls); h->shapePc.push_back(pc); h->shapeRow.push_back(firstRow); h->shapeUnaligned.push_back(0);
+  for (int r = 0; r < R; r++) h->shapeReq.push_back(req[r]);
+  if ((size_t)(s + 1) * 2 > cap) jaShapeTableBuild(h, (size_t)(s + 1) * 2);
+  return s;
+}
+// a refusal after the shape lookup: the handle exactly as it was (the caller puts back what it wrote into the rows of jReq below M0)
+static void jaShapesUndo(asched* h, JaShapes& g) {
+  Dev& d = h->dev;
+  const int S0 = g.S0, R = h->R, M = g.M0;
+  if (g.fastGrown) {
+    h->fsDelta.resize(S0); h->fsMin.resize(S0); h->fsNever.resize(S0); h->fitOf.resize(S0); h->fitTab.resize(g.F0);
+    for (auto it = h->fitIds.begin(); it != h->fitIds.end();) it = it->second >= g.F0 ? h->fitIds.erase(it) : std::next(it);
+    memcpy(h->fsMinField, g.minFieldSaved, sizeof g.minFieldSaved); memcpy(h->fsMinExtra, g.minExtraSaved, sizeof g.minExtraSaved);
+    d.f.F = g.F0; h->rowLiteral = g.rowLiteralSaved;
+  }
+  if (!g.revived.empty()) h->shapeRow = g.shapeRowSaved;
+  h->shapeClass.resize(S0); h->shapePc.resize(S0); h->shapeReq.resize((size_t)S0 * R); h->shapeRow.resize(S0); h->shapeUnaligned.resize(S0);
+  h->shapeTable.clear(); h->shapeHash.clear();
+  if (g.mirrorsGrown) {
+    h->jReq.resize((size_t)M * R); h->M = M; h->S = S0;
+    d.cfg = g.cfgSaved; h->keyWide = g.keyWideSaved; h->keyCoarse = g.keyCoarseSaved;
+    deriveAwayRows(h, g.cfgSaved.hasAway != 0);
+  }
+}
+// what the rebuild can refuse, checked on the host first: the key layout of the table with its new shapes (layoutKeys) and LIT_TMAX for a new row on the literal
+// iteration path.  h->jReq, h->M and h->S are the table's after the call (g.mirrorsGrown).  0, or the code with the reason in why
+static int jaShapesRefusal(asched* h, JaShapes& g, bool anyAway, std::string& why) {
+  const int S1 = h->S;
+  deriveAwayRows(h, anyAway);
+  if (h->nodesSet) {
+    if (int lrc = layoutKeys(h)) { why = h->err; return lrc; }
+    for (int s = g.S0; s < S1; s++) {
+      std::vector<int32_t> classes{h->shapeClass[s]};
+      for (int k = h->awayRowOff[s]; k < h->awayRowOff[s + 1]; k++) classes.push_back(h->awayRowClass[k]);
+      for (int32_t c : classes) {
+        size_t nTypes = 0;
+        for (size_t t = 0; t < h->types.size(); t++) if (h->types[t].numNodes > 0 && classMatchesType(h, c, h->types[t])) nTypes++;
+        const bool literal = h->shapeUnaligned[s] || (nTypes > 1 && !(h->allocAligned && h->idRankMonotone));
+        if (literal && nTypes > LIT_TMAX) { why = "a requirement class on the literal iteration path matches more than LIT_TMAX node types"; return ASCHED_ERR_UNSUPPORTED; }
+      }
+    }
+  }
+  return 0;
+}
+// the in-place path for new shapes (asched_set_append_in_place): decided before anything changes.  negNew: the call brings a negative request.  Sets g.inPlace or
+// g.inWhy and, in place, extends the per-shape tables of buildFast; 0, or the code with the reason in why
+static int jaInPlaceDecide(asched* h, JaShapes& g, bool anyAway, bool negNew, std::string& why) {
+  Dev& d = h->dev;
+  const int R = h->R, M = g.M0, S0 = g.S0, S1 = h->S, A1 = (int)h->awayRowClass.size(), Wm = d.cfg.W;
+  const DevCfg& cfgSaved = g.cfgSaved;
+  bool layoutSame = h->keyWide == g.keyWideSaved && h->keyCoarse == g.keyCoarseSaved && d.cfg.keyClamp == cfgSaved.keyClamp && d.cfg.idxBits == cfgSaved.idxBits &&
+                    d.cfg.keyGuard == cfgSaved.keyGuard && d.cfg.keyWords == cfgSaved.keyWords;
+  for (int c = 0; c < h->K; c++) layoutSame = layoutSame && d.cfg.keyLo[c] == cfgSaved.keyLo[c] && d.cfg.keyWidth[c] == cfgSaved.keyWidth[c] && d.cfg.keyShift[c] == cfgSaved.keyShift[c] &&
+                                              d.cfg.indexedRes[c] == cfgSaved.indexedRes[c];
+  if (M <= 0 || S0 <= 0) g.inWhy = 6;   // (buildFast's predicate can turn true)
+  else if (!h->nodesSet || !h->dClassMask || !h->dShapeClass || !d.shapeMask || h->fitOf.size() != (size_t)S0 || h->fsDelta.size() != (size_t)S0) g.inWhy = 1;
+  else if (!layoutSame) g.inWhy = 2;
+  else if (anyAway && !cfgSaved.hasAway) g.inWhy = 3;
+  else if (negNew && (d.f.structOk || d.f.cascadeFuse)) g.inWhy = 5;   // (buildFast's reqNonNeg: the structure and the fused pass go with the first negative request)
+  else {
+    // the row tables of the grown shape table, then per new shape what buildFast derives (it reads h->rowLiteral)
+    g.shapeClassExt1 = h->shapeClass; g.shapeReqExt1 = h->shapeReq;
+    for (int k = 0; k < A1; k++) {
+      g.shapeClassExt1.push_back(h->awayRowClass[k]);
+      for (int r = 0; r < R; r++) g.shapeReqExt1.push_back(h->shapeReq[(size_t)h->awayRowShape[k] * R + r]);
+    }
+    g.rowLiteralSaved = h->rowLiteral; memcpy(g.minFieldSaved, h->fsMinField, sizeof g.minFieldSaved); memcpy(g.minExtraSaved, h->fsMinExtra, sizeof g.minExtraSaved);
+    g.fastGrown = true;
+    if (int rrc = buildRowTables(h, g.shapeClassExt1, g.rowTypeOff1, g.rowTypes1)) { why = h->err; return rrc; }
+    for (int s = S0; s < S1; s++) fastShapeAdd(h, s);
+    if (d.f.structOk && d.f.F > SMAX) g.inWhy = 4;   // (the rebuild that follows derives all of it again)
+    else g.inPlace = true;
+  }
+  if (g.inPlace) {
+    // the rows of the derived away classes this call adds: ids behind the old ones (deriveAwayRows numbers them in shape order)
+    g.classRows1.assign((size_t)(h->Cext - g.Cext0) * Wm, 0);
+    for (int c = g.Cext0; c < h->Cext; c++)
+      for (int n = 0; n < h->N; n++) if (classMatchesNode(h, c, n)) g.classRows1[(size_t)(c - g.Cext0) * Wm + (n >> 6)] |= 1ull << (n & 63);
+  }
+  return 0;
+}
+// the template of shape s among those of one call: its position in tplShape, added on first use (128 bytes a shape, not a row)
+static int32_t jaTemplateOf(std::unordered_map<int32_t, int32_t>& tplOf, std::vector<int32_t>& tplShape, int32_t s) {
+  auto it = tplOf.find(s);
+  if (it == tplOf.end()) { it = tplOf.emplace(s, (int32_t)tplShape.size()).first; tplShape.push_back(s); }
+  return it->second;
+}
+// the template records of those shapes, as buildFast would fill a row of each (gang, node and run are the row's own), into platform memory at dst
+static void jaTemplatesUpload(asched* h, const std::vector<int32_t>& tplShape, void* dst) {
+  const int R = h->R;
+  std::vector<JobRec> tpl(tplShape.size());
+  for (size_t t = 0; t < tpl.size(); t++) fastRecFill(h, tpl[t], tplShape[t], &h->shapeReq[(size_t)tplShape[t] * R], h->shapePc[tplShape[t]], -1, -1, 0);
+  plat_h2d(dst, tpl.data(), sizeof(JobRec) * tpl.size());
+}
+// the shape-dependent blocks of a call with new shapes, staged before anything changes: the unfeasible-key arrays for S1 shapes and, in place, the grown mask tables
+static void jaStageShapes(asched* h, JaShapes& g, StagedBlocks& sb) {
+  Dev& d = h->dev;
+  const int S1 = h->S, Sext0 = g.S0 + g.A0, Sext1 = S1 + (int)h->awayRowClass.size(), Wm = d.cfg.W;
+  sb.stage(&h->jobBufs, &d.unfeasible, (size_t)S1, 0, nullptr, 0); sb.stage(&h->jobBufs, &d.unfeasibleReason, (size_t)S1 * 4, 0, nullptr, 0);
+  if (!g.inPlace) return;
+  if (Sext1 > Sext0) {
+    sb.stage(&h->maskBufs, &g.shapeMask1, 8 * (size_t)Sext1 * Wm, 0, nullptr, -1, true);
+    sb.stage(&h->maskBufs, &h->dShapeClass, 4 * g.shapeClassExt1.size(), 4 * g.shapeClassExt1.size(), g.shapeClassExt1.data(), 0);
+    sb.stage(&h->maskBufs, &d.shapeReq, 8 * g.shapeReqExt1.size(), 8 * g.shapeReqExt1.size(), g.shapeReqExt1.data(), 0);
+    sb.stage(&h->maskBufs, &d.awayRowOff, 4 * h->awayRowOff.size(), 4 * h->awayRowOff.size(), h->awayRowOff.data(), 0);
+    sb.stage(&h->maskBufs, &d.rowLiteral, h->rowLiteral.size(), h->rowLiteral.size(), h->rowLiteral.data(), 0);
+    sb.stage(&h->maskBufs, &d.rowTypeOff, 4 * g.rowTypeOff1.size(), 4 * g.rowTypeOff1.size(), g.rowTypeOff1.data(), 0);
+    sb.stage(&h->maskBufs, &d.rowTypes, 4 * g.rowTypes1.size(), 4 * g.rowTypes1.size(), g.rowTypes1.data(), 0);
+  }
+  if (h->Cext > g.Cext0) sb.stage(&h->maskBufs, &h->dClassMask, 8 * (size_t)h->Cext * Wm, 8 * (size_t)g.Cext0 * Wm, nullptr, -1);   // (the old rows device to device; the new ones are uploaded below)
+  if (d.f.structOk && d.f.F > g.F0) {
+    sb.stage(&h->fastBufs, &d.shapeTab, sizeof(ShapeReq) * h->fitTab.size(), sizeof(ShapeReq) * h->fitTab.size(), h->fitTab.data(), 0);
+    if (d.fitBits) sb.stage(&h->fastBufs, &d.fitBits, 8 * ((size_t)d.f.F * d.fitW + 64), 0, nullptr, 0);   // (scratch the next base build fills, as in asched_nodes_append)
+  }
+}
+// in place, once the staged blocks are committed: the packed minima, the class-mask rows of the new derived classes and the new rows of the shape mask
+// (plat_shapes_append; saScratch: platform memory for request / class / output row of each).  0, or -1 with the platform's error
+static int jaInPlaceApply(asched* h, JaShapes& g, char* saScratch) {
+  Dev& d = h->dev;
+  const int R = h->R, S0 = g.S0, S1 = h->S, A0 = g.A0, A1 = (int)h->awayRowClass.size(), Wm = d.cfg.W;
+  fastMinimaPack(h);
+  if (const char* ms = getenv("ASCHED_SHAPE_MASK")) if (d.fitBits && ms[0] == '1') d.f.maskMode = d.f.F <= 64 ? 1 : d.f.F <= 128 ? 2 : 0;   // (buildFast's rule, for the grown F)
+  if (h->Cext > g.Cext0) plat_h2d(h->dClassMask + (size_t)g.Cext0 * Wm, g.classRows1.data(), g.classRows1.size() * 8);
+  if (g.shapeMask1) {
+    const int nNew = (S1 - S0) + (A1 - A0);
+    std::vector<int32_t> rowCls(nNew), rowOut(nNew); std::vector<int64_t> rowReq((size_t)nNew * R);
+    for (int k = 0; k < nNew; k++) {
+      const int row = k < S1 - S0 ? S0 + k : S1 + A0 + (k - (S1 - S0));
+      rowOut[k] = row; rowCls[k] = g.shapeClassExt1[row];
+      for (int r = 0; r < R; r++) rowReq[(size_t)k * R + r] = g.shapeReqExt1[(size_t)row * R + r];
+    }
+    int64_t* dReq = (int64_t*)saScratch; int32_t* dCls = (int32_t*)(dReq + (size_t)nNew * R);
+    plat_h2d(dReq, rowReq.data(), rowReq.size() * 8); plat_h2d(dCls, rowCls.data(), (size_t)nNew * 4); plat_h2d(dCls + nNew, rowOut.data(), (size_t)nNew * 4);
+    SaArgs sa; memset(&sa, 0, sizeof sa);
+    sa.N = h->N; sa.Npad = d.cfg.Npad; sa.W = Wm; sa.R = R; sa.rows = nNew;
+    sa.totalRes = d.totalRes; sa.classMask = h->dClassMask;
+    sa.rowClass = dCls; sa.rowOut = dCls + nNew; sa.rowReq = dReq;
+    sa.outMask = g.shapeMask1; sa.inMask = d.shapeMask;
+    sa.copy0 = (long long)S0 * Wm; sa.src1 = (long long)S0 * Wm; sa.dst1 = (long long)S1 * Wm; sa.copy1 = (long long)A0 * Wm;
+    int src = plat_take_failure() ? -1 : plat_shapes_append(d, sa);
+    if (src) return -1;
+    plat_shapes_append_ms(h->saMs);
+    h->maskBufs.release(d.shapeMask);
+    d.shapeMask = g.shapeMask1;
+  }
+  return 0;
+}
 int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
   if (!h) return ASCHED_ERR_INVALID;
   plat_enter(h->plat);
@@ -1821,25 +2003,10 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
   const int G1 = G0 + (int)newGangs.size();
   // the shape of every row: a hash over the shapes the handle holds; new shapes get the next ids in order of first occurrence (undone by `undo` on a later refusal)
   if (m > 0 && h->shapeTable.empty()) jaShapeTableBuild(h, (size_t)S0);
-  std::vector<int32_t> revived, shapeRowSaved;   // shapes without a resident row that this call gives one, and shapeRow as it was (for `undo`)
+  JaShapes g; g.begin(h);
+  std::vector<int32_t>& revived = g.revived; std::vector<int32_t>& shapeRowSaved = g.shapeRowSaved;
   for (int i = 0; i < m; i++) {
-    const int64_t* req = rows->req + (size_t)i * R;
-    const uint64_t hv = jaShapeHash(aCls[i], aPc[i], req, R);
-    size_t cap = h->shapeTable.size(), pos = hv & (cap - 1);
-    auto same = [&](int32_t s) {
-      if (h->shapeHash[s] != hv || h->shapeClass[s] != aCls[i] || h->shapePc[s] != aPc[i]) return false;
-      for (int r = 0; r < R; r++) if (h->shapeReq[(size_t)s * R + r] != req[r]) return false;
-      return true;
-    };
-    while (h->shapeTable[pos] >= 0 && !same(h->shapeTable[pos])) pos = (pos + 1) & (cap - 1);
-    if (h->shapeTable[pos] < 0) {
-      const int32_t s = (int32_t)h->shapeClass.size();
-      h->shapeTable[pos] = s; h->shapeHash.push_back(hv);
-      h->shapeClass.push_back(aCls[i]); h->shapePc.push_back(aPc[i]); h->shapeRow.push_back(M + i); h->shapeUnaligned.push_back(0);
-      for (int r = 0; r < R; r++) h->shapeReq.push_back(req[r]);
-      aShape[i] = s;
-      if ((size_t)(s + 1) * 2 > cap) jaShapeTableBuild(h, (size_t)(s + 1) * 2);
-    } else aShape[i] = h->shapeTable[pos];
+    aShape[i] = jaShapeFind(h, aCls[i], aPc[i], rows->req + (size_t)i * R, M + i);
     if (!aAligned[i]) h->shapeUnaligned[aShape[i]] = 1;   // (a property of the shape: a resident shape's flag is already what this row says)
     if (aShape[i] < S0) {
       int32_t& first = h->shapeRow[aShape[i]];
@@ -1849,91 +2016,30 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
   }
   const int S1 = (int)h->shapeClass.size();
   const bool newShapes = S1 > S0 || !revived.empty();   // (a revived shape takes the path of a new one: the records are rebuilt from the mirrors, DESIGN 3.12)
-  const DevCfg cfgSaved = d.cfg; const bool keyWideSaved = h->keyWide, keyCoarseSaved = h->keyCoarse;
-  const int Cext0 = h->Cext, A0 = (int)h->awayRowClass.size();   // derived classes and away rows before the call
-  bool mirrorsGrown = false;
-  // the in-place path extends what buildFast left on the handle before it knows that every block can be had: `undo` takes it back
-  bool fastGrown = false; const int F0 = d.f.F; std::vector<uint8_t> rowLiteralSaved; int64_t minFieldSaved[MAXK], minExtraSaved[MAXE];
-  auto undo = [&]() {   // a refusal after the shape lookup: the handle exactly as it was
-    if (!newShapes) return;
-    if (fastGrown) {
-      h->fsDelta.resize(S0); h->fsMin.resize(S0); h->fsNever.resize(S0); h->fitOf.resize(S0); h->fitTab.resize(F0);
-      for (auto it = h->fitIds.begin(); it != h->fitIds.end();) it = it->second >= F0 ? h->fitIds.erase(it) : std::next(it);
-      memcpy(h->fsMinField, minFieldSaved, sizeof minFieldSaved); memcpy(h->fsMinExtra, minExtraSaved, sizeof minExtraSaved);
-      d.f.F = F0; h->rowLiteral = rowLiteralSaved;
-    }
-    if (!revived.empty()) h->shapeRow = shapeRowSaved;
-    h->shapeClass.resize(S0); h->shapePc.resize(S0); h->shapeReq.resize((size_t)S0 * R); h->shapeRow.resize(S0); h->shapeUnaligned.resize(S0);
-    h->shapeTable.clear(); h->shapeHash.clear();
-    if (mirrorsGrown) {
-      h->jReq.resize((size_t)M * R); h->M = M; h->S = S0;
-      d.cfg = cfgSaved; h->keyWide = keyWideSaved; h->keyCoarse = keyCoarseSaved;
-      deriveAwayRows(h, cfgSaved.hasAway != 0);
-    }
-  };
+  const int Cext0 = g.Cext0, A0 = g.A0;   // derived classes and away rows before the call
+  auto undo = [&]() { if (newShapes) jaShapesUndo(h, g); };   // a refusal after the shape lookup: the handle exactly as it was
   if (newShapes) {
     // what the rebuild can refuse, checked on the host first: the key layout of the grown table (layoutKeys) and LIT_TMAX for a new row on the literal iteration path
-    h->jReq.insert(h->jReq.end(), rows->req, rows->req + (size_t)m * R); h->M = M1; h->S = S1; mirrorsGrown = true;
-    deriveAwayRows(h, anyAway);
-    if (h->nodesSet) {
-      if (int lrc = layoutKeys(h)) { std::string why = h->err; undo(); return fail(h, lrc, "jobs_append: " + why); }
-      for (int s = S0; s < S1; s++) {
-        std::vector<int32_t> classes{h->shapeClass[s]};
-        for (int k = h->awayRowOff[s]; k < h->awayRowOff[s + 1]; k++) classes.push_back(h->awayRowClass[k]);
-        for (int32_t c : classes) {
-          size_t nTypes = 0;
-          for (size_t t = 0; t < h->types.size(); t++) if (h->types[t].numNodes > 0 && classMatchesType(h, c, h->types[t])) nTypes++;
-          const bool literal = h->shapeUnaligned[s] || (nTypes > 1 && !(h->allocAligned && h->idRankMonotone));
-          if (literal && nTypes > LIT_TMAX) { undo(); return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_append: a requirement class on the literal iteration path matches more than LIT_TMAX node types"); }
-        }
-      }
-    }
+    h->jReq.insert(h->jReq.end(), rows->req, rows->req + (size_t)m * R); h->M = M1; h->S = S1; g.mirrorsGrown = true;
+    std::string why;
+    if (int rrc = jaShapesRefusal(h, g, anyAway, why)) { undo(); return fail(h, rrc, "jobs_append: " + why); }
   }
   // ---- the in-place path for new shapes (asched_set_append_in_place): decided here, before anything changes.  inWhy: why the rebuild is taken although the switch is on
-  bool inPlace = false; int inWhy = 0;
-  const int A1 = (int)h->awayRowClass.size(), Sext0 = S0 + A0, Sext1 = S1 + A1, Wm = d.cfg.W;
-  std::vector<int32_t> shapeClassExt1, rowTypeOff1, rowTypes1, tplShape, aTpl; std::vector<int64_t> shapeReqExt1; std::vector<uint64_t> classRows1;
+  bool& inPlace = g.inPlace; int& inWhy = g.inWhy;
+  const int A1 = (int)h->awayRowClass.size(), Sext0 = S0 + A0, Sext1 = S1 + A1;
+  std::vector<int32_t> tplShape, aTpl;
   if (newShapes && h->appendInPlace) {
     bool negNew = false;
     for (size_t k = 0; k < (size_t)m * R && !negNew; k++) negNew = rows->req[k] < 0;
-    bool layoutSame = h->keyWide == keyWideSaved && h->keyCoarse == keyCoarseSaved && d.cfg.keyClamp == cfgSaved.keyClamp && d.cfg.idxBits == cfgSaved.idxBits &&
-                      d.cfg.keyGuard == cfgSaved.keyGuard && d.cfg.keyWords == cfgSaved.keyWords;
-    for (int c = 0; c < h->K; c++) layoutSame = layoutSame && d.cfg.keyLo[c] == cfgSaved.keyLo[c] && d.cfg.keyWidth[c] == cfgSaved.keyWidth[c] && d.cfg.keyShift[c] == cfgSaved.keyShift[c] &&
-                                                d.cfg.indexedRes[c] == cfgSaved.indexedRes[c];
-    if (M <= 0 || S0 <= 0) inWhy = 6;   // (buildFast's predicate can turn true)
-    else if (!h->nodesSet || !h->dClassMask || !h->dShapeClass || !d.shapeMask || h->fitOf.size() != (size_t)S0 || h->fsDelta.size() != (size_t)S0) inWhy = 1;
-    else if (!layoutSame) inWhy = 2;
-    else if (anyAway && !cfgSaved.hasAway) inWhy = 3;
-    else if (negNew && (d.f.structOk || d.f.cascadeFuse)) inWhy = 5;   // (buildFast's reqNonNeg: the structure and the fused pass go with the first negative request)
-    else {
-      // the row tables of the grown shape table, then per new shape what buildFast derives (it reads h->rowLiteral)
-      shapeClassExt1 = h->shapeClass; shapeReqExt1 = h->shapeReq;
-      for (int k = 0; k < A1; k++) {
-        shapeClassExt1.push_back(h->awayRowClass[k]);
-        for (int r = 0; r < R; r++) shapeReqExt1.push_back(h->shapeReq[(size_t)h->awayRowShape[k] * R + r]);
-      }
-      rowLiteralSaved = h->rowLiteral; memcpy(minFieldSaved, h->fsMinField, sizeof minFieldSaved); memcpy(minExtraSaved, h->fsMinExtra, sizeof minExtraSaved);
-      fastGrown = true;
-      if (int rrc = buildRowTables(h, shapeClassExt1, rowTypeOff1, rowTypes1)) { std::string why = h->err; undo(); return fail(h, rrc, "jobs_append: " + why); }
-      for (int s = S0; s < S1; s++) fastShapeAdd(h, s);
-      if (d.f.structOk && d.f.F > SMAX) inWhy = 4;   // (the rebuild that follows derives all of it again)
-      else inPlace = true;
-    }
+    std::string why;
+    if (int rrc = jaInPlaceDecide(h, g, anyAway, negNew, why)) { undo(); return fail(h, rrc, "jobs_append: " + why); }
   }
   if (inPlace) {
-    // the rows of the derived away classes this call adds: ids behind the old ones (deriveAwayRows numbers them in shape order)
-    classRows1.assign((size_t)(h->Cext - Cext0) * Wm, 0);
-    for (int c = Cext0; c < h->Cext; c++)
-      for (int n = 0; n < h->N; n++) if (classMatchesNode(h, c, n)) classRows1[(size_t)(c - Cext0) * Wm + (n >> 6)] |= 1ull << (n & 63);
     // one template record per shape without a resident row below M (new or revived): every row of such a shape has aSrc < 0
     if (d.f.structOk && d.jrec) {
       std::unordered_map<int32_t, int32_t> tplOf;
       aTpl.assign(m, -1);
-      for (int i = 0; i < m; i++) if (aSrc[i] < 0) {
-        auto it = tplOf.find(aShape[i]);
-        if (it == tplOf.end()) { it = tplOf.emplace(aShape[i], (int32_t)tplShape.size()).first; tplShape.push_back(aShape[i]); }
-        aTpl[i] = it->second;
-      }
+      for (int i = 0; i < m; i++) if (aSrc[i] < 0) aTpl[i] = jaTemplateOf(tplOf, tplShape, aShape[i]);
     }
   }
   const size_t nTpl = tplShape.size();
@@ -2008,24 +2114,7 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
     sb.stage(&h->jobBufs, &d.gangSeen, (gangCap1 + 1) * 4, 0, nullptr, 0); sb.stage(&h->jobBufs, &d.gangArr, gangArrCap1 * 4, 0, nullptr, 0);
     sb.stage(&h->jobBufs, &d.gangTotal, (gangCap1 + 1) * (size_t)R * 8, 0, nullptr, 0); sb.stage(&h->jobBufs, &d.gangAllEvicted, gangCap1 + 1, 0, nullptr, 0);
   }
-  if (newShapes) { sb.stage(&h->jobBufs, &d.unfeasible, (size_t)S1, 0, nullptr, 0); sb.stage(&h->jobBufs, &d.unfeasibleReason, (size_t)S1 * 4, 0, nullptr, 0); }
-  uint64_t* shapeMask1 = nullptr;   // the grown shape mask [old shape rows | new shape rows | old away rows | new away rows]: filled by plat_shapes_append below
-  if (inPlace) {
-    if (Sext1 > Sext0) {
-      sb.stage(&h->maskBufs, &shapeMask1, 8 * (size_t)Sext1 * Wm, 0, nullptr, -1, true);
-      sb.stage(&h->maskBufs, &h->dShapeClass, 4 * shapeClassExt1.size(), 4 * shapeClassExt1.size(), shapeClassExt1.data(), 0);
-      sb.stage(&h->maskBufs, &d.shapeReq, 8 * shapeReqExt1.size(), 8 * shapeReqExt1.size(), shapeReqExt1.data(), 0);
-      sb.stage(&h->maskBufs, &d.awayRowOff, 4 * h->awayRowOff.size(), 4 * h->awayRowOff.size(), h->awayRowOff.data(), 0);
-      sb.stage(&h->maskBufs, &d.rowLiteral, h->rowLiteral.size(), h->rowLiteral.size(), h->rowLiteral.data(), 0);
-      sb.stage(&h->maskBufs, &d.rowTypeOff, 4 * rowTypeOff1.size(), 4 * rowTypeOff1.size(), rowTypeOff1.data(), 0);
-      sb.stage(&h->maskBufs, &d.rowTypes, 4 * rowTypes1.size(), 4 * rowTypes1.size(), rowTypes1.data(), 0);
-    }
-    if (h->Cext > Cext0) sb.stage(&h->maskBufs, &h->dClassMask, 8 * (size_t)h->Cext * Wm, 8 * (size_t)Cext0 * Wm, nullptr, -1);   // (the old rows device to device; the new ones are uploaded below)
-    if (d.f.structOk && d.f.F > F0) {
-      sb.stage(&h->fastBufs, &d.shapeTab, sizeof(ShapeReq) * h->fitTab.size(), sizeof(ShapeReq) * h->fitTab.size(), h->fitTab.data(), 0);
-      if (d.fitBits) sb.stage(&h->fastBufs, &d.fitBits, 8 * ((size_t)d.f.F * d.fitW + 64), 0, nullptr, 0);   // (scratch the next base build fills, as in asched_nodes_append)
-    }
-  }
+  if (newShapes) jaStageShapes(h, g, sb);   // the unfeasible-key arrays for S1 shapes and, in place, the grown mask tables
   if (grow) {
     const size_t c = cap1;
     void* s32[] = {&d.schedAtPrio, &d.jobNode, &d.jobCutoff, &d.optGhost, &d.jcAssigned, &d.jcReason, &d.pcNode, &d.pcSap, &d.pcPap, &d.pcMethod, &d.jcGangCard, &d.jcUniValue, &d.jcStagedBy, &d.jcPreSib,
@@ -2057,7 +2146,7 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
     h->jQueue.insert(h->jQueue.end(), aQueue.begin(), aQueue.end()); h->jPc.insert(h->jPc.end(), aPc.begin(), aPc.end()); h->jReqClass.insert(h->jReqClass.end(), aCls.begin(), aCls.end());
     h->jShape.insert(h->jShape.end(), aShape.begin(), aShape.end()); h->jNode.resize(M1, -1); h->jRunPrio.resize(M1, 0); h->jGangDense.insert(h->jGangDense.end(), aGang.begin(), aGang.end());
     h->jAway.resize(M1, 0); h->jGangUniKey.insert(h->jGangUniKey.end(), aUniKey.begin(), aUniKey.end());
-    if (!mirrorsGrown) h->jReq.insert(h->jReq.end(), rows->req, rows->req + (size_t)m * R);
+    if (!g.mirrorsGrown) h->jReq.insert(h->jReq.end(), rows->req, rows->req + (size_t)m * R);
     std::vector<uint32_t> aQPrio(m, 0); std::vector<int64_t> aSubmit(m, 0);
     if (rows->queue_priority) aQPrio.assign(rows->queue_priority, rows->queue_priority + m);
     if (rows->submit_time) aSubmit.assign(rows->submit_time, rows->submit_time + m);
@@ -2071,39 +2160,11 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
     for (int k = 0; k < 7; k++) plat_h2d(e32 + k * mm, cols[k]->data(), mm * 4);
     plat_h2d(e32 + 7 * mm, aQPrio.data(), mm * 4);
     plat_h2d(h->jpScratch + o64, aSubmit.data(), mm * 8); plat_h2d(h->jpScratch + oReq, rows->req, mm * 8 * R); plat_h2d(h->jpScratch + oAl, aAligned.data(), mm);
-    if (inPlace) {
-      fastMinimaPack(h);
-      if (const char* ms = getenv("ASCHED_SHAPE_MASK")) if (d.fitBits && ms[0] == '1') d.f.maskMode = d.f.F <= 64 ? 1 : d.f.F <= 128 ? 2 : 0;   // (buildFast's rule, for the grown F)
-      if (h->Cext > Cext0) plat_h2d(h->dClassMask + (size_t)Cext0 * Wm, classRows1.data(), classRows1.size() * 8);
-      if (shapeMask1) {
-        const int nNew = nNewRows;
-        std::vector<int32_t> rowCls(nNew), rowOut(nNew); std::vector<int64_t> rowReq((size_t)nNew * R);
-        for (int k = 0; k < nNew; k++) {
-          const int row = k < S1 - S0 ? S0 + k : S1 + A0 + (k - (S1 - S0));
-          rowOut[k] = row; rowCls[k] = shapeClassExt1[row];
-          for (int r = 0; r < R; r++) rowReq[(size_t)k * R + r] = shapeReqExt1[(size_t)row * R + r];
-        }
-        int64_t* dReq = (int64_t*)(h->jpScratch + oSa); int32_t* dCls = (int32_t*)(dReq + (size_t)nNew * R);
-        plat_h2d(dReq, rowReq.data(), rowReq.size() * 8); plat_h2d(dCls, rowCls.data(), (size_t)nNew * 4); plat_h2d(dCls + nNew, rowOut.data(), (size_t)nNew * 4);
-        SaArgs sa; memset(&sa, 0, sizeof sa);
-        sa.N = h->N; sa.Npad = d.cfg.Npad; sa.W = Wm; sa.R = R; sa.rows = nNew;
-        sa.totalRes = d.totalRes; sa.classMask = h->dClassMask;
-        sa.rowClass = dCls; sa.rowOut = dCls + nNew; sa.rowReq = dReq;
-        sa.outMask = shapeMask1; sa.inMask = d.shapeMask;
-        sa.copy0 = (long long)S0 * Wm; sa.src1 = (long long)S0 * Wm; sa.dst1 = (long long)S1 * Wm; sa.copy1 = (long long)A0 * Wm;
-        int src = plat_take_failure() ? -1 : plat_shapes_append(d, sa);
-        if (src) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
-        plat_shapes_append_ms(h->saMs);
-        h->maskBufs.release(d.shapeMask);
-        d.shapeMask = shapeMask1;
-      }
-    }
+    if (inPlace && jaInPlaceApply(h, g, h->jpScratch + oSa)) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
     JaArgs a; memset(&a, 0, sizeof a);
     a.M = M; a.m = m; a.nb2 = nb2; a.R = R; a.writeRec = ((!newShapes || inPlace) && d.f.structOk && d.jrec) ? 1 : 0;
     if (inPlace && nTpl) {
-      std::vector<JobRec> tpl(nTpl);
-      for (size_t t = 0; t < nTpl; t++) fastRecFill(h, tpl[t], tplShape[t], &h->shapeReq[(size_t)tplShape[t] * R], h->shapePc[tplShape[t]], -1, -1, 0);
-      plat_h2d(h->jpScratch + oTplIdx, aTpl.data(), (size_t)m * 4); plat_h2d(h->jpScratch + oTpl, tpl.data(), sizeof(JobRec) * nTpl);
+      plat_h2d(h->jpScratch + oTplIdx, aTpl.data(), (size_t)m * 4); jaTemplatesUpload(h, tplShape, h->jpScratch + oTpl);
       a.tpl = (const JobRec*)(h->jpScratch + oTpl); a.aTpl = (const int32_t*)(h->jpScratch + oTplIdx);
     }
     a.aQueue = e32; a.aPc = e32 + mm; a.aShape = e32 + 2 * mm; a.aGang = e32 + 3 * mm; a.aGangCard = e32 + 4 * mm; a.aGangUni = e32 + 5 * mm; a.aSrc = e32 + 6 * mm;
@@ -2179,6 +2240,179 @@ int32_t asched_jobs_append_shape_stats(asched_t* h, int32_t* out) {
   plat_enter(h->plat);
   for (int k = 0; k < 8; k++) out[k] = h->jasStats[k];
   out[0] = h->appendInPlace ? 1 : 0;
+  return 0;
+}
+
+// ---- asched_jobs_respec (kernels_jobs_respec.h): a retried job's scheduling requirements are rewritten before it re-enters its queue (scheduler.go:1342-1383 through
+// job.WithJobSchedulingInfo: node anti-affinity for every attempted run, :637-658 adopted at :1369-1376 — a new requirement class; the retry policy's memory bump, :683 ff.
+// adopted at :1347-1354 — a new request vector).  The named rows, which have no run, take another class and / or request in place; the handle is left as
+// asched_jobs_set of the edited table would leave it.  Neither field is part of the order key, so nothing is sorted or merged: per entry the target shape is found in
+// the table asched_jobs_append uses, new and revived shapes take the steps of the append (in place with asched_set_append_in_place, else rebuildMasks), and one scatter
+// writes shape, request, grid flag and JobRec of each row.  A record comes from a resident row of the target shape that no entry names, else from a template (DESIGN 3.20).
+int32_t asched_jobs_respec(asched_t* h, int32_t n, const int32_t* job, const int32_t* req_class, const int64_t* req) {
+  if (!h) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  const int M = h->M, R = h->R;
+  Dev& d = h->dev;
+  // ---- every refusal before anything changes
+  if (!h->jobsSet || h->jShape.size() != (size_t)M || h->jReqClass.size() != (size_t)M || h->jReq.size() != (size_t)M * R || h->jNode.size() != (size_t)M || h->jAway.size() != (size_t)M ||
+      h->shapeRow.size() != (size_t)h->S)
+    return fail(h, ASCHED_ERR_INVALID, "jobs_respec: no job table on this handle (jobs_set first)");
+  if (n < 0 || (n > 0 && (!job || (!req_class && !req)))) return fail(h, ASCHED_ERR_INVALID, "jobs_respec: bad arguments");
+  if (h->mkJobsBuilt) return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_respec: the job set carries the market order (jobs_set instead)");
+  if (n > (1 << 29)) return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_respec: more than 2^29 entries");
+  if (h->jpSeen.size() != (size_t)M) h->jpSeen.assign(M, 0);
+  auto unsee = [&](int upTo) { for (int i = 0; i < upTo; i++) h->jpSeen[job[i]] = 0; };
+  {
+    int seen = 0, code = ASCHED_ERR_INVALID;
+    const char* why = nullptr;
+    for (int i = 0; i < n && !why; i++) {
+      const int j = job[i];
+      if (j < 0 || j >= M) { why = "jobs_respec: a row outside the job table"; break; }
+      if (h->jpSeen[j]) { why = "jobs_respec: a row named twice"; break; }
+      h->jpSeen[j] = 1; seen = i + 1;
+      if (req_class && (req_class[i] < 0 || req_class[i] >= h->C)) why = "jobs_respec: req_class out of range (asched_req_classes_append brings a new class first)";
+      else if (h->jNode[j] >= 0) why = "jobs_respec: a row has a run (jobs_patch ends the run first)";
+      else if (h->jAway[j]) { why = "jobs_respec: a cross-pool away row"; code = ASCHED_ERR_UNSUPPORTED; }
+    }
+    if (why) { unsee(seen); return fail(h, code, why); }
+  }
+  // the entries that change something: row, class, request, grid flag
+  std::vector<int32_t> cJob, cCls; std::vector<int64_t> cReq; std::vector<uint8_t> cAligned;
+  for (int i = 0; i < n; i++) {
+    const int j = job[i];
+    const int32_t cls = req_class ? req_class[i] : h->jReqClass[j];
+    const int64_t* rq = req ? req + (size_t)i * R : &h->jReq[(size_t)j * R];
+    if (cls == h->jReqClass[j] && !memcmp(rq, &h->jReq[(size_t)j * R], sizeof(int64_t) * R)) continue;
+    uint8_t al = 1;
+    for (int c = 0; c < h->K; c++) if (rq[h->indexedCol[c]] % h->indexedRes[c]) al = 0;
+    cJob.push_back(j); cCls.push_back(cls); cReq.insert(cReq.end(), rq, rq + R); cAligned.push_back(al);
+  }
+  const int nc = (int)cJob.size(), S0 = h->S;
+  // the target shape of every entry (undone by `undo` on a later refusal) and the source of its record: the first row of a resident shape unless this call names it
+  if (nc > 0 && h->shapeTable.empty()) jaShapeTableBuild(h, (size_t)S0);
+  JaShapes g; g.begin(h);
+  std::vector<int32_t> cShape(nc), cSrc(nc, -1), cTpl(nc, -1), cOld(nc);
+  for (int k = 0; k < nc; k++) {
+    const int j = cJob[k];
+    const int32_t s = cShape[k] = jaShapeFind(h, cCls[k], h->jPc[j], &cReq[(size_t)k * R], j);
+    cOld[k] = h->jShape[j];
+    if (!cAligned[k]) h->shapeUnaligned[s] = 1;   // (a property of the shape)
+    if (s < S0) {
+      int32_t& first = h->shapeRow[s];
+      if (first < 0) { if (g.revived.empty()) g.shapeRowSaved = h->shapeRow; g.revived.push_back(s); first = j; }   // a delete or an earlier respec emptied the shape
+      else if (!h->jpSeen[first]) cSrc[k] = first;
+    }
+  }
+  unsee(n);
+  const int S1 = (int)h->shapeClass.size();
+  const bool newShapes = S1 > S0 || !g.revived.empty();   // (a revived shape takes the path of a new one, as in asched_jobs_append)
+  const bool anyAway = d.cfg.hasAway != 0;   // (the rows keep their priority classes)
+  std::vector<int64_t> oldReq;
+  auto undo = [&]() {   // a refusal after the shape lookup: the handle exactly as it was
+    if (!newShapes) return;
+    if (g.mirrorsGrown) for (int k = 0; k < nc; k++) memcpy(&h->jReq[(size_t)cJob[k] * R], &oldReq[(size_t)k * R], sizeof(int64_t) * R);
+    jaShapesUndo(h, g);
+  };
+  auto mirrorReq = [&]() { for (int k = 0; k < nc; k++) memcpy(&h->jReq[(size_t)cJob[k] * R], &cReq[(size_t)k * R], sizeof(int64_t) * R); };
+  if (newShapes) {
+    // what the rebuild can refuse, checked on the host first, on the request mirror of the edited table
+    oldReq.resize((size_t)nc * R);
+    for (int k = 0; k < nc; k++) memcpy(&oldReq[(size_t)k * R], &h->jReq[(size_t)cJob[k] * R], sizeof(int64_t) * R);
+    mirrorReq(); h->S = S1; g.mirrorsGrown = true;
+    std::string why;
+    if (int rrc = jaShapesRefusal(h, g, anyAway, why)) { undo(); return fail(h, rrc, "jobs_respec: " + why); }
+  }
+  if (newShapes && h->appendInPlace) {
+    bool negNew = false;
+    for (size_t k = 0; k < cReq.size() && !negNew; k++) negNew = cReq[k] < 0;
+    std::string why;
+    if (int rrc = jaInPlaceDecide(h, g, anyAway, negNew, why)) { undo(); return fail(h, rrc, "jobs_respec: " + why); }
+  }
+  // one template record per target shape that some entry has no source row for; the per-shape tables of buildFast must cover the shape (else the rebuild)
+  bool rebuild = newShapes && !g.inPlace;
+  std::vector<int32_t> tplShape;
+  if (!rebuild && d.f.structOk && d.jrec) {
+    std::unordered_map<int32_t, int32_t> tplOf;
+    for (int k = 0; k < nc; k++) if (cSrc[k] < 0) cTpl[k] = jaTemplateOf(tplOf, tplShape, cShape[k]);
+    if (!tplShape.empty() && (h->fitOf.size() != (size_t)S1 || h->fsDelta.size() != (size_t)S1 || h->rowLiteral.size() < (size_t)S1)) { rebuild = true; g.inWhy = 1; tplShape.clear(); }
+  }
+  if (rebuild && g.inPlace) {   // (the tables the in-place decision grew are derived again by the rebuild; the blocks it would have staged are not needed)
+    g.inPlace = false; g.shapeMask1 = nullptr;
+  }
+  const size_t nTpl = tplShape.size();
+  const int nNewRows = g.inPlace ? (S1 - S0) + ((int)h->awayRowClass.size() - g.A0) : 0;
+  // ---- every device block before anything changes: running out of device memory here is a refusal too
+  const size_t oAl = up256(sizeof(int32_t) * 4 * (size_t)nc), oReq = oAl + up256((size_t)nc), oTpl = oReq + up256(sizeof(int64_t) * (size_t)nc * R),
+               oSa = oTpl + up256(sizeof(JobRec) * nTpl), need = oSa + up256((size_t)nNewRows * (8 + 8 * (size_t)R));
+  KeptBlock<char> scratch{h->jpBufs, h->jpScratch, h->jpScratchBytes};
+  if (nc > 0 && !scratch.tryGrow(need)) { undo(); return fail(h, ASCHED_ERR_DEVICE, "jobs_respec: out of device memory for the scratch; the handle is as it was"); }
+  StagedBlocks sb;
+  if (newShapes) jaStageShapes(h, g, sb);
+  if (!sb.allocate()) {
+    scratch.drop();
+    undo();
+    return fail(h, ASCHED_ERR_DEVICE, "jobs_respec: out of device memory for the grown shape tables; the handle is as it was");
+  }
+  // ---- what jobs_set resets (the job table half edited).  On the rebuild path the call ends with rebuildMasks: the fast structure goes
+  residentTouchJobs(h, rebuild, !rebuild);
+  h->saMs[0] = h->saMs[1] = 0;
+  scratch.adopt();
+  int emptied = 0, fromTpl = 0;
+  if (nc > 0) {
+    sb.fill();
+    plat_sync();
+    sb.commit();
+    // the host mirrors
+    if (!g.mirrorsGrown) mirrorReq();
+    for (int k = 0; k < nc; k++) { h->jReqClass[cJob[k]] = cCls[k]; h->jShape[cJob[k]] = cShape[k]; }
+    h->S = S1; d.cfg.S = S1;
+    // shapeRow: an old shape whose first row left gets its next row in ONE forward pass over the jShape mirror (-1: the shape is left without a row, until
+    // asched_shapes_compact); a target shape's first row is the smallest row it now has
+    { std::vector<uint8_t> lost; int left = 0;
+      for (int k = 0; k < nc; k++) if (h->shapeRow[cOld[k]] == cJob[k]) {
+        if (lost.empty()) lost.assign(S1, 0);
+        if (!lost[cOld[k]]) { lost[cOld[k]] = 1; left++; }
+        h->shapeRow[cOld[k]] = -1;
+      }
+      for (int i = 0; i < M && left > 0; i++) { const int32_t s = h->jShape[i]; if (lost[s] && h->shapeRow[s] < 0) { h->shapeRow[s] = i; left--; } }
+      emptied = left;
+      for (int k = 0; k < nc; k++) { int32_t& first = h->shapeRow[cShape[k]]; if (first < 0 || cJob[k] < first) first = cJob[k]; } }
+    // the entries: the only upload proportional to anything
+    int32_t* e32 = (int32_t*)h->jpScratch; const size_t nn = (size_t)nc;
+    plat_h2d(e32, cJob.data(), nn * 4); plat_h2d(e32 + nn, cShape.data(), nn * 4); plat_h2d(e32 + 2 * nn, cSrc.data(), nn * 4); plat_h2d(e32 + 3 * nn, cTpl.data(), nn * 4);
+    plat_h2d(h->jpScratch + oAl, cAligned.data(), nn); plat_h2d(h->jpScratch + oReq, cReq.data(), nn * 8 * R);
+    if (g.inPlace && jaInPlaceApply(h, g, h->jpScratch + oSa)) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+    JsArgs a; memset(&a, 0, sizeof a);
+    a.n = nc; a.R = R; a.writeRec = (!rebuild && d.f.structOk && d.jrec) ? 1 : 0;
+    a.pJob = e32; a.pShape = e32 + nn; a.pSrc = e32 + 2 * nn; a.pTpl = e32 + 3 * nn;
+    a.pAligned = (const uint8_t*)(h->jpScratch + oAl); a.pReq = (const int64_t*)(h->jpScratch + oReq);
+    if (nTpl) { jaTemplatesUpload(h, tplShape, h->jpScratch + oTpl); a.tpl = (const JobRec*)(h->jpScratch + oTpl); }
+    if (a.writeRec) for (int k = 0; k < nc; k++) if (cTpl[k] >= 0) fromTpl++;
+    int prc = plat_take_failure() ? -1 : plat_jobs_respec(d, a);
+    if (prc) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  }
+  { int32_t* t = h->jsStats;
+    t[0] = n; t[1] = n - nc; t[2] = S1 - S0; t[3] = (int32_t)g.revived.size(); t[4] = emptied; t[5] = rebuild ? 1 : 0; t[6] = g.inWhy; t[7] = fromTpl; }
+  if (plat_take_failure()) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+  d.cfg.Q = 0;
+  if (rebuild) {   // the shape-dependent tables, by the code jobs_set ends with (the key layout was decided above)
+    int rc = rebuildMasks(h);
+    if (rc) return rc;
+    rc = runControl(h, CMD_UPSERT_RESET);
+    if (rc) return rc;
+    rc = runControl(h, CMD_RESET_JOBS);
+    h->allocPristine = h->nodesSet;
+    h->evictedDirty = false;
+    return rc;
+  }
+  // job dynamic state: everything unbound until round_prepare, as asched_jobs_patch leaves it
+  return resetDynamicState(h, M);
+}
+int32_t asched_jobs_respec_stats(asched_t* h, int32_t* out) {
+  if (!h || !out) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  for (int k = 0; k < 8; k++) out[k] = h->jsStats[k];
   return 0;
 }
 
@@ -2297,7 +2531,7 @@ int32_t asched_req_classes_append(asched_t* h, const asched_req_classes* more) {
   uint64_t* mask1 = (uint64_t*)sb.fresh(&h->dClassMask);
   // ---- what jobs_set resets (the class tables half grown).  Off the in-place path the call ends with rebuildMasks: the fast structure goes
   residentTouchJobs(h, why != 0);
-  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats);
+  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->jsStats, 0, sizeof h->jsStats);
   h->caMs[0] = h->caMs[1] = 0;
   { int32_t* t = h->caStats;
     t[0] = n; t[1] = nT1; t[2] = nT2; t[3] = inPlace ? Cext0 - C0 : 0; t[4] = why ? 1 : 0; t[5] = why; t[6] = h->C; t[7] = h->Cext; }
@@ -2497,7 +2731,7 @@ int32_t asched_shapes_compact(asched_t* h, int32_t flags, int32_t* class_new_id)
   uint64_t* shapeMask1 = (uint64_t*)sb.fresh(&d.shapeMask); uint64_t* classMask1 = (uint64_t*)sb.fresh(&h->dClassMask);
   // ---- what jobs_set resets (the tables half compacted).  Off the in-place path the call ends with rebuildMasks: the fast structure goes
   residentTouchJobs(h, why != 0);
-  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->caStats, 0, sizeof h->caStats);
+  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->jsStats, 0, sizeof h->jsStats); memset(h->caStats, 0, sizeof h->caStats);
   h->scMs[0] = h->scMs[1] = h->scMs[2] = 0; h->scHostMs = 0;
   if (anyDead) {
     plat_h2d(scratch, shapeNew.data(), 4 * (size_t)S0);

@@ -96,6 +96,10 @@ static void plat_jobs_patch_ms(double* out /*[4]*/);   // measurement hook: devi
 // a.p.kept / a.p.nKept.  Synchronous: the new order is complete on return; plat_jobs_patch_ms reports its passes.  The CPU build's definition sits in kernels_jobs_reprioritise.h.
 struct JrArgs;
 static int plat_jobs_reprioritise(Dev& d, JrArgs& a, int32_t* keptBuf);
+// retried jobs change class and request in place (kernels_jobs_respec.h): one scatter over the entries — shape, request words, grid flag and JobRec of each named row.
+// Synchronous: the rows are complete on return.  The CPU build's definition sits in kernels_jobs_respec.h.
+struct JsArgs;
+static int plat_jobs_respec(Dev& d, JsArgs& a);
 // newly submitted jobs behind the resident job table (kernels_jobs_append.h): row fill + keys, the patch's sort, the patch's merge by rank of the old order (a.p.kept) and the
 // sorted new keys into a.p.out.  Synchronous: rows and order are complete on return.  The CPU build's definition sits in kernels_jobs_append.h.
 struct JaArgs;

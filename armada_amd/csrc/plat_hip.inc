@@ -936,6 +936,17 @@ extern "C" int asched_internal_jr_scatter(const Dev* d, const JrArgs* a, hipStre
 static int plat_jobs_reprioritise(Dev& d, JrArgs& a, int32_t* keptBuf) {
   return jpPasses(d, a.p, keptBuf, [&](hipStream_t st) { return asched_internal_jr_scatter(&d, &a, st); });
 }
+// retried jobs change class and request in place (kernels_jobs_respec.h; k_js_scatter in armada_sched_mgpu.hip): one launch on the handle's stream, waited for
+#include "kernels_jobs_respec.h"
+extern "C" int asched_internal_js_scatter(const Dev* d, const JsArgs* a, hipStream_t s);
+static int plat_jobs_respec(Dev& d, JsArgs& a) {
+  PlatCtx* c = t_ctx;
+  hipStream_t st = c->stream;
+  bool ok = asched_internal_js_scatter(&d, &a, st) == 0;
+  ok = ok && hipOk(hipGetLastError(), "k_js launch") && hipOk(hipStreamSynchronize(st), "k_js");
+  if (!ok) { if (c->err.empty()) c->err = "k_js_scatter launch failed"; return -1; }
+  return 0;
+}
 // newly submitted jobs behind the resident job table (kernels_jobs_append.h; k_ja_fill in armada_sched_mgpu.hip, the sort and the merge are the patch's kernels).
 // ASCHED_JA_TIMES=1 puts events around the three passes (tools/probe_jobs_append.py).
 #include "kernels_jobs_append.h"

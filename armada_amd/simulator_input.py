@@ -571,6 +571,129 @@ def run_cycles_reprioritising_rebuilt(lib, sim: SimulatorInput, events, per_cycl
     return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, 1, False, resident="delete", reprio=list(events))
 
 
+RETRY_HOST_LABEL = 9001   # the label key _run_cycles_retrying gives every node its number under (kubernetes.io/hostname): not indexed, so the nodes stay one node type
+
+
+def _run_cycles_retrying(lib, sim: SimulatorInput, per_cycle, max_cycles, respec, fail_share, bump_share, max_retries, seed, in_place):
+    from .binding import AFFINITY_OPS, Scheduler
+    from .workloads import MEM
+    wl = sim.workload
+    m = wl.num_jobs
+    arrive = arrival_cycles(sim, per_cycle)
+    rng = np.random.default_rng(seed)
+    node = np.full(m, -1, np.int32)
+    run_prio = np.zeros(m, np.int32)
+    started = np.full(m, -1.0)
+    done = np.zeros(m, bool)
+    changed = np.zeros(m, bool)
+    req = np.array(wl.job_req, dtype=np.int64)        # per job: the request, which a memory bump moves
+    cls = np.zeros(m, np.int32)                       # per job: its requirement class; class 0 is the empty one
+    attempted = [[] for _ in range(m)]                # per job: the nodes of its failed runs
+    class_of = {(): 0}                                # attempted nodes (sorted) -> class id, in order of creation
+    leased = np.zeros(0, np.int64)                    # the jobs the previous cycle's round leased
+    out = []
+    retried = bumped = respecs_rebuilt = 0
+    s = Scheduler(lib, wl.config)
+    s.nodes_upsert(wl.node_total, id_rank=wl.node_id_rank, labels=[[(RETRY_HOST_LABEL, n)] for n in range(wl.num_nodes)])
+    have = 0
+    t = 0.0
+
+    def class_lists():
+        keys = sorted(class_of, key=class_of.get)
+        return [[] for _ in keys], [None if not k else [[(RETRY_HOST_LABEL, AFFINITY_OPS["NotIn"], list(k))]] for k in keys]
+
+    for cycle in range(max_cycles):
+        finished = (node >= 0) & (started >= 0) & (started + sim.job_runtime_s <= t)
+        done |= finished
+        node[finished] = -1
+        changed |= finished
+        # the failures: a seeded share of the jobs leased in the last cycle, each at most max_retries times; a share of those also takes the memory bump
+        failed = np.array([j for j in leased if node[j] >= 0 and len(attempted[j]) < max_retries and rng.random() < fail_share], dtype=np.int64)
+        bump = np.array([rng.random() < bump_share for _ in failed], dtype=bool)
+        new_classes = []
+        for j, b in zip(failed, bump):
+            attempted[j].append(int(node[j]))
+            key = tuple(sorted(set(attempted[j])))
+            if key not in class_of:
+                class_of[key] = len(class_of)
+                new_classes.append(key)
+            cls[j] = class_of[key]
+            if b:
+                req[j, MEM] += req[j, MEM] // 2
+            node[j], started[j] = -1, -1.0
+            changed[j] = True
+        retried += len(failed); bumped += int(bump.sum())
+        if done.all():
+            break
+        upto = int(np.searchsorted(arrive, cycle, side="right"))
+        if respec:
+            if cycle == 0:
+                s.jobs_set(req[:upto], queue=wl.job_queue[:upto], pc=wl.job_pc[:upto], submit_time=wl.job_submit[:upto], node=node[:upto],
+                           scheduled_at_priority=run_prio[:upto], run_timestamp=np.zeros(upto, np.int64), req_class=cls[:upto], class_tolerations=[[]])
+                if in_place:
+                    s.set_append_in_place(True)
+            elif upto > have:
+                s.jobs_append(req[have:upto], queue=wl.job_queue[have:upto], pc=wl.job_pc[have:upto], submit_time=wl.job_submit[have:upto], req_class=cls[have:upto])
+            rows = np.nonzero(changed)[0].astype(np.int32)
+            if len(rows):                             # syncState's order: the failed runs end first ...
+                running = node[rows] >= 0
+                s.jobs_patch(rows, node[rows], np.where(running, run_prio[rows], 0), np.where(running, np.maximum(started[rows], 0) * 1e9, 0).astype(np.int64))
+            if new_classes:                           # ... then the retried jobs re-enter their queues under their new scheduling requirements
+                first = s.req_classes_append([[] for _ in new_classes], affinities=[[[(RETRY_HOST_LABEL, AFFINITY_OPS["NotIn"], list(k))]] for k in new_classes])
+                assert first == class_of[new_classes[0]]
+            if len(failed):
+                s.jobs_respec(failed.astype(np.int32), cls[failed], req[failed])
+                respecs_rebuilt += s.jobs_respec_stats()["rebuilt"]
+        else:
+            running = node[:upto] >= 0
+            tol, aff = class_lists()
+            s.jobs_set(req[:upto], queue=wl.job_queue[:upto], pc=wl.job_pc[:upto], submit_time=wl.job_submit[:upto], node=node[:upto],
+                       scheduled_at_priority=np.where(running, run_prio[:upto], 0), run_timestamp=np.where(running, np.maximum(started[:upto], 0) * 1e9, 0).astype(np.int64),
+                       req_class=cls[:upto], class_tolerations=tol, class_affinities=aff if len(tol) > 1 else None)
+        changed[:] = False
+        have = upto
+        queued = [np.array([j for j in q if j < have and not done[j] and node[j] < 0], dtype=np.int32) for q in wl.queued]
+        nq = wl.num_queues
+        s.round_prepare(wl.queue_weight, queued, global_tokens=float(wl.global_burst), global_burst=wl.global_burst, global_rate_inf=wl.rate_inf,
+                        queue_tokens=[float(wl.queue_burst)] * nq, queue_burst=[wl.queue_burst] * nq, queue_rate_inf=[wl.rate_inf] * nq)
+        r = s.schedule_round()
+        sched = {int(j): int(n) for j, n in r.scheduled.items()}
+        pre = {int(j): int(n) for j, n in r.preempted.items()}
+        for j, n in sched.items():
+            node[j], started[j], run_prio[j] = n, t, r.scheduled_priority[j]
+            changed[j] = True
+        for j in pre:
+            node[j], started[j] = -1, -1.0
+            changed[j] = True
+        leased = np.array(sorted(sched), dtype=np.int64)
+        out.append({"time_s": t, "scheduled": sched, "preempted": pre, "termination_reason": r.termination_reason, "rows": have,
+                    "retried": retried, "bumped": bumped, "classes": len(class_of)})
+        if respec:
+            out[-1]["respecs_rebuilt"] = respecs_rebuilt
+        if have == m and not sched and not pre and not (node >= 0).any():
+            break   # everything has arrived, nothing runs and nothing can be placed: the rest never will
+        t += sim.cycle_period_s
+    s.close()
+    return out
+
+
+def run_cycles_retrying(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000, fail_share: float = 0.2, bump_share: float = 0.5,
+                        max_retries: int = 2, seed: int = 0, in_place: bool = True):
+    """run_cycles_arriving plus RETRIES (scheduler.go:1342-1383): at the start of a cycle a seeded share `fail_share` of the jobs the last round leased fail, each at most
+    `max_retries` times.  A failed job loses its run (jobs_patch) and is requeued with node anti-affinity against every node it has run on — a requirement class of its
+    own per set of attempted nodes, brought with Scheduler.req_classes_append — and, for a share `bump_share` of the failures, half as much memory again; both are
+    applied with ONE Scheduler.jobs_respec per cycle.  Every node carries its number under the label key RETRY_HOST_LABEL.  The schedulability probe of the reference
+    (submitChecker.Check, :671) stays the caller's.  Records as run_cycles_arriving, plus the retries, bumps and classes so far and the respecs that rebuilt."""
+    return _run_cycles_retrying(lib, sim, per_cycle, max_cycles, True, fail_share, bump_share, max_retries, seed, in_place)
+
+
+def run_cycles_retrying_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000, fail_share: float = 0.2, bump_share: float = 0.5,
+                                max_retries: int = 2, seed: int = 0):
+    """the rebuilt counterpart of run_cycles_retrying: jobs_set of the grown table with the edited classes and requests, and every class created so far, in every
+    cycle — what any library, the oracle included, can run.  Same failures (the same seed over the same leases), same records."""
+    return _run_cycles_retrying(lib, sim, per_cycle, max_cycles, False, fail_share, bump_share, max_retries, seed, False)
+
+
 def run_cycles_compacting_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000, every: int = 1):
     """the rebuilt counterpart of run_cycles_compacting: jobs_set of the live rows (every job that has arrived and was not dropped at a compacting cycle, with its run
     state) in every cycle — what any library, the oracle included, can run.  Same rows, same records."""

@@ -402,12 +402,39 @@ int32_t ASCHED_FN(jobs_patch)(asched_t*, int32_t n, const int32_t* job, const in
    Refused before anything changes — ASCHED_ERR_INVALID: no job table, n < 0, n > 0 without job or queue_priority, a row outside [0, M), a row named twice;
    ASCHED_ERR_UNSUPPORTED: the job set carries the market order, more than 2^29 entries; ASCHED_ERR_DEVICE with "the handle is as it was" in last_error: out of device
    memory for the scratch.  Any other ASCHED_ERR_DEVICE (a failed launch or copy) is NOT such a refusal: the handle then needs asched_jobs_set, as documented for
-   jobs_patch.  No other field changes: queue, priority class, submit time, request and gang of a row are fixed for as long as it is in the table. */
+   jobs_patch.  No other field changes: queue, priority class, submit time and gang of a row are fixed for as long as it is in the table; its requirement class and
+   request change only through asched_jobs_respec. */
 int32_t ASCHED_FN(jobs_reprioritise)(asched_t*, int32_t n, const int32_t* job, const uint32_t* queue_priority);
 /* how the last jobs_reprioritise ran: out[0] entries, [1] entries that name a row in the order (queue >= 0), [2] entries whose priority did not change, [3] 1 = this
    call made the order-key inputs resident (the first incremental call on the job table), [4..7] device microseconds of scatter / remove / sort / merge (measured only
    with ASCHED_JP_TIMES=1, else 0).  Zeros after jobs_set. */
 int32_t ASCHED_FN(jobs_reprioritise_stats)(asched_t*, int32_t* out /*[8]*/);
+/* A retry of resident jobs: when a run fails and the job is requeued, the reference rewrites its scheduling requirements before it re-enters its queue
+   (scheduler.go:1342-1383, through job.WithJobSchedulingInfo): node anti-affinity for every attempted run (createSchedulingInfoWithNodeAntiAffinityForAttemptedRuns,
+   :637-658, adopted at :1369-1376) — a new (tolerations, selector, affinity) set, here a new requirement class — and the retry policy's memory bump
+   (createSchedulingInfoWithMemoryBump, :683 ff., adopted at :1347-1354) — a new request vector, here a new scheduling-key shape.  The job keeps its id, queue, priority
+   class, submit time and gang.
+   entry i: row job[i] now has requirement class req_class[i] (NULL: every class unchanged) and the request req[i][R] (NULL: every request unchanged).  A new class is
+   brought first with asched_req_classes_append; req_class[i] must be below the handle's number of real classes.  Accepted rows are rows without a run: of any queue
+   >= -1, gang members, with any request vector — off the index grid, or one no node holds.  An entry equal to the row's current (class, request) is legal and changes
+   nothing.  The pre-sorted order depends on neither field, so nothing is sorted or merged; a shape the table does not hold, or holds without a row, takes the path it
+   takes in asched_jobs_append (in place with asched_set_append_in_place where its conditions hold, else the rebuild; asched_jobs_respec_stats says which and why).  A
+   shape that loses its last row stays known, as after asched_jobs_delete, until asched_shapes_compact.
+   After a successful call the handle is in the state asched_jobs_set would have left, given the same job table with req_class and req replaced in the named rows and
+   the same class list — for every entry point (rounds after either form of round_prepare, scheduling_order, round_queued, fit_select_batch, node_types_matching_job,
+   the submit check, job_key_unfeasible, the optimiser, any later resident call in any order), including everything jobs_set and jobs_patch reset; shape ids and dead
+   shapes are not observable.  n == 0 performs the resets only.
+   Refused before anything changes — ASCHED_ERR_INVALID: no job table, n < 0, n > 0 with both arrays NULL or without job, a row outside [0, M), a row named twice, a
+   class out of range, a row that has a run (the caller ends the run with asched_jobs_patch first, in syncState's order); ASCHED_ERR_UNSUPPORTED: the job set carries
+   the market order, a cross-pool away row, more than 2^29 entries, whatever the rebuild for a new shape would refuse (an order key beyond 128 bits, LIT_TMAX);
+   ASCHED_ERR_DEVICE with "the handle is as it was" in last_error: out of device memory for the scratch or the staged blocks.  Any other ASCHED_ERR_DEVICE is NOT such
+   a refusal: the handle then needs asched_jobs_set, as documented for jobs_patch. */
+int32_t ASCHED_FN(jobs_respec)(asched_t*, int32_t n, const int32_t* job /*[n] rows, each at most once*/, const int32_t* req_class /*[n] or NULL: unchanged*/,
+                               const int64_t* req /*[n][R] or NULL: unchanged*/);
+/* how the last jobs_respec ran: out[0] entries, [1] entries that changed nothing, [2] new shapes, [3] revived shapes (known, without a row before the call), [4] shapes
+   this call left without a row, [5] 1 = masks and fast structure were rebuilt, [6] the reason code of asched_jobs_append_shape_stats (0 = in place or nothing to
+   grow), [7] records written from templates.  Zeros after jobs_set. */
+int32_t ASCHED_FN(jobs_respec_stats)(asched_t*, int32_t* out /*[8]*/);
 /* syncState's upsert of the newly submitted jobs into the jobDb at the start of a cycle (scheduler.go:478-535; jobdb/jobdb.go:572-700, the insertion into the per-queue
    sorted set at :691-700): rows->m rows are added behind the M rows the handle holds; the new job ids are M .. M+m-1.  Rows must stay in ascending job-id order, as for
    jobs_set (newly submitted ULIDs sort after the resident ones; the caller sorts the batch).  The requirement classes are those of the last jobs_set.

@@ -927,6 +927,79 @@ func (g *GpuRound) ReprioritiseJobs(jobs []*jobdb.Job) error {
 	return g.check(C.asched_jobs_reprioritise(g.h, C.int32_t(n), i32p(row), (*C.uint32_t)(unsafe.Pointer(&prio[0]))))
 }
 
+// RespecJobs tells the library the scheduling requirements the scheduler rewrote for the jobs it requeued after a failed run (asched_jobs_respec), without
+// re-describing the job set: scheduler.go:1342-1383 gives a retried job node anti-affinity against every attempted run
+// (createSchedulingInfoWithNodeAntiAffinityForAttemptedRuns, :637-658, adopted at :1369-1376) and, under the retry policy, more memory
+// (createSchedulingInfoWithMemoryBump, :683 ff., adopted at :1347-1354), both through job.WithJobSchedulingInfo; the caller passes the jobs as they are after that
+// call.  A (tolerations, selector, affinity) set the table has not seen joins first with asched_req_classes_append, as in AppendJobs.  Every job must be one of the
+// last UploadJobs or of an AppendJobs since, each at most once, and queued: the failed run has been ended with PatchJobs, so in the sync step RespecJobs stands after
+// PatchJobs and before DeleteJobs.  ErrNeedsUpload on the first cycle, on a market-driven pool and for a job that still has a run.  The schedulability probe
+// (submitChecker.Check, :671) stays the caller's.  Not compiled: there is no Go toolchain where the library is built.
+func (g *GpuRound) RespecJobs(jobs []*jobdb.Job) error {
+	if g.jobs == nil || (g.market != nil && g.market.Enabled) {
+		return ErrNeedsUpload
+	}
+	if g.jobRow == nil {
+		g.jobRow = make(map[string]int32, len(g.jobs))
+		for i, j := range g.jobs {
+			g.jobRow[j.Id()] = int32(i)
+		}
+	}
+	n := len(jobs)
+	if n == 0 {
+		return g.check(C.asched_jobs_respec(g.h, 0, nil, nil, nil))
+	}
+	R := len(g.resNames)
+	row, cls := make([]int32, n), make([]int32, n)
+	req := make([]int64, n*R)
+	newClassIdx := map[string]int32{}
+	var newClasses []reqClass
+	for i, j := range jobs {
+		r, ok := g.jobRow[j.Id()]
+		if !ok {
+			return fmt.Errorf("RespecJobs: job %s is not one of the uploaded jobs", j.Id())
+		}
+		if !j.Queued() {
+			return ErrNeedsUpload
+		}
+		row[i] = r
+		copy(req[i*R:], g.vec(j.AllResourceRequirements()))
+		key, rc := g.classKey(j)
+		ci, ok := g.classes[key]
+		if !ok {
+			if ci, ok = newClassIdx[key]; !ok {
+				ci = int32(len(g.classes) + len(newClasses))
+				newClassIdx[key] = ci
+				newClasses = append(newClasses, rc)
+			}
+		}
+		cls[i] = ci
+	}
+	var pins runtime.Pinner
+	defer pins.Unpin()
+	if len(newClasses) > 0 {
+		if err := g.uploadLabelValueInts(); err != nil {
+			return err
+		}
+		var c C.asched_req_classes
+		marshalClasses(newClasses).set(&c, &pins)
+		if err := g.check(C.asched_req_classes_append(g.h, &c)); err != nil {
+			return err
+		}
+		for k, id := range newClassIdx {
+			g.classes[k] = id
+		}
+	}
+	pins.Pin(&row[0]); pins.Pin(&cls[0]); pins.Pin(&req[0])
+	if err := g.check(C.asched_jobs_respec(g.h, C.int32_t(n), i32p(row), i32p(cls), i64p(req))); err != nil {
+		return err
+	}
+	for i, j := range jobs {
+		g.jobs[row[i]] = j // (the object with the new scheduling info: what a later UploadJobs of g.jobs would describe)
+	}
+	return nil
+}
+
 // DeleteJobs drops the rows of jobs in a terminal state from the uploaded job table (asched_jobs_delete): what syncState does after its upserts, every cycle
 // (scheduler.go:539-549; Txn.BatchDelete / delete, jobdb/jobdb.go:941-990).  The shim's sync step is AppendJobs(new submissions), PatchJobs(run-state changes),
 // DeleteJobs(terminal jobs), then Schedule.  ids: each one of the last UploadJobs or of an AppendJobs since, at most once.  The library renumbers the remaining rows
