@@ -652,8 +652,10 @@ static int plat_build_base(Dev& d) {
   hipLaunchKernelGGL(k_base_fill, dim3((nb2 + 255) / 256), dim3(256), 0, t_ctx->stream, d, nb2);
   unsigned long long* a = (unsigned long long*)d.baseKey;
   if (nb2 <= 4096) {
-    // pad region beyond nb2 is never touched: the tile kernel is only used when the array is a multiple of 4096
-    for (int k = 2; k <= nb2; k <<= 1) for (int j = k >> 1; j > 0; j >>= 1) hipLaunchKernelGGL(k_bitonic_step, dim3((nb2 + 255) / 256), dim3(256), 0, t_ctx->stream, a, j, k);
+    // k_bitonic_step has no bound on its index and baseKey holds exactly nb2 keys (buildFast): the launch is exactly nb2 threads — one workgroup of 64 or 128
+    // for pools of <= 128 nodes, whole workgroups of 256 above.  (The tile kernel is only used when the array is a multiple of 4096.)
+    const int tpb = std::min(nb2, 256);
+    for (int k = 2; k <= nb2; k <<= 1) for (int j = k >> 1; j > 0; j >>= 1) hipLaunchKernelGGL(k_bitonic_step, dim3(nb2 / tpb), dim3(tpb), 0, t_ctx->stream, a, j, k);
   } else {
     int tiles = nb2 / 4096;
     hipLaunchKernelGGL(k_bitonic_tile, dim3(tiles), dim3(1024), 0, t_ctx->stream, a, 2, 4096, 1);  // all steps with k <= 4096
