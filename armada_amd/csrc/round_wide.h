@@ -29,7 +29,9 @@
 //
 // Exactness rests on the same three facts as the stream run: the keys are the ones updatePQItem would compute (same operations, same order); the packed key
 // orders like Less for finite non-negative costs; integer accounting is order independent.  tests/test_z_wide_runs.py and `tests/soak.py wide` compare whole
-// rounds with the oracle for 65 ... 1 024 queues (CPU build and -m gpu).
+// rounds with the oracle for 65 ... 1 024 queues (CPU build and -m gpu) on seeded workloads; tests/test_z_wide_run_edges.py pins the passes on hand-built pools at their
+// edges: the rank pass (slices of W_PER, groups of W_RG, ties by a name rank that is NOT the queue index, a tying barrier), the chunked key passes (WQ_CHUNK: barriers,
+// an evicted part in front, keys that fall along a queue), the stop rules (queue and global tokens, lookback, a pool too small) and a handle going wide, few, wide.
 #pragma once
 
 enum { W_SEG = 0, W_EVSUM, W_QSUM, W_STITCH, W_PACK, W_FIX, W_RANK, W_SCATTER, W_COMMIT_E, W_COMMIT_Q, W_EXCL, W_SKIP_FIND, W_SKIP_MARK, W_EXCLF };   // (W_EXCL: not a pass of a wide run — the pass behind asched_excluded_nodes shares the op)

@@ -8,7 +8,7 @@
     python tests/soak.py optimiser 2000     # rounds with the experimental fairness optimiser on (asched_set_optimiser), incl. gangs only it can place
     python tests/soak.py market 2000        # market-driven rounds (asched_set_market): tied and distinct bids, gangs, away types, rate limits
     python tests/soak.py away 1500          # crowded rounds with a third of the running jobs cross-pool away jobs and "<queue>-away" contexts (tests/test_z_cross_pool_away.py)
-    python tests/soak.py wide 500           # more than 64 queues: wide runs (round_wide.h) — 65 ... 400 queues, evicted jobs returning, gangs, bursts, lookback limits
+    python tests/soak.py wide 500           # more than 64 queues: wide runs (round_wide.h) — 65 ... 400 queues, evicted jobs returning, gangs, bursts, lookback limits; a permuted queue name rank, per-queue tokens, in a third of the seeds runs of identical neighbouring queues (keys tie)
     python tests/soak.py hcedges 250        # tests/test_z_hc_engine_edges.py's recipe at random: 30 ... 1100 live dirty nodes, fragments used up and reopened, 1-8 queues, 0 / 1 / 2 non-indexed columns; bulk merge from 64 entries
     python tests/soak.py features 400      # tests/test_z_feature_mix.py rounds (affinity, conditional away, extra column, limits ...)
     python tests/soak.py ops 3000           # tests/test_z_nodedb_op_sequences.py NodeDb-level operation sequences
@@ -96,6 +96,28 @@ def sharded_rounds(lib, wl, fp, world):
     for e in err:
         if e is not None: raise e
     return got
+
+
+def tie_queue_runs(wl, rng):
+    """runs of 2 ... 5 neighbouring queues made identical, so that their keys tie and the queue name rank decides (tests/test_z_wide_run_edges.py family A on a seeded
+    workload): one weight, no allocation (their running jobs go to the last queue, which is in no run) and the requests and classes of the first queue's list, position by
+    position, up to the first gang member of either list"""
+    nq = wl.num_queues
+    q = 0
+    while q + 5 < nq - 1:
+        k = int(rng.integers(2, 6))
+        if rng.random() < 0.5:
+            wl.queue_weight[q:q + k] = wl.queue_weight[q]
+            wl.job_queue[(wl.job_node >= 0) & (wl.job_queue >= q) & (wl.job_queue < q + k)] = nq - 1
+            lead = wl.queued[q]
+            for o in range(q + 1, q + k):
+                ids = wl.queued[o]
+                m = min(len(ids), len(lead))
+                gang = np.nonzero((wl.job_gang[lead[:m]] >= 0) | (wl.job_gang[ids[:m]] >= 0))[0]
+                m = int(gang[0]) if len(gang) else m
+                wl.job_req[ids[:m]] = wl.job_req[lead[:m]]
+                wl.job_pc[ids[:m]] = wl.job_pc[lead[:m]]
+        q += k
 
 
 def main():
@@ -215,11 +237,16 @@ def main():
                 wl.global_burst = int(rng.choice([nj, nj // 3, 500])); wl.queue_burst = int(rng.choice([nj, max(10, 4 * nj // nq), 16])); wl.rate_inf = bool(rng.random() < 0.2)
                 if rng.random() < 0.3:
                     wl.config.max_queue_lookback = int(rng.choice([20, 200, 3000]))
+                import test_z_wide_run_edges as T   # its prepare: a name rank and tokens per queue
+                name_rank = rng.permutation(nq)
+                tokens = np.minimum(rng.choice([0, 1, 7, 8, 9, 33, 200, wl.queue_burst], size=nq), wl.queue_burst)
+                if seed % 3 == 0:
+                    tie_queue_runs(wl, rng)
                 res = []
                 for lib in (orc, hs):
-                    s = W.load(lib, wl); W.prepare(s, wl); res.append(s.schedule_round())
+                    s = W.load(lib, wl); T.prepare(s, wl, name_rank, tokens); res.append(s.schedule_round())
                     if lib is hs and os.environ.get("SOAK_STATS"):
-                        st = s.round_stats(); print(seed, nq, {k: st[k] for k in ("fast_iterations", "generic_iterations", "stream_runs", "stream_jobs")}, len(res[-1].scheduled), len(res[-1].preempted))
+                        st = s.round_stats(); print(seed, nq, seed % 3 == 0, {k: st[k] for k in ("fast_iterations", "generic_iterations", "stream_runs", "stream_jobs")}, len(res[-1].scheduled), len(res[-1].preempted))
                     s.close()
                 same_and_no_hole(wl, res)
             elif kind == "features":
