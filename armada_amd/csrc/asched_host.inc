@@ -253,7 +253,7 @@ struct asched {
   DevBufs evrBufs; EvrArgs evr; void* evrZero = nullptr; size_t evrZeroBytes = 0;   // the words the passes add into are ONE block: one memset per round
   std::vector<uint8_t> nodeUnsched;                // [N] asched_nodes.unschedulable (nodeFlags bit 0 is unschedulable && overAllocated)
   std::vector<uint8_t> evrNodePre, evrNodeReasons; std::vector<int32_t> evrNodeEvicted, evrQJobs, evrQOff, evrJob, evrNode; std::vector<int64_t> evrQRes;   // the downloaded report
-  double evrMs[3] = {0, 0, 0};                     // device ms of the three passes of the last round (ASCHED_EVR_TIMES=1; asched_round_timing)
+  double evrMs[kPassFamilies[PASS_EVR].passes] = {};                     // device ms of the three passes of the last round (ASCHED_EVR_TIMES=1; asched_round_timing)
   std::vector<int32_t> labelSlots;                 // sorted indexed label keys
   std::vector<std::vector<int32_t>> slotValues;    // per slot: sorted values present on nodes
   std::vector<int32_t> uniOffHost;
@@ -328,25 +328,25 @@ struct asched {
   // occurrence with their table, and the two minima before they are packed (INT64_MAX: no shape yet)
   bool appendInPlace = false;        // the switch: a property of the handle, survives jobs_set and nodes_upsert
   int32_t jasStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_append_shape_stats
-  double saMs[2] = {0, 0};           // device ms of the new mask rows / the row copies of the last in-place append (ASCHED_JA_TIMES=1)
+  double saMs[kPassFamilies[PASS_SA].passes] = {};           // device ms of the new mask rows / the row copies of the last in-place append (ASCHED_JA_TIMES=1)
   std::vector<uint64_t> fsDelta, fsMin; std::vector<uint8_t> fsNever; std::vector<int32_t> fitOf; std::vector<ShapeReq> fitTab;
   std::map<std::tuple<uint64_t, uint64_t, int64_t, int64_t, int32_t, int32_t>, int32_t> fitIds;
   int64_t fsMinField[MAXK] = {0}, fsMinExtra[MAXE] = {0};
   // ---- asched_req_classes_append (kernels_req_classes_append.h): new requirement classes behind the C resident ones
   int32_t caStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_req_classes_append_stats
-  double caMs[2] = {0, 0}, caHostMs[2] = {0, 0};   // device ms of the new rows / the row copies; host ms of the taint scan / the tier-2 rows of the last call (ASCHED_CA_TIMES=1)
+  double caMs[kPassFamilies[PASS_CA].passes] = {}, caHostMs[2] = {0, 0};   // device ms of the new rows / the row copies; host ms of the taint scan / the tier-2 rows of the last call (ASCHED_CA_TIMES=1)
   // ---- asched_shapes_compact (kernels_shapes_compact.h): dead shapes, fit shapes and requirement classes leave the resident tables
   int32_t scStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_shapes_compact_stats
-  double scMs[3] = {0, 0, 0}, scHostMs = 0;        // device ms of rows / gathers / class bits, host ms of the mirror remap of the last call (ASCHED_SC_TIMES=1)
-  double jaMs[3] = {0, 0, 0};        // device ms of row fill / sort / merge of the last append (ASCHED_JA_TIMES=1)
+  double scMs[kPassFamilies[PASS_SC].passes] = {}, scHostMs = 0;        // device ms of rows / gathers / class bits, host ms of the mirror remap of the last call (ASCHED_SC_TIMES=1)
+  double jaMs[kPassFamilies[PASS_JA].passes] = {};        // device ms of row fill / sort / merge of the last append (ASCHED_JA_TIMES=1)
   DevBufs jpBufs; char* jpScratch = nullptr; size_t jpScratchBytes = 0;   // the entries, the sort array and the kept list of a patch: one block, kept between calls and only ever grown
-  double jpMs[4] = {0, 0, 0, 0};     // device ms of the four passes of the last patch (ASCHED_JP_TIMES=1)
+  double jpMs[kPassFamilies[PASS_JP].passes] = {};     // device ms of the four passes of the last patch (ASCHED_JP_TIMES=1)
   int32_t jrStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_reprioritise_stats (kernels_jobs_reprioritise.h)
   int32_t jsStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_respec_stats (kernels_jobs_respec.h)
   // ---- asched_jobs_delete (kernels_jobs_delete.h).  A scheduling-key shape that lost its last row keeps its id with shapeRow[s] == -1 (an append that uses it goes
   // through the rebuild path); a gang that lost its last row keeps its dense id with no members and leaves gangMap
   int32_t jdStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_delete_stats
-  double jdMs[5] = {0, 0, 0, 0, 0};  // device ms of mark / scan / gather / order / gang lists of the last delete (ASCHED_JD_TIMES=1)
+  double jdMs[kPassFamilies[PASS_JD].passes] = {};  // device ms of mark / scan / gather / order / gang lists of the last delete (ASCHED_JD_TIMES=1)
   double jdHostMs = 0;               // wall ms of the host's compaction of its mirrors in the last delete
   // ---- asched_nodes_patch (kernels_nodes_patch.h).  What nodes_upsert was given and no other mirror holds (index, allocatable, over_allocated: N x (9 + 8R) bytes;
   // total, id_rank, unschedulable, taints and labels are nodeTotal, nodeIdRank, nodeUnsched, nodeTaints and nodeLabels above): the rebuild path of a patch runs
@@ -358,23 +358,23 @@ struct asched {
   std::vector<uint8_t> npSeen;       // [N] all zero between calls: a node named twice in one patch
   DevBufs npBufs; char* npScratch = nullptr; size_t npScratchBytes = 0;   // the entries of a patch: one block, kept between calls and only ever grown
   int32_t npStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_nodes_patch_stats
-  double npMs[2] = {0, 0};           // device ms of scatter / mask words of the last patch (ASCHED_NP_TIMES=1)
+  double npMs[kPassFamilies[PASS_NP].passes] = {};           // device ms of scatter / mask words of the last patch (ASCHED_NP_TIMES=1)
   // ---- asched_nodes_delete (kernels_nodes_delete.h).  slotValueCount: nodes that carry slotValues[s][k] — a value that loses its last node takes the rebuild path, as a
   // node type that loses its last node does (types[].numNodes).  The keep flags are a block of their own, all 1 between calls; the rest of the scratch is kept and only grown
   std::vector<std::vector<int32_t>> slotValueCount;
   DevBufs ndBufs; uint8_t* ndKeep = nullptr; size_t ndKeepCap = 0; char* ndScratch = nullptr; size_t ndScratchBytes = 0;
   std::vector<int32_t> ndMap;        // [N] the old -> new map of the last delete on the host (the remap of the jNode mirror)
   int32_t ndStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_nodes_delete_stats
-  double ndMs[7] = {0, 0, 0, 0, 0, 0, 0};   // device ms of the passes of the last delete (ASCHED_ND_TIMES=1)
+  double ndMs[kPassFamilies[PASS_ND].passes] = {};   // device ms of the passes of the last delete (ASCHED_ND_TIMES=1)
   // ---- asched_nodes_append (kernels_nodes_append.h).  The entries of an append: one block, kept between calls and only ever grown
   DevBufs naBufs; char* naScratch = nullptr; size_t naScratchBytes = 0;
   int32_t naStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_nodes_append_stats
-  double naMs[4] = {0, 0, 0, 0};     // device ms of planes / narrow arrays / index order / mask rows of the last append (ASCHED_NA_TIMES=1)
+  double naMs[kPassFamilies[PASS_NA].passes] = {};     // device ms of planes / narrow arrays / index order / mask rows of the last append (ASCHED_NA_TIMES=1)
   // ---- asched_round_prepare_resident (kernels_queued_lists.h).  The flag bytes, the prefix words, the lists and their offsets belong to the handle: sized from the
   // capacities of the job table (jobCap rows, ordCap order entries), kept across rounds and only ever grown; the held rows of a call in a block of their own
   struct { DevBufs bufs; uint8_t* flag = nullptr; uint32_t* prefix = nullptr; int32_t* list = nullptr; int32_t* off = nullptr; size_t rowCap = 0, ordCap = 0;
            DevBufs heldBufs; int32_t* held = nullptr; size_t heldCap = 0; } ql;
-  double qlMs[3] = {0, 0, 0};        // device ms of mark / hold / compact of the last round_prepare_resident (ASCHED_QL_TIMES=1)
+  double qlMs[kPassFamilies[PASS_QL].passes] = {};        // device ms of mark / hold / compact of the last round_prepare_resident (ASCHED_QL_TIMES=1)
   bool queuedValid = false; int queuedTotal = 0;   // dev.queuedOff / dev.queuedJobs are what the last round_prepare / round_prepare_resident left (asched_round_queued)
   double roundTotalMs = 0, roundControlMs = 0, roundPhaseMs[4] = {0, 0, 0, 0};   // split round: whole sequence / persistent passes / evict-1, evict-3, final bulk phases (host clock)
   int submitWideUnits = 0, submitWidePasses = 0, submitSeqUnits = 0, submitGangUnits = 0, submitNodePasses = 0, submitLitUnits = 0;   // how the last submit_check ran (submit_stats)
@@ -1643,7 +1643,7 @@ int32_t asched_jobs_patch(asched_t* h, int32_t n, const int32_t* job, const int3
   // ---- what jobs_set resets (the job table half patched).  evrSized stays, on purpose: a patch changes no size
   residentTouchJobs(h, false, true);
   Dev& d = h->dev;
-  for (int k = 0; k < 4; k++) h->jpMs[k] = 0;
+  plat_pass_clear(PASS_JP, h->jpMs);
   if (n > 0) {
     // the host mirrors (round_prepare's host aggregation path reads jNode)
     for (int i = 0; i < n; i++) {
@@ -1666,8 +1666,8 @@ int32_t asched_jobs_patch(asched_t* h, int32_t n, const int32_t* job, const int3
     int prc = plat_take_failure() ? -1 : plat_jobs_patch(d, a, keptBuf);
     if (prc) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
     if (nT > 0) { std::swap(d.ordAll, h->jp.ordSpare); std::swap(h->ordCap, h->ordSpareCap); }
-    plat_jobs_patch_ms(h->jpMs);
-    if (const char* e = getenv("ASCHED_JP_TIMES")) if (e[0] == '1')
+    plat_pass_ms(PASS_JP, h->jpMs);
+    if (plat_pass_printed(PASS_JP))
       fprintf(stderr, "[asched jobs_patch] jobs %d entries %d in the order %d: scatter %.4f ms, remove %.4f ms, sort %.4f ms, merge %.4f ms\n", M, n, nT, h->jpMs[0], h->jpMs[1], h->jpMs[2], h->jpMs[3]);
   }
   // job dynamic state: everything unbound until round_prepare, as at the end of jobs_set
@@ -1712,7 +1712,7 @@ int32_t asched_jobs_reprioritise(asched_t* h, int32_t n, const int32_t* job, con
   // ---- what jobs_set resets (the order half built).  evrSized stays, as in asched_jobs_patch and for its reason
   residentTouchJobs(h, false, true);
   Dev& d = h->dev;
-  for (int k = 0; k < 4; k++) h->jpMs[k] = 0;
+  plat_pass_clear(PASS_JP, h->jpMs);
   const bool madeResident = n > 0 && !h->jp.built;
   if (n > 0) {
     // the host mirror: jobs_append and jobs_delete stage and squeeze it, and a later first build uploads it
@@ -1730,8 +1730,8 @@ int32_t asched_jobs_reprioritise(asched_t* h, int32_t n, const int32_t* job, con
     int prc = plat_take_failure() ? -1 : plat_jobs_reprioritise(d, a, keptBuf);
     if (prc) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
     if (nT > 0) { std::swap(d.ordAll, h->jp.ordSpare); std::swap(h->ordCap, h->ordSpareCap); }
-    plat_jobs_patch_ms(h->jpMs);
-    if (const char* e = getenv("ASCHED_JP_TIMES")) if (e[0] == '1')
+    plat_pass_ms(PASS_JP, h->jpMs);
+    if (plat_pass_printed(PASS_JP))
       fprintf(stderr, "[asched jobs_reprioritise] jobs %d entries %d in the order %d: scatter %.4f ms, remove %.4f ms, sort %.4f ms, merge %.4f ms\n", M, n, nT, h->jpMs[0], h->jpMs[1], h->jpMs[2], h->jpMs[3]);
   }
   { int32_t* t = h->jrStats;
@@ -1945,7 +1945,7 @@ static int jaInPlaceApply(asched* h, JaShapes& g, char* saScratch) {
     sa.copy0 = (long long)S0 * Wm; sa.src1 = (long long)S0 * Wm; sa.dst1 = (long long)S1 * Wm; sa.copy1 = (long long)A0 * Wm;
     int src = plat_take_failure() ? -1 : plat_shapes_append(d, sa);
     if (src) return -1;
-    plat_shapes_append_ms(h->saMs);
+    plat_pass_ms(PASS_SA, h->saMs);
     h->maskBufs.release(d.shapeMask);
     d.shapeMask = g.shapeMask1;
   }
@@ -2131,8 +2131,8 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
   }
   // ---- what jobs_set resets (the job table half appended).  A new shape off the in-place path ends with rebuildMasks: the fast structure goes
   residentTouchJobs(h, newShapes && !inPlace);
-  for (int k = 0; k < 3; k++) h->jaMs[k] = 0;
-  h->saMs[0] = h->saMs[1] = 0;
+  plat_pass_clear(PASS_JA, h->jaMs);
+  plat_pass_clear(PASS_SA, h->saMs);
   scratch.adopt();
   if (m > 0) {
     // the blocks: copies and fills queued on the handle's stream, the old blocks released once they are through
@@ -2176,7 +2176,7 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
     if (nT > 0) { a.p.keys = (JpKey*)(h->jpScratch + oKeys); a.p.kept = d.ordAll; a.p.out = target; }
     int prc = plat_take_failure() ? -1 : plat_jobs_append(d, a);
     if (prc) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
-    plat_jobs_append_ms(h->jaMs);
+    plat_pass_ms(PASS_JA, h->jaMs);
     // the order buffers: the target becomes the order; the spare is the old order where that is long enough, else the second new block
     { int32_t* oldAll = d.ordAll; int32_t* oldSpare = h->jp.ordSpare;
       const size_t oldAllCap = h->ordCap, oldSpareCap = h->ordSpareCap;
@@ -2199,7 +2199,7 @@ int32_t asched_jobs_append(asched_t* h, const asched_jobs* rows) {
       }
       plat_h2d(d.ordAllOff, off.data(), off.size() * 4);
       h->ordOffHost.swap(off); h->ordQueues = Qj1; }
-    if (const char* e = getenv("ASCHED_JA_TIMES")) if (e[0] == '1')
+    if (plat_pass_printed(PASS_JA))
       fprintf(stderr, "[asched jobs_append] jobs %d rows %d in the order %d: fill %.4f ms, sort %.4f ms, merge %.4f ms; shapes in place %d: mask rows %.4f ms, row copies %.4f ms\n", M, m, nT,
               h->jaMs[0], h->jaMs[1], h->jaMs[2], inPlace ? (S1 - S0) + (int)revived.size() : 0, h->saMs[0], h->saMs[1]);
   }
@@ -2356,7 +2356,7 @@ int32_t asched_jobs_respec(asched_t* h, int32_t n, const int32_t* job, const int
   }
   // ---- what jobs_set resets (the job table half edited).  On the rebuild path the call ends with rebuildMasks: the fast structure goes
   residentTouchJobs(h, rebuild, !rebuild);
-  h->saMs[0] = h->saMs[1] = 0;
+  plat_pass_clear(PASS_SA, h->saMs);
   scratch.adopt();
   int emptied = 0, fromTpl = 0;
   if (nc > 0) {
@@ -2532,7 +2532,7 @@ int32_t asched_req_classes_append(asched_t* h, const asched_req_classes* more) {
   // ---- what jobs_set resets (the class tables half grown).  Off the in-place path the call ends with rebuildMasks: the fast structure goes
   residentTouchJobs(h, why != 0);
   memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->jsStats, 0, sizeof h->jsStats);
-  h->caMs[0] = h->caMs[1] = 0;
+  plat_pass_clear(PASS_CA, h->caMs);
   { int32_t* t = h->caStats;
     t[0] = n; t[1] = nT1; t[2] = nT2; t[3] = inPlace ? Cext0 - C0 : 0; t[4] = why ? 1 : 0; t[5] = why; t[6] = h->C; t[7] = h->Cext; }
   if (inPlace) {
@@ -2548,7 +2548,7 @@ int32_t asched_req_classes_append(asched_t* h, const asched_req_classes* more) {
     a.inMask = h->dClassMask; a.copy0 = (long long)C0 * W; a.src1 = (long long)C0 * W; a.dst1 = (long long)C1 * W; a.copy1 = (long long)(Cext0 - C0) * W;
     const int src = plat_take_failure() ? -1 : plat_req_classes_append(d, a);
     if (src) { plat_free(scratch); sb.drop(); return fail(h, ASCHED_ERR_DEVICE, plat_last_error()); }
-    plat_req_classes_append_ms(h->caMs);
+    plat_pass_ms(PASS_CA, h->caMs);
 #ifdef ASCHED_HOSTSIM
     { // the CPU build: every row decided by node type against the node-by-node match
       std::vector<uint64_t> got((size_t)n * W);
@@ -2566,7 +2566,7 @@ int32_t asched_req_classes_append(asched_t* h, const asched_req_classes* more) {
       shapeClassExt.insert(shapeClassExt.end(), h->awayRowClass.begin(), h->awayRowClass.end());
       plat_h2d(h->dShapeClass, shapeClassExt.data(), 4 * shapeClassExt.size());
     }
-    if (const char* e = getenv("ASCHED_CA_TIMES")) if (e[0] == '1')
+    if (plat_pass_printed(PASS_CA))
       fprintf(stderr, "[asched req_classes_append] nodes %d classes %d (by node type %d, on the host %d), derived rows moved %d: new rows %.4f ms, row copies %.4f ms; host: taint scan %.4f ms, host rows %.4f ms\n",
               h->N, n, nT1, nT2, Cext0 - C0, h->caMs[0], h->caMs[1], h->caHostMs[0], h->caHostMs[1]);
   }
@@ -2732,7 +2732,7 @@ int32_t asched_shapes_compact(asched_t* h, int32_t flags, int32_t* class_new_id)
   // ---- what jobs_set resets (the tables half compacted).  Off the in-place path the call ends with rebuildMasks: the fast structure goes
   residentTouchJobs(h, why != 0);
   memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->jsStats, 0, sizeof h->jsStats); memset(h->caStats, 0, sizeof h->caStats);
-  h->scMs[0] = h->scMs[1] = h->scMs[2] = 0; h->scHostMs = 0;
+  plat_pass_clear(PASS_SC, h->scMs); h->scHostMs = 0;
   if (anyDead) {
     plat_h2d(scratch, shapeNew.data(), 4 * (size_t)S0);
     if (F0 > 0) plat_h2d(scratch + oFit, fitNew.data(), 4 * (size_t)F0);
@@ -2750,7 +2750,7 @@ int32_t asched_shapes_compact(asched_t* h, int32_t flags, int32_t* class_new_id)
     }
     const int src = plat_take_failure() ? -1 : plat_shapes_compact(d, a);
     if (src) { plat_free(scratch); sb.drop(); return fail(h, ASCHED_ERR_DEVICE, plat_last_error()); }
-    plat_shapes_compact_ms(h->scMs);
+    plat_pass_ms(PASS_SC, h->scMs);
     plat_free(scratch);
     if (inPlace) {
       sb.commit();
@@ -2780,7 +2780,7 @@ int32_t asched_shapes_compact(asched_t* h, int32_t flags, int32_t* class_new_id)
       for (size_t j = lo; j < hi; j++) { h->jShape[j] = shapeNew[h->jShape[j]]; if (remapCls) h->jReqClass[j] = clsNew[h->jReqClass[j]]; }
     });
     h->scHostMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (const char* e = getenv("ASCHED_SC_TIMES")) if (e[0] == '1')
+    if (plat_pass_printed(PASS_SC))
       fprintf(stderr, "[asched shapes_compact] jobs %d shapes %d -> %d fit %d -> %d classes %d -> %d (ext %d -> %d) %s: rows %.4f ms, gathers %.4f ms, class bits %.4f ms; host mirrors %.4f ms\n",
               M, S0, S1, F0, F1, C0, C1, Cext0, Cext1, why ? "rebuild" : "in place", h->scMs[0], h->scMs[1], h->scMs[2], h->scHostMs);
   }
@@ -2875,7 +2875,7 @@ int32_t asched_jobs_delete(asched_t* h, int32_t n, const int32_t* job, int32_t* 
   }
   // ---- what jobs_set resets (the job table half compacted)
   residentTouchJobs(h);
-  for (int k = 0; k < 5; k++) h->jdMs[k] = 0;
+  plat_pass_clear(PASS_JD, h->jdMs);
   h->jdHostMs = 0;
   int gangsEmptied = 0, shapesEmptied = 0;
   if (n > 0) {
@@ -2904,7 +2904,7 @@ int32_t asched_jobs_delete(asched_t* h, int32_t n, const int32_t* job, int32_t* 
       gone.assign(M, 0);
       return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
     }
-    plat_jobs_delete_ms(h->jdMs);
+    plat_pass_ms(PASS_JD, h->jdMs);
     if (gangLen1 > 0) plat_d2d(d.gangJobs, a.gangOut, sizeof(int32_t) * (size_t)gangLen1);
     if (new_id) {   // old -> new: the scan's exclusive prefix, -1 for the rows that left
       plat_d2h(new_id, a.newId, sizeof(int32_t) * (size_t)M);
@@ -2964,7 +2964,7 @@ int32_t asched_jobs_delete(asched_t* h, int32_t n, const int32_t* job, int32_t* 
     }
     h->M = M1; d.cfg.M = M1;
     h->jdHostMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (const char* e = getenv("ASCHED_JD_TIMES")) if (e[0] == '1')
+    if (plat_pass_printed(PASS_JD))
       fprintf(stderr, "[asched jobs_delete] jobs %d entries %d in the order %d: mark %.4f ms, scan %.4f ms, gather %.4f ms, order %.4f ms, gang lists %.4f ms, host mirrors %.4f ms\n", M, n, nT,
               h->jdMs[0], h->jdMs[1], h->jdMs[2], h->jdMs[3], h->jdMs[4], h->jdHostMs);
   }
@@ -3088,7 +3088,7 @@ int32_t asched_nodes_patch(asched_t* h, const asched_nodes_patch_rows* rows) {
     in.unschedulable = uns.data(); in.over_allocated = over.data();
     in.taint_off = tOff.data(); in.taint_key = tKey.data(); in.taint_value = tVal.data(); in.taint_effect = tEff.data();
     in.label_off = lOff.data(); in.label_key = lKey.data(); in.label_value = lVal.data();
-    memset(h->npStats, 0, sizeof h->npStats); h->npMs[0] = h->npMs[1] = 0;
+    memset(h->npStats, 0, sizeof h->npStats); plat_pass_clear(PASS_NP, h->npMs);
     int rc = nodesUpsertBody(h, &in);
     if (rc) return rc;
     h->npStats[0] = n; h->npStats[1] = typeChanged; h->npStats[2] = 1; h->npStats[3] = why;
@@ -3104,7 +3104,7 @@ int32_t asched_nodes_patch(asched_t* h, const asched_nodes_patch_rows* rows) {
   if (n > 0 && !scratch.grow(need)) return fail(h, ASCHED_ERR_DEVICE, "nodes_patch: out of device memory for the patch entries; the handle is as it was");
   // ---- what nodes_upsert resets (the node table half patched: asched_nodes_upsert before anything else)
   residentTouchNodes(h);
-  memset(h->npStats, 0, sizeof h->npStats); h->npMs[0] = h->npMs[1] = 0;
+  memset(h->npStats, 0, sizeof h->npStats); plat_pass_clear(PASS_NP, h->npMs);
   h->npStats[0] = n; h->npStats[1] = typeChanged;
   if (n > 0) {
     // the host mirrors, and the totals by difference (addNodeToStats, nodedb.go:44-55)
@@ -3150,8 +3150,8 @@ int32_t asched_nodes_patch(asched_t* h, const asched_nodes_patch_rows* rows) {
     }
     int prc = plat_take_failure() ? -1 : plat_nodes_patch(d, a);
     if (prc) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
-    plat_nodes_patch_ms(h->npMs);
-    if (const char* e = getenv("ASCHED_NP_TIMES")) if (e[0] == '1')
+    plat_pass_ms(PASS_NP, h->npMs);
+    if (plat_pass_printed(PASS_NP))
       fprintf(stderr, "[asched nodes_patch] nodes %d entries %d words %d mask rows %d: scatter %.4f ms, mask words %.4f ms\n", N, n, a.nW, a.Cext + a.Sext + a.T, h->npMs[0], h->npMs[1]);
   }
   return resetDynamicState(h, M);
@@ -3280,7 +3280,7 @@ int32_t asched_nodes_delete(asched_t* h, int32_t n, const int32_t* node, int32_t
   }
   // ---- what nodes_upsert resets (the tables half compacted: asched_nodes_upsert and asched_jobs_set before anything else)
   residentTouchNodes(h);
-  memset(h->ndStats, 0, sizeof h->ndStats); for (int k = 0; k < 7; k++) h->ndMs[k] = 0;
+  memset(h->ndStats, 0, sizeof h->ndStats); plat_pass_clear(PASS_ND, h->ndMs);
   int renumbered = 0;
   if (n > 0) {
     sb.fill();
@@ -3305,7 +3305,7 @@ int32_t asched_nodes_delete(asched_t* h, int32_t n, const int32_t* node, int32_t
       h->ndBufs.freeAll(); h->ndKeep = nullptr; h->ndKeepCap = 0; h->ndScratch = nullptr; h->ndScratchBytes = 0;
       return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
     }
-    plat_nodes_delete_ms(h->ndMs);
+    plat_pass_ms(PASS_ND, h->ndMs);
     // the old -> new map on the host: the scan's exclusive prefix, -1 for the rows that left
     h->ndMap.resize(N);
     plat_d2h(h->ndMap.data(), a.newId, sizeof(int32_t) * (size_t)N);
@@ -3361,7 +3361,7 @@ int32_t asched_nodes_delete(asched_t* h, int32_t n, const int32_t* node, int32_t
       if (haveFast) d.fitW = (N1 + 63) / 64;
       if (h->jobsSet) exclSetup(h);   // (the [cap][W] bit rows of the failed-selection store: B_RESET_JOBS forgets the records anyway)
     }
-    if (const char* e = getenv("ASCHED_ND_TIMES")) if (e[0] == '1')
+    if (plat_pass_printed(PASS_ND))
       fprintf(stderr, "[asched nodes_delete] nodes %d entries %d jobs %d mask rows %d path %s: mark + check %.4f ms, scan %.4f ms, gather %.4f ms, index order %.4f ms, mask rows %.4f ms, job remap %.4f ms, unmark %.4f ms\n",
               N, n, M, a.rows[0] + a.rows[1] + a.rows[2] + a.rows[3], why ? "rebuild" : "device", h->ndMs[0], h->ndMs[1], h->ndMs[2], h->ndMs[3], h->ndMs[4], h->ndMs[5], h->ndMs[6]);
   }
@@ -3538,7 +3538,7 @@ int32_t asched_nodes_append(asched_t* h, const asched_nodes_append_rows* rows) {
     in.unschedulable = uns.data(); in.over_allocated = over.data();
     in.taint_off = tOff.data(); in.taint_key = tKey.data(); in.taint_value = tVal.data(); in.taint_effect = tEff.data();
     in.label_off = lOff.data(); in.label_key = lKey.data(); in.label_value = lVal.data();
-    memset(h->naStats, 0, sizeof h->naStats); for (int k = 0; k < 4; k++) h->naMs[k] = 0;
+    memset(h->naStats, 0, sizeof h->naStats); plat_pass_clear(PASS_NA, h->naMs);
     memset(h->npStats, 0, sizeof h->npStats); memset(h->ndStats, 0, sizeof h->ndStats);
     int rc = nodesUpsertBody(h, &in);
     if (rc) return rc;
@@ -3592,7 +3592,7 @@ int32_t asched_nodes_append(asched_t* h, const asched_nodes_append_rows* rows) {
   prof.lap("allocations");
   // ---- what nodes_upsert resets (the handle between two tables: asched_nodes_upsert before anything else)
   residentTouchNodes(h);
-  memset(h->naStats, 0, sizeof h->naStats); for (int k = 0; k < 4; k++) h->naMs[k] = 0;
+  memset(h->naStats, 0, sizeof h->naStats); plat_pass_clear(PASS_NA, h->naMs);
   memset(h->npStats, 0, sizeof h->npStats); memset(h->ndStats, 0, sizeof h->ndStats);
   if (m > 0) {
     // the host mirrors first (classMatchesNode reads them); the totals and the counts by addition (addNodeToStats, nodedb.go:44-55)
@@ -3656,7 +3656,7 @@ int32_t asched_nodes_append(asched_t* h, const asched_nodes_append_rows* rows) {
       sb.drop();
       return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
     }
-    plat_nodes_append_ms(h->naMs);
+    plat_pass_ms(PASS_NA, h->naMs);
     prof.lap("memsets and the passes");
     // the blocks swapped in, the old ones released (plat_nodes_append has waited for the device); the node-indexed scratch that stays gets the start a fresh upload gives it
     sb.commit();
@@ -3665,7 +3665,7 @@ int32_t asched_nodes_append(asched_t* h, const asched_nodes_append_rows* rows) {
     if (haveFast) d.fitW = (N1 + 63) / 64;
     if (h->jobsSet) exclSetup(h);   // (the [cap][W] bit rows of the failed-selection store: B_RESET_JOBS forgets the records anyway)
     prof.lap("releases and exclSetup");
-    if (const char* e = getenv("ASCHED_NA_TIMES")) if (e[0] == '1')
+    if (plat_pass_printed(PASS_NA))
       fprintf(stderr, "[asched nodes_append] nodes %d entries %d mask rows %d fresh blocks %zu: planes %.4f ms, narrow arrays %.4f ms, index order %.4f ms, mask rows %.4f ms\n",
               N, m, a.rows[0] + a.rows[1] + a.rows[2] + a.rows[3], sb.blocks.size(), h->naMs[0], h->naMs[1], h->naMs[2], h->naMs[3]);
   }
@@ -4334,8 +4334,8 @@ static int deriveQueuedLists(asched* h, int Q, int32_t nHeld, const int32_t* hel
   a.vec = (((uintptr_t)d.jNode0 | (uintptr_t)d.jQueue) & 15) == 0;
   if (plat_take_failure() || plat_queued_lists(d, a, ordTotal, ql.list, ql.prefix, ql.off, total)) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
   d.queuedOff = ql.off; d.queuedJobs = ql.list;
-  plat_queued_lists_ms(h->qlMs);
-  if (const char* e = getenv("ASCHED_QL_TIMES")) if (e[0] == '1')
+  plat_pass_ms(PASS_QL, h->qlMs);
+  if (plat_pass_printed(PASS_QL))
     fprintf(stderr, "[asched round_prepare_resident] rows %d order entries %d queues %d held %d queued %d: mark %.4f ms, hold %.4f ms, compact %.4f ms\n",
             M, ordTotal, Q, a.nHeld, *total, h->qlMs[0], h->qlMs[1], h->qlMs[2]);
   return 0;
@@ -4920,7 +4920,7 @@ int32_t asched_schedule_round(asched_t* h, asched_round_result* out) { if (!h) r
     int rc = runRoundSplit(h, io);
     if (rc) return rc;
     h->roundMs = h->roundTotalMs;
-    if (report) { h->evrState = asched::EVR_VALID; plat_evict_report_ms(h->evrMs); }
+    if (report) { h->evrState = asched::EVR_VALID; plat_pass_ms(PASS_EVR, h->evrMs); }
   }
   return downloadResult(h, out, io);
 }
@@ -5138,7 +5138,7 @@ int32_t asched_round_evictor_report(asched_t* h, asched_evictor_report* out) { i
   out->node_preemptible = h->evrNodePre.data(); out->node_reasons = h->evrNodeReasons.data(); out->node_evicted_jobs = h->evrNodeEvicted.data();
   out->queue_evicted_jobs = h->evrQJobs.data(); out->queue_evicted_resources = h->evrQRes.data(); out->queue_evicted_off = h->evrQOff.data();
   out->evicted_job = h->evrJob.data(); out->evicted_node = h->evrNode.data();
-  if (const char* e = getenv("ASCHED_EVR_TIMES")) if (e[0] == '1')
+  if (plat_pass_printed(PASS_EVR))
     fprintf(stderr, "[asched evict_report] nodes %d jobs %d evicted %d: job pass %.4f ms, node pass %.4f ms, queue pass %.4f ms\n", a.N, a.M, a.n1, h->evrMs[0], h->evrMs[1], h->evrMs[2]);
   return 0;
 }

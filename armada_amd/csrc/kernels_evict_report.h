@@ -119,5 +119,4 @@ static int plat_evict_report(Dev& d, const EvrArgs& a, int pass) {
   t_ctx->launches++;
   return 0;
 }
-static void plat_evict_report_ms(double* out) { out[0] = out[1] = out[2] = 0; }
 #endif

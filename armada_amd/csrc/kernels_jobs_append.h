@@ -74,7 +74,6 @@ static int plat_jobs_append(Dev& d, JaArgs& a) {
   }
   return 0;
 }
-static void plat_jobs_append_ms(double* out) { out[0] = out[1] = out[2] = 0; }
 // (plat.h's device-to-device copy, which only the append uses: the CPU build's other stand-ins sit in tests/hostsim/hostsim.cpp, and this one belongs beside plat_h2d there)
 static void plat_d2d(void* dst, const void* src, size_t n) { memcpy(dst, src, n); }
 #endif

@@ -93,5 +93,4 @@ static int plat_jobs_delete(Dev& d, JdArgs& a) {
   for (int i = 0; i < a.n; i++) jdMark(a, i, 1);
   return 0;
 }
-static void plat_jobs_delete_ms(double* out) { for (int k = 0; k < 5; k++) out[k] = 0; }
 #endif

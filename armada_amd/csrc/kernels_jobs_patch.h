@@ -135,5 +135,4 @@ static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf) {
   for (int i = 0; i < a.nb2; i++) jpScatter(d, a, i);
   return plat_jobs_reseat(d, a, keptBuf);
 }
-static void plat_jobs_patch_ms(double* out) { out[0] = out[1] = out[2] = out[3] = 0; }
 #endif

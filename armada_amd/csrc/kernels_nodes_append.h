@@ -116,5 +116,4 @@ static int plat_nodes_append(Dev& d, NaArgs& a) {
   for (long long t = 0; t < rows * a.W1; t++) naMaskWord(a, t);
   return 0;
 }
-static void plat_nodes_append_ms(double* out) { for (int k = 0; k < 4; k++) out[k] = 0; }
 #endif

@@ -121,5 +121,4 @@ static int plat_nodes_delete(Dev& d, NdArgs& a) {
   for (int i = 0; i < a.n; i++) ndMark(a, i, 1);
   return 0;
 }
-static void plat_nodes_delete_ms(double* out) { for (int k = 0; k < 7; k++) out[k] = 0; }
 #endif

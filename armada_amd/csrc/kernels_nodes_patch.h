@@ -76,5 +76,4 @@ static int plat_nodes_patch(Dev& d, const NpArgs& a) {
   for (long long t = 0; t < work; t++) npMaskWord(d, a, t);
   return 0;
 }
-static void plat_nodes_patch_ms(double* out) { out[0] = out[1] = 0; }
 #endif

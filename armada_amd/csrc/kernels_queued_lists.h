@@ -56,5 +56,4 @@ static int plat_queued_lists(Dev& d, const QlArgs& a, int ordTotal, int32_t* lis
   for (int i = 0; i < a.nHeld; i++) qlHold(a, i);
   return plat_compact(d, d.ordAll, ordTotal, a.flag, list, prefix, d.ordAllOff, a.Q, off, total);
 }
-static void plat_queued_lists_ms(double* out) { for (int k = 0; k < 3; k++) out[k] = 0; }
 #endif

@@ -61,5 +61,4 @@ static int plat_req_classes_append(Dev& d, CaArgs& a) {
   }
   return 0;
 }
-static void plat_req_classes_append_ms(double* out) { out[0] = out[1] = 0; }
 #endif

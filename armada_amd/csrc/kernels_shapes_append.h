@@ -62,5 +62,4 @@ static int plat_shapes_append(Dev& d, SaArgs& a) {
     }
   return 0;
 }
-static void plat_shapes_append_ms(double* out) { out[0] = out[1] = 0; }
 #endif

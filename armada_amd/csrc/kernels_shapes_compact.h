@@ -90,5 +90,4 @@ static int plat_shapes_compact(Dev& d, ScArgs& a) {
   if (a.nodeCls) for (int n = 0; n < a.N; n++) { const uint64_t v = scClsBits(a.nodeCls[n], a.liveCls); if (v != a.nodeCls[n]) a.nodeCls[n] = v; }
   return 0;
 }
-static void plat_shapes_compact_ms(double* out) { out[0] = out[1] = out[2] = 0; }
 #endif

@@ -1,10 +1,11 @@
-// plat.h — the platform interface asched_host.inc is written against: declarations only.  Two implementations, each linked by name inside the one
+// plat.h — the platform interface asched_host.inc is written against: declarations, and the table of the measurement hooks.  Two implementations, each linked by name inside the one
 // translation unit that includes asched_host.inc: plat_hip.inc (the product: HIP streams, kernel launches, RCCL) and tests/hostsim/hostsim.cpp (the CPU
 // build of the tests: serial loops over the same per-element device functions).  PlatCtx is defined per build.  Default arguments live here only.
 // Included after the control code (round_run.h, round_opt.h, round_price.h: Dev, MktDev, OptArgs, PriceArgs, asched_allreduce_fn) and before the definitions.
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
 #include <string>
 #include <vector>
 #include "round_opt.h"
@@ -86,14 +87,44 @@ static int plat_preempt_join(Dev& d, const PjArgs& a);
 // the round's other launches: nothing is waited for.  A pass over no elements (no jobs, no nodes) is not launched.  The CPU build's definition sits in kernels_evict_report.h.
 struct EvrArgs;
 static int plat_evict_report(Dev& d, const EvrArgs& a, int pass);
-static void plat_evict_report_ms(double* out /*[3]*/);   // measurement hook: device ms of the passes of the last round (events around them when ASCHED_EVR_TIMES=1, else zeros)
+// ---- measurement hooks: the device ms of the passes of the calls below.  A family is switched on by its environment variable (= 1, read once per process); the
+// HIP build then puts events around the family's passes and plat_pass_ms(family, out) gives out[0 .. passes) of the last call of the entered context, zeros for a
+// call that ran no pass or did not end well; without the variable, and in the CPU build, zeros.  plat_pass_printed: asched_host.inc prints the family's line.
+enum PassLayout { PASS_SEQ, PASS_REV, PASS_PAIRS };   // out[k] is between events k and k + 1 / the same with out[] in reverse order / between events 2k and 2k + 1, each pass with a flag of its own
+enum PassFamily {
+  PASS_EVR,   // the evictor report: job pass / node pass / queue pass of the last round (read once the round is over)
+  PASS_JP,    // plat_jobs_patch and plat_jobs_reprioritise: scatter / remove / sort / merge
+  PASS_JA,    // plat_jobs_append: row fill / sort / merge
+  PASS_SA,    // plat_shapes_append: the new mask rows / the row copies
+  PASS_CA,    // plat_req_classes_append: the new rows / the row copies
+  PASS_SC,    // plat_shapes_compact: rows / gathers / class bits
+  PASS_JD,    // plat_jobs_delete: mark / scan / gather / order / gang lists
+  PASS_NP,    // plat_nodes_patch: scatter / mask words
+  PASS_ND,    // plat_nodes_delete_check + plat_nodes_delete: mark + check / scan / gather / index order / mask rows / job remap / unmark
+  PASS_NA,    // plat_nodes_append: planes / narrow arrays / index order / mask rows
+  PASS_QL,    // plat_queued_lists: mark / hold / compact
+  PASS_FAMILIES
+};
+struct PassFamilyInfo { const char* env; int passes; PassLayout layout; };
+static constexpr PassFamilyInfo kPassFamilies[PASS_FAMILIES] = {
+  {"ASCHED_EVR_TIMES", 3, PASS_PAIRS}, {"ASCHED_JP_TIMES", 4, PASS_SEQ}, {"ASCHED_JA_TIMES", 3, PASS_SEQ}, {"ASCHED_JA_TIMES", 2, PASS_REV}, {"ASCHED_CA_TIMES", 2, PASS_REV},
+  {"ASCHED_SC_TIMES", 3, PASS_SEQ}, {"ASCHED_JD_TIMES", 5, PASS_SEQ}, {"ASCHED_NP_TIMES", 2, PASS_SEQ}, {"ASCHED_ND_TIMES", 7, PASS_SEQ}, {"ASCHED_NA_TIMES", 4, PASS_SEQ},
+  {"ASCHED_QL_TIMES", 3, PASS_SEQ},
+};
+static void plat_pass_ms(PassFamily f, double* out /*[kPassFamilies[f].passes]*/);
+static inline bool plat_pass_printed(PassFamily f) { const char* e = getenv(kPassFamilies[f].env); return e && e[0] == '1'; }
+static inline void plat_pass_clear(PassFamily f, double* ms) { for (int k = 0; k < kPassFamilies[f].passes; k++) ms[k] = 0; }   // (a call that runs no pass reports zeros)
+#ifdef ASCHED_HOSTSIM
+// the CPU build's one definition: no device, every pass time is zero.  It sits here, not in tests/hostsim/hostsim.cpp, so that a CPU build made from an older
+// tests/ tree (which has no such definition) still links against this layer
+static void plat_pass_ms(PassFamily f, double* out) { plat_pass_clear(f, out); }
+#endif
 // the run-state patch of the resident job table (kernels_jobs_patch.h): scatter + keys, remove (plat_compact into keptBuf [a.total]), sort, merge by rank into a.out;
 // fills a.kept / a.nKept.  Synchronous: the new order is complete on return.  The CPU build's definition sits in kernels_jobs_patch.h.
 struct JpArgs;
 static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf);
-static void plat_jobs_patch_ms(double* out /*[4]*/);   // measurement hook: device ms of scatter / remove / sort / merge of the last call (events around them when ASCHED_JP_TIMES=1, else zeros)
 // queue priorities of resident jobs change (kernels_jobs_reprioritise.h): its scatter + keys, then the patch's remove, sort and merge by rank into a.p.out; fills
-// a.p.kept / a.p.nKept.  Synchronous: the new order is complete on return; plat_jobs_patch_ms reports its passes.  The CPU build's definition sits in kernels_jobs_reprioritise.h.
+// a.p.kept / a.p.nKept.  Synchronous: the new order is complete on return; PASS_JP reports its passes.  The CPU build's definition sits in kernels_jobs_reprioritise.h.
 struct JrArgs;
 static int plat_jobs_reprioritise(Dev& d, JrArgs& a, int32_t* keptBuf);
 // retried jobs change class and request in place (kernels_jobs_respec.h): one scatter over the entries — shape, request words, grid flag and JobRec of each named row.
@@ -104,36 +135,30 @@ static int plat_jobs_respec(Dev& d, JsArgs& a);
 // sorted new keys into a.p.out.  Synchronous: rows and order are complete on return.  The CPU build's definition sits in kernels_jobs_append.h.
 struct JaArgs;
 static int plat_jobs_append(Dev& d, JaArgs& a);
-static void plat_jobs_append_ms(double* out /*[3]*/);   // measurement hook: device ms of row fill / sort / merge of the last call (events around them when ASCHED_JA_TIMES=1, else zeros)
 // new scheduling-key shapes join the shape mask (kernels_shapes_append.h): the resident rows copied device to device into the fresh block a.outMask, then the new rows,
 // one wave per 64-node word.  Synchronous: the fresh block is complete on return; nothing the handle points to is written.  The CPU build's definition sits in
 // kernels_shapes_append.h.
 struct SaArgs;
 static int plat_shapes_append(Dev& d, SaArgs& a);
-static void plat_shapes_append_ms(double* out /*[2]*/);   // measurement hook: device ms of the new mask rows / the row copies of the last call (events around them when ASCHED_JA_TIMES=1, else zeros)
 // new requirement classes join the class mask (kernels_req_classes_append.h): the resident rows copied device to device into the fresh block a.outMask (the derived
 // classes' rows dC rows further up), then the new rows and, where a.nodeCls is given, the new bits of every node, one wave per 64-node word.  Synchronous: the fresh
 // block is complete on return; of what the handle points to only a.nodeCls is written.  The CPU build's definition sits in kernels_req_classes_append.h.
 struct CaArgs;
 static int plat_req_classes_append(Dev& d, CaArgs& a);
-static void plat_req_classes_append_ms(double* out /*[2]*/);   // measurement hook: device ms of the new rows / the row copies of the last call (events around them when ASCHED_CA_TIMES=1, else zeros)
 // dead shapes and classes leave the resident tables (kernels_shapes_compact.h): the remap of a.jShape and the job records in place, the gathers of the mask rows into
 // the fresh blocks a.shapeOut / a.clsOut, the bit compaction of a.nodeCls in place.  Synchronous: everything is complete on return.  The CPU build's definition sits
 // in kernels_shapes_compact.h.
 struct ScArgs;
 static int plat_shapes_compact(Dev& d, ScArgs& a);
-static void plat_shapes_compact_ms(double* out /*[3]*/);   // measurement hook: device ms of rows / gathers / class bits of the last call (events around them when ASCHED_SC_TIMES=1, else zeros)
 // rows leave the resident job table (kernels_jobs_delete.h): mark, scan (plat_compact over the keep flags into a.src / a.newId; its count must be a.M1), the gather of the
 // static per-job arrays into the blocks of a.out*, the compaction and renumbering of the order (a.ordOut) and of the gang lists (a.gangOut), unmark.  Synchronous: everything
 // is complete on return.  The CPU build's definition sits in kernels_jobs_delete.h.
 struct JdArgs;
 static int plat_jobs_delete(Dev& d, JdArgs& a);
-static void plat_jobs_delete_ms(double* out /*[5]*/);   // measurement hook: device ms of mark / scan / gather / order / gang lists of the last call (events around them when ASCHED_JD_TIMES=1, else zeros)
 // cordons and capacity changes of resident nodes (kernels_nodes_patch.h): the scatter of the entries, then the touched words of the class, shape and type masks.
 // Synchronous: node arrays and masks are complete on return.  The CPU build's definition sits in kernels_nodes_patch.h.
 struct NpArgs;
 static int plat_nodes_patch(Dev& d, const NpArgs& a);
-static void plat_nodes_patch_ms(double* out /*[2]*/);   // measurement hook: device ms of scatter / mask words of the last call (events around them when ASCHED_NP_TIMES=1, else zeros)
 // rows leave the resident node table (kernels_nodes_delete.h).  plat_nodes_delete_check: mark, then the check of the running jobs; *bad is the lowest job row that runs on
 // a named node or ND_NONE, and in the first case the flags are set again: nothing else was written.  plat_nodes_delete: the scan (its count must be a.N1), the gathers
 // into the blocks of a.out*, the index order, the mask rows, the remap of the running jobs' nodes, unmark.  Synchronous: everything is complete on return.  The CPU
@@ -141,18 +166,15 @@ static void plat_nodes_patch_ms(double* out /*[2]*/);   // measurement hook: dev
 struct NdArgs;
 static int plat_nodes_delete_check(Dev& d, NdArgs& a, int32_t* bad);
 static int plat_nodes_delete(Dev& d, NdArgs& a);
-static void plat_nodes_delete_ms(double* out /*[7]*/);   // measurement hook: device ms of mark + check / scan / gather / index order / mask rows / job remap / unmark of the last call (events around them when ASCHED_ND_TIMES=1, else zeros)
 // new rows join the resident node table (kernels_nodes_append.h): the planes, the narrow arrays, the merge of the index order and the mask rows, all into the fresh
 // blocks of a.out*; nothing the handle points to is written.  Synchronous: everything is complete on return.  The CPU build's definition sits in kernels_nodes_append.h.
 struct NaArgs;
 static int plat_nodes_append(Dev& d, NaArgs& a);
-static void plat_nodes_append_ms(double* out /*[4]*/);   // measurement hook: device ms of planes / narrow arrays / index order / mask rows of the last call (events around them when ASCHED_NA_TIMES=1, else zeros)
 // the queued lists of a round from the resident job order (kernels_queued_lists.h): mark (a flag byte per row of a.flag), hold (the rows of a.held cleared), then
 // plat_compact of dev.ordAll[0, ordTotal) by the flags with dev.ordAllOff as segment offsets: list [total], prefix [ordTotal] scratch, off [a.Q + 1], all platform memory.
 // *total is on the host on return.  The CPU build's definition sits in kernels_queued_lists.h.
 struct QlArgs;
 static int plat_queued_lists(Dev& d, const QlArgs& a, int ordTotal, int32_t* list, uint32_t* prefix, int32_t* off, int* total);
-static void plat_queued_lists_ms(double* out /*[3]*/);   // measurement hook: device ms of mark / hold / compact of the last call (events around them when ASCHED_QL_TIMES=1, else zeros)
 static int plat_run_fit_capacity(Dev& d, const std::vector<int32_t>& shapes, std::vector<int32_t>& firstNode, std::vector<long long>& capacity, const int32_t* nodeByRankHost);
 static int plat_run_submit_gangs(Dev& d, const std::vector<int32_t>& off, const std::vector<int32_t>& jobs, std::vector<int32_t>& out);
 static double plat_last_fit_ms();

@@ -2,6 +2,7 @@
 // helper mailbox, cancel word), the run-time RCCL binding and exchange areas, memory and copies, and every kernel launch.  Host code only.  Included by
 // armada_sched.hip after the kernels it launches (round_kernel.h, k_control, kernels_*.h) and after plat.h; the other code objects' kernels are reached
 // through the hidden extern "C" launch wrappers declared here.  tests/hostsim/hostsim.cpp implements the same plat.h serially for the CPU build.
+#include <atomic>
 #include <chrono>
 #include <cstring>
 #include <string>
@@ -16,6 +17,15 @@
 // Every ABI entry starts with plat_enter(handle context): hipSetDevice for the calling thread (the current device is thread-local in HIP,
 // and a goroutine may run on any OS thread) and the thread-local pointer the plat_* helpers below work on.
 struct HelpBox;
+// one per family of plat.h's kPassFamilies: the events are created at the first timed call of the handle and destroyed in plat_close
+constexpr int PASS_MAX_EVENTS = 8;
+constexpr int passEvents(int f) { return kPassFamilies[f].layout == PASS_PAIRS ? 2 * kPassFamilies[f].passes : kPassFamilies[f].passes + 1; }
+constexpr bool passEventsFit() { for (int f = 0; f < PASS_FAMILIES; f++) if (passEvents(f) > PASS_MAX_EVENTS) return false; return true; }
+static_assert(passEventsFit(), "a family of kPassFamilies records more events than a PassTimer holds");
+struct PassTimer {
+  hipEvent_t ev[PASS_MAX_EVENTS] = {};
+  unsigned timed = 0;   // bit 0: the last call ran to its end with events around its passes (PASS_PAIRS: bit k, for pass k of the last round)
+};
 struct PlatCtx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -31,17 +41,7 @@ struct PlatCtx {
   bool inRound = false;             // between plat_round_begin / plat_round_end: the deadline runs from the begin, the cancel word is consumed at the end
   std::chrono::steady_clock::time_point roundT0;
   hipEvent_t rEv0 = nullptr, rEv1 = nullptr;
-  hipEvent_t evrEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool evrTimed[3] = {false, false, false};   // ASCHED_EVR_TIMES=1: around the passes of the evictor report
-  hipEvent_t jaEv[4] = {nullptr, nullptr, nullptr, nullptr}; bool jaTimed = false;   // ASCHED_JA_TIMES=1: around the passes of the job-table append
-  hipEvent_t saEv[3] = {nullptr, nullptr, nullptr}; bool saTimed = false;   // ASCHED_JA_TIMES=1: around the row copies and the mask rows of an in-place append of new shapes
-  hipEvent_t caEv[3] = {nullptr, nullptr, nullptr}; bool caTimed = false;   // ASCHED_CA_TIMES=1: around the row copies and the new rows of asched_req_classes_append
-  hipEvent_t scEv[4] = {nullptr, nullptr, nullptr, nullptr}; bool scTimed = false;   // ASCHED_SC_TIMES=1: around the passes of asched_shapes_compact
-  hipEvent_t jpEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool jpTimed = false;  // ASCHED_JP_TIMES=1: around the passes of the job-table patch
-  hipEvent_t ndEv[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool ndTimed = false;   // ASCHED_ND_TIMES=1: around the passes of the node-table delete
-  hipEvent_t naEv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; bool naTimed = false;   // ASCHED_NA_TIMES=1: around the passes of the node-table append
-  hipEvent_t jdEv[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; bool jdTimed = false;   // ASCHED_JD_TIMES=1: around the passes of the job-table delete
-  hipEvent_t npEv[3] = {nullptr, nullptr, nullptr}; bool npTimed = false;   // ASCHED_NP_TIMES=1: around the passes of the node-table patch
-  hipEvent_t qlEv[4] = {nullptr, nullptr, nullptr, nullptr}; bool qlTimed = false;   // ASCHED_QL_TIMES=1: around the passes that derive the queued lists
+  PassTimer pass[PASS_FAMILIES];   // ASCHED_*_TIMES=1: the events around the passes of the table calls and of the evictor report, and which of them the last call timed
   float roundTotalMs = 0.f, roundControlMs = 0.f; int roundLaunches = 0;
   int32_t* cmpScratch = nullptr; size_t cmpScratchInts = 0;   // block counts + total of the grid-wide compaction
   int optIndexN = -1, optIndexM = -1;   // sizes the optimiser's node -> jobs index in the scratch was built for (asched_host.inc decides when it may be reused)
@@ -257,17 +257,7 @@ static void plat_close(PlatCtx* c) {
   plat_comm_destroy_ctx(c);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   for (hipEvent_t e : {c->ev0, c->ev1, c->fitEv0, c->fitEv1, c->litEvMid, c->rEv0, c->rEv1}) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->evrEv) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->jpEv) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->jaEv) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->saEv) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->caEv) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->scEv) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->npEv) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->jdEv) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->ndEv) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->naEv) if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->qlEv) if (e) (void)hipEventDestroy(e);
+  for (PassTimer& t : c->pass) for (hipEvent_t e : t.ev) if (e) (void)hipEventDestroy(e);
   if (c->helpBox) (void)hipFree(c->helpBox);
   if (c->cmpScratch) (void)hipFree(c->cmpScratch);
   if (c->optScratch) (void)hipFree(c->optScratch);
@@ -843,6 +833,42 @@ static int plat_run_fit_batch_lit(Dev& d, const int32_t* nodeType, int nTypes, c
   if (const char* e = getenv("ASCHED_FIT_LIT_TIMES")) if (e[0] == '1') fprintf(stderr, "[asched fit_lit] nodes %d queries %d level %d: index build %.4f ms, query %.4f ms\n", N, nq, level, (double)buildMs, (double)queryMs);
   return 0;
 }
+// ---- the pass timer of plat.h's measurement hooks (kPassFamilies), and the end every table call shares
+// A family's variable is read at the first call of the family in the process.  passBegin: the family's events, created at the first timed call of the handle, or nullptr
+// when the family is off or an event could not be created (that call runs untimed: the events that exist stay, nothing is latched); it clears the timed flag, so a
+// call that returns early reports zeros.  Untimed, a call pays one null test per passRecord and issues no HIP call of the timer's.
+static bool passTimesOn(int f) {
+  static std::atomic<signed char> on[PASS_FAMILIES];   // 0: not read yet, 1: off, 2: on
+  signed char v = on[f].load(std::memory_order_relaxed);
+  if (!v) { v = plat_pass_printed((PassFamily)f) ? 2 : 1; on[f].store(v, std::memory_order_relaxed); }
+  return v == 2;
+}
+static hipEvent_t* passBegin(int f, int pass = 0) {
+  PassTimer& t = t_ctx->pass[f];
+  t.timed &= ~(1u << pass);
+  if (!passTimesOn(f)) return nullptr;
+  const int n = passEvents(f);
+  if (!t.ev[n - 1]) for (int i = 0; i < n; i++) if (!t.ev[i] && hipEventCreate(&t.ev[i]) != hipSuccess) { t.ev[i] = nullptr; return nullptr; }
+  return t.ev;
+}
+static inline void passRecord(hipEvent_t* ev, int i, hipStream_t st) { if (ev) (void)hipEventRecord(ev[i], st); }
+static inline void passTimed(int f, hipEvent_t* ev, int pass = 0) { if (ev) t_ctx->pass[f].timed |= 1u << pass; }
+static void plat_pass_ms(PassFamily f, double* out) {
+  const PassFamilyInfo& fam = kPassFamilies[f]; const PassTimer& t = t_ctx->pass[f];
+  for (int k = 0; k < fam.passes; k++) {
+    const int e = fam.layout == PASS_PAIRS ? 2 * k : fam.layout == PASS_REV ? fam.passes - 1 - k : k, bit = fam.layout == PASS_PAIRS ? k : 0;
+    float ms = 0.f; if (((t.timed >> bit) & 1) && hipEventElapsedTime(&ms, t.ev[e], t.ev[e + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
+}
+// the end of a synchronous call: the last launch error ("<k> launch"), the wait for the stream ("<k>"), "<failed> launch failed" where nothing said more, and the family's
+// timed flag (f < 0: the call has no timer)
+static int launchTail(bool ok, const char* k, const char* failed, int f = -1, hipEvent_t* ev = nullptr) {
+  PlatCtx* c = t_ctx;
+  if (ok) { const hipError_t e = hipGetLastError(); if (e != hipSuccess) ok = hipOk(e, (std::string(k) + " launch").c_str()); }
+  if (ok) { const hipError_t e = hipStreamSynchronize(c->stream); if (e != hipSuccess) ok = hipOk(e, k); }
+  if (!ok) { if (c->err.empty()) c->err = std::string(failed) + " launch failed"; return -1; }
+  if (f >= 0) passTimed(f, ev);
+  return 0;
+}
 // the preemption-cause join (kernels_preempt_join.h; kernels in armada_sched_mgpu.hip).  ASCHED_PJOIN_TIMES=1 prints the device time of every call (tools/probe_preemption_causes.py).
 #include "kernels_preempt_join.h"
 extern "C" int asched_internal_preempt_join(const Dev* d, const PjArgs* a, hipStream_t s);
@@ -852,318 +878,170 @@ static int plat_preempt_join(Dev& d, const PjArgs& a) {
   (void)hipEventRecord(c->fitEv0, st);
   bool ok = asched_internal_preempt_join(&d, &a, st) == 0;
   (void)hipEventRecord(c->fitEv1, st);
-  ok = ok && hipOk(hipGetLastError(), "k_pj launch") && hipOk(hipStreamSynchronize(st), "k_pj");
-  if (!ok) { if (c->err.empty()) c->err = "k_pj launch failed"; return -1; }
+  if (launchTail(ok, "k_pj", "k_pj")) return -1;
   (void)hipEventElapsedTime(&c->lastFitMs, c->fitEv0, c->fitEv1);
   if (const char* e = getenv("ASCHED_PJOIN_TIMES")) if (e[0] == '1') fprintf(stderr, "[asched preempt_join] nodes %d scheduled %d preempted %d: %.4f ms\n", a.N, a.ns, a.np, (double)c->lastFitMs);
   return 0;
 }
-// the evictor report of a round's phase 1 (kernels_evict_report.h; kernels in armada_sched_mgpu.hip): one launch per pass on the round's stream.  ASCHED_EVR_TIMES=1 puts
-// a pair of events around every pass; plat_evict_report_ms reads them once the round is over (tools/probe_evictor_report.py).
+// the evictor report of a round's phase 1 (kernels_evict_report.h; kernels in armada_sched_mgpu.hip): one launch per pass on the round's stream.  PASS_EVR puts a pair
+// of events around every pass, with a flag per pass; they are read once the round is over (tools/probe_evictor_report.py).
 #include "kernels_evict_report.h"
 extern "C" int asched_internal_evict_report(const Dev* d, const EvrArgs* a, int pass, hipStream_t s);
-static hipEvent_t* evrEvents() {
-  static const bool on = [] { const char* e = getenv("ASCHED_EVR_TIMES"); return e && e[0] == '1'; }();
-  PlatCtx* c = t_ctx;
-  if (!on) return nullptr;
-  if (!c->evrEv[5]) for (int i = 0; i < 6; i++) if (!c->evrEv[i] && hipEventCreate(&c->evrEv[i]) != hipSuccess) { c->evrEv[i] = nullptr; return nullptr; }
-  return c->evrEv;
-}
 static int plat_evict_report(Dev& d, const EvrArgs& a, int pass) {
   if ((pass == EVR_PASS_JOBS && a.M <= 0) || (pass == EVR_PASS_NODES && a.N <= 0)) return 0;
   PlatCtx* c = t_ctx;
-  hipEvent_t* ev = evrEvents();
-  if (ev) (void)hipEventRecord(ev[2 * pass], c->stream);
+  hipEvent_t* ev = passBegin(PASS_EVR, pass);
+  passRecord(ev, 2 * pass, c->stream);
   bool ok = asched_internal_evict_report(&d, &a, pass, c->stream) == 0;
-  if (ev) { (void)hipEventRecord(ev[2 * pass + 1], c->stream); c->evrTimed[pass] = true; }
+  passRecord(ev, 2 * pass + 1, c->stream);
+  passTimed(PASS_EVR, ev, pass);
   c->roundLaunches++;
   if (!ok) { c->err = "k_evr launch failed"; return -1; }
   return 0;
 }
-// device ms of the three passes of the last round (after the round's end: the events have completed); zeros without ASCHED_EVR_TIMES=1
-static void plat_evict_report_ms(double* out) {
-  hipEvent_t* ev = evrEvents();
-  for (int k = 0; k < 3; k++) { float ms = 0.f; if (ev && t_ctx->evrTimed[k] && hipEventElapsedTime(&ms, ev[2 * k], ev[2 * k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
-}
 // the run-state patch of the resident job table (kernels_jobs_patch.h; kernels in armada_sched_mgpu.hip): scatter + keys, the compaction of the untouched rows (its count
-// comes back to the host: the merge is sized by it), the sort, the merge.  ASCHED_JP_TIMES=1 puts events around the four passes (tools/probe_jobs_patch.py).
+// comes back to the host: the merge is sized by it), the sort, the merge.  PASS_JP (tools/probe_jobs_patch.py).
 #include "kernels_jobs_patch.h"
 extern "C" int asched_internal_jp_scatter(const Dev* d, const JpArgs* a, hipStream_t s);
 extern "C" int asched_internal_jp_sort(const JpArgs* a, hipStream_t s);
 extern "C" int asched_internal_jp_merge(const Dev* d, const JpArgs* a, hipStream_t s);
-static hipEvent_t* jpEvents() {
-  static const bool on = [] { const char* e = getenv("ASCHED_JP_TIMES"); return e && e[0] == '1'; }();
-  PlatCtx* c = t_ctx;
-  if (!on) return nullptr;
-  if (!c->jpEv[4]) for (int i = 0; i < 5; i++) if (!c->jpEv[i] && hipEventCreate(&c->jpEv[i]) != hipSuccess) { c->jpEv[i] = nullptr; return nullptr; }
-  return c->jpEv;
-}
 // the four passes behind one another; scatter: the launch of the caller's scatter (the patch's or the reprioritise's), launched between the first two events
 template <class Scatter> static int jpPasses(Dev& d, JpArgs& a, int32_t* keptBuf, Scatter scatter) {
   PlatCtx* c = t_ctx;
   hipStream_t st = c->stream;
-  hipEvent_t* ev = jpEvents();
-  c->jpTimed = false;
-  if (ev) (void)hipEventRecord(ev[0], st);
+  hipEvent_t* ev = passBegin(PASS_JP);
+  passRecord(ev, 0, st);
   bool ok = scatter(st) == 0;
-  if (ev) (void)hipEventRecord(ev[1], st);
+  passRecord(ev, 1, st);
   a.kept = keptBuf; a.nKept = 0;
   if (ok && a.nT > 0) {
     int nk = 0;
     if (plat_compact(d, d.ordAll, a.total, a.keep, keptBuf, nullptr, nullptr, 0, nullptr, &nk)) return -1;
     a.nKept = nk;
     if (a.nT + a.nKept != a.total) { c->err = "jobs_patch: the job order lost or gained rows"; return -1; }
-    if (ev) (void)hipEventRecord(ev[2], st);
+    passRecord(ev, 2, st);
     ok = asched_internal_jp_sort(&a, st) == 0;
-  } else if (ev) (void)hipEventRecord(ev[2], st);
-  if (ev) (void)hipEventRecord(ev[3], st);
+  } else passRecord(ev, 2, st);
+  passRecord(ev, 3, st);
   ok = ok && asched_internal_jp_merge(&d, &a, st) == 0;
-  if (ev) (void)hipEventRecord(ev[4], st);
-  ok = ok && hipOk(hipGetLastError(), "k_jp launch") && hipOk(hipStreamSynchronize(st), "k_jp");
-  if (!ok) { if (c->err.empty()) c->err = "k_jp launch failed"; return -1; }
-  c->jpTimed = ev != nullptr;
-  return 0;
+  passRecord(ev, 4, st);
+  return launchTail(ok, "k_jp", "k_jp", PASS_JP, ev);
 }
-static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf) {
-  return jpPasses(d, a, keptBuf, [&](hipStream_t st) { return asched_internal_jp_scatter(&d, &a, st); });
-}
-static void plat_jobs_patch_ms(double* out) {
-  hipEvent_t* ev = jpEvents();
-  for (int k = 0; k < 4; k++) { float ms = 0.f; if (ev && t_ctx->jpTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
-}
+static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf) { return jpPasses(d, a, keptBuf, [&](hipStream_t st) { return asched_internal_jp_scatter(&d, &a, st); }); }
 // queue priorities of resident jobs change (kernels_jobs_reprioritise.h; k_jr_scatter in armada_sched_mgpu.hip): its own scatter, then the patch's remove, sort and
-// merge.  The events and plat_jobs_patch_ms are the patch's (ASCHED_JP_TIMES=1; tools/probe_jobs_reprioritise.py).
+// merge.  The events are the patch's (PASS_JP; tools/probe_jobs_reprioritise.py).
 #include "kernels_jobs_reprioritise.h"
 extern "C" int asched_internal_jr_scatter(const Dev* d, const JrArgs* a, hipStream_t s);
-static int plat_jobs_reprioritise(Dev& d, JrArgs& a, int32_t* keptBuf) {
-  return jpPasses(d, a.p, keptBuf, [&](hipStream_t st) { return asched_internal_jr_scatter(&d, &a, st); });
-}
+static int plat_jobs_reprioritise(Dev& d, JrArgs& a, int32_t* keptBuf) { return jpPasses(d, a.p, keptBuf, [&](hipStream_t st) { return asched_internal_jr_scatter(&d, &a, st); }); }
 // retried jobs change class and request in place (kernels_jobs_respec.h; k_js_scatter in armada_sched_mgpu.hip): one launch on the handle's stream, waited for
 #include "kernels_jobs_respec.h"
 extern "C" int asched_internal_js_scatter(const Dev* d, const JsArgs* a, hipStream_t s);
-static int plat_jobs_respec(Dev& d, JsArgs& a) {
-  PlatCtx* c = t_ctx;
-  hipStream_t st = c->stream;
-  bool ok = asched_internal_js_scatter(&d, &a, st) == 0;
-  ok = ok && hipOk(hipGetLastError(), "k_js launch") && hipOk(hipStreamSynchronize(st), "k_js");
-  if (!ok) { if (c->err.empty()) c->err = "k_js_scatter launch failed"; return -1; }
-  return 0;
-}
+static int plat_jobs_respec(Dev& d, JsArgs& a) { return launchTail(asched_internal_js_scatter(&d, &a, t_ctx->stream) == 0, "k_js", "k_js_scatter"); }
 // newly submitted jobs behind the resident job table (kernels_jobs_append.h; k_ja_fill in armada_sched_mgpu.hip, the sort and the merge are the patch's kernels).
-// ASCHED_JA_TIMES=1 puts events around the three passes (tools/probe_jobs_append.py).
+// PASS_JA (tools/probe_jobs_append.py).
 #include "kernels_jobs_append.h"
 extern "C" int asched_internal_ja_fill(const Dev* d, const JaArgs* a, hipStream_t s);
-static hipEvent_t* jaEvents() {
-  static const bool on = [] { const char* e = getenv("ASCHED_JA_TIMES"); return e && e[0] == '1'; }();
-  PlatCtx* c = t_ctx;
-  if (!on) return nullptr;
-  if (!c->jaEv[3]) for (int i = 0; i < 4; i++) if (!c->jaEv[i] && hipEventCreate(&c->jaEv[i]) != hipSuccess) { c->jaEv[i] = nullptr; return nullptr; }
-  return c->jaEv;
-}
 static int plat_jobs_append(Dev& d, JaArgs& a) {
-  PlatCtx* c = t_ctx;
-  hipStream_t st = c->stream;
-  hipEvent_t* ev = jaEvents();
-  c->jaTimed = false;
-  if (ev) (void)hipEventRecord(ev[0], st);
+  hipStream_t st = t_ctx->stream;
+  hipEvent_t* ev = passBegin(PASS_JA);
+  passRecord(ev, 0, st);
   bool ok = asched_internal_ja_fill(&d, &a, st) == 0;
-  if (ev) (void)hipEventRecord(ev[1], st);
+  passRecord(ev, 1, st);
   if (ok && a.p.nT > 0) ok = asched_internal_jp_sort(&a.p, st) == 0;
-  if (ev) (void)hipEventRecord(ev[2], st);
+  passRecord(ev, 2, st);
   if (ok && a.p.nT > 0) ok = asched_internal_jp_merge(&d, &a.p, st) == 0;
-  if (ev) (void)hipEventRecord(ev[3], st);
-  ok = ok && hipOk(hipGetLastError(), "k_ja launch") && hipOk(hipStreamSynchronize(st), "k_ja");
-  if (!ok) { if (c->err.empty()) c->err = "k_ja launch failed"; return -1; }
-  c->jaTimed = ev != nullptr;
-  return 0;
+  passRecord(ev, 3, st);
+  return launchTail(ok, "k_ja", "k_ja", PASS_JA, ev);
 }
-static void plat_jobs_append_ms(double* out) {
-  hipEvent_t* ev = jaEvents();
-  for (int k = 0; k < 3; k++) { float ms = 0.f; if (ev && t_ctx->jaTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
-}
-// new scheduling-key shapes join the shape mask (kernels_shapes_append.h; k_sa_mask in armada_sched_mgpu.hip).  ASCHED_JA_TIMES=1 puts events around the row copies
-// and the mask rows (tools/probe_jobs_append_shapes.py).
+// new rows join a mask whose resident rows move into a fresh block: the shape mask (kernels_shapes_append.h; k_sa_mask in armada_sched_mgpu.hip; PASS_SA, switched by
+// the job append's variable; tools/probe_jobs_append_shapes.py) and the class mask (kernels_req_classes_append.h; k_ca_rows; PASS_CA; tools/probe_req_classes_append.py).
+// The row copies between events 0 and 1, the launch of the new rows between 1 and 2.
 #include "kernels_shapes_append.h"
-extern "C" int asched_internal_sa_mask(const SaArgs* a, hipStream_t s);
-static hipEvent_t* saEvents() {
-  static const bool on = [] { const char* e = getenv("ASCHED_JA_TIMES"); return e && e[0] == '1'; }();
-  PlatCtx* c = t_ctx;
-  if (!on) return nullptr;
-  if (!c->saEv[2]) for (int i = 0; i < 3; i++) if (!c->saEv[i] && hipEventCreate(&c->saEv[i]) != hipSuccess) { c->saEv[i] = nullptr; return nullptr; }
-  return c->saEv;
-}
-static int plat_shapes_append(Dev& d, SaArgs& a) {
-  (void)d;
-  PlatCtx* c = t_ctx;
-  hipStream_t st = c->stream;
-  hipEvent_t* ev = saEvents();
-  c->saTimed = false;
-  if (ev) (void)hipEventRecord(ev[0], st);
-  if (a.copy0 > 0) plat_d2d(a.outMask, a.inMask, (size_t)a.copy0 * 8);
-  if (a.copy1 > 0) plat_d2d(a.outMask + a.dst1, a.inMask + a.src1, (size_t)a.copy1 * 8);
-  if (ev) (void)hipEventRecord(ev[1], st);
-  bool ok = asched_internal_sa_mask(&a, st) == 0;
-  if (ev) (void)hipEventRecord(ev[2], st);
-  ok = ok && hipOk(hipGetLastError(), "k_sa launch") && hipOk(hipStreamSynchronize(st), "k_sa");
-  if (!ok) { if (c->err.empty()) c->err = "k_sa_mask launch failed"; return -1; }
-  c->saTimed = ev != nullptr;
-  return 0;
-}
-static void plat_shapes_append_ms(double* out) {   // out[0]: the mask rows, out[1]: the copies
-  hipEvent_t* ev = saEvents();
-  for (int k = 0; k < 2; k++) { float ms = 0.f; if (ev && t_ctx->saTimed && hipEventElapsedTime(&ms, ev[1 - k], ev[2 - k]) != hipSuccess) ms = 0.f; out[k] = ms; }
-}
-// new requirement classes join the class mask (kernels_req_classes_append.h; k_ca_rows in armada_sched_mgpu.hip).  ASCHED_CA_TIMES=1 puts events around the row copies
-// and the new rows (tools/probe_req_classes_append.py).
 #include "kernels_req_classes_append.h"
+extern "C" int asched_internal_sa_mask(const SaArgs* a, hipStream_t s);
 extern "C" int asched_internal_ca_rows(const CaArgs* a, hipStream_t s);
-static hipEvent_t* caEvents() {
-  static const bool on = [] { const char* e = getenv("ASCHED_CA_TIMES"); return e && e[0] == '1'; }();
-  PlatCtx* c = t_ctx;
-  if (!on) return nullptr;
-  if (!c->caEv[2]) for (int i = 0; i < 3; i++) if (!c->caEv[i] && hipEventCreate(&c->caEv[i]) != hipSuccess) { c->caEv[i] = nullptr; return nullptr; }
-  return c->caEv;
-}
-static int plat_req_classes_append(Dev& d, CaArgs& a) {
-  (void)d;
-  PlatCtx* c = t_ctx;
-  hipStream_t st = c->stream;
-  hipEvent_t* ev = caEvents();
-  c->caTimed = false;
-  if (ev) (void)hipEventRecord(ev[0], st);
+template <class Args> static int maskRowsAppend(Args& a, int (*rows)(const Args*, hipStream_t), PassFamily f, const char* k, const char* failed) {
+  hipStream_t st = t_ctx->stream;
+  hipEvent_t* ev = passBegin(f);
+  passRecord(ev, 0, st);
   if (a.copy0 > 0) plat_d2d(a.outMask, a.inMask, (size_t)a.copy0 * 8);
   if (a.copy1 > 0) plat_d2d(a.outMask + a.dst1, a.inMask + a.src1, (size_t)a.copy1 * 8);
-  if (ev) (void)hipEventRecord(ev[1], st);
-  bool ok = asched_internal_ca_rows(&a, st) == 0;
-  if (ev) (void)hipEventRecord(ev[2], st);
-  ok = ok && hipOk(hipGetLastError(), "k_ca launch") && hipOk(hipStreamSynchronize(st), "k_ca");
-  if (!ok) { if (c->err.empty()) c->err = "k_ca_rows launch failed"; return -1; }
-  c->caTimed = ev != nullptr;
-  return 0;
+  passRecord(ev, 1, st);
+  bool ok = rows(&a, st) == 0;
+  passRecord(ev, 2, st);
+  return launchTail(ok, k, failed, f, ev);
 }
-static void plat_req_classes_append_ms(double* out) {   // out[0]: the new rows, out[1]: the copies
-  hipEvent_t* ev = caEvents();
-  for (int k = 0; k < 2; k++) { float ms = 0.f; if (ev && t_ctx->caTimed && hipEventElapsedTime(&ms, ev[1 - k], ev[2 - k]) != hipSuccess) ms = 0.f; out[k] = ms; }
-}
-// dead shapes and classes leave the resident tables (kernels_shapes_compact.h; k_sc_* in armada_sched_mgpu.hip).  ASCHED_SC_TIMES=1 puts events around the three
-// passes (tools/probe_shapes_compact.py).
+static int plat_shapes_append(Dev&, SaArgs& a) { return maskRowsAppend(a, asched_internal_sa_mask, PASS_SA, "k_sa", "k_sa_mask"); }
+static int plat_req_classes_append(Dev&, CaArgs& a) { return maskRowsAppend(a, asched_internal_ca_rows, PASS_CA, "k_ca", "k_ca_rows"); }
+// dead shapes and classes leave the resident tables (kernels_shapes_compact.h; k_sc_* in armada_sched_mgpu.hip).  PASS_SC (tools/probe_shapes_compact.py).
 #include "kernels_shapes_compact.h"
 extern "C" int asched_internal_sc_rows(const ScArgs* a, hipStream_t s);
 extern "C" int asched_internal_sc_gather(const ScArgs* a, hipStream_t s);
 extern "C" int asched_internal_sc_clsbits(const ScArgs* a, hipStream_t s);
-static hipEvent_t* scEvents() {
-  static const bool on = [] { const char* e = getenv("ASCHED_SC_TIMES"); return e && e[0] == '1'; }();
-  PlatCtx* c = t_ctx;
-  if (!on) return nullptr;
-  if (!c->scEv[3]) for (int i = 0; i < 4; i++) if (!c->scEv[i] && hipEventCreate(&c->scEv[i]) != hipSuccess) { c->scEv[i] = nullptr; return nullptr; }
-  return c->scEv;
-}
-static int plat_shapes_compact(Dev& d, ScArgs& a) {
-  (void)d;
-  PlatCtx* c = t_ctx;
-  hipStream_t st = c->stream;
-  hipEvent_t* ev = scEvents();
-  c->scTimed = false;
-  if (ev) (void)hipEventRecord(ev[0], st);
+static int plat_shapes_compact(Dev&, ScArgs& a) {
+  hipStream_t st = t_ctx->stream;
+  hipEvent_t* ev = passBegin(PASS_SC);
+  passRecord(ev, 0, st);
   bool ok = asched_internal_sc_rows(&a, st) == 0;
-  if (ev) (void)hipEventRecord(ev[1], st);
+  passRecord(ev, 1, st);
   ok = ok && asched_internal_sc_gather(&a, st) == 0;
-  if (ev) (void)hipEventRecord(ev[2], st);
+  passRecord(ev, 2, st);
   ok = ok && asched_internal_sc_clsbits(&a, st) == 0;
-  if (ev) (void)hipEventRecord(ev[3], st);
-  ok = ok && hipOk(hipGetLastError(), "k_sc launch") && hipOk(hipStreamSynchronize(st), "k_sc");
-  if (!ok) { if (c->err.empty()) c->err = "k_sc launch failed"; return -1; }
-  c->scTimed = ev != nullptr;
-  return 0;
-}
-static void plat_shapes_compact_ms(double* out) {   // rows / gathers / class bits
-  hipEvent_t* ev = scEvents();
-  for (int k = 0; k < 3; k++) { float ms = 0.f; if (ev && t_ctx->scTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
+  passRecord(ev, 3, st);
+  return launchTail(ok, "k_sc", "k_sc", PASS_SC, ev);
 }
 // rows leave the resident job table (kernels_jobs_delete.h; k_jd_* in armada_sched_mgpu.hip, the scans are plat_compact's).  Each compaction brings its count back to the
-// host, which checks it against what the host counted before the next pass is sized by it.  ASCHED_JD_TIMES=1 puts events around the five passes (tools/probe_jobs_delete.py).
+// host, which checks it against what the host counted before the next pass is sized by it.  PASS_JD (tools/probe_jobs_delete.py).
 #include "kernels_jobs_delete.h"
 extern "C" int asched_internal_jd_mark(const JdArgs* a, int value, hipStream_t s);
 extern "C" int asched_internal_jd_gather(const JdArgs* a, hipStream_t s);
 extern "C" int asched_internal_jd_remap(const JdArgs* a, int32_t* list, int n, hipStream_t s);
-static hipEvent_t* jdEvents() {
-  static const bool on = [] { const char* e = getenv("ASCHED_JD_TIMES"); return e && e[0] == '1'; }();
-  PlatCtx* c = t_ctx;
-  if (!on) return nullptr;
-  if (!c->jdEv[5]) for (int i = 0; i < 6; i++) if (!c->jdEv[i] && hipEventCreate(&c->jdEv[i]) != hipSuccess) { c->jdEv[i] = nullptr; return nullptr; }
-  return c->jdEv;
-}
 static int plat_jobs_delete(Dev& d, JdArgs& a) {
   PlatCtx* c = t_ctx;
   hipStream_t st = c->stream;
-  hipEvent_t* ev = jdEvents();
-  c->jdTimed = false;
-  if (ev) (void)hipEventRecord(ev[0], st);
+  hipEvent_t* ev = passBegin(PASS_JD);
+  passRecord(ev, 0, st);
   if (asched_internal_jd_mark(&a, 0, st)) { c->err = "k_jd_mark launch failed"; return -1; }
-  if (ev) (void)hipEventRecord(ev[1], st);
+  passRecord(ev, 1, st);
   int m1 = 0;
   if (plat_compact(d, nullptr, a.M, a.keep, a.src, a.newId, nullptr, 0, nullptr, &m1)) return -1;
   if (m1 != a.M1) { c->err = "jobs_delete: the scan kept another number of rows than the host counted"; return -1; }
-  if (ev) (void)hipEventRecord(ev[2], st);
+  passRecord(ev, 2, st);
   if (asched_internal_jd_gather(&a, st)) { c->err = "k_jd_gather launch failed"; return -1; }
-  if (ev) (void)hipEventRecord(ev[3], st);
+  passRecord(ev, 3, st);
   if (a.total > 0) {
     int t1 = 0;
     if (plat_compact(d, a.ordIn, a.total, a.keep, a.ordOut, nullptr, nullptr, 0, nullptr, &t1)) return -1;
     if (t1 != a.total1) { c->err = "jobs_delete: the job order lost or gained rows"; return -1; }
     if (asched_internal_jd_remap(&a, a.ordOut, a.total1, st)) { c->err = "k_jd_remap launch failed"; return -1; }
   }
-  if (ev) (void)hipEventRecord(ev[4], st);
+  passRecord(ev, 4, st);
   if (a.gangLen > 0) {
     int g1 = 0;
     if (plat_compact(d, a.gangIn, a.gangLen, a.keep, a.gangOut, nullptr, nullptr, 0, nullptr, &g1)) return -1;
     if (g1 != a.gangLen1) { c->err = "jobs_delete: the gang lists lost or gained rows"; return -1; }
     if (asched_internal_jd_remap(&a, a.gangOut, a.gangLen1, st)) { c->err = "k_jd_remap launch failed"; return -1; }
   }
-  if (ev) (void)hipEventRecord(ev[5], st);
-  bool ok = asched_internal_jd_mark(&a, 1, st) == 0;
-  ok = ok && hipOk(hipGetLastError(), "k_jd launch") && hipOk(hipStreamSynchronize(st), "k_jd");
-  if (!ok) { if (c->err.empty()) c->err = "k_jd launch failed"; return -1; }
-  c->jdTimed = ev != nullptr;
-  return 0;
+  passRecord(ev, 5, st);
+  return launchTail(asched_internal_jd_mark(&a, 1, st) == 0, "k_jd", "k_jd", PASS_JD, ev);
 }
-static void plat_jobs_delete_ms(double* out) {
-  hipEvent_t* ev = jdEvents();
-  for (int k = 0; k < 5; k++) { float ms = 0.f; if (ev && t_ctx->jdTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
-}
-// cordons and capacity changes of resident nodes (kernels_nodes_patch.h; k_np_scatter / k_np_mask in armada_sched_mgpu.hip).  ASCHED_NP_TIMES=1 puts events around
-// the two passes (tools/probe_nodes_patch.py).
+// cordons and capacity changes of resident nodes (kernels_nodes_patch.h; k_np_scatter / k_np_mask in armada_sched_mgpu.hip).  PASS_NP (tools/probe_nodes_patch.py).
 #include "kernels_nodes_patch.h"
 extern "C" int asched_internal_np_scatter(const Dev* d, const NpArgs* a, hipStream_t s);
 extern "C" int asched_internal_np_mask(const Dev* d, const NpArgs* a, hipStream_t s);
-static hipEvent_t* npEvents() {
-  static const bool on = [] { const char* e = getenv("ASCHED_NP_TIMES"); return e && e[0] == '1'; }();
-  PlatCtx* c = t_ctx;
-  if (!on) return nullptr;
-  if (!c->npEv[2]) for (int i = 0; i < 3; i++) if (!c->npEv[i] && hipEventCreate(&c->npEv[i]) != hipSuccess) { c->npEv[i] = nullptr; return nullptr; }
-  return c->npEv;
-}
 static int plat_nodes_patch(Dev& d, const NpArgs& a) {
-  PlatCtx* c = t_ctx;
-  hipStream_t st = c->stream;
-  hipEvent_t* ev = npEvents();
-  c->npTimed = false;
-  if (ev) (void)hipEventRecord(ev[0], st);
+  hipStream_t st = t_ctx->stream;
+  hipEvent_t* ev = passBegin(PASS_NP);
+  passRecord(ev, 0, st);
   bool ok = asched_internal_np_scatter(&d, &a, st) == 0;
-  if (ev) (void)hipEventRecord(ev[1], st);
+  passRecord(ev, 1, st);
   ok = ok && asched_internal_np_mask(&d, &a, st) == 0;
-  if (ev) (void)hipEventRecord(ev[2], st);
-  ok = ok && hipOk(hipGetLastError(), "k_np launch") && hipOk(hipStreamSynchronize(st), "k_np");
-  if (!ok) { if (c->err.empty()) c->err = "k_np launch failed"; return -1; }
-  c->npTimed = ev != nullptr;
-  return 0;
-}
-static void plat_nodes_patch_ms(double* out) {
-  hipEvent_t* ev = npEvents();
-  for (int k = 0; k < 2; k++) { float ms = 0.f; if (ev && t_ctx->npTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
+  passRecord(ev, 2, st);
+  return launchTail(ok, "k_np", "k_np", PASS_NP, ev);
 }
 // rows leave the resident node table (kernels_nodes_delete.h; k_nd_* in armada_sched_mgpu.hip, the scans are plat_compact's).  The check brings its word back to the host
-// before anything is written; each compaction brings its count back.  ASCHED_ND_TIMES=1 puts events around the seven passes (tools/probe_nodes_delete.py).
+// before anything is written; each compaction brings its count back.  PASS_ND spans both calls: the check clears the flag and records events 0 and 1, the delete
+// records 2 to 7 and sets it (tools/probe_nodes_delete.py).
 #include "kernels_nodes_delete.h"
 extern "C" int asched_internal_nd_mark(const NdArgs* a, int value, hipStream_t s);
 extern "C" int asched_internal_nd_check(const NdArgs* a, hipStream_t s);
@@ -1171,26 +1049,17 @@ extern "C" int asched_internal_nd_gather(const NdArgs* a, hipStream_t s);
 extern "C" int asched_internal_nd_rank(const NdArgs* a, hipStream_t s);
 extern "C" int asched_internal_nd_mask(const NdArgs* a, hipStream_t s);
 extern "C" int asched_internal_nd_job(const NdArgs* a, hipStream_t s);
-static hipEvent_t* ndEvents() {
-  static const bool on = [] { const char* e = getenv("ASCHED_ND_TIMES"); return e && e[0] == '1'; }();
-  PlatCtx* c = t_ctx;
-  if (!on) return nullptr;
-  if (!c->ndEv[7]) for (int i = 0; i < 8; i++) if (!c->ndEv[i] && hipEventCreate(&c->ndEv[i]) != hipSuccess) { c->ndEv[i] = nullptr; return nullptr; }
-  return c->ndEv;
-}
-static int plat_nodes_delete_check(Dev& d, NdArgs& a, int32_t* bad) {
-  (void)d;
+static int plat_nodes_delete_check(Dev&, NdArgs& a, int32_t* bad) {
   PlatCtx* c = t_ctx;
   hipStream_t st = c->stream;
-  hipEvent_t* ev = ndEvents();
-  c->ndTimed = false;
+  hipEvent_t* ev = passBegin(PASS_ND);
   *bad = ND_NONE;
   const int32_t none = ND_NONE;
-  if (ev) (void)hipEventRecord(ev[0], st);
+  passRecord(ev, 0, st);
   if (!hipOk(hipMemcpyAsync(a.bad, &none, sizeof none, hipMemcpyHostToDevice, st), "nodes_delete check word")) return -1;
   if (asched_internal_nd_mark(&a, 0, st)) { c->err = "k_nd_mark launch failed"; return -1; }
   if (asched_internal_nd_check(&a, st)) { c->err = "k_nd_check launch failed"; return -1; }
-  if (ev) (void)hipEventRecord(ev[1], st);
+  passRecord(ev, 1, st);
   int32_t t = ND_NONE;
   if (!hipOk(hipMemcpyAsync(&t, a.bad, sizeof t, hipMemcpyDeviceToHost, st), "nodes_delete check word") || !hipOk(hipStreamSynchronize(st), "k_nd_check")) return -1;
   *bad = t;
@@ -1202,103 +1071,68 @@ static int plat_nodes_delete_check(Dev& d, NdArgs& a, int32_t* bad) {
 static int plat_nodes_delete(Dev& d, NdArgs& a) {
   PlatCtx* c = t_ctx;
   hipStream_t st = c->stream;
-  hipEvent_t* ev = ndEvents();
+  hipEvent_t* ev = passBegin(PASS_ND);
   int n1 = 0;
   if (plat_compact(d, nullptr, a.N, a.keep, a.src, a.newId, nullptr, 0, nullptr, &n1)) return -1;
   if (n1 != a.N1) { c->err = "nodes_delete: the scan kept another number of rows than the host counted"; return -1; }
-  if (ev) (void)hipEventRecord(ev[2], st);
+  passRecord(ev, 2, st);
   if (!a.jobsOnly && asched_internal_nd_gather(&a, st)) { c->err = "k_nd_gather launch failed"; return -1; }
-  if (ev) (void)hipEventRecord(ev[3], st);
+  passRecord(ev, 3, st);
   if (!a.jobsOnly) {
     int r1 = 0;
     if (plat_compact(d, a.rankIn, a.N, a.keep, a.rankOut, nullptr, nullptr, 0, nullptr, &r1)) return -1;
     if (r1 != a.N1) { c->err = "nodes_delete: the index order lost or gained rows"; return -1; }
     if (asched_internal_nd_rank(&a, st)) { c->err = "k_nd_rank launch failed"; return -1; }
   }
-  if (ev) (void)hipEventRecord(ev[4], st);
+  passRecord(ev, 4, st);
   if (!a.jobsOnly && asched_internal_nd_mask(&a, st)) { c->err = "k_nd_mask launch failed"; return -1; }
-  if (ev) (void)hipEventRecord(ev[5], st);
+  passRecord(ev, 5, st);
   if (asched_internal_nd_job(&a, st)) { c->err = "k_nd_job launch failed"; return -1; }
-  if (ev) (void)hipEventRecord(ev[6], st);
+  passRecord(ev, 6, st);
   bool ok = asched_internal_nd_mark(&a, 1, st) == 0;
-  if (ev) (void)hipEventRecord(ev[7], st);
-  ok = ok && hipOk(hipGetLastError(), "k_nd launch") && hipOk(hipStreamSynchronize(st), "k_nd");
-  if (!ok) { if (c->err.empty()) c->err = "k_nd launch failed"; return -1; }
-  c->ndTimed = ev != nullptr;
-  return 0;
+  passRecord(ev, 7, st);
+  return launchTail(ok, "k_nd", "k_nd", PASS_ND, ev);
 }
-static void plat_nodes_delete_ms(double* out) {
-  hipEvent_t* ev = ndEvents();
-  for (int k = 0; k < 7; k++) { float ms = 0.f; if (ev && t_ctx->ndTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
-}
-// new rows join the resident node table (kernels_nodes_append.h; k_na_* in armada_sched_mgpu.hip).  ASCHED_NA_TIMES=1 puts events around the four passes
-// (tools/probe_nodes_append.py).
+// new rows join the resident node table (kernels_nodes_append.h; k_na_* in armada_sched_mgpu.hip).  PASS_NA (tools/probe_nodes_append.py).
 #include "kernels_nodes_append.h"
 extern "C" int asched_internal_na_planes(const NaArgs* a, hipStream_t s);
 extern "C" int asched_internal_na_narrow(const NaArgs* a, hipStream_t s);
 extern "C" int asched_internal_na_rank(const NaArgs* a, hipStream_t s);
 extern "C" int asched_internal_na_mask(const NaArgs* a, hipStream_t s);
-static hipEvent_t* naEvents() {
-  static const bool on = [] { const char* e = getenv("ASCHED_NA_TIMES"); return e && e[0] == '1'; }();
-  PlatCtx* c = t_ctx;
-  if (!on) return nullptr;
-  if (!c->naEv[4]) for (int i = 0; i < 5; i++) if (!c->naEv[i] && hipEventCreate(&c->naEv[i]) != hipSuccess) { c->naEv[i] = nullptr; return nullptr; }
-  return c->naEv;
-}
-static int plat_nodes_append(Dev& d, NaArgs& a) {
-  (void)d;
+static int plat_nodes_append(Dev&, NaArgs& a) {
   PlatCtx* c = t_ctx;
   hipStream_t st = c->stream;
-  hipEvent_t* ev = naEvents();
-  c->naTimed = false;
-  if (ev) (void)hipEventRecord(ev[0], st);
+  hipEvent_t* ev = passBegin(PASS_NA);
+  passRecord(ev, 0, st);
   if (asched_internal_na_planes(&a, st)) { c->err = "k_na_plane launch failed"; return -1; }
-  if (ev) (void)hipEventRecord(ev[1], st);
+  passRecord(ev, 1, st);
   if (asched_internal_na_narrow(&a, st)) { c->err = "k_na_narrow launch failed"; return -1; }
-  if (ev) (void)hipEventRecord(ev[2], st);
+  passRecord(ev, 2, st);
   if (asched_internal_na_rank(&a, st)) { c->err = "k_na_rank launch failed"; return -1; }
-  if (ev) (void)hipEventRecord(ev[3], st);
+  passRecord(ev, 3, st);
   bool ok = asched_internal_na_mask(&a, st) == 0;
-  if (ev) (void)hipEventRecord(ev[4], st);
-  ok = ok && hipOk(hipGetLastError(), "k_na launch") && hipOk(hipStreamSynchronize(st), "k_na");
-  if (!ok) { if (c->err.empty()) c->err = "k_na launch failed"; return -1; }
-  c->naTimed = ev != nullptr;
-  return 0;
-}
-static void plat_nodes_append_ms(double* out) {
-  hipEvent_t* ev = naEvents();
-  for (int k = 0; k < 4; k++) { float ms = 0.f; if (ev && t_ctx->naTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
+  passRecord(ev, 4, st);
+  return launchTail(ok, "k_na", "k_na", PASS_NA, ev);
 }
 // the queued lists of a round from the resident job order (kernels_queued_lists.h; k_ql_mark / k_ql_hold in armada_sched_mgpu.hip, the compaction is plat_compact,
-// which brings the total back to the host).  ASCHED_QL_TIMES=1 puts events around the three passes (tools/probe_round_prepare_resident.py).
+// which brings the total back to the host: the call ends without a further wait, or, timed, with the wait for its last event).  PASS_QL (tools/probe_round_prepare_resident.py).
 #include "kernels_queued_lists.h"
 extern "C" int asched_internal_ql_mark(const QlArgs* a, hipStream_t s);
 extern "C" int asched_internal_ql_hold(const QlArgs* a, hipStream_t s);
-static hipEvent_t* qlEvents() {
-  static const bool on = [] { const char* e = getenv("ASCHED_QL_TIMES"); return e && e[0] == '1'; }();
-  PlatCtx* c = t_ctx;
-  if (!on) return nullptr;
-  if (!c->qlEv[3]) for (int i = 0; i < 4; i++) if (!c->qlEv[i] && hipEventCreate(&c->qlEv[i]) != hipSuccess) { c->qlEv[i] = nullptr; return nullptr; }
-  return c->qlEv;
-}
 static int plat_queued_lists(Dev& d, const QlArgs& a, int ordTotal, int32_t* list, uint32_t* prefix, int32_t* off, int* total) {
   PlatCtx* c = t_ctx;
   hipStream_t st = c->stream;
-  hipEvent_t* ev = qlEvents();
-  c->qlTimed = false;
-  if (ev) (void)hipEventRecord(ev[0], st);
+  hipEvent_t* ev = passBegin(PASS_QL);
+  passRecord(ev, 0, st);
   if (asched_internal_ql_mark(&a, st)) { c->err = "k_ql_mark launch failed"; return -1; }
-  if (ev) (void)hipEventRecord(ev[1], st);
+  passRecord(ev, 1, st);
   if (asched_internal_ql_hold(&a, st)) { c->err = "k_ql_hold launch failed"; return -1; }
-  if (ev) (void)hipEventRecord(ev[2], st);
+  passRecord(ev, 2, st);
   if (plat_compact(d, d.ordAll, ordTotal, a.flag, list, prefix, d.ordAllOff, a.Q, off, total)) return -1;
-  if (ev) { (void)hipEventRecord(ev[3], st); if (!hipOk(hipEventSynchronize(ev[3]), "queued-list events")) return -1; }
-  c->qlTimed = ev != nullptr;
+  passRecord(ev, 3, st);
+  if (ev && !hipOk(hipEventSynchronize(ev[3]), "queued-list events")) return -1;
+  passTimed(PASS_QL, ev);
   return 0;
-}
-static void plat_queued_lists_ms(double* out) {
-  hipEvent_t* ev = qlEvents();
-  for (int k = 0; k < 3; k++) { float ms = 0.f; if (ev && t_ctx->qlTimed && hipEventElapsedTime(&ms, ev[k], ev[k + 1]) != hipSuccess) ms = 0.f; out[k] = ms; }
 }
 // a caller-side buffer may be memory of this handle's GPU (a tensor the collective reduces in place: used directly) or host memory (staged)
 static bool plat_is_device_ptr(const void* p) {
