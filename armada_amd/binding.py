@@ -265,6 +265,7 @@ ALL_SYMBOLS = [
     "set_evictor_report", "round_evictor_report",
     "jobs_patch", "jobs_append", "jobs_append_stats", "jobs_delete", "jobs_delete_stats",
     "jobs_reprioritise", "jobs_reprioritise_stats",
+    "round_commit", "round_commit_stats",
     "jobs_respec", "jobs_respec_stats",
     "set_append_in_place", "jobs_append_shape_stats",
     "req_classes_append", "req_classes_append_stats",
@@ -281,6 +282,7 @@ OPTIONAL_SYMBOLS = {"comm_unique_id", "comm_init", "comm_init_external", "comm_d
                     "jobs_delete", "jobs_delete_stats",                 # (likewise: tests/test_z_jobs_delete.py)
                     "jobs_reprioritise", "jobs_reprioritise_stats",     # (likewise: tests/test_z_jobs_reprioritise.py)
                     "jobs_respec", "jobs_respec_stats",                 # (likewise: tests/test_z_jobs_respec.py)
+                    "round_commit", "round_commit_stats",               # (jobs_patch of the round's own result: tests/test_z_round_commit.py)
                     "set_append_in_place", "jobs_append_shape_stats",   # (how jobs_append treats new shapes, not what it leaves: tests/test_z_jobs_append_shapes.py)
                     "req_classes_append", "req_classes_append_stats",   # (an incremental jobs_set: the oracle is given the whole class list; tests/test_z_req_classes_append.py)
                     "shapes_compact", "shapes_compact_stats",           # (the oracle is given the job table afresh and never holds a dead shape: tests/test_z_shapes_compact.py)
@@ -485,6 +487,8 @@ class Library:
         f("jobs_patch", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i32p, _i64p])
         f("jobs_reprioritise", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _u32p])
         f("jobs_reprioritise_stats", C.c_int32, [C.c_void_p, _i32p])
+        f("round_commit", C.c_int32, [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, _i32p, _i32p, _i32p, _i64p])
+        f("round_commit_stats", C.c_int32, [C.c_void_p, _i32p])
         f("jobs_respec", C.c_int32, [C.c_void_p, C.c_int32, _i32p, _i32p, _i64p])
         f("jobs_respec_stats", C.c_int32, [C.c_void_p, _i32p])
         f("jobs_append", C.c_int32, [C.c_void_p, C.POINTER(CJobs)])
@@ -802,6 +806,28 @@ class Scheduler:
         out = np.zeros(8, np.int32)
         self._check(fn(self.h, _ptr(out, C.c_int32)))
         return dict(entries=int(out[0]), in_order=int(out[1]), unchanged=int(out[2]), made_resident=int(out[3]), device_ms=[int(x) / 1000.0 for x in out[4:8]])
+
+    def round_commit(self, run_timestamp, step=0, rows=None, node=None, scheduled_at_priority=None, run_timestamp_extra=None):
+        """the two Upserts a cycle ends with, from the result of the round the handle holds: every scheduled job runs on its node at its priority, leased at
+        `run_timestamp` + position * `step` (ns), every preempted job loses its run — and the caller's other run-state changes of the cycle, `rows` / `node` /
+        `scheduled_at_priority` / `run_timestamp_extra` with jobs_patch's meaning, in the same pass.  Read the preemption causes and the evictor report first.
+        Leaves the handle as jobs_set of the edited table would; go on with round_prepare."""
+        fn = self._preemption_fn("round_commit")
+        jb = _arr([] if rows is None else rows, np.int32).reshape(-1)
+        n = len(jb)
+        nd = _arr([] if node is None else np.broadcast_to(np.asarray(node, dtype=np.int32), (n,)), np.int32).reshape(-1)
+        assert len(nd) == n, "node"
+        sp = None if scheduled_at_priority is None else _arr(np.broadcast_to(np.asarray(scheduled_at_priority, dtype=np.int32), (n,)), np.int32)
+        ts = None if run_timestamp_extra is None else _arr(np.broadcast_to(np.asarray(run_timestamp_extra, dtype=np.int64), (n,)), np.int64)
+        self._check(fn(self.h, int(run_timestamp), int(step), n, _ptr(jb, C.c_int32), _ptr(nd, C.c_int32), _ptr(sp, C.c_int32), _ptr(ts, C.c_int64)))
+
+    def round_commit_stats(self):
+        """how the last round_commit ran: scheduled / preempted / extra entries, entries that name a row in the order, whether the call made the order-key inputs
+        resident (the first incremental call on the table), device ms of scatter / remove + sort / merge (measured with ASCHED_JP_TIMES=1, else zeros)"""
+        fn = self._preemption_fn("round_commit_stats")
+        out = np.zeros(8, np.int32)
+        self._check(fn(self.h, _ptr(out, C.c_int32)))
+        return dict(scheduled=int(out[0]), preempted=int(out[1]), extra=int(out[2]), in_order=int(out[3]), made_resident=int(out[4]), device_ms=[int(x) / 1000.0 for x in out[5:8]])
 
     def jobs_respec(self, jobs, req_class=None, req=None):
         """a retry of resident jobs (scheduler.go:1342-1383): rows `jobs` of the job table, which have no run, get the requirement class `req_class` (None: unchanged;

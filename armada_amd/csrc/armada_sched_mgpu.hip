@@ -470,6 +470,19 @@ extern "C" int asched_internal_jr_scatter(const Dev* d, const JrArgs* a, hipStre
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ------------------------------------------------------------------------------------------------ a round's result applied to the resident jobs (kernels_round_commit.h)
+// scatter + keys: one thread per entry, the entry read from the uploaded extras or from the lists the round left (neighbouring threads read neighbouring words), plain
+// stores; the remove, the sort and the merge by rank are the patch's (plat_compact, asched_internal_jp_sort / _jp_merge on RcArgs::p)
+#include "kernels_round_commit.h"
+__global__ __launch_bounds__(MG_THREADS) void k_rc_scatter(Dev d, RcArgs a) {
+  long long i = MG_IDX();
+  if (i < a.p.nb2) rcScatter(d, a, (int)i);
+}
+extern "C" int asched_internal_rc_scatter(const Dev* d, const RcArgs* a, hipStream_t st) {
+  if (a->p.nb2 > 0) hipLaunchKernelGGL(k_rc_scatter, dim3(mgBlocks(a->p.nb2)), dim3(MG_THREADS), 0, st, *d, *a);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 // ------------------------------------------------------------------------------------------------ retried jobs change class and request in place (kernels_jobs_respec.h)
 // one thread per entry, plain stores: every row is named at most once and a record's source row is named by no entry
 #include "kernels_jobs_respec.h"

@@ -30,6 +30,7 @@
 #include "kernels_evict_report.h"   // EvrArgs and, in the CPU build of the tests, plat_evict_report
 #include "kernels_jobs_patch.h"     // JpArgs and, in the CPU build of the tests, plat_jobs_patch
 #include "kernels_jobs_reprioritise.h"   // JrArgs and, in the CPU build of the tests, plat_jobs_reprioritise
+#include "kernels_round_commit.h"        // RcArgs and, in the CPU build of the tests, plat_round_commit
 #include "kernels_jobs_respec.h"         // JsArgs and, in the CPU build of the tests, plat_jobs_respec
 #include "kernels_jobs_append.h"    // JaArgs and, in the CPU build of the tests, plat_jobs_append
 #include "kernels_shapes_append.h"  // SaArgs and, in the CPU build of the tests, plat_shapes_append
@@ -288,6 +289,7 @@ struct asched {
   // the round's result arrays live in ONE pinned host arena (downloadResult): every piece is copied asynchronously on the handle's stream and the host waits once
   // (round 4: eleven staged copies through pageable vectors, ~35 us each — a third of a small round, profiles/r05g_small_round_timeline.txt)
   void* resPin = nullptr; size_t resPinBytes = 0; int resNs = 0, resNp = 0;
+  const int32_t *resSJob = nullptr, *resSNode = nullptr, *resSPrio = nullptr, *resPJob = nullptr;   // the last round's lists in resPin (downloadResult), read by asched_round_commit
   RoundScalars rsHost;
   double roundMs = 0; int roundLaunches = 0;
   double submitMs = 0;
@@ -342,6 +344,7 @@ struct asched {
   DevBufs jpBufs; char* jpScratch = nullptr; size_t jpScratchBytes = 0;   // the entries, the sort array and the kept list of a patch: one block, kept between calls and only ever grown
   double jpMs[kPassFamilies[PASS_JP].passes] = {};     // device ms of the four passes of the last patch (ASCHED_JP_TIMES=1)
   int32_t jrStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_reprioritise_stats (kernels_jobs_reprioritise.h)
+  int32_t rcStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_round_commit_stats (kernels_round_commit.h)
   int32_t jsStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // asched_jobs_respec_stats (kernels_jobs_respec.h)
   // ---- asched_jobs_delete (kernels_jobs_delete.h).  A scheduling-key shape that lost its last row keeps its id with shapeRow[s] == -1 (an append that uses it goes
   // through the rebuild path); a gang that lost its last row keeps its dense id with no members and leaves gangMap
@@ -1573,7 +1576,7 @@ int32_t asched_jobs_set(asched_t* h, const asched_jobs* j, const asched_req_clas
   d.unfeasible = h->jobBufs.alloc<uint8_t>(std::max(h->S, 1)); d.unfeasibleReason = h->jobBufs.alloc<int32_t>(std::max(h->S, 1));
   h->jobCap = M; h->gangCap = h->G; h->gangArrCap = (size_t)gangOff[h->G + 1]; h->gangJobsCap = gangJobs.size(); h->gangOffCap = gangOff.size();
   h->ordCap = ord.size(); h->ordSpareCap = 0; h->ordOffCap = h->ordOffHost.size(); h->gangOffHost = gangOff;
-  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->jsStats, 0, sizeof h->jsStats); memset(h->caStats, 0, sizeof h->caStats);
+  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->rcStats, 0, sizeof h->rcStats); memset(h->jsStats, 0, sizeof h->jsStats); memset(h->caStats, 0, sizeof h->caStats);
   memset(h->scStats, 0, sizeof h->scStats);
   h->jobsSet = true; h->prepared = false;
   h->jQPrioHost.swap(qprio); h->jSubmitHost.swap(submit); h->jRunTsHost.swap(runTs);   // (asched_jobs_patch uploads them when it is first called; nothing is copied here)
@@ -1604,6 +1607,72 @@ static void jpMakeResident(asched* h, int total) {
   h->jp.built = true;
 }
 
+// ---- what the two run-state calls share (asched_jobs_patch; asched_round_commit, whose entries are these plus the lists of the round)
+// the entries a caller gives, checked before anything changes: nullptr, or the reason without the call's name (code: its error code).  nT grows by the entries that name
+// a row of a queue >= 0.  h->jpSeen [M] is all zero on return but for what the caller marked (2) before: the rows another source of the same call names
+static const char* jpCheckEntries(asched* h, int n, const int32_t* job, const int32_t* node, int& nT, int& code) {
+  const int M = h->M;
+  if (h->jpSeen.size() != (size_t)M) h->jpSeen.assign(M, 0);
+  int seen = 0;
+  const char* why = nullptr;
+  for (int i = 0; i < n && !why; i++) {
+    const int j = job[i];
+    if (j < 0 || j >= M) { why = "a row outside the job table"; break; }
+    if (h->jpSeen[j]) { why = h->jpSeen[j] == 2 ? "an extra row that the round's scheduled or preempted list names (send that change with a later jobs_patch)" : "a row named twice"; break; }
+    h->jpSeen[j] = 1; seen = i + 1;
+    if (node[i] < -1 || node[i] >= (h->nodesSet ? h->N : 0)) why = "node outside [-1, N)";   // (no node table: only -1)
+    else if (node[i] >= 0 && h->jAway[j]) { why = "a cross-pool away row may only lose its run"; code = ASCHED_ERR_UNSUPPORTED; }
+    else if (h->jQueue[j] >= 0) nT++;
+  }
+  for (int i = 0; i < seen; i++) h->jpSeen[job[i]] = 0;
+  return why;
+}
+// one scratch block, kept and only ever grown: the rows of the n entries | node and priority of the nx uploaded ones | their timestamps | the sort array | the kept rows
+struct JpPlan { int n, nx, nT, total, nb2; size_t oNode, oTs, oKeys, oKept, need; };
+static JpPlan jpPlan(asched* h, int n, int nx, int nT) {
+  JpPlan p;
+  p.n = n; p.nx = nx; p.nT = nT;
+  p.total = h->ordOffHost.empty() ? 0 : h->ordOffHost[std::min<size_t>((size_t)h->ordQueues, h->ordOffHost.size() - 1)];
+  p.nb2 = n;
+  if (nT > 0) { p.nb2 = JP_TILE; while (p.nb2 < n) p.nb2 <<= 1; }
+  p.oNode = up256(sizeof(int32_t) * (size_t)n); p.oTs = p.oNode + up256(sizeof(int32_t) * 2 * (size_t)nx); p.oKeys = p.oTs + up256(sizeof(int64_t) * (size_t)nx);
+  p.oKept = p.oKeys + (nT > 0 ? up256(sizeof(JpKey) * (size_t)p.nb2) : 0);
+  p.need = p.oKept + (nT > 0 ? up256(sizeof(int32_t) * (size_t)p.total) : 0);
+  return p;
+}
+// the host mirrors of the entries a caller gives (round_prepare's host aggregation path reads jNode); prio / ts nullptr: zeros
+static void jpMirror(asched* h, int n, const int32_t* job, const int32_t* node, const int32_t* prio, const int64_t* ts) {
+  for (int i = 0; i < n; i++) {
+    const int j = job[i];
+    h->jNode[j] = node[i]; h->jRunPrio[j] = prio ? prio[i] : 0; h->jRunTsHost[j] = ts ? ts[i] : 0;
+  }
+}
+// after the mirrors hold the call's values, p.n > 0: the order-key inputs become resident with the first incremental call on the job table, the p.nx uploaded entries go
+// into the scratch (prio / ts nullptr: zeros), and `a` describes the call to the platform layer
+static void jpStage(asched* h, const JpPlan& p, JpArgs& a, int32_t*& keptBuf, const int32_t* job, const int32_t* node, const int32_t* prio, const int64_t* ts) {
+  if (!h->jp.built) jpMakeResident(h, p.total);
+  memset(&a, 0, sizeof a);
+  a.M = h->M; a.n = p.n; a.nT = p.nT; a.total = p.total; a.nb2 = p.nb2;
+  const size_t nx = (size_t)p.nx;
+  int32_t *eJob = (int32_t*)h->jpScratch, *eNode = (int32_t*)(h->jpScratch + p.oNode), *ePrio = eNode + nx; int64_t* eTs = (int64_t*)(h->jpScratch + p.oTs);
+  if (nx) {
+    plat_h2d(eJob, job, sizeof(int32_t) * nx); plat_h2d(eNode, node, sizeof(int32_t) * nx);
+    if (prio) plat_h2d(ePrio, prio, sizeof(int32_t) * nx); else plat_memset(ePrio, 0, sizeof(int32_t) * nx);
+    if (ts) plat_h2d(eTs, ts, sizeof(int64_t) * nx); else plat_memset(eTs, 0, sizeof(int64_t) * nx);
+  }
+  a.pJob = eJob; a.pNode = eNode; a.pPrio = ePrio; a.pTs = eTs;
+  a.keep = h->jp.keep; a.jQPrio = h->jp.qprio; a.jSubmit = h->jp.submit; a.jRunTs = h->jp.runTs;
+  keptBuf = nullptr;
+  if (p.nT > 0) { a.keys = (JpKey*)(h->jpScratch + p.oKeys); keptBuf = (int32_t*)(h->jpScratch + p.oKept); a.out = h->jp.ordSpare; }
+}
+// the platform layer ended well: the merged order is the order, and the pass times are the call's
+static void jpSeated(asched* h, const JpPlan& p, const char* who) {
+  if (p.nT > 0) { std::swap(h->dev.ordAll, h->jp.ordSpare); std::swap(h->ordCap, h->ordSpareCap); }
+  plat_pass_ms(PASS_JP, h->jpMs);
+  if (plat_pass_printed(PASS_JP))
+    fprintf(stderr, "[asched %s] jobs %d entries %d in the order %d: scatter %.4f ms, remove %.4f ms, sort %.4f ms, merge %.4f ms\n", who, h->M, p.n, p.nT, h->jpMs[0], h->jpMs[1], h->jpMs[2], h->jpMs[3]);
+}
+
 // jobdb.Txn.Upsert for run-state changes (scheduling/scheduling_algo.go:280-283 with the jobs of :956-981; jobdb/jobdb.go:572-700): the named rows get a new active run
 // or lose theirs, on the device (kernels_jobs_patch.h).  Leaves the handle as asched_jobs_set would have, given the table with those rows replaced — without the static
 // masks, the JobRec upload, the sort of all jobs or a new fast structure: none of them depends on run state.
@@ -1617,62 +1686,99 @@ int32_t asched_jobs_patch(asched_t* h, int32_t n, const int32_t* job, const int3
   if (n < 0 || (n > 0 && (!job || !node))) return fail(h, ASCHED_ERR_INVALID, "jobs_patch: bad arguments");
   if (h->mkJobsBuilt) return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_patch: the job set carries the market order, which depends on run state too (jobs_set instead)");
   if (n > (1 << 29)) return fail(h, ASCHED_ERR_UNSUPPORTED, "jobs_patch: more than 2^29 entries");
-  if (h->jpSeen.size() != (size_t)M) h->jpSeen.assign(M, 0);
-  int bad = 0, nT = 0;
-  const char* why = nullptr;
-  int code = ASCHED_ERR_INVALID;
-  for (int i = 0; i < n && !why; i++) {
-    const int j = job[i];
-    if (j < 0 || j >= M) { why = "jobs_patch: a row outside the job table"; break; }
-    if (h->jpSeen[j]) { why = "jobs_patch: a row named twice"; break; }
-    h->jpSeen[j] = 1; bad = i + 1;
-    if (node[i] < -1 || node[i] >= (h->nodesSet ? h->N : 0)) why = "jobs_patch: node outside [-1, N)";   // (no node table: only -1)
-    else if (node[i] >= 0 && h->jAway[j]) { why = "jobs_patch: a cross-pool away row may only lose its run"; code = ASCHED_ERR_UNSUPPORTED; }
-    else if (h->jQueue[j] >= 0) nT++;
-  }
-  if (why) { for (int i = 0; i < bad; i++) h->jpSeen[job[i]] = 0; return fail(h, code, why); }
-  for (int i = 0; i < n; i++) h->jpSeen[job[i]] = 0;
-  // one scratch block, kept and only ever grown: the entries | the sort array | the kept rows.  Sized before anything changes: running out of device memory here is a refusal too
-  const int total = h->ordOffHost.empty() ? 0 : h->ordOffHost[std::min<size_t>((size_t)h->ordQueues, h->ordOffHost.size() - 1)];
-  int nb2 = n;
-  if (nT > 0) { nb2 = JP_TILE; while (nb2 < n) nb2 <<= 1; }
-  const size_t oTs = up256(sizeof(int32_t) * 3 * (size_t)n), oKeys = oTs + up256(sizeof(int64_t) * (size_t)n), oKept = oKeys + (nT > 0 ? up256(sizeof(JpKey) * (size_t)nb2) : 0),
-               need = oKept + (nT > 0 ? up256(sizeof(int32_t) * (size_t)total) : 0);
+  int nT = 0, code = ASCHED_ERR_INVALID;
+  if (const char* why = jpCheckEntries(h, n, job, node, nT, code)) return fail(h, code, std::string("jobs_patch: ") + why);
+  // sized before anything changes: running out of device memory here is a refusal too
+  const JpPlan p = jpPlan(h, n, n, nT);
   KeptBlock<char> scratch{h->jpBufs, h->jpScratch, h->jpScratchBytes};
-  if (n > 0 && !scratch.grow(need)) return fail(h, ASCHED_ERR_DEVICE, "jobs_patch: out of device memory for the patch scratch; the handle is as it was");
+  if (n > 0 && !scratch.grow(p.need)) return fail(h, ASCHED_ERR_DEVICE, "jobs_patch: out of device memory for the patch scratch; the handle is as it was");
   // ---- what jobs_set resets (the job table half patched).  evrSized stays, on purpose: a patch changes no size
   residentTouchJobs(h, false, true);
   Dev& d = h->dev;
   plat_pass_clear(PASS_JP, h->jpMs);
   if (n > 0) {
-    // the host mirrors (round_prepare's host aggregation path reads jNode)
-    for (int i = 0; i < n; i++) {
-      const int j = job[i];
-      h->jNode[j] = node[i]; h->jRunPrio[j] = scheduled_at_priority ? scheduled_at_priority[i] : 0; h->jRunTsHost[j] = run_timestamp ? run_timestamp[i] : 0;
-    }
-    if (!h->jp.built) jpMakeResident(h, total);   // first patch of this job table: the order-key inputs become resident (the run timestamps as patched above)
-    JpArgs a; memset(&a, 0, sizeof a);
-    a.M = M; a.n = n; a.nT = nT; a.total = total; a.nb2 = nb2;
-    std::vector<int32_t> prioZero; std::vector<int64_t> tsZero;
-    if (!scheduled_at_priority) { prioZero.assign(n, 0); scheduled_at_priority = prioZero.data(); }
-    if (!run_timestamp) { tsZero.assign(n, 0); run_timestamp = tsZero.data(); }
-    int32_t* e32 = (int32_t*)h->jpScratch; int64_t* e64 = (int64_t*)(h->jpScratch + oTs);
-    plat_h2d(e32, job, sizeof(int32_t) * (size_t)n); plat_h2d(e32 + n, node, sizeof(int32_t) * (size_t)n); plat_h2d(e32 + 2 * (size_t)n, scheduled_at_priority, sizeof(int32_t) * (size_t)n);
-    plat_h2d(e64, run_timestamp, sizeof(int64_t) * (size_t)n);
-    a.pJob = e32; a.pNode = e32 + n; a.pPrio = e32 + 2 * (size_t)n; a.pTs = e64;
-    a.keep = h->jp.keep; a.jQPrio = h->jp.qprio; a.jSubmit = h->jp.submit; a.jRunTs = h->jp.runTs;
-    int32_t* keptBuf = nullptr;
-    if (nT > 0) { a.keys = (JpKey*)(h->jpScratch + oKeys); keptBuf = (int32_t*)(h->jpScratch + oKept); a.out = h->jp.ordSpare; }
+    jpMirror(h, n, job, node, scheduled_at_priority, run_timestamp);
+    JpArgs a; int32_t* keptBuf = nullptr;
+    jpStage(h, p, a, keptBuf, job, node, scheduled_at_priority, run_timestamp);   // first patch of this job table: the order-key inputs become resident (the run timestamps as patched above)
     int prc = plat_take_failure() ? -1 : plat_jobs_patch(d, a, keptBuf);
     if (prc) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
-    if (nT > 0) { std::swap(d.ordAll, h->jp.ordSpare); std::swap(h->ordCap, h->ordSpareCap); }
-    plat_pass_ms(PASS_JP, h->jpMs);
-    if (plat_pass_printed(PASS_JP))
-      fprintf(stderr, "[asched jobs_patch] jobs %d entries %d in the order %d: scatter %.4f ms, remove %.4f ms, sort %.4f ms, merge %.4f ms\n", M, n, nT, h->jpMs[0], h->jpMs[1], h->jpMs[2], h->jpMs[3]);
+    jpSeated(h, p, "jobs_patch");
   }
   // job dynamic state: everything unbound until round_prepare, as at the end of jobs_set
   d.cfg.Q = 0;
   return resetDynamicState(h, M);
+}
+
+// the result of the round the handle holds, applied to the resident jobs with the caller's other run-state changes of the cycle (scheduling/scheduling_algo.go:276-285:
+// txn.Upsert(preemptedJobs) / txn.Upsert(scheduledJobs), the jobs of :956-981): asched_jobs_patch of (the scheduled list ++ the preempted list ++ the extras) without
+// the lists leaving the device (kernels_round_commit.h).  The host's mirrors follow the copies downloadResult left in pinned memory: nothing is read back.
+int32_t asched_round_commit(asched_t* h, int64_t run_timestamp, int64_t run_timestamp_step, int32_t n_extra, const int32_t* job, const int32_t* node,
+                            const int32_t* scheduled_at_priority, const int64_t* run_timestamp_extra) {
+  if (!h) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  const int M = h->M, nx = n_extra;
+  // ---- every refusal before anything changes
+  if (!h->jobsSet || h->jQPrioHost.size() != (size_t)M || h->jSubmitHost.size() != (size_t)M || h->jRunTsHost.size() != (size_t)M || h->jNode.size() != (size_t)M)
+    return fail(h, ASCHED_ERR_INVALID, "round_commit: no job table on this handle (jobs_set first)");
+  if (nx < 0 || (nx > 0 && (!job || !node))) return fail(h, ASCHED_ERR_INVALID, "round_commit: bad arguments");
+  if (h->mkJobsBuilt) return fail(h, ASCHED_ERR_UNSUPPORTED, "round_commit: the job set carries the market order, which depends on run state too (jobs_set instead)");
+  const int ns = h->resNs, np = h->resNp;
+  if (!h->haveRoundResult || (ns + np > 0 && !h->resPin))
+    return fail(h, ASCHED_ERR_INVALID, "round_commit: no round result on this handle (schedule_round first; every call that changes the handle drops the result)");
+  if (h->roundExchanged) return fail(h, ASCHED_ERR_UNSUPPORTED, "round_commit: not after round_exchange (the lists on this handle are this replica's own round, not the resolved one)");
+  if ((long long)nx + ns + np > (1 << 29)) return fail(h, ASCHED_ERR_UNSUPPORTED, "round_commit: more than 2^29 entries");
+  const int n = nx + ns + np;
+  const int32_t *sJob = h->resSJob, *sNode = h->resSNode, *sPrio = h->resSPrio, *pJob = h->resPJob;
+  if (h->jpSeen.size() != (size_t)M) h->jpSeen.assign(M, 0);
+  // the rows the result names: marked (2) while the extras are checked against them
+  int nT = 0, code = ASCHED_ERR_INVALID, marked = 0;
+  const char* why = nullptr;
+  for (int i = 0; i < ns + np && !why; i++) {
+    const int j = i < ns ? sJob[i] : pJob[i - ns];
+    if (j < 0 || j >= M || h->jpSeen[j] || (i < ns && (sNode[i] < 0 || sNode[i] >= (h->nodesSet ? h->N : 0)))) { why = "the round result held does not describe this job table"; break; }
+    h->jpSeen[j] = 2; marked = i + 1;
+    if (i < ns && h->jAway[j]) { why = "a cross-pool away row may only lose its run"; code = ASCHED_ERR_UNSUPPORTED; }
+    else if (h->jQueue[j] >= 0) nT++;
+  }
+  if (!why) why = jpCheckEntries(h, nx, job, node, nT, code);
+  for (int i = 0; i < marked; i++) h->jpSeen[i < ns ? sJob[i] : pJob[i - ns]] = 0;
+  if (why) return fail(h, code, std::string("round_commit: ") + why);
+  // sized before anything changes: running out of device memory here is a refusal too
+  const JpPlan p = jpPlan(h, n, nx, nT);
+  KeptBlock<char> scratch{h->jpBufs, h->jpScratch, h->jpScratchBytes};
+  if (n > 0 && !scratch.grow(p.need)) return fail(h, ASCHED_ERR_DEVICE, "round_commit: out of device memory for the scratch; the handle is as it was");
+  // ---- what jobs_set resets (the job table half patched).  The lists stay where they are, on the device and in pinned memory: only haveRoundResult goes
+  residentTouchJobs(h, false, true);
+  Dev& d = h->dev;
+  plat_pass_clear(PASS_JP, h->jpMs);
+  const bool madeResident = n > 0 && !h->jp.built;
+  if (n > 0) {
+    jpMirror(h, nx, job, node, scheduled_at_priority, run_timestamp_extra);
+    for (int i = 0; i < ns; i++) {
+      const int j = sJob[i];
+      h->jNode[j] = sNode[i]; h->jRunPrio[j] = sPrio[i]; h->jRunTsHost[j] = (int64_t)((uint64_t)run_timestamp + (uint64_t)i * (uint64_t)run_timestamp_step);
+    }
+    for (int i = 0; i < np; i++) { const int j = pJob[i]; h->jNode[j] = -1; h->jRunPrio[j] = 0; h->jRunTsHost[j] = 0; }
+    RcArgs a; memset(&a, 0, sizeof a);
+    int32_t* keptBuf = nullptr;
+    jpStage(h, p, a.p, keptBuf, job, node, scheduled_at_priority, run_timestamp_extra);
+    a.nx = nx; a.ns = ns; a.np = np; a.ts0 = run_timestamp; a.tsStep = run_timestamp_step; a.pJobW = (int32_t*)h->jpScratch;
+    int prc = plat_take_failure() ? -1 : plat_round_commit(d, a, keptBuf);
+    if (prc) return fail(h, ASCHED_ERR_DEVICE, plat_last_error());
+    jpSeated(h, p, "round_commit");
+  }
+  { int32_t* t = h->rcStats;
+    t[0] = ns; t[1] = np; t[2] = nx; t[3] = nT; t[4] = madeResident ? 1 : 0;
+    t[5] = (int32_t)(h->jpMs[0] * 1000.0 + 0.5); t[6] = (int32_t)((h->jpMs[1] + h->jpMs[2]) * 1000.0 + 0.5); t[7] = (int32_t)(h->jpMs[3] * 1000.0 + 0.5); }
+  // job dynamic state: everything unbound until round_prepare, as at the end of jobs_set
+  d.cfg.Q = 0;
+  return resetDynamicState(h, M);
+}
+int32_t asched_round_commit_stats(asched_t* h, int32_t* out) {
+  if (!h || !out) return ASCHED_ERR_INVALID;
+  plat_enter(h->plat);
+  for (int k = 0; k < 8; k++) out[k] = h->rcStats[k];
+  return 0;
 }
 
 // `armadactl reprioritize` for resident jobs (jobdb/reconciliation.go:198-200 records the requested priority, scheduler.go:1198-1199 applies it with job.WithPriority,
@@ -2531,7 +2637,7 @@ int32_t asched_req_classes_append(asched_t* h, const asched_req_classes* more) {
   uint64_t* mask1 = (uint64_t*)sb.fresh(&h->dClassMask);
   // ---- what jobs_set resets (the class tables half grown).  Off the in-place path the call ends with rebuildMasks: the fast structure goes
   residentTouchJobs(h, why != 0);
-  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->jsStats, 0, sizeof h->jsStats);
+  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->rcStats, 0, sizeof h->rcStats); memset(h->jsStats, 0, sizeof h->jsStats);
   plat_pass_clear(PASS_CA, h->caMs);
   { int32_t* t = h->caStats;
     t[0] = n; t[1] = nT1; t[2] = nT2; t[3] = inPlace ? Cext0 - C0 : 0; t[4] = why ? 1 : 0; t[5] = why; t[6] = h->C; t[7] = h->Cext; }
@@ -2731,7 +2837,7 @@ int32_t asched_shapes_compact(asched_t* h, int32_t flags, int32_t* class_new_id)
   uint64_t* shapeMask1 = (uint64_t*)sb.fresh(&d.shapeMask); uint64_t* classMask1 = (uint64_t*)sb.fresh(&h->dClassMask);
   // ---- what jobs_set resets (the tables half compacted).  Off the in-place path the call ends with rebuildMasks: the fast structure goes
   residentTouchJobs(h, why != 0);
-  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->jsStats, 0, sizeof h->jsStats); memset(h->caStats, 0, sizeof h->caStats);
+  memset(h->jaStats, 0, sizeof h->jaStats); memset(h->jasStats, 0, sizeof h->jasStats); memset(h->jdStats, 0, sizeof h->jdStats); memset(h->jrStats, 0, sizeof h->jrStats); memset(h->rcStats, 0, sizeof h->rcStats); memset(h->jsStats, 0, sizeof h->jsStats); memset(h->caStats, 0, sizeof h->caStats);
   plat_pass_clear(PASS_SC, h->scMs); h->scHostMs = 0;
   if (anyDead) {
     plat_h2d(scratch, shapeNew.data(), 4 * (size_t)S0);
@@ -4596,6 +4702,7 @@ static int downloadResult(asched* h, asched_round_result* out, const int32_t* io
   int64_t* qAlloc = (int64_t*)(b + oA);
   double* qF = (double*)(b + oF); double *qDc = qF + Q, *qUc = qDc + Q, *qTok = qUc + Q;
   int32_t* reason = (int32_t*)(b + oR);
+  h->resSJob = sJob; h->resSNode = sNode; h->resSPrio = sPrio; h->resPJob = pJob;
   if (ns) { plat_d2h_async(sJob, d.resJob, 4 * (size_t)ns); plat_d2h_async(sNode, d.resNode, 4 * (size_t)ns); plat_d2h_async(sPrio, d.resPrio, 4 * (size_t)ns); plat_d2h_async(sMeth, d.resMethod, 4 * (size_t)ns); }
   if (np) { plat_d2h_async(pJob, d.resPreJob, 4 * (size_t)np); plat_d2h_async(pNode, d.resPreNode, 4 * (size_t)np); }
   if (Q) {

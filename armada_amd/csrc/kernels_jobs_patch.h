@@ -80,20 +80,23 @@ JP_FN bool jpRowLess(const Dev& d, const JpArgs& a, int j, const JpKey& k) {
   return j < k.idx;
 }
 
+// the slot of a row of no queue and of the padding: behind every real key (a queue has 31 bits)
+JP_FN JpKey jpSentinel() { JpKey k; k.a = ~0ull; k.b = 0; k.t1 = 0; k.t2 = 0; k.idx = INT32_MAX; k.pad_ = 0; return k; }
+// row j now runs on `node` (-1: no run) at `prio`, leased at `ts`: its run fields and those of its JobRec, its keep flag, and -> its NEW key (the scatter of the patch
+// and of the round commit, kernels_round_commit.h)
+JP_FN JpKey jpSeat(const Dev& d, const JpArgs& a, int j, int node, int prio, int64_t ts) {
+  d.jNode0[j] = node; d.jRunPrio[j] = prio; d.jLeaseMs[j] = ts / 1000000; a.jRunTs[j] = ts;
+  a.keep[j] = 0;
+  if (d.jrec) {
+    JobRec& r = d.jrec[j];
+    r.node0 = node; r.runPrio = prio; r.nlRun = (uint8_t)jpLevels(d.cfg, r.preemptible ? prio : INT32_MAX);
+  }
+  return d.jQueue[j] >= 0 ? jpKeyOf(d, a, j) : jpSentinel();
+}
 // slot i < nb2 of the sort array; i < n: entry i first
 JP_FN void jpScatter(const Dev& d, const JpArgs& a, int i) {
-  JpKey k; k.a = ~0ull; k.b = 0; k.t1 = 0; k.t2 = 0; k.idx = INT32_MAX; k.pad_ = 0;   // behind every real key (a queue has 31 bits)
-  if (i < a.n) {
-    const int j = a.pJob[i], node = a.pNode[i], prio = a.pPrio[i];
-    const int64_t ts = a.pTs[i];
-    d.jNode0[j] = node; d.jRunPrio[j] = prio; d.jLeaseMs[j] = ts / 1000000; a.jRunTs[j] = ts;
-    a.keep[j] = 0;
-    if (d.jrec) {
-      JobRec& r = d.jrec[j];
-      r.node0 = node; r.runPrio = prio; r.nlRun = (uint8_t)jpLevels(d.cfg, r.preemptible ? prio : INT32_MAX);
-    }
-    if (d.jQueue[j] >= 0) k = jpKeyOf(d, a, j);
-  }
+  JpKey k = jpSentinel();
+  if (i < a.n) k = jpSeat(d, a, a.pJob[i], a.pNode[i], a.pPrio[i], a.pTs[i]);
   if (a.keys) a.keys[i] = k;
 }
 // i < nT + nKept + n: the touched rows, the kept rows, the keep flags

@@ -93,7 +93,7 @@ static int plat_evict_report(Dev& d, const EvrArgs& a, int pass);
 enum PassLayout { PASS_SEQ, PASS_REV, PASS_PAIRS };   // out[k] is between events k and k + 1 / the same with out[] in reverse order / between events 2k and 2k + 1, each pass with a flag of its own
 enum PassFamily {
   PASS_EVR,   // the evictor report: job pass / node pass / queue pass of the last round (read once the round is over)
-  PASS_JP,    // plat_jobs_patch and plat_jobs_reprioritise: scatter / remove / sort / merge
+  PASS_JP,    // plat_jobs_patch, plat_jobs_reprioritise and plat_round_commit: scatter / remove / sort / merge
   PASS_JA,    // plat_jobs_append: row fill / sort / merge
   PASS_SA,    // plat_shapes_append: the new mask rows / the row copies
   PASS_CA,    // plat_req_classes_append: the new rows / the row copies
@@ -127,6 +127,11 @@ static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf);
 // a.p.kept / a.p.nKept.  Synchronous: the new order is complete on return; PASS_JP reports its passes.  The CPU build's definition sits in kernels_jobs_reprioritise.h.
 struct JrArgs;
 static int plat_jobs_reprioritise(Dev& d, JrArgs& a, int32_t* keptBuf);
+// a round's result applied to the resident jobs (kernels_round_commit.h): its scatter + keys over the caller's entries and the lists the round left in d.resJob /
+// resNode / resPrio / resPreJob, then the patch's remove, sort and merge by rank into a.p.out; fills a.p.kept / a.p.nKept.  Synchronous: the new order is complete on
+// return; PASS_JP reports its passes.  The CPU build's definition sits in kernels_round_commit.h.
+struct RcArgs;
+static int plat_round_commit(Dev& d, RcArgs& a, int32_t* keptBuf);
 // retried jobs change class and request in place (kernels_jobs_respec.h): one scatter over the entries — shape, request words, grid flag and JobRec of each named row.
 // Synchronous: the rows are complete on return.  The CPU build's definition sits in kernels_jobs_respec.h.
 struct JsArgs;

@@ -933,6 +933,11 @@ static int plat_jobs_patch(Dev& d, JpArgs& a, int32_t* keptBuf) { return jpPasse
 #include "kernels_jobs_reprioritise.h"
 extern "C" int asched_internal_jr_scatter(const Dev* d, const JrArgs* a, hipStream_t s);
 static int plat_jobs_reprioritise(Dev& d, JrArgs& a, int32_t* keptBuf) { return jpPasses(d, a.p, keptBuf, [&](hipStream_t st) { return asched_internal_jr_scatter(&d, &a, st); }); }
+// a round's result applied to the resident jobs (kernels_round_commit.h; k_rc_scatter in armada_sched_mgpu.hip): its own scatter, then the patch's remove, sort and
+// merge.  The events are the patch's (PASS_JP; tools/probe_round_commit.py).
+#include "kernels_round_commit.h"
+extern "C" int asched_internal_rc_scatter(const Dev* d, const RcArgs* a, hipStream_t s);
+static int plat_round_commit(Dev& d, RcArgs& a, int32_t* keptBuf) { return jpPasses(d, a.p, keptBuf, [&](hipStream_t st) { return asched_internal_rc_scatter(&d, &a, st); }); }
 // retried jobs change class and request in place (kernels_jobs_respec.h; k_js_scatter in armada_sched_mgpu.hip): one launch on the handle's stream, waited for
 #include "kernels_jobs_respec.h"
 extern "C" int asched_internal_js_scatter(const Dev* d, const JsArgs* a, hipStream_t s);

@@ -385,7 +385,7 @@ def run_cycles_arriving_rebuilt(lib, sim: SimulatorInput, per_cycle: Optional[in
     return _run_cycles_arriving(lib, sim, per_cycle, max_cycles, False)
 
 
-def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, every, deleted, resident=None, in_place=False, reprio=None, retire=0, classes=False):
+def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, every, deleted, resident=None, in_place=False, reprio=None, retire=0, classes=False, commit=False):
     from .binding import Scheduler
     wl = sim.workload
     m = wl.num_jobs
@@ -400,6 +400,7 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
     started = np.full(m, -1.0)
     done = np.zeros(m, bool)
     changed = np.zeros(m, bool)
+    told = np.zeros(m, bool)                          # run_cycles_committed: the runs whose end the last round_commit has already told the handle
     qprio = np.zeros(m, np.uint32)                    # per JOB: the priority within its queue, which the events of run_cycles_reprioritising move
     job_of_row = np.zeros(0, np.int64)                # the driver's own row <-> job map: the table's rows are the jobs that arrived and were not deleted, in job order
     row_of_job = np.full(m, -1, np.int64)
@@ -433,7 +434,8 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
         finished = (node >= 0) & (started >= 0) & (started + sim.job_runtime_s <= t)
         done |= finished
         node[finished] = -1
-        changed |= finished
+        changed |= finished & ~told
+        told[:] = False
         if done.all():
             break
         upto = int(np.searchsorted(arrive, cycle, side="right"))
@@ -521,6 +523,12 @@ def _run_cycles_compacting(lib, sim: SimulatorInput, per_cycle, max_cycles, ever
             out[-1]["compacts"], out[-1]["shapes_retired"], out[-1]["classes_retired"] = compacts, shapes_retired, classes_retired
         if have == m and not sched and not pre and not (node >= 0).any():
             break   # everything has arrived, nothing runs and nothing can be placed: the rest never will
+        if commit:
+            # the round's result is applied where it lies (Scheduler.round_commit: no entry is built for it), every lease at the cycle's time; the extras are the runs
+            # that will have ended when the next cycle begins.  A job the round leased that ends within the period is the result's row: its end goes with jobs_patch
+            told = (node >= 0) & (started >= 0) & (started + sim.job_runtime_s <= t + sim.cycle_period_s) & ~changed
+            s.round_commit(int(max(t, 0) * 1e9), 0, row_of_job[told].astype(np.int32), -1)
+            changed[:] = False
         t += sim.cycle_period_s
     s.close()
     return out
@@ -555,6 +563,13 @@ def run_cycles_resident(lib, sim: SimulatorInput, per_cycle: Optional[int] = Non
     hold_finished they stay in the table and are named in `held` every cycle instead, which costs O(finished rows) per cycle.  in_place: as for run_cycles_arriving
     (shapes that the deletes emptied come back in place as well).  Records as run_cycles_compacting."""
     return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, 1, True, resident="held" if hold_finished else "delete", in_place=in_place)
+
+
+def run_cycles_committed(lib, sim: SimulatorInput, per_cycle: Optional[int] = None, max_cycles: int = 1000):
+    """run_cycles_resident's cycle with the round's result COMMITTED on the device: right after the round, Scheduler.round_commit applies the scheduled and preempted
+    lists the handle still holds (txn.Upsert(preemptedJobs) / txn.Upsert(scheduledJobs), scheduling_algo.go:276-285) — no entry is built from the result — with the
+    runs that end before the next cycle as its extras.  What is left for jobs_patch is the end of a run the same round began.  Records as run_cycles_resident."""
+    return _run_cycles_compacting(lib, sim, per_cycle, max_cycles, 1, True, resident="delete", commit=True)
 
 
 def run_cycles_reprioritising(lib, sim: SimulatorInput, events, per_cycle: Optional[int] = None, max_cycles: int = 1000):

@@ -388,6 +388,33 @@ int32_t ASCHED_FN(jobs_set)(asched_t*, const asched_jobs* jobs, const asched_req
    No other field changes (a finished job stays as a row without a run until asched_jobs_delete removes it); newly submitted rows are appended with
    asched_jobs_append. */
 int32_t ASCHED_FN(jobs_patch)(asched_t*, int32_t n, const int32_t* job, const int32_t* node, const int32_t* scheduled_at_priority, const int64_t* run_timestamp);
+/* The two Upserts a pool's cycle ends with (scheduling/scheduling_algo.go:276-285: txn.Upsert(preemptedJobs), txn.Upsert(scheduledJobs), the jobs of :956-981),
+   taken from the result of the round the handle holds: the lists asched_round_result pointed at are still on the device, so the caller builds and sends no entry for
+   them.  The handle must hold a round result (asched_schedule_round, and no call that changes the handle since).  After a successful call the handle is in the state
+   asched_jobs_patch would leave, given this entry list in any order — the state asched_jobs_set would leave for the table with those run fields replaced — for every
+   entry point, including everything jobs_patch resets (no round prepared, no result held, the state epoch, the dynamic state; the caller goes on with round_prepare):
+     i in [0, num_scheduled): row scheduled_job[i] runs on scheduled_node[i] at scheduled_priority[i], leased at run_timestamp + i * run_timestamp_step (ns), i the
+       position in the result's ascending list (the reference's scheduled list is maps.Values, of unspecified order: any monotone assignment is legal; step 0 gives
+       every lease the cycle's time);
+     i in [0, num_preempted): row preempted_job[i] has node -1, priority 0, timestamp 0;
+     the n_extra entries of the caller, with jobs_patch's meaning (the other run-state changes of the cycle, such as the runs that ended): re-seated in the same
+       remove / sort / merge pass.  scheduled_at_priority / run_timestamp_extra NULL: zeros.
+   A round that scheduled and preempted nothing, with n_extra == 0, performs the resets only.
+   READ BEFORE THE COMMIT what belongs to the round: asched_round_preemption_causes and asched_round_evictor_report are invalid afterwards, as after jobs_patch.  The
+   pointers of the last asched_round_result stay readable exactly as long as they do after jobs_patch today: until the next round on the handle (the commit reads the
+   lists, it does not write or free them).
+   Refused before anything changes, as by jobs_patch — ASCHED_ERR_INVALID: no job table, no round result held (never run, or reset by any call since), n_extra < 0,
+   n_extra > 0 without job or node, an extra row outside [0, M), an extra node outside [-1, N), an extra row named twice, an extra row that the round's scheduled or
+   preempted list names (the caller sends that change with a later jobs_patch); ASCHED_ERR_UNSUPPORTED: the job set carries the market order, more than 2^29 entries
+   in all, a cross-pool away row that would gain a run (from the extras or from the scheduled list), a result that asched_round_exchange has resolved against other
+   replicas since (the lists are this replica's own round); ASCHED_ERR_DEVICE with "the handle is as it was" in last_error: out of device memory for the scratch.
+   Any other ASCHED_ERR_DEVICE (a failed launch or copy) is NOT such a refusal: the handle then needs asched_jobs_set, as documented for jobs_patch. */
+int32_t ASCHED_FN(round_commit)(asched_t*, int64_t run_timestamp, int64_t run_timestamp_step, int32_t n_extra, const int32_t* job, const int32_t* node,
+                                const int32_t* scheduled_at_priority, const int64_t* run_timestamp_extra);
+/* how the last round_commit ran: out[0] scheduled entries, [1] preempted entries, [2] extra entries, [3] entries that name a row in the order (queue >= 0), [4] 1 = this
+   call made the order-key inputs resident (the first incremental call on the job table), [5..7] device microseconds of scatter / remove + sort / merge (measured only
+   with ASCHED_JP_TIMES=1, else 0).  Zeros after jobs_set. */
+int32_t ASCHED_FN(round_commit_stats)(asched_t*, int32_t* out /*[8]*/);
 /* `armadactl reprioritize` for resident jobs, one job or a whole job set: jobdb/reconciliation.go:198-200 records the requested priority, scheduler.go:1198-1199
    applies it (job.WithPriority(job.RequestedPriority()), jobdb/job.go:523), and Txn.Upsert takes the job out of its queue's sorted set and puts it back under the new
    key (jobdb/jobdb.go:583-587, :695-699); the queue priority is the second word of that key (SchedulingOrderCompare, jobdb/comparison.go:70-79).

@@ -891,6 +891,35 @@ func (g *GpuRound) PatchJobs(scheduled, preempted []*schedulercontext.JobSchedul
 	return g.check(C.asched_jobs_patch(g.h, C.int32_t(n), i32p(job), i32p(node), i32p(prio), i64p(ts)))
 }
 
+// CommitRound is PatchJobs for the round this GpuRound has just run, without the scheduled and preempted entries (asched_round_commit): the library applies the lists
+// of its own result — every scheduled job runs on its node at its ScheduledAtPriority, leased at leasedAt; every preempted job loses its run — where they lie on the
+// device, so nothing is built or sent for them.  ended: ids of jobs whose run finished or whose lease was returned since the last cycle, none of them a job of the
+// result (such a change goes with the next PatchJobs).  Call it after Schedule and after the result, the preemption descriptions and the evictor report have been
+// read: it resets what PatchJobs resets.  The next call is Schedule, as after UploadJobs.
+func (g *GpuRound) CommitRound(ended []string, leasedAt time.Time) error {
+	if len(ended) == 0 {
+		return g.check(C.asched_round_commit(g.h, C.int64_t(leasedAt.UnixNano()), 0, 0, nil, nil, nil, nil))
+	}
+	if g.jobRow == nil {
+		g.jobRow = make(map[string]int32, len(g.jobs))
+		for i, j := range g.jobs {
+			g.jobRow[j.Id()] = int32(i)
+		}
+	}
+	job, node := make([]int32, 0, len(ended)), make([]int32, 0, len(ended))
+	for _, id := range ended {
+		row, ok := g.jobRow[id]
+		if !ok {
+			return fmt.Errorf("CommitRound: job %s is not one of the uploaded jobs", id)
+		}
+		job, node = append(job, row), append(node, -1)
+	}
+	var pins runtime.Pinner
+	defer pins.Unpin()
+	pins.Pin(&job[0]); pins.Pin(&node[0])
+	return g.check(C.asched_round_commit(g.h, C.int64_t(leasedAt.UnixNano()), 0, C.int32_t(len(job)), i32p(job), i32p(node), nil, nil))
+}
+
 // ReprioritiseJobs tells the library the queue priorities `armadactl reprioritize` changed since the last cycle, for one job or a whole job set, without re-describing the
 // job set (asched_jobs_reprioritise): jobdb/reconciliation.go:198-200 records the requested priority and the scheduler applies it with
 // job.WithPriority(job.RequestedPriority()) (scheduler.go:1198-1199, jobdb/job.go:523); the caller passes the jobs it called WithPriority on, as they are after the call.
